@@ -2,7 +2,7 @@
 # coding=utf-8
 """bench.py -- throughput of Duet's step E/F hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          # started plainly: spawns one process per GPU itself
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   # started plainly: spawns one process per GPU itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch of synthetic input that is already resident in HBM.
@@ -23,7 +23,8 @@ N > 1   BASELINE.json configs[2]: the synthetic whole genome (24 contigs, 2e7 ma
         (`--collective torch`: torch.distributed "nccl"; the line's `collective` says which); "scaling": "strong".  Rank 0 also
         times the same problem on its GPU alone (`same_problem_on_1_gpu`), so the line carries its own 1-GPU reference
         (`value_vs_1gpu_same_problem` = value / that).
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  `--dump-outputs DIR`: after the timed steps rank 0 writes what the last one computed (the
+per-candidate pred and ps a caller receives) as DIR/pred.npy and DIR/ps.npy (see dump_outputs).
 
 Algorithmic bytes: ef_classify 12 B/mark + 22 B/candidate + 8 B/read per launch; the whole
 E/F step B_EF = 12 M + 27 C + 8 R; stage A0 18 B/mark.  Kernel durations come from HIP events on the kernel's own
@@ -510,6 +511,7 @@ def sharded_run(args, ctx, torch, coll, rank, world, local_rank, one_gpu):
         c_oracle = cpu_leg()
         g = gathered.cpu().numpy()
         got = dist.merge_results(soa, owned, [dist.unpack_block(g[r], n_max, sizes[r]) for r in range(world)])
+        dumped = dump_outputs(args.dump_outputs, got[0], got[1]) if args.dump_outputs else None
         rc, want_pred, want_ps = c_oracle.ef(soa, 50, 2)
         parity = bool(rc == 0 and np.array_equal(got[0], want_pred) and np.array_equal(got[1], want_ps))
         # the SAME problem on this rank's GPU alone (the other ranks wait at the barrier below): the 1-GPU point of the
@@ -550,6 +552,7 @@ def sharded_run(args, ctx, torch, coll, rank, world, local_rank, one_gpu):
                        'parallelism': 'contig-sharded x%d (LPT on mark counts)' % world, 'svlen_thres': 50,
                        'suppread_thres': 2},
             'parity_vs_oracle': parity,
+            'dumped_outputs': dumped,
             'collective': coll.name,
             'roofline': {'kernel': 'ef_classify', 'bound': 'hbm', 'achieved': slow['ef_classify_GBs'], 'peak': HBM_PEAK_GBS,
                          'unit': 'GB/s', 'frac': slow['ef_classify_frac_of_8TBs'], 'traffic': None,
@@ -820,6 +823,30 @@ def write_detail(full, world):
     return None
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, pred, ps):
+    """--dump-outputs DIR: what the timed path's last step handed its caller -- per candidate the haplotype code (pred, u8)
+    and the phase set (ps, u32) -- as DIR/pred.npy (float32) and DIR/ps.npy (float64: exact for every u32).  The inputs are
+    seeded, so two builds run with the same arguments can be compared file for file.  Above 64 MB in all, the same fixed,
+    seeded sample of candidates from both arrays, sorted, with its indices in DIR/sample_index.npy (float64).
+    -> {name: number of elements}"""
+    arrays = {'pred': np.asarray(pred).astype(np.float32), 'ps': np.asarray(ps).astype(np.float64)}
+    n = len(arrays['pred'])
+    per_item = sum(a.itemsize for a in arrays.values())
+    budget = DUMP_BUDGET_BYTES - 4096                    # (the .npy headers)
+    if n * per_item > budget:
+        k = budget // (per_item + 8)
+        idx = np.sort(np.random.default_rng(20250101).choice(n, size=k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays['sample_index'] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {name: int(a.size) for name, a in arrays.items()}
+
+
 METRIC = 'SV support-read marks clustered+phased /sec; bit-exact phased_sv.vcf vs ref'
 VALUE_IS = 'phased_only (step E/F on pre-clustered candidates); the literal clustered+phased figure is value_clustered_and_phased'
 DTYPE = 'u32/u64 integer + f64 threshold compares'
@@ -839,6 +866,7 @@ def single_gpu_run(args, ctx, torch):
         last_slot = gg.slot
         iso = step_kernels_profiled(ctx, dp, stream, torch, n=max(min(args.steps, 100), 50))
     pred, ps = dp.results(last_slot)
+    dumped = dump_outputs(args.dump_outputs, pred, ps) if args.dump_outputs else None
     c_oracle = cpu_leg()
     rc, want_pred, want_ps = c_oracle.ef(soa, 50, 2)
     parity = bool(rc == 0 and np.array_equal(pred, want_pred) and np.array_equal(ps, want_ps))
@@ -869,6 +897,7 @@ def single_gpu_run(args, ctx, torch):
                                              'U[0,400), mean ~600, capped at 8100 + 3 % U[8101,20000] (8d: exp mean 600); '
                                              'the reference sha256 in tests/golden/seeded.json pins exactly these inputs'},
         'parity_vs_oracle': parity,
+        'dumped_outputs': dumped,
         'kernels_us_isolated': {n: round(float(iso.kernel_ms[i]) * 1e3, 2) for i, n in enumerate(_lib.KERNEL_NAMES)},
         'roofline': roofline_block(kname, soa, k_ms, k_n, k_src,
                                    note='config 2 is 15.5 MB per launch (~1.9 us at peak): launch-latency bound; '
@@ -949,8 +978,12 @@ def main():
     ap.add_argument('--collective', choices=('duet', 'torch'), default='duet',
                     help='N > 1: the all-gather of the data path -- "duet": duet_comm_* inside libduet_ef.so, what `duet --gpus N` ships '
                          '(default); "torch": torch.distributed backend "nccl" (rounds 1-4)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (per candidate pred and ps) as DIR/<name>.npy')
     ap.add_argument('--launch-dry-run', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     from duet_amd import launch
     if args.gpus > 1 and not launch.under_launcher():

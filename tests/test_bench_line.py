@@ -85,3 +85,27 @@ def test_line_sheds_blocks_rather_than_growing():
     out = bench.compact_line(full, None)
     assert len(json.dumps(out)) < bench.LINE_BUDGET
     assert 'roofline' in out and 'cpu_baseline' in out and 'value' in out
+
+
+def test_dump_outputs_exact_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: pred (u8) and ps (u32) as float32 / float64 .npy, exact; above the budget the same seeded sample of
+    both, with its indices, and the files stay inside the budget."""
+    import numpy as np
+    rng = np.random.default_rng(7)
+    pred = rng.integers(0, 4, 1000).astype(np.uint8)
+    ps = rng.integers(0, 2 ** 32, 1000, dtype=np.uint64).astype(np.uint32)
+    got = bench.dump_outputs(str(tmp_path / 'a'), pred, ps)
+    assert got == {'pred': 1000, 'ps': 1000}
+    p, s = np.load(str(tmp_path / 'a' / 'pred.npy')), np.load(str(tmp_path / 'a' / 'ps.npy'))
+    assert p.dtype == np.float32 and s.dtype == np.float64
+    assert np.array_equal(p.astype(np.uint8), pred) and np.array_equal(s.astype(np.uint32), ps)
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 4096 + 1200)
+    for d in ('b', 'c'):
+        got = bench.dump_outputs(str(tmp_path / d), pred, ps)
+        assert got == {'pred': 60, 'ps': 60, 'sample_index': 60}
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))) <= bench.DUMP_BUDGET_BYTES
+    idx = np.load(str(tmp_path / 'b' / 'sample_index.npy')).astype(np.int64)
+    assert np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(str(tmp_path / 'b' / 'ps.npy')), ps[idx].astype(np.float64))
+    for f in ('pred.npy', 'ps.npy', 'sample_index.npy'):
+        assert np.array_equal(np.load(str(tmp_path / 'b' / f)), np.load(str(tmp_path / 'c' / f)))

@@ -115,13 +115,13 @@ def test_missing_rank_times_out_on_the_rccl_path():
 
 
 def test_two_ranks_over_real_rccl(tmp_path):
-    """`duet --gpus 2` with the in-library collective over real RCCL -- when this box has two devices (the driver's GPU box has
-    one: skipped there; an 8-GPU node runs it)."""
+    """`duet --gpus 2` with the in-library collective over real RCCL, against the single-GPU run of the same work dir.  With two
+    devices: two ranks, one per device.  With one device RCCL refuses two ranks on it ("Duplicate GPU detected"), so the pieces
+    run apart on the same work dir: the two ranks in the one-GPU mode (DUET_ONE_GPU=1: both on device 0, the records through the
+    TCP star), and the in-library collective over real RCCL as ONE rank (DUET_FORCE_RANKS=1)."""
     import subprocess
     import sys
     n = int(subprocess.check_output([sys.executable, '-c', 'import torch; print(torch.cuda.device_count())']).decode().strip() or 0)
-    if n < 2:
-        pytest.skip('one visible device: two RCCL ranks cannot share it')
     from duet_amd import synth
     from tests import helpers as H
     home = str(tmp_path / 'w')
@@ -129,11 +129,16 @@ def test_two_ranks_over_real_rccl(tmp_path):
     r = fresh_interpreter('from duet_amd.sv_phasing import sv_phasing\nsv_phasing(%r, 50, 2, 4, False)\n' % home, {}, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     one = open(home + '/phased_sv.vcf', 'rb').read()
-    os.remove(home + '/phased_sv.vcf')
-    r = fresh_interpreter('from duet_amd.sv_phasing import sv_phasing\nsv_phasing(%r, 50, 2, 4, False, gpus=2)\n' % home,
-                          {'DUET_RDZV_TIMEOUT': '120'}, timeout=600)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    assert open(home + '/phased_sv.vcf', 'rb').read() == one and one.count(b'Duet.') > 100
+    assert one.count(b'Duet.') > 100
+    runs = [(2, {})] if n >= 2 else [(2, {'DUET_ONE_GPU': '1'}), (1, {'DUET_FORCE_RANKS': '1', 'NCCL_DEBUG': 'VERSION'})]
+    for gpus, env in runs:
+        os.remove(home + '/phased_sv.vcf')
+        r = fresh_interpreter('from duet_amd.sv_phasing import sv_phasing\nsv_phasing(%r, 50, 2, 4, False, gpus=%d)\n' % (home, gpus),
+                              dict(env, DUET_RDZV_TIMEOUT='120'), timeout=600)
+        assert r.returncode == 0, (gpus, env, r.stderr.decode()[-2000:])
+        if 'DUET_FORCE_RANKS' in env:
+            assert b'RCCL version' in r.stdout + r.stderr    # (the library announces itself when its communicator is set up)
+        assert open(home + '/phased_sv.vcf', 'rb').read() == one, (gpus, env)
 
 
 def test_svim_host_entry_refuses_contig_ids_beyond_the_depth_description():

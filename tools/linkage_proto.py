@@ -1,8 +1,9 @@
 """Design check (CPU): stage A0 in exact fixed point -- the serial rule of oracle/cluster_oracle.c against the\nround-based evaluation the device uses (all mutual nearest neighbours of a round merged at once, ties by index), partition by\npartition on the test generators' marks.  Prints rounds and work per size class; expects 0 mismatches."""
-import sys, ctypes, numpy as np, time
-sys.path.insert(0, '/root/repo')
+import sys, ctypes, numpy as np, time, os
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
 from duet_amd import synth
-sys.path.insert(0, '/root/repo/tests')
+sys.path.insert(0, os.path.join(REPO, 'tests'))
 import subprocess, os
 subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-o", "/tmp/liblinkage_proto.so", os.path.join(os.path.dirname(os.path.abspath(__file__)), "linkage_proto.c"), "-lm"])
 lib = ctypes.CDLL('/tmp/liblinkage_proto.so')
@@ -16,13 +17,13 @@ def run(marks, T=0.9, part_max=100, norm=900.0, gap=1000, name=''):
     print(name, 'M', len(m['pos']), 'T', T, 'parts', s[:,0].tolist(), 'MISMATCH', s[:,1].tolist(), 'avg rounds', [round(a/max(b,1),2) for a,b in zip(s[:,2], s[:,0])], 'max', s[:,3].tolist(), 'alive/n', [round(a/max(b,1),2) for a,b in zip(s[:,4], s[:,5])])
     return int(s[:,1].sum())
 import importlib.util
-spec = importlib.util.spec_from_file_location('tgc', '/root/repo/tests/test_gpu_cluster.py')
+spec = importlib.util.spec_from_file_location('tgc', os.path.join(REPO, 'tests', 'test_gpu_cluster.py'))
 bad = 0
 contigs = [synth.bench_contig('1', 200000, 100000, 1)]
 bad += run(synth.raw_marks(contigs, 1), name='config2')
 # generators from the GPU test (copied call pattern)
 import types
-src = open('/root/repo/tests/test_gpu_cluster.py').read()
+src = open(os.path.join(REPO, 'tests', 'test_gpu_cluster.py')).read()
 ns = {}
 exec(src.split("@pytest.fixture")[0].replace("pytestmark = pytest.mark.gpu", ""), ns)
 exec("def random_marks" + src.split("def random_marks")[1].split("@pytest.mark.parametrize")[0], ns)
