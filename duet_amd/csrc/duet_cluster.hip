@@ -130,10 +130,6 @@ struct ClParams {
     // a fork without an event (cl_gate): the kernel in front of which the side stream forks off writes the run's epoch here as it starts
     uint32_t *fork_flag;
     uint32_t fork_epoch;
-    // small inputs, the partitions of 33..64 marks on four wavefronts each (cl_wide_list on the side stream): cl_fast_all says when it
-    // starts (cl_box is through then) and takes the classes of fast_classes only
-    uint32_t *box_done_flag;
-    uint32_t fast_classes;
 };
 
 __device__ __forceinline__ uint64_t centre_of(uint32_t pos, uint32_t span) { return (uint64_t)pos + (span >> 1); }
@@ -2285,21 +2281,16 @@ __global__ __launch_bounds__(64, 6) void cl_tight_all(const ClParams p, uint32_t
 // Small inputs (one launch's worth of partitions: the chip is not full and a partition's own chain of dependent steps is what
 // takes the time): the threshold graph and, in the same wavefront, the full-triangle linkage for what it does not settle --
 // one launch, nothing handed on.  Measured at 1.0 M marks: 86 us against 70 + 60 us for the two tiers above.
-constexpr size_t kFastSmemBytes32 = cmax(sizeof(FastSmem<32, 1>), cmax(sizeof(FastSmem<16, 1>), sizeof(FastSmem<8, 1>)));
-constexpr size_t kLinkSmemBytes32 = cmax(sizeof(LinkSmem<32, 1, 32>), cmax(sizeof(LinkSmem<16, 1, 16>), sizeof(LinkSmem<8, 1, 8>)));
-constexpr size_t kFastSmemBytes = cmax(sizeof(FastSmem<64, 1>), kFastSmemBytes32);
-constexpr size_t kLinkSmemBytes = cmax(sizeof(LinkSmem<64, 1, 64>), kLinkSmemBytes32);
+constexpr size_t kFastSmemBytes = cmax(cmax(sizeof(FastSmem<64, 1>), sizeof(FastSmem<32, 1>)), cmax(sizeof(FastSmem<16, 1>), sizeof(FastSmem<8, 1>)));
+constexpr size_t kLinkSmemBytes = cmax(cmax(sizeof(LinkSmem<64, 1, 64>), sizeof(LinkSmem<32, 1, 32>)),
+                                       cmax(sizeof(LinkSmem<16, 1, 16>), sizeof(LinkSmem<8, 1, 8>)));
 
-// C64: the class of 33..64 marks is this launch's too (else the four-wavefront units of cl_wide_list have it: the launch holds the scratch of
-// 32 rows, 10 KB instead of 19, and all its workgroups are resident at once at 1.0 M marks)
-template <bool C64>
 __global__ __launch_bounds__(64) void cl_fast_all(const ClParams p, const uint32_t *lists, const uint32_t *cnts /* [kClasses][kShards] */)
 {
     CL_STAMP_INIT(4);
-    __shared__ __align__(16) unsigned char smem[C64 ? kFastSmemBytes : kFastSmemBytes32];
-    __shared__ __align__(16) unsigned char smem_link[C64 ? kLinkSmemBytes : kLinkSmemBytes32];
+    __shared__ __align__(16) unsigned char smem[kFastSmemBytes];
+    __shared__ __align__(16) unsigned char smem_link[kLinkSmemBytes];
     __shared__ uint32_t s_pref[kShards + 1];               // the running sums of ONE class's shard counters at a time
-    if (p.box_done_flag && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(p.box_done_flag, p.fork_epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     // the classes' totals (one wavefront: a lane per shard)
     uint32_t tot[4];
 #pragma unroll
@@ -2307,7 +2298,7 @@ __global__ __launch_bounds__(64) void cl_fast_all(const ClParams p, const uint32
         uint32_t x = cnts[c * kShards + (threadIdx.x & 63u)];
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) x += (uint32_t)__shfl_xor((int)x, d, 64);
-        tot[c] = (((p.fast_classes >> c) & 1u) && (C64 || c < 3)) ? x : 0u;
+        tot[c] = x;
     }
     const size_t M = p.M;
     const uint32_t span = p.tps * kScanTile;
@@ -2322,9 +2313,8 @@ __global__ __launch_bounds__(64) void cl_fast_all(const ClParams p, const uint32
             loaded = c;
         }
         const WorkList l{lists + (size_t)c * M, s_pref, span, 0u};
-        if (c == 3) {
-            if constexpr (C64) fast_unit<64, 1, 64, kFastThenLink>(p, l, vb, smem, smem_link);
-        } else if (c == 2) fast_unit<32, 1, 32, kFastThenLink>(p, l, (vb - b3) * 2, smem, smem_link);
+        if (c == 3) fast_unit<64, 1, 64, kFastThenLink>(p, l, vb, smem, smem_link);
+        else if (c == 2) fast_unit<32, 1, 32, kFastThenLink>(p, l, (vb - b3) * 2, smem, smem_link);
         else if (c == 1) fast_unit<16, 1, 16, kFastThenLink>(p, l, (vb - b2) * 4, smem, smem_link);
         else fast_unit<8, 1, 8, kFastThenLink>(p, l, (vb - b1) * 8, smem, smem_link);
     }
@@ -2807,25 +2797,6 @@ __global__ __launch_bounds__(512) void cl_wide_big(const ClParams p, const uint3
     for (uint32_t i = blockIdx.x; i < cnt; i += gridDim.x) wide_unit<128>(p, big_list[i], p.gather_rows != 0u, X);
 }
 
-// the listed partitions of the classes c_lo .. 3 (up to 64 marks; their rows where cl_box laid them out).  Tests only (DUET_DBG_CLUSTER_WIDE_ALL):
-// measured at 1.0 M marks the four-wavefront units LOSE on these partitions, whatever sizes they take (profiles/history/r06_wide_units.txt)
-__global__ __launch_bounds__(256) void cl_wide_list(const ClParams p, const uint32_t *lists, const uint32_t *cnts /* [kClasses][kShards] */, uint32_t c_lo)
-{
-    CL_STAMP_INIT(5);
-    __shared__ WideSmem<64> X;
-    __shared__ uint32_t s_pref[kShards + 1];
-    const uint32_t span = p.tps * kScanTile;
-    for (uint32_t c = 3; c + 1u > c_lo; --c) {
-        __syncthreads();
-        if (threadIdx.x < 64u) worklist_prefix(cnts + c * kShards, s_pref);
-        __syncthreads();
-        const WorkList l{lists + (size_t)c * p.M, s_pref, span, 0u};
-        const uint32_t L = l.size();
-        for (uint32_t i = blockIdx.x; i < L; i += gridDim.x) wide_unit<64>(p, l[i], false, X);
-        if (c == 0u) break;
-    }
-}
-
 // One LANE PER CLUSTER: a wavefront takes 64 consecutive partitions (their count lives on the device: the grid strides over an upper
 // bound), and their clusters -- records dense from each partition's start, candidates cbase[part] ... -- are dealt to the lanes
 // 64 at a time: a lane finds its cluster's partition among the wave's 64 by bisection over the lanes' candidate bases (six
@@ -2835,9 +2806,11 @@ __global__ __launch_bounds__(256) void cl_wide_list(const ClParams p, const uint
 // A fork without an event (round 6).  hipEventRecord on the main stream + hipStreamWaitEvent on the side stream cost the MAIN stream
 // 7-14 us each time (the record's barrier packet sits in front of its next kernel: timelines of rounds 4-6).  Instead the main stream
 // runs a one-lane kernel that writes the run's epoch to a device word, and the side stream -- whose launches were queued long before --
-// starts with a one-lane kernel that waits for that word.  The main stream never waits for the side stream here (the JOIN stays an
-// event), so a side queue that the device schedules late only starts late: nothing can deadlock; the wait is bounded all the same
-// (2 s, then the kernel traps: a loud failure, not a hang).  Kernel boundaries on both queues do the cache maintenance around it.
+// starts with a one-lane kernel that waits for that word.  The JOIN goes the same way on small inputs: the side stream's last kernel
+// writes a word, and the main stream waits for it in a gate kernel or, up to 2 M marks, inside cl_pc_sums (large inputs join through
+// an event).  So the main stream does wait on the device for the side stream; every such wait is bounded (2 s, then the kernel traps:
+// a loud failure, not a hang), and only a context whose cl_gate_try saw the two queues run side by side forks through gates.  Kernel
+// boundaries on both queues do the cache maintenance around it.
 __global__ void cl_signal(uint32_t *flag, uint32_t epoch)
 {
     if (threadIdx.x == 0) __hip_atomic_store(flag, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
@@ -2868,18 +2841,6 @@ __global__ void cl_gate_try(const uint32_t *flag, uint32_t epoch, uint32_t *open
         if (wall_clock64() - t0 > 2000000ull) { ok = 0; break; }
     }
     *opened = ok;
-}
-
-// (the join of two side streams in one launch)
-__global__ void cl_gate2(const uint32_t *flag_a, const uint32_t *flag_b, uint32_t epoch)
-{
-    if (threadIdx.x != 0) return;
-    const unsigned long long t0 = wall_clock64();
-    while ((int32_t)(__hip_atomic_load(flag_a, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) - epoch) < 0 ||
-           (int32_t)(__hip_atomic_load(flag_b, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) - epoch) < 0) {
-        __builtin_amdgcn_s_sleep(16);
-        if (wall_clock64() - t0 > 200000000ull) __builtin_trap();
-    }
 }
 
 // clusters per partition -> their sums over every 64 partitions and over every 2048: what cl_emit needs to number the candidates itself (rounds 1-5: a
@@ -3355,14 +3316,12 @@ int cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_cluste
     const uint32_t epoch = ++ctx->cl_epoch;
     const bool tiers = !small || (ctx->dbg & DUET_DBG_CLUSTER_TIERS);
     // small inputs: every partition of more than 64 marks on its own workgroup of eight wavefronts (wide_unit), on the side stream beside cl_box and
-    // cl_fast_all; DUET_DBG_CLUSTER_WIDE_ALL: every listed partition on four wavefronts as well (tests)
+    // cl_fast_all
     // (up to 2 M marks: a wide unit holds 143 KB of LDS, i.e. a CU, for 50 us -- at 4 M marks the 80-odd of them take a third of the chip from
     // cl_fast_all for that long and the pipeline is 1 % slower with them, 0.423 against 0.419 ms; level at 2 M)
+    // (measured, profiles/history/r06_wide_units.txt: for the listed partitions of up to 64 marks four-wavefront units LOSE -- cl_fast_all is
+    // bound by the chip's throughput there, not by a chain -- so only the partitions of more than 64 marks take wide units)
     const bool wide = !tiers && M <= (2u << 20) && !(ctx->dbg & DUET_DBG_CLUSTER_WIDE_OFF);
-    const bool wide_all = wide && (ctx->dbg & DUET_DBG_CLUSTER_WIDE_ALL);
-    // (measured, profiles/history/r06_wide_units.txt: for the listed partitions of up to 64 marks the four-wavefront units LOSE -- cl_fast_all is
-    // bound by the chip's throughput there, not by a chain -- so only the partitions of more than 64 marks take them outside the tests)
-    const bool wide_list = wide_all;
     auto join_signal = [&]() -> int {
         // the join the same way on small inputs: the side stream says when it is through, a gate on the main stream waits for it (the
         // side stream's launches are queued in front of that gate, so even one shared hardware queue would run them first)
@@ -3408,24 +3367,8 @@ int cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_cluste
         hipLaunchKernelGGL((cl_box<false, false>), dim3(nb_sc), dim3(kBoxThreads), 0, st, p, (const uint32_t *)tile_first, lists, cnts, (const uint8_t *)nullptr, (const PartSum *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
     if ((box_applies || gate_forks) && (rc = launch_big(!box_applies && gate_forks))) return rc;
     if (!tiers) {
-        // one launch for the classes of up to 64 marks (32 beside the wide units), nothing handed on
-        if (wide_list && !gate_forks) {
-            HIP_TRY(ctx, hipEventRecord(ctx->cl_join[1], st));
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->cl_side[1], ctx->cl_join[1], 0));
-        }
-        p.fast_classes = wide_all ? 0u : 15u;
-        p.box_done_flag = (wide_list && gate_forks) ? ctx->cl_flags + 8 : nullptr;
-        if (wide_list) hipLaunchKernelGGL(cl_fast_all<false>, dim3(gridw), dim3(64), 0, st, p, (const uint32_t *)lists, (const uint32_t *)cnts);
-        else hipLaunchKernelGGL(cl_fast_all<true>, dim3(gridw), dim3(64), 0, st, p, (const uint32_t *)lists, (const uint32_t *)cnts);
-        if (wide_list) {
-            // the listed partitions of 33..64 marks on a side stream of their own: behind cl_box (cl_fast_all's first workgroup says when that
-            // is), beside cl_fast_all and the partitions of more than 64
-            if (gate_forks) hipLaunchKernelGGL(cl_gate, dim3(1), dim3(64), 0, ctx->cl_side[1], (const uint32_t *)(ctx->cl_flags + 8), epoch);
-            const uint32_t gwl = std::min(8192u, std::max(256u, M / 512u));
-            hipLaunchKernelGGL(cl_wide_list, dim3(gwl), dim3(256), 0, ctx->cl_side[1], p, (const uint32_t *)lists, (const uint32_t *)cnts, 0u);
-            if (gate_forks) hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, ctx->cl_side[1], ctx->cl_flags + 12, epoch);
-            else HIP_TRY(ctx, hipEventRecord(ctx->cl_join[2], ctx->cl_side[1]));
-        }
+        // one launch for the classes of up to 64 marks, nothing handed on
+        hipLaunchKernelGGL(cl_fast_all, dim3(gridw), dim3(64), 0, st, p, (const uint32_t *)lists, (const uint32_t *)cnts);
     } else if (small) {
         hipLaunchKernelGGL(cl_tight_all, dim3(gridw), dim3(64), 0, st, p, lists, (const uint32_t *)cnts, over);
     } else {
@@ -3450,12 +3393,11 @@ int cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_cluste
     }
     // what they handed on
     if (tiers) hipLaunchKernelGGL(cl_tier2_all, dim3(std::min(gridw, 2048u)), dim3(64), 0, st, p, (const uint32_t *)lists, (const uint32_t *)over, small ? 1u : 0u);
-    if (!small || (wide_list && !gate_forks)) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->cl_join[2], 0));
+    if (!small) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->cl_join[2], 0));
     // (the join inside cl_pc_sums: its waiting workgroups hold wave slots -- up to M / 2048 workgroups of four wavefronts when every mark is a partition of its
     // own -- so only up to 2 M marks, where they cannot take more than half of the chip's from the side stream's kernels; beyond, a one-lane gate kernel)
-    const bool join_in_sums = gate_forks && !wide_list && M <= (2u << 20);
-    if (gate_forks && wide_list) hipLaunchKernelGGL(cl_gate2, dim3(1), dim3(64), 0, st, (const uint32_t *)(ctx->cl_flags + 4), (const uint32_t *)(ctx->cl_flags + 12), epoch);
-    else if (gate_forks && !join_in_sums) hipLaunchKernelGGL(cl_gate, dim3(1), dim3(64), 0, st, (const uint32_t *)(ctx->cl_flags + 4), epoch);
+    const bool join_in_sums = gate_forks && M <= (2u << 20);
+    if (gate_forks && !join_in_sums) hipLaunchKernelGGL(cl_gate, dim3(1), dim3(64), 0, st, (const uint32_t *)(ctx->cl_flags + 4), epoch);
     else if (!gate_forks) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->cl_join[0], 0));
     // clusters per partition -> their sums per 64 and per 2048 partitions (cl_emit numbers the candidates from them); with gate forks the launch is
     // also the join of the side stream

@@ -224,7 +224,7 @@ struct Params {
     uint32_t ctg_small[kSmallK + 1];  //   (scalar loads instead of a dependent HBM round trip)
     const uint32_t *dyn_c;            // device-planned runs (DYN kernels): the candidate count lives on the device, C is an upper bound
     const uint16_t *cand_contig;      // ... and, when the plan came from the candidates' contig column, that column (else null)
-    uint32_t dbg;                     // diagnostic ablation bits (0 in production)
+    uint32_t dbg;                     // diagnostic DUET_DBG_* bits (0 in production)
     uint32_t heavy_t;                 // ef_classify: candidates with more marks than this leave the lanes' serial walk for the wave-cooperative one
     unsigned long long *stamps;       // diagnostic build only: [kernel][block][8] wall-clock stamps
 };
@@ -243,7 +243,7 @@ struct CandState {
     // is the whole vote (:74-84) and its PS is also the last voter's PS (:77); with several PS it feeds :85-105.
     uint32_t ps_a = kEmpty, ps_b = kEmpty, n_a = 0, n_b = 0, nv = 0;
     uint32_t a1 = 0, a2 = 0, b1 = 0, b2 = 0;  // hap-1 / hap-2 counts per group
-    uint32_t ta1 = 0, ta2 = 0, tb1 = 0, tb2 = 0;   // PC sums; A's are per-chunk partials folded into TA1/TA2
+    uint32_t tb1 = 0, tb2 = 0;     // PC sums of group B (group A's: TA1 / TA2)
     uint64_t TA1 = 0, TA2 = 0;
     bool more = false;
 
@@ -251,36 +251,9 @@ struct CandState {
     __device__ __forceinline__ uint32_t seed() const { return ps_a; }        // kEmpty when nobody voted
 };
 
-// thread walks marks [lo, hi) of its candidate; tags of mark m sit at s_tag[m - cs].
-// An absent mark is the all-ones word: its "ps" is kEmpty and its "pc" 2^30-1, so it is neither a new PS nor a voter
-// without a separate test.
-__device__ __forceinline__ void consume_range_r4(CandState &st, const uint64_t *s_tag, uint32_t lo, uint32_t hi, uint32_t cs)
-{
-    for (uint32_t m = lo; m < hi; ++m) {
-        const uint64_t tag = s_tag[m - cs];
-        const uint32_t ps = (uint32_t)tag, w = (uint32_t)(tag >> 32);
-        const uint32_t pc = w & 0x3FFFFFFFu, hap = w >> 30;
-        const bool voter = pc <= kPcMax;
-        st.first_ps = st.first_ps == kEmpty ? ps : st.first_ps;
-        st.multi = st.multi || (ps != st.first_ps && ps != kEmpty);
-        st.nv += voter;
-        st.ps_a = (voter && st.ps_a == kEmpty) ? ps : st.ps_a;
-        const bool in_a = voter && ps == st.ps_a;
-        const bool rest = voter && !in_a;
-        st.ps_b = (rest && st.ps_b == kEmpty) ? ps : st.ps_b;
-        const bool in_b = rest && ps == st.ps_b;
-        st.more = st.more || (rest && !in_b);
-        const bool is1 = hap == 1, is2 = hap == 2;
-        st.n_a += in_a; st.n_b += in_b;
-        st.a1 += in_a && is1; st.a2 += in_a && is2;
-        st.b1 += in_b && is1; st.b2 += in_b && is2;
-        st.ta1 += (in_a && is1) ? pc : 0u; st.ta2 += (in_a && is2) ? pc : 0u;
-        st.tb1 += (in_b && is1) ? pc : 0u; st.tb2 += (in_b && is2) ? pc : 0u;
-    }
-    st.TA1 += st.ta1; st.TA2 += st.ta2; st.ta1 = 0; st.ta2 = 0;
-}
-
-// The same walk with a shorter body (round 5; the counters put the vector units at 80 % busy and the walk at 18 x 35 of a wave's 1,012
+// Thread walks marks [lo, hi) of its candidate; tags of mark m sit at s_tag[m - cs].  An absent mark is the all-ones word: its "ps"
+// is kEmpty and its "pc" 2^30-1, so it is neither a new PS nor a voter without a separate test.
+// Round 5 shortened round 4's loop body (the counters put the vector units at 80 % busy and the walk at 18 x 35 of a wave's 1,012
 // vector instructions, and every restructuring with control flow in it lost -- so: the same straight line, fewer instructions).
 //   * haplotype 1 / 2 as ONE signed compare each on the tag's upper word (hap | pc): hap 1 <=> (int)w >= 0x40000000,
 //     hap 2 <=> (int)w < -0x40000000 -- no shift;
@@ -290,7 +263,7 @@ __device__ __forceinline__ void consume_range_r4(CandState &st, const uint64_t *
 //     wavefront's), a PC that counts is at most 8100, so count < 2^8 and sum < 2^21 share a word and ONE select + ONE add replace an
 //     add-with-carry, a select and an add -- four times;
 //   * the marks are walked by LDS address, not by index + address.
-// Exact: the same integers come out (tests force this walk, round 4's, and the wavefront's on every candidate).
+// Exact: the oracle's integers come out (tests force this walk and the wavefront's on every candidate).
 // (the three vector instructions the walk is made of besides compares, min / max and adds -- spelled out, with the predicate as the
 // lane mask it is: written in C++ the compiler issues a second compare for every negated predicate and a select + add for every
 // "counter += predicate")
@@ -532,7 +505,7 @@ __device__ __forceinline__ uint32_t decide_store(const Params &p, TileShared &sh
                 int pred = (p.dbg & DUET_DBG_EF_FP_DECIDE) ? 0 : decide01_int((int)n_ps, v, deg, svread, refread, need_fp);
                 need_fp = need_fp || (p.dbg & DUET_DBG_EF_FP_DECIDE) != 0;
                 if (need_fp) pred = decide((int)n_ps, v, deg, svread, refread);
-                code = (p.dbg & 2) ? 0 : (uint8_t)pred;
+                code = (uint8_t)pred;
                 ps_out = st.ps_a == kEmpty ? 0u : st.ps_a;                // class 1: the single PS = last voter's PS (:77)
                 if (n_ps == 0 || (st.a1 == 0 && st.a2 == 0)) code |= kNeedNearest;                 // :106
             }
@@ -540,7 +513,6 @@ __device__ __forceinline__ uint32_t decide_store(const Params &p, TileShared &sh
         p.out_pred[c] = code;
         p.out_ps[c] = ps_out;
     }
-    if (p.dbg & 1) want_seed = false;
     return want_seed ? st.seed() : kEmpty;
 }
 
@@ -729,13 +701,12 @@ __global__ __launch_bounds__(kCandPerBlock, 6) void ef_classify(const Params p)
             // ---- consume: each thread walks its candidate's part of this chunk ----------------------
             uint32_t lo = max(my_b, cs);
             const uint32_t hi = min(my_e, cs + (uint32_t)kChunk);
-            if (!kept || (p.dbg & 4)) lo = hi;
+            if (!kept) lo = hi;
             // candidates with more marks than heavy_t: the wavefront walks them together, 64 marks per step, after the lanes
             // have walked the others side by side
             const bool heavy = lo < hi && my_e - my_b > min(p.heavy_t, 255u);      // (the lane walk packs counts into bytes)
             unsigned long long hm = __ballot(heavy);
-            if (p.dbg & DUET_DBG_EF_WALK_R4) consume_range_r4(st, s_tag, heavy ? hi : lo, hi, cs);
-            else consume_range(st, s_tag, heavy ? hi : lo, hi, cs);
+            consume_range(st, s_tag, heavy ? hi : lo, hi, cs);
             while (hm) {
                 const uint32_t h = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)__ffsll((long long)hm) - 1u));
                 hm &= hm - 1ull;
@@ -1807,12 +1778,9 @@ __device__ __noinline__ uint32_t own_insert_slow(uint32_t *s_tab, uint32_t key, 
 
 constexpr uint32_t kOwnWin = 64;                   // seeds strictly inside the tile's range of asking positions that are kept as a list
 
-// DYN: the device-planned run of the fused clustered + phased pipeline -- the candidate count and the contig offsets exist on the
-// device only (the grid strides over the real tiles; the offsets, K + 1 <= 65 words, come into LDS once per workgroup)
-template <bool DYN>
+// host-planned runs only: one tile per workgroup
 __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
 {
-    __shared__ uint32_t s_coff[kSmallK + 1];
     __shared__ uint32_t s_tab[kOwnTab];                        // the hash set of the contig's seeds
     __shared__ uint32_t s_key[kOwnKeys];                       // (rare path) the distinct seeds, compacted, then in sorted blocks of 64
     __shared__ uint32_t s_one[kOwnKeys];                       // (rare path) ... ascending
@@ -1825,15 +1793,11 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     STAMP(2, 0);
     if (blockIdx.x == 0 && tid == 0) p.status[1] = 0;          // the summary pool's counter, for the next run's ef_classify
-    const uint32_t n_cands = DYN ? *p.dyn_c : p.C;
-    const uint32_t nK = DYN ? p.K : p.n_small;
-    if (DYN) {
-        if (tid <= nK) s_coff[tid] = p.ctg_off[tid];
-        __syncthreads();
-    }
-    // contig k's first candidate: out of the kernel arguments (host-planned: scalar loads, no memory) or out of LDS
-    auto coff = [&](uint32_t kk) -> uint32_t { return DYN ? s_coff[kk] : p.ctg_small[kk]; };
-  for (uint32_t tile = blockIdx.x; (uint64_t)tile * 256u < n_cands; tile += gridDim.x) {
+    const uint32_t n_cands = p.C;
+    const uint32_t nK = p.n_small;
+    // contig k's first candidate: out of the kernel arguments (scalar loads, no memory)
+    auto coff = [&](uint32_t kk) -> uint32_t { return p.ctg_small[kk]; };
+    const uint32_t tile = blockIdx.x;
     const uint32_t c0 = tile * 256u, c = c0 + tid;
     const bool live = c < n_cands;
     const uint32_t last = min(c0 + 255u, n_cands - 1);
@@ -2106,8 +2070,6 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
         STAMP(2, 6);
         __syncthreads();                                                    // the set is reused
     }
-    if (!DYN) break;
-  }
 }
 
 // plan time: ctg_start[c] = 1 for the first candidate of every non-empty contig
@@ -2437,7 +2399,7 @@ int duet_ef_run_device(duet_ctx *ctx, const duet_ef_problem *pr, uint8_t *out_pr
     else
         hipExtLaunchKernelGGL(ef_classify<false>, dim3(blocks), dim3(kCandPerBlock), 0, stream, ev[0], ev[1], 0, p);
     if (own) {
-        hipExtLaunchKernelGGL(ef_finalize_own<false>, dim3(blocks), dim3(256), 0, stream, ev[4], ev[5], 0, p);
+        hipExtLaunchKernelGGL(ef_finalize_own, dim3(blocks), dim3(256), 0, stream, ev[4], ev[5], 0, p);
         ctx->ef_last_params.assign((const unsigned char *)&p, (const unsigned char *)&p + sizeof(p));
         ctx->ef_last_stream = stream;
         ctx->ef_seeds_stale = true;
@@ -2445,7 +2407,7 @@ int duet_ef_run_device(duet_ctx *ctx, const duet_ef_problem *pr, uint8_t *out_pr
         ctx->ef_seeds_stale = false;
         hipExtLaunchKernelGGL(ef_seed_sort, dim3(pr->n_contigs), dim3(kSortThreads), 0, stream, ev[2], ev[3], 0, p);
         // Tiles per workgroup: the per-workgroup costs (launch, the tile's contigs, the seeds into LDS) once per 512 / 1024
-        // candidates where there are enough of them to fill the chip anyway -- measured (tools/gpu/r4_fin.sh), 1 / 2 / 4 tiles:
+        // candidates where there are enough of them to fill the chip anyway -- measured (round 4), 1 / 2 / 4 tiles:
         // 1e5 candidates 6.3 / 8.5 / 11.2 us, 2e6 20.6 / 18.4 / 18.8 us, 2e7 127 / 91 / 75 us
         const uint32_t C = pr->n_cands;
         int tpb = (!p.n_small || C < 1000000u) ? 1 : (C < 8000000u ? 2 : 4);
@@ -2549,22 +2511,16 @@ int duet_ef_run_planned_on_device(duet_ctx *ctx, const duet_ef_problem *pr, uint
         hipLaunchKernelGGL((ef_classify<true, true>), dim3(G), dim3(kCandPerBlock), 0, stream, p);
     else
         hipLaunchKernelGGL((ef_classify<false, true>), dim3(G), dim3(kCandPerBlock), 0, stream, p);
-    // The own-set finalize (ef_finalize_own) is NOT taken here by default: stage A0 hands its candidates over by type, then position,
+    // The own-set finalize (ef_finalize_own) is not taken here: stage A0 hands its candidates over by type, then position,
     // and a tile of a sparse type (DUP, INV: a percent of the candidates each) spans a quarter of the contig and carries a hundred
     // seed entries that EVERY tile then reads -- measured on configs[1]'s marks: 35.6 us against 34.3 for E/F alone, 270.9 against
-    // 269.1 us for the pipeline (in position order the same candidates take 23.4 against 28.8).  DUET_DBG_EF_OWN_ALL takes it
-    // (tests/test_gpu_fused.py runs the pipeline both ways).
-    const uint32_t three = DUET_DBG_EF_OWN_OFF | DUET_DBG_EF_FIN_TPB2 | DUET_DBG_EF_FIN_TPB4 | DUET_DBG_EF_NO_SEED_HASH;
-    if (K <= (uint32_t)kSmallK && !(ctx->dbg & three) && (ctx->dbg & DUET_DBG_EF_OWN_ALL)) {
-        hipLaunchKernelGGL(ef_finalize_own<true>, dim3(G), dim3(256), 0, stream, p);
-    } else {
+    // 269.1 us for the pipeline (in position order the same candidates take 23.4 against 28.8).
     hipLaunchKernelGGL(ef_seed_sort, dim3(K), dim3(kSortThreads), 0, stream, p);
     // (two tiles per workgroup where the bound says millions of candidates: the per-workgroup round trips once per 512)
     if (d_cand_contig && (C >= 8000000u || (ctx->dbg & DUET_DBG_EF_FIN_TPB2)))
         hipLaunchKernelGGL((ef_finalize<true, 2>), dim3(G), dim3(256), 0, stream, p);
     else
         hipLaunchKernelGGL(ef_finalize<true>, dim3(G), dim3(256), 0, stream, p);
-    }
     HIP_TRY(ctx, hipGetLastError());
     ctx->pending_check = true;
     return DUET_OK;

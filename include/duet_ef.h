@@ -136,26 +136,25 @@ DUET_API int duet_ef_run_host(duet_ctx *ctx, const duet_ef_problem *prob, uint8_
  * collect into *stats, and reset. */
 DUET_API int duet_ef_profile_collect(duet_ctx *ctx, duet_ef_stats *stats);
 
-/* Diagnostics: low bits ablate E/F kernel phases (tools/ablate.py); DUET_DBG_CLUSTER_EXACT sends every A0
- * partition through the exact linkage instead of the bounding-box / threshold-graph fast paths (the outputs are
- * identical; tests use it to exercise both).  0 in production. */
+/* Diagnostics: each bit forces a kernel path or launch structure other than the one the input would take (the outputs
+ * are identical; tests use them to exercise every path), e.g. DUET_DBG_CLUSTER_EXACT sends every A0 partition through the exact linkage
+ * instead of the bounding-box / threshold-graph fast paths.  0 in production.  The bit values 0x1, 0x2, 0x4,
+ * 0x200000 and 0x10000000 are unused and have no effect. */
 #define DUET_DBG_EF_NO_SEED_HASH 0x40u   /* E/F: ef_seed_sort orders an unsorted seed list itself instead of taking its distinct values through a hash set first */
 #define DUET_DBG_EF_FIN_TPB2 0x20u       /* E/F: ef_finalize takes two tiles of 256 candidates per workgroup whatever the size (default from 1 M candidates on) */
 #define DUET_DBG_EF_FIN_TPB4 0x80u       /* ... four (default from 8 M candidates on) */
 #define DUET_DBG_EF_HEAVY_ALL 0x80000u   /* E/F: ef_classify walks EVERY kept candidate wave-cooperatively (64 marks per step; default: those with more than 32 marks) */
 #define DUET_DBG_EF_HEAVY_OFF 0x100000u  /* ... only those of more than 255 marks (the lane walk keeps its counts in bytes): every other candidate by its own lane, mark after mark */
-#define DUET_DBG_EF_WALK_R4 0x200000u    /* E/F: ef_classify's lane walk with round 4's loop body (35 vector instructions per mark) instead of round 5's shorter one */
 #define DUET_DBG_EF_FP_DECIDE 0x400000u  /* E/F: ef_classify takes every class-0 / class-1 decision through the binary64 expressions (rounds 1-4) instead of the
                                             integer form with the binary64 fallback */
 #define DUET_DBG_EF_OWN_OFF 0x800000u     /* E/F: three launches (ef_classify, ef_seed_sort, ef_finalize) at every size; default up to 1024 tiles of 256 candidates
                                           * and 64 contigs: two -- every finalize tile builds its contig's seed set itself (ef_finalize_own) */
-#define DUET_DBG_EF_OWN_ALL 0x1000000u    /* ... the two launches at every size (up to 64 contigs) */
+#define DUET_DBG_EF_OWN_ALL 0x1000000u    /* ... the two launches at every size (up to 64 contigs; host-planned runs only) */
 #define DUET_DBG_EF_OWN_SMALLTAB 0x2000000u /* ... and their seed set in LDS holds 8 distinct seeds (default 2048): contigs with more take the array-free walk */
 #define DUET_DBG_CLUSTER_EVENT_FORKS 0x4000000u /* A0: the side streams fork off behind hipEventRecord / hipStreamWaitEvent (rounds 1-5) instead of a signal kernel on the
                                           * main stream and a gate kernel on the side stream (round 6) */
 #define DUET_DBG_CLUSTER_WIDE_OFF 0x8000000u /* A0: small inputs keep ONE wavefront per partition of more than 64 marks (rounds 1-5: cl_tight_big + cl_link_one) instead
                                               * of a workgroup of eight (cl_find_big + cl_wide_big: wide_unit) */
-#define DUET_DBG_CLUSTER_WIDE_ALL 0x10000000u /* A0: small inputs send EVERY listed partition through the multi-wavefront units (cl_wide_list; tests: measured, they lose there) */
 #define DUET_DBG_CLUSTER_EXACT 0x100u
 #define DUET_DBG_CLUSTER_LARGE 0x200u   /* A0: take the launch structure of large inputs (> 4 M marks: one launch per size class,
                                            generic tile-offset scan in the sort, scans with a spine launch) whatever the size */

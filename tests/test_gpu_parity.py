@@ -225,7 +225,7 @@ def test_two_ps_everywhere_summary_pool(ctx):
         check_against_c_oracle(ctx, soa, 0, 0)
 
 
-HEAVY_ALL, HEAVY_OFF, WALK_R4, FP_DECIDE = 0x80000, 0x100000, 0x200000, 0x400000     # include/duet_ef.h: DUET_DBG_EF_HEAVY_ALL / _OFF / _WALK_R4 / _FP_DECIDE
+HEAVY_ALL, HEAVY_OFF, FP_DECIDE = 0x80000, 0x100000, 0x400000     # include/duet_ef.h: DUET_DBG_EF_HEAVY_ALL / _OFF / _FP_DECIDE
 
 
 @pytest.mark.parametrize('case', ['fuzz', 'multi_ps', 'two_ps_pool', 'tail', 'cross_chunk', 'config2'])
@@ -259,7 +259,7 @@ def test_wave_cooperative_walk_and_lane_walk_agree(ctx, case):
     else:
         soas = [engine.soa_from_synth(H.case_contigs('config2', 1))]
     for soa in soas:
-        for dbg in (HEAVY_ALL, HEAVY_OFF, 0, WALK_R4, WALK_R4 | HEAVY_OFF, FP_DECIDE, FP_DECIDE | WALK_R4 | HEAVY_OFF):
+        for dbg in (HEAVY_ALL, HEAVY_OFF, 0, FP_DECIDE, FP_DECIDE | HEAVY_OFF):
             ctx.set_debug(dbg)
             try:
                 check_against_c_oracle(ctx, soa)
@@ -343,7 +343,7 @@ def test_decision_on_the_thresholds_integer_and_binary64(ctx):
     assert soa.n_cands > 5000
     rc, want_pred, _ = c_oracle.ef(soa, 50, 2)
     assert rc == 0 and len(set(want_pred.tolist())) == 4           # every outcome occurs
-    for dbg in (0, FP_DECIDE, HEAVY_ALL, WALK_R4):
+    for dbg in (0, FP_DECIDE, HEAVY_ALL):
         ctx.set_debug(dbg)
         try:
             check_against_c_oracle(ctx, soa, 50, 2)
