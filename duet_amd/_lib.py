@@ -28,7 +28,8 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_ef_profile_collect', 'duet_ef_get_seed_ps', 'duet_cluster_run_device', 'duet_cluster_run_host', 'duet_svim_phase_device', 'duet_svim_phase_host', 'duet_rows_run_device',
            'duet_ef_rows_run_host', 'duet_eval_run_host', 'duet_comm_unique_id', 'duet_comm_create', 'duet_comm_allgather_device',
            'duet_comm_allgather_host', 'duet_comm_destroy', 'duet_comm_set_timeout', 'duet_comm_block_bytes',
-           'duet_comm_ef_allgather', 'duet_comm_rccl_version', 'duet_comm_info', 'duet_comm_selftest')
+           'duet_comm_ef_allgather', 'duet_comm_rccl_version', 'duet_comm_info', 'duet_comm_selftest',
+           'duet_ef_features_device', 'duet_ef_features_host', 'duet_tune_sweep_device', 'duet_tune_sweep_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -86,6 +87,24 @@ class EvalProblem(ctypes.Structure):
 
 class EvalCounts(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ('call_tp', 'base_tp', 'call_gt', 'base_gt', 'call_hp', 'base_hp')]
+
+
+# threshold sweep (include/duet_ef.h, "Threshold sweep"; duet_amd/tune.py)
+TUNE_NAMES = ('c0_min_sv_num', 'c2_min_sv_ratio', 'c2_max_avgsc_diff', 'c2_min_sv_num', 'c2_min_hap0', 'c1_onehap_sv_ratio_lo',
+              'c1_onehap_sv_ratio_hi', 'c1_hapread_ratio', 'c1_max_avgsc_diff', 'c1_twohap_sv_ratio_1', 'c1_twohap_sv_ratio_2',
+              'c1_max_ref_num', 'c1_twohap_sv_ratio_3', 'c1_max_totsc_ratio')
+TUNE_DEFAULTS = (4.0, 0.72, 1369.5, 3.0, 6.0, 0.24, 0.9, 0.75, 2400.0, 0.3, 0.45, 10.0, 0.75, 9.72)
+FEATURE_DTYPE = np.dtype([('t1', '<u8'), ('t2', '<u8'), ('hap1', '<u4'), ('hap2', '<u4'), ('hap0', '<u4'), ('allhap', '<u4'),
+                          ('deg', '<u4'), ('svread', '<u4'), ('refread', '<u4'), ('ps', '<u4'), ('eligible', 'u1'), ('kept', 'u1'),
+                          ('cls', 'u1'), ('reserved0', 'u1'), ('reserved1', '<u4')])
+COUNTS_NAMES = ('n_calls', 'n_groups', 'call_tp', 'base_tp', 'call_gt', 'base_gt', 'call_hp', 'base_hp', 'n_raise', 'reserved')
+COUNTS_DTYPE = np.dtype([(n, '<u4') for n in COUNTS_NAMES])
+TUNE_IN_CALLS, TUNE_RAISES, TUNE_MATCHED = 0x1000, 0x2000, 0x4000
+
+
+class TuneTruth(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ('n_uid', 'n_groups', 'n_pairs', 'reserved')] + \
+               [(n, ctypes.c_void_p) for n in ('cand_flags', 'cand_group', 'cand_uid', 'cand_pair', 'group_pair_off', 'pair_uid')]
 
 
 class DuetLibraryError(RuntimeError):
@@ -156,6 +175,12 @@ def load():
                                            ctypes.c_uint32, ctypes.c_void_p]
     lib.duet_comm_info.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int)] * 5
     lib.duet_comm_selftest.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+    lib.duet_ef_features_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(EfProblem), ctypes.c_void_p, ctypes.c_void_p]
+    lib.duet_ef_features_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(EfProblem), ctypes.c_void_p]
+    lib.duet_tune_sweep_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                           ctypes.POINTER(TuneTruth), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.duet_tune_sweep_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                         ctypes.POINTER(TuneTruth), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.duet_comm_destroy.restype = None
     lib.duet_comm_destroy.argtypes = [ctypes.c_void_p]
     _lib = lib
@@ -378,6 +403,41 @@ class Context(object):
         if rc:
             self._raise(rc)
         return out
+
+    def features_host(self, soa, svlen_thres, suppread_thres):
+        """duet_ef_features_host -> structured array of FEATURE_DTYPE[C].  Raises ZeroDivisionError where E/F would."""
+        prob, keep = problem_from_arrays(soa, svlen_thres, suppread_thres)
+        out = np.zeros(soa.n_cands, dtype=FEATURE_DTYPE)
+        rc = self.lib.duet_ef_features_host(self.handle, ctypes.byref(prob), _ptr(out))
+        del keep
+        if rc:
+            self._raise(rc)
+        return out
+
+    def sweep_host(self, feat, vectors, truth=None, want_pred=False, want_ps=False):
+        """duet_tune_sweep_host: feat FEATURE_DTYPE[C], vectors float64[K, 14], truth = dict of the prepared arrays
+        (duet_amd/tune.py: prepare_truth) or None -> (counts COUNTS_DTYPE[K], pred u8[K, C] or None, ps u32[C] or None)"""
+        feat = np.ascontiguousarray(feat, dtype=FEATURE_DTYPE)
+        vec = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1, len(TUNE_NAMES))
+        C, K = len(feat), len(vec)
+        counts = np.zeros(K, dtype=COUNTS_DTYPE)
+        pred = np.zeros((K, C), dtype=np.uint8) if want_pred else None
+        ps = np.zeros(C, dtype=np.uint32) if want_ps else None
+        t, keep = None, []
+        if truth is not None:
+            t = TuneTruth()
+            t.n_uid, t.n_groups, t.n_pairs = int(truth['n_uid']), int(truth['n_groups']), int(truth['n_pairs'])
+            for name, dt in (('cand_flags', np.uint16), ('cand_group', np.uint32), ('cand_uid', np.uint32), ('cand_pair', np.uint32),
+                             ('group_pair_off', np.uint32), ('pair_uid', np.uint32)):
+                a = np.ascontiguousarray(truth[name], dtype=dt)
+                keep.append(a)
+                setattr(t, name, a.ctypes.data if a.size else None)
+        rc = self.lib.duet_tune_sweep_host(self.handle, _ptr(feat), C, _ptr(vec), K, ctypes.byref(t) if t is not None else None,
+                                           _ptr(counts), _ptr(pred), _ptr(ps))
+        del keep
+        if rc:
+            self._raise(rc)
+        return counts, pred, ps
 
     def seed_ps(self, contig, cap=1 << 20):
         out = np.zeros(cap, dtype=np.uint32)

@@ -31,12 +31,21 @@ def pipeline(a):
         (stages.sv_calling, (a.OUTPUT, a.REFERENCE, a.BAM, a.cluster_max_distance, a.sv_min_size, a.thread, a.sv_caller,
                              a.min_support_read)),
         (stages.snp_phasing, (a.OUTPUT, a.REFERENCE, a.BAM, a.thread)),
-        (sv_phasing, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs, a.device, a.gpus)),
+        (sv_phasing, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs, a.device, a.gpus,
+                      a.threshold_vector)),
     )
 
 
 def main(argv):
     a = parse_args(argv)
+    a.threshold_vector = None
+    if a.thresholds is not None:
+        # (additive: the decision's constants from a file -- checked before any stage runs)
+        if a.gpus > 1 or a.sv_caller == 'svim-gpu' or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise SystemExit('duet: --thresholds works on the single-GPU path with an external SV caller only '
+                             '(not with --gpus > 1 or -b svim-gpu)')
+        from duet_amd import tune
+        a.threshold_vector = tune.load_vector(a.thresholds)
     check_envs(a.REFERENCE, a.BAM)
     os.makedirs(a.OUTPUT, exist_ok=True)
     set_logging(a.OUTPUT)

@@ -14,6 +14,19 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// device buffers freed with their owner (hipFree after duet_ctx_destroy's device synchronisation)
+struct DuetOwnedBufs {
+    DevBuf b[16];
+    DuetOwnedBufs() = default;
+    DuetOwnedBufs(const DuetOwnedBufs &) = delete;
+    DuetOwnedBufs &operator=(const DuetOwnedBufs &) = delete;
+    ~DuetOwnedBufs()
+    {
+        for (DevBuf &x : b)
+            if (x.ptr) (void)hipFree(x.ptr);
+    }
+};
+
 struct duet_ctx {
     int device = 0;
     std::string err;
@@ -66,6 +79,7 @@ struct duet_ctx {
     hipStream_t ef_last_stream = nullptr;
     bool ef_seeds_stale = false;
     bool pending_check = false;
+    DuetOwnedBufs tune_ws;                 // threshold sweep (duet_tune.hip): E/F outputs of the feature export, sweep workspace, host-run staging
 };
 
 extern thread_local std::string duet_g_last_error;

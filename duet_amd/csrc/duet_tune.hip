@@ -1,0 +1,550 @@
+// duet_tune.hip -- threshold sweep: per-candidate feature export and the T1-T5 tree of predict_hp
+// (src/duet/sv_phasing_fn.py:142-183) applied with K threshold vectors at once, scored against a prepared truth set
+// (the counts of src/scripts/evaluation.py:99-159).  ABI and conventions: include/duet_ef.h, "Threshold sweep".
+//
+//   tune_features   one wavefront per candidate: filter (:189-190), PS-class (:191-194), vote (:70-111) against the seed sets
+//                   the E/F kernels of the same context left behind (duet_ef.hip; not changed by this file)
+//   tune_decide     a tile of 256 candidates per workgroup, its features read once, then 32 vectors applied to it; the
+//                   counts go out through integer atomics (wave-aggregated) and per-vector bit sets of truth ids and of
+//                   (phase-set group, truth id) pairs
+//   tune_groups     per (vector, group): the "same" / "flip" choice of :143-148 and the union of the chosen truth ids
+//   tune_popcount   per vector: the sizes of the three truth-id sets
+#include "duet_internal.h"
+
+#include <cmath>
+#include <cstring>
+
+namespace {
+
+constexpr uint32_t kEmpty = 0xFFFFFFFFu;
+constexpr uint64_t kUntagged = ~0ull;
+constexpr int kStage = 1024;                  // tune_features: voter words staged in LDS per pass over a candidate's marks (8 KiB)
+constexpr int kVecPerBlock = 32;              // tune_decide: vectors applied to one tile of candidates
+constexpr size_t kWsBudget = (size_t)256 << 20;   // sweep workspace per batch of vectors
+
+int fail(duet_ctx *ctx, int code, const char *msg) { return duet_fail(ctx, code, msg); }
+
+// the tag word's fields (include/duet_ef.h: DUET_TAG)
+__device__ __forceinline__ uint32_t tg_ps(uint64_t t) { return (uint32_t)t; }
+__device__ __forceinline__ uint32_t tg_pc(uint64_t t) { return (uint32_t)(t >> 32) & 0x3FFFFFFFu; }
+__device__ __forceinline__ uint32_t tg_hap(uint64_t t) { return (uint32_t)(t >> 62); }
+
+__device__ __forceinline__ uint32_t lower_bound(const uint32_t *a, uint32_t n, uint32_t key)
+{
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// sv_phasing_fn.py:107-111 -- the nearest seed, ties to the larger one (n >= 1)
+__device__ __forceinline__ uint32_t nearest_seed(const uint32_t *a, uint32_t n, uint32_t pos)
+{
+    const uint32_t i = lower_bound(a, n, pos);
+    const uint32_t lo = i > 0 ? i - 1 : 0;
+    const uint32_t hi = i < n - 1 ? i : n - 1;
+    const int64_t dl = llabs((int64_t)pos - (int64_t)a[lo]);
+    const int64_t dh = llabs((int64_t)pos - (int64_t)a[hi]);
+    return dl < dh ? a[lo] : a[hi];
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_max64(uint64_t v)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t w = __shfl_xor(v, o);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+struct FeatArgs {
+    uint32_t C, K, n_reads, svlen_thres, suppread_thres;
+    const uint64_t *read_tag;
+    const uint32_t *cand_pos, *cand_svlen, *cand_svread, *cand_refread, *cand_off, *mark_read;
+    const uint8_t *cand_gt_ok;
+    const uint32_t *ctg_off, *n_one, *onebuf;     // the E/F workspace: contig offsets, seed counts, ascending seed arrays
+    duet_tune_feature *out;
+};
+
+// the tag of mark m, kUntagged for a mark whose read has no tag
+__device__ __forceinline__ uint64_t mark_tag(const FeatArgs &a, uint32_t m)
+{
+    const uint32_t r = a.mark_read[m];
+    return (r == kEmpty || r >= a.n_reads) ? kUntagged : a.read_tag[r];
+}
+__device__ __forceinline__ bool is_voter(uint64_t t) { return t != kUntagged && tg_pc(t) <= DUET_PC_MAX; }
+
+// One candidate per workgroup of one wavefront: every walk over the marks goes 64 at a time, so a candidate of any degree and any
+// number of phase sets takes the same code.  The multi-PS winner (:85-105): among voters whose PS is a seed, the PS with the most
+// voters, ties to the one seen first -- i.e. the largest (count, -first index) over the first occurrences.
+__global__ __launch_bounds__(64) void tune_features(const FeatArgs a)
+{
+    __shared__ uint64_t s_w[kStage];
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t c = blockIdx.x; c < a.C; c += gridDim.x) {
+        const uint32_t b = a.cand_off[c], e = a.cand_off[c + 1];
+        const uint32_t svread = a.cand_svread[c], refread = a.cand_refread[c];
+        duet_tune_feature f;
+        memset(&f, 0, sizeof(f));
+        f.deg = e - b;
+        f.svread = svread;
+        f.refread = refread;
+        const bool kept = a.cand_svlen[c] >= a.svlen_thres && svread >= a.suppread_thres && a.cand_gt_ok[c] != 0;
+        f.kept = kept ? 1 : 0;
+        if (kept) {
+            // PS-class: distinct PS among ALL tagged marks (no PC test, :192-194)
+            uint32_t p0 = 0;
+            bool have = false, multi = false;
+            for (uint32_t m0 = b; m0 < e && !multi; m0 += 64) {
+                const uint32_t m = m0 + lane;
+                const uint64_t t = m < e ? mark_tag(a, m) : kUntagged;
+                const bool tagged = t != kUntagged;
+                const uint64_t bal = __ballot(tagged);
+                if (!have && bal) {
+                    p0 = __shfl(tg_ps(t), __ffsll((unsigned long long)bal) - 1);
+                    have = true;
+                }
+                if (have) multi = __any(tagged && tg_ps(t) != p0);
+            }
+            f.cls = multi ? 2 : (have ? 1 : 0);
+            // the contig and its seed set
+            uint32_t lo = 0, hi = a.K;
+            while (hi - lo > 1) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (a.ctg_off[mid] <= c) lo = mid; else hi = mid;
+            }
+            const uint32_t n_seed = a.n_one[lo];
+            const uint32_t *seeds = a.onebuf + a.ctg_off[lo] + lo + 1;
+            if (n_seed) {
+                f.eligible = 1;
+                uint32_t hap1 = 0, hap2 = 0, allhap = 0, ps = 0;
+                uint64_t t1 = 0, t2 = 0;
+                if (f.cls == 1) {                                   // :74-84
+                    for (uint32_t m0 = b; m0 < e; m0 += 64) {
+                        const uint32_t m = m0 + lane;
+                        const uint64_t t = m < e ? mark_tag(a, m) : kUntagged;
+                        if (is_voter(t)) {
+                            if (tg_hap(t) == 1) { ++hap1; t1 += tg_pc(t); }
+                            else if (tg_hap(t) == 2) { ++hap2; t2 += tg_pc(t); }
+                        }
+                    }
+                    hap1 = wave_sum(hap1); hap2 = wave_sum(hap2);
+                    t1 = wave_sum64(t1); t2 = wave_sum64(t2);
+                    allhap = hap1 + hap2;
+                    ps = p0;                                        // every voter carries the one PS
+                } else if (f.cls == 2) {                            // :85-105
+                    uint64_t best = 0;                              // (count << 32) | ~(index of the first occurrence)
+                    for (uint32_t i0 = b; i0 < e; i0 += 64) {
+                        const uint32_t i = i0 + lane;
+                        const uint64_t t = i < e ? mark_tag(a, i) : kUntagged;
+                        const bool voter = is_voter(t);
+                        allhap += voter ? 1u : 0u;
+                        const uint64_t my = voter ? ((1ull << 32) | tg_ps(t)) : 0ull;
+                        const uint32_t ni = n_seed;
+                        bool cand = false;
+                        if (voter) {
+                            const uint32_t at = lower_bound(seeds, ni, tg_ps(t));
+                            cand = at < ni && seeds[at] == tg_ps(t);     // :91
+                        }
+                        if (!__any(cand)) continue;
+                        uint32_t n = 0;
+                        bool first = cand;
+                        for (uint32_t j0 = b; j0 < e; j0 += kStage) {
+                            const uint32_t cnt = e - j0 < (uint32_t)kStage ? e - j0 : (uint32_t)kStage;
+                            __syncthreads();
+                            for (uint32_t jj = lane; jj < cnt; jj += 64) {
+                                const uint64_t u = mark_tag(a, j0 + jj);
+                                s_w[jj] = is_voter(u) ? ((1ull << 32) | tg_ps(u)) : 0ull;
+                            }
+                            __syncthreads();
+                            if (cand)
+                                for (uint32_t jj = 0; jj < cnt; ++jj)
+                                    if (s_w[jj] == my) {
+                                        ++n;
+                                        if (j0 + jj < i) first = false;
+                                    }
+                        }
+                        const uint64_t key = (cand && first) ? (((uint64_t)n << 32) | (uint64_t)(~(i - b))) : 0ull;
+                        const uint64_t w = wave_max64(key);
+                        best = w > best ? w : best;
+                    }
+                    allhap = wave_sum(allhap);
+                    if (best) {
+                        const uint32_t at = b + ~(uint32_t)best;
+                        const uint32_t win = tg_ps(mark_tag(a, at));
+                        for (uint32_t m0 = b; m0 < e; m0 += 64) {
+                            const uint32_t m = m0 + lane;
+                            const uint64_t t = m < e ? mark_tag(a, m) : kUntagged;
+                            if (is_voter(t) && tg_ps(t) == win) {
+                                if (tg_hap(t) == 1) { ++hap1; t1 += tg_pc(t); }
+                                else if (tg_hap(t) == 2) { ++hap2; t2 += tg_pc(t); }
+                            }
+                        }
+                        hap1 = wave_sum(hap1); hap2 = wave_sum(hap2);
+                        t1 = wave_sum64(t1); t2 = wave_sum64(t2);
+                        f.hap0 = allhap - hap1 - hap2;              // only with a winner (:105)
+                        ps = win;
+                    }
+                }
+                if (f.cls == 0 || (hap1 == 0 && hap2 == 0)) ps = nearest_seed(seeds, n_seed, a.cand_pos[c]);   // :106-111
+                f.hap1 = hap1; f.hap2 = hap2; f.allhap = allhap; f.t1 = t1; f.t2 = t2; f.ps = ps;
+            }
+        }
+        if (lane == 0) a.out[c] = f;
+    }
+}
+
+// What the tree compares, in binary64 exactly as Python computes it (:112-139)
+struct Derived {
+    double sv_ratio, hr, diff, totsc, svread, refread, hap0;
+    uint32_t cls;
+    bool onehap, a1pos, t1gt;
+};
+
+__device__ __forceinline__ Derived derive(const duet_tune_feature &f)
+{
+    Derived d;
+    d.cls = f.cls;
+    d.hr = (double)f.allhap / (double)f.deg;                                        // :112
+    const double a1 = f.hap1 > 0 ? (double)f.t1 / (double)f.hap1 : 0.0;             // :113-114
+    const double a2 = f.hap2 > 0 ? (double)f.t2 / (double)f.hap2 : 0.0;             // :115-116
+    d.sv_ratio = (double)f.svread / (double)((uint64_t)f.svread + (uint64_t)f.refread);   // :123
+    const uint64_t lo = f.t1 < f.t2 ? f.t1 : f.t2, hi = f.t1 < f.t2 ? f.t2 : f.t1;
+    d.totsc = lo > 0 ? (double)hi / (double)lo : 0.0;                               // :124-125
+    d.onehap = lo == 0 && hi != 0;                                                  // onehap_totsc != 0, :126-127
+    d.diff = fabs(a2 - a1);                                                         // :132
+    d.svread = (double)f.svread;
+    d.refread = (double)f.refread;
+    d.hap0 = (double)f.hap0;
+    d.a1pos = a1 > 0;
+    d.t1gt = f.t1 > f.t2;
+    return d;
+}
+
+// predict_hp (:142-183) with the constants of vector t
+__device__ __forceinline__ uint32_t decide_vec(const Derived &d, const duet_tune_thresholds &t)
+{
+    uint32_t pred = 0;
+    if (d.cls == 0) {                                                               // :145-147
+        if (d.sv_ratio == 1.0 && d.svread >= t.c0_min_sv_num) pred = 3;
+    } else if (d.cls == 2) {                                                        // :148-155
+        if (d.sv_ratio >= t.c2_min_sv_ratio) {
+            if (d.diff <= t.c2_max_avgsc_diff) { if (d.svread >= t.c2_min_sv_num) pred = 3; }
+            else { if (d.hap0 >= t.c2_min_hap0) pred = 3; }
+        }
+    } else {                                                                        // :156-182
+        const bool gate = (d.hr <= t.c1_hapread_ratio && d.diff <= t.c1_max_avgsc_diff) || d.hr > t.c1_hapread_ratio;
+        if (d.onehap) {
+            if (d.sv_ratio <= t.c1_onehap_sv_ratio_lo) pred = 0;
+            else if (d.sv_ratio <= t.c1_onehap_sv_ratio_hi) { if (gate) pred = d.a1pos ? 1 : 2; }
+            else { if (gate) pred = 3; }
+        } else {
+            if (d.sv_ratio <= t.c1_twohap_sv_ratio_1) pred = 0;
+            else if (d.sv_ratio <= t.c1_twohap_sv_ratio_2) pred = d.refread > t.c1_max_ref_num ? 0 : (d.t1gt ? 1 : 2);
+            else if (d.sv_ratio <= t.c1_twohap_sv_ratio_3) pred = d.totsc <= t.c1_max_totsc_ratio ? 3 : (d.t1gt ? 1 : 2);
+            else pred = 3;
+        }
+    }
+    return pred;
+}
+
+struct SweepArgs {
+    const duet_tune_feature *feat;
+    uint32_t C, v0, nv;                  // this batch: vectors v0 .. v0 + nv
+    const duet_tune_thresholds *vec;
+    duet_tune_counts *counts;            // [K]
+    uint8_t *out_pred;                   // [K * C] or null
+    uint32_t *out_ps;                    // [C] or null (written by the first batch)
+    // truth (has_truth)
+    int has_truth;
+    uint32_t n_groups, n_uid, n_pairs;
+    const uint16_t *flags;
+    const uint32_t *group, *uid, *pair, *group_pair_off, *pair_uid;
+    // workspace of the batch, per vector: gcnt[3 * n_groups] (present, same calls, flip calls), then bit sets of
+    // uw words (tp ids, gt ids, hp ids) and pw words (same pairs, flip pairs)
+    uint32_t *ws;
+    uint32_t ws_words, uw, pw;
+};
+
+__device__ __forceinline__ void set_bit(uint32_t *w, uint32_t i)
+{
+    const uint32_t m = 1u << (i & 31);
+    if (!(__atomic_load_n(&w[i >> 5], __ATOMIC_RELAXED) & m)) atomicOr(&w[i >> 5], m);
+}
+
+// lane 0 of the wave adds the wave's count of `pred` to *dst
+__device__ __forceinline__ void wave_count(uint32_t *dst, bool pred)
+{
+    const uint64_t bal = __ballot(pred);
+    if (bal && (threadIdx.x & 63) == __ffsll((unsigned long long)bal) - 1) atomicAdd(dst, (uint32_t)__popcll(bal));
+}
+
+__global__ __launch_bounds__(256) void tune_decide(const SweepArgs a)
+{
+    __shared__ duet_tune_thresholds s_t[kVecPerBlock];
+    const uint32_t vb0 = blockIdx.y * kVecPerBlock;
+    const uint32_t nvb = a.nv - vb0 < (uint32_t)kVecPerBlock ? a.nv - vb0 : (uint32_t)kVecPerBlock;
+    {
+        const double *src = (const double *)(a.vec + a.v0 + vb0);
+        double *dst = (double *)s_t;
+        for (uint32_t i = threadIdx.x; i < nvb * 14u; i += 256u) dst[i] = src[i];
+    }
+    __syncthreads();
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    const bool live = c < a.C;
+    duet_tune_feature f;
+    if (live) f = a.feat[c];
+    else memset(&f, 0, sizeof(f));
+    const bool elig = live && f.eligible;
+    if (!elig) f.deg = 1;                                        // (no division by zero in derive for the lanes that never decide)
+    const Derived d = derive(f);
+    if (a.out_ps && live && a.v0 == 0 && blockIdx.y == 0) a.out_ps[c] = elig ? f.ps : 0u;
+    uint16_t fl = 0;
+    uint32_t g = 0, u = 0, pr = 0;
+    if (a.has_truth && elig) {
+        fl = a.flags[c];
+        if (fl & DUET_TUNE_IN_CALLS) g = a.group[c];
+        if (fl & DUET_TUNE_MATCHED) { u = a.uid[c]; pr = a.pair[c]; }
+    }
+    for (uint32_t j = 0; j < nvb; ++j) {
+        const uint32_t vb = vb0 + j, v = a.v0 + vb;
+        const uint32_t pred = elig ? decide_vec(d, s_t[j]) : 0u;
+        if (a.out_pred && live) a.out_pred[(size_t)v * a.C + c] = (uint8_t)pred;
+        if (!a.counts) continue;
+        duet_tune_counts *cnt = a.counts + v;
+        if (!a.has_truth) {
+            wave_count(&cnt->n_calls, pred != 0);
+            continue;
+        }
+        const bool call = pred != 0 && (fl & DUET_TUNE_IN_CALLS);
+        if (!__any(call)) continue;
+        wave_count(&cnt->n_calls, call);
+        wave_count(&cnt->n_raise, call && (fl & DUET_TUNE_RAISES));
+        uint32_t *ws = a.ws + (size_t)vb * a.ws_words;
+        uint32_t *gcnt = ws, *tp = ws + 3ull * a.n_groups, *gt = tp + a.uw, *same = gt + 2ull * a.uw, *flip = same + a.pw;
+        if (call) set_bit(gcnt + 3ull * g, 0);
+        const bool hit = call && (fl & DUET_TUNE_MATCHED);
+        wave_count(&cnt->call_tp, hit);
+        const uint32_t hb = hit ? (uint32_t)(fl >> (3 * (pred - 1))) & 7u : 0u;
+        wave_count(&cnt->call_gt, hb & 1u);
+        if (hit) {
+            set_bit(tp, u);
+            if (hb & 1u) set_bit(gt, u);
+            if (hb & 2u) { atomicAdd(gcnt + 3ull * g + 1, 1u); set_bit(same, pr); }
+            if (hb & 4u) { atomicAdd(gcnt + 3ull * g + 2, 1u); set_bit(flip, pr); }
+        }
+    }
+}
+
+// per (vector, group): the labelling with more call ids plus truth ids, ties to "flip" (:143-148); its truth ids into the hp set
+__global__ __launch_bounds__(256) void tune_groups(const SweepArgs a)
+{
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x, vb = blockIdx.y;
+    const bool live = g < a.n_groups;
+    uint32_t *ws = a.ws + (size_t)vb * a.ws_words;
+    uint32_t *gcnt = ws, *hp = ws + 3ull * a.n_groups + 2ull * a.uw, *same = hp + a.uw, *flip = same + a.pw;
+    duet_tune_counts *cnt = a.counts + a.v0 + vb;
+    const bool present = live && gcnt[3ull * g] != 0;
+    wave_count(&cnt->n_groups, present);
+    uint32_t take_c = 0;
+    if (present) {
+        const uint32_t p0 = a.group_pair_off[g], p1 = a.group_pair_off[g + 1];
+        uint32_t sb = 0, fb = 0;
+        for (uint32_t p = p0; p < p1; ++p) {
+            sb += (same[p >> 5] >> (p & 31)) & 1u;
+            fb += (flip[p >> 5] >> (p & 31)) & 1u;
+        }
+        const uint32_t sc = gcnt[3ull * g + 1], fc = gcnt[3ull * g + 2];
+        const bool take_same = (uint64_t)sc + sb > (uint64_t)fc + fb;
+        const uint32_t *bits = take_same ? same : flip;
+        take_c = take_same ? sc : fc;
+        for (uint32_t p = p0; p < p1; ++p)
+            if ((bits[p >> 5] >> (p & 31)) & 1u) set_bit(hp, a.pair_uid[p]);
+    }
+    take_c = wave_sum(take_c);
+    if ((threadIdx.x & 63) == 0 && take_c) atomicAdd(&cnt->call_hp, take_c);
+}
+
+__global__ __launch_bounds__(256) void tune_popcount(const SweepArgs a)
+{
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x, vb = blockIdx.y;
+    const uint32_t *tp = a.ws + (size_t)vb * a.ws_words + 3ull * a.n_groups;
+    uint32_t n[3] = {0, 0, 0};
+    if (w < a.uw)
+        for (int s = 0; s < 3; ++s) n[s] = (uint32_t)__popc(tp[(size_t)s * a.uw + w]);
+    duet_tune_counts *cnt = a.counts + a.v0 + vb;
+    uint32_t *dst[3] = {&cnt->base_tp, &cnt->base_gt, &cnt->base_hp};
+    for (int s = 0; s < 3; ++s) {
+        const uint32_t t = wave_sum(n[s]);
+        if ((threadIdx.x & 63) == 0 && t) atomicAdd(dst[s], t);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int duet_ef_features_device(duet_ctx *ctx, const duet_ef_problem *pr, duet_tune_feature *out, void *stream_)
+{
+    if (!ctx || !pr) return fail(ctx, DUET_ERR_INVALID, "null argument");
+    int rc = duet_ef_validate(ctx, pr);
+    if (rc) return rc;
+    const uint32_t C = pr->n_cands;
+    if (C == 0) return DUET_OK;
+    if (!out) return fail(ctx, DUET_ERR_INVALID, "null feature array");
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf *bp = &ctx->tune_ws.b[0], *bs = &ctx->tune_ws.b[1];
+    if ((rc = duet_reserve(ctx, *bp, C)) || (rc = duet_reserve(ctx, *bs, (size_t)C * 4))) return rc;
+    // E/F itself: the seed sets, and the status the caller gets back
+    if ((rc = duet_ef_run_device(ctx, pr, (uint8_t *)bp->ptr, (uint32_t *)bs->ptr, stream))) return rc;
+    if ((rc = duet_ef_materialise_seeds(ctx))) return rc;
+    FeatArgs a;
+    memset(&a, 0, sizeof(a));
+    a.C = C; a.K = pr->n_contigs; a.n_reads = pr->n_reads;
+    a.svlen_thres = pr->svlen_thres; a.suppread_thres = pr->suppread_thres;
+    a.read_tag = pr->read_tag;
+    a.cand_pos = pr->cand_pos; a.cand_svlen = pr->cand_svlen; a.cand_svread = pr->cand_svread;
+    a.cand_refread = pr->cand_refread; a.cand_off = pr->cand_off; a.mark_read = pr->mark_read; a.cand_gt_ok = pr->cand_gt_ok;
+    a.ctg_off = ctx->d_ctg_off; a.n_one = ctx->d_n_one; a.onebuf = (const uint32_t *)ctx->ws_one.ptr;
+    a.out = out;
+    const uint32_t grid = C < (1u << 20) ? C : (1u << 20);
+    hipLaunchKernelGGL(tune_features, dim3(grid), dim3(64), 0, stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return duet_ef_check(ctx, stream);
+}
+
+int duet_ef_features_host(duet_ctx *ctx, const duet_ef_problem *pr, duet_tune_feature *out)
+{
+    if (!ctx || !pr) return fail(ctx, DUET_ERR_INVALID, "null argument");
+    int rc = duet_ef_validate(ctx, pr);
+    if (rc) return rc;
+    const uint32_t C = pr->n_cands;
+    if (C == 0) return DUET_OK;
+    if (!out) return fail(ctx, DUET_ERR_INVALID, "null feature array");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->own_stream;
+    duet_ef_problem d;
+    if ((rc = duet_ef_upload(ctx, pr, &d, s))) return rc;
+    DevBuf *bf = &ctx->tune_ws.b[2];
+    if ((rc = duet_reserve(ctx, *bf, (size_t)C * sizeof(duet_tune_feature)))) return rc;
+    rc = duet_ef_features_device(ctx, &d, (duet_tune_feature *)bf->ptr, s);
+    if (rc && rc != DUET_ERR_DIV_ZERO) return rc;
+    const std::string msg = ctx->err;
+    HIP_TRY(ctx, hipMemcpy(out, bf->ptr, (size_t)C * sizeof(duet_tune_feature), hipMemcpyDeviceToHost));
+    if (rc) ctx->err = msg;
+    return rc;
+}
+
+int duet_tune_sweep_device(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *vec,
+                           uint32_t n_vec, const duet_tune_truth *truth, duet_tune_counts *counts, uint8_t *out_pred,
+                           uint32_t *out_ps, void *stream_)
+{
+    if (!ctx) return fail(nullptr, DUET_ERR_INVALID, "null context");
+    if (n_cands && !feat) return fail(ctx, DUET_ERR_INVALID, "null feature array");
+    if (n_vec && !vec) return fail(ctx, DUET_ERR_INVALID, "null threshold vectors");
+    if (truth && !counts) return fail(ctx, DUET_ERR_INVALID, "a truth set needs the counts array");
+    if (truth && n_cands && (!truth->cand_flags || !truth->cand_group || !truth->cand_uid || !truth->cand_pair ||
+                             !truth->group_pair_off || (truth->n_pairs && !truth->pair_uid)))
+        return fail(ctx, DUET_ERR_INVALID, "null truth array");
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (counts && n_vec) HIP_TRY(ctx, hipMemsetAsync(counts, 0, (size_t)n_vec * sizeof(duet_tune_counts), stream));
+    if (n_cands == 0 || n_vec == 0) return DUET_OK;
+    SweepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.feat = feat; a.C = n_cands; a.vec = vec; a.counts = counts; a.out_pred = out_pred; a.out_ps = out_ps;
+    size_t per_vec = 0;
+    if (truth) {
+        a.has_truth = 1;
+        a.n_groups = truth->n_groups; a.n_uid = truth->n_uid; a.n_pairs = truth->n_pairs;
+        a.flags = truth->cand_flags; a.group = truth->cand_group; a.uid = truth->cand_uid; a.pair = truth->cand_pair;
+        a.group_pair_off = truth->group_pair_off; a.pair_uid = truth->pair_uid;
+        a.uw = (truth->n_uid + 31) / 32;
+        a.pw = (truth->n_pairs + 31) / 32;
+        per_vec = 3ull * truth->n_groups + 3ull * a.uw + 2ull * a.pw + 1;
+        if (per_vec > 0xFFFFFFFFull) return fail(ctx, DUET_ERR_INVALID, "truth set too large");
+        a.ws_words = (uint32_t)per_vec;
+    }
+    // vectors per batch: what the workspace budget holds (at least one), and what one grid dimension takes
+    uint32_t batch = n_vec;
+    if (per_vec) {
+        const size_t fit = kWsBudget / (per_vec * 4);
+        if (fit < batch) batch = fit ? (uint32_t)fit : 1u;
+    }
+    if (batch > 65535u * kVecPerBlock) batch = 65535u * kVecPerBlock;
+    int rc;
+    if (per_vec && (rc = duet_reserve(ctx, ctx->tune_ws.b[3], (size_t)batch * per_vec * 4))) return rc;
+    a.ws = (uint32_t *)ctx->tune_ws.b[3].ptr;
+    const uint32_t tiles = (n_cands + 255) / 256;
+    for (uint32_t v0 = 0; v0 < n_vec; v0 += batch) {
+        const uint32_t nv = n_vec - v0 < batch ? n_vec - v0 : batch;
+        a.v0 = v0; a.nv = nv;
+        if (per_vec) HIP_TRY(ctx, hipMemsetAsync(a.ws, 0, (size_t)nv * per_vec * 4, stream));
+        hipLaunchKernelGGL(tune_decide, dim3(tiles, (nv + kVecPerBlock - 1) / kVecPerBlock), dim3(256), 0, stream, a);
+        if (per_vec) {
+            if (a.n_groups) hipLaunchKernelGGL(tune_groups, dim3((a.n_groups + 255) / 256, nv), dim3(256), 0, stream, a);
+            if (a.uw) hipLaunchKernelGGL(tune_popcount, dim3((a.uw + 255) / 256, nv), dim3(256), 0, stream, a);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return DUET_OK;
+}
+
+int duet_tune_sweep_host(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *vec,
+                         uint32_t n_vec, const duet_tune_truth *truth, duet_tune_counts *counts, uint8_t *out_pred, uint32_t *out_ps)
+{
+    if (!ctx) return fail(nullptr, DUET_ERR_INVALID, "null context");
+    if (n_cands && !feat) return fail(ctx, DUET_ERR_INVALID, "null feature array");
+    if (n_vec && !vec) return fail(ctx, DUET_ERR_INVALID, "null threshold vectors");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->own_stream;
+    DevBuf *B = ctx->tune_ws.b;
+    const size_t C = n_cands, K = n_vec;
+    int rc;
+    // staging: 4 features, 5 vectors, 6 counts, 7 pred, 8 ps, 9.. truth arrays
+    auto up = [&](int i, const void *src, size_t bytes) -> int {
+        int r = duet_reserve(ctx, B[i], bytes ? bytes : 16);
+        if (r) return r;
+        if (bytes && src) HIP_TRY(ctx, hipMemcpyAsync(B[i].ptr, src, bytes, hipMemcpyHostToDevice, s));
+        return DUET_OK;
+    };
+    if ((rc = up(4, feat, C * sizeof(duet_tune_feature))) || (rc = up(5, vec, K * sizeof(duet_tune_thresholds)))) return rc;
+    if (counts && (rc = up(6, nullptr, K * sizeof(duet_tune_counts)))) return rc;
+    if (out_pred && (rc = up(7, nullptr, K * C))) return rc;
+    if (out_ps && (rc = up(8, nullptr, C * 4))) return rc;
+    duet_tune_truth dt;
+    if (truth) {
+        dt = *truth;
+        if ((rc = up(9, truth->cand_flags, C * 2)) || (rc = up(10, truth->cand_group, C * 4)) || (rc = up(11, truth->cand_uid, C * 4)) ||
+            (rc = up(12, truth->cand_pair, C * 4)) || (rc = up(13, truth->group_pair_off, ((size_t)truth->n_groups + 1) * 4)) ||
+            (rc = up(14, truth->pair_uid, (size_t)truth->n_pairs * 4)))
+            return rc;
+        dt.cand_flags = (const uint16_t *)B[9].ptr; dt.cand_group = (const uint32_t *)B[10].ptr;
+        dt.cand_uid = (const uint32_t *)B[11].ptr; dt.cand_pair = (const uint32_t *)B[12].ptr;
+        dt.group_pair_off = (const uint32_t *)B[13].ptr; dt.pair_uid = (const uint32_t *)B[14].ptr;
+    }
+    rc = duet_tune_sweep_device(ctx, (const duet_tune_feature *)B[4].ptr, n_cands, (const duet_tune_thresholds *)B[5].ptr, n_vec,
+                                truth ? &dt : nullptr, counts ? (duet_tune_counts *)B[6].ptr : nullptr,
+                                out_pred ? (uint8_t *)B[7].ptr : nullptr, out_ps ? (uint32_t *)B[8].ptr : nullptr, s);
+    if (rc) return rc;
+    if (counts && K) HIP_TRY(ctx, hipMemcpyAsync(counts, B[6].ptr, K * sizeof(duet_tune_counts), hipMemcpyDeviceToHost, s));
+    if (out_pred && K * C) HIP_TRY(ctx, hipMemcpyAsync(out_pred, B[7].ptr, K * C, hipMemcpyDeviceToHost, s));
+    if (out_ps && C) HIP_TRY(ctx, hipMemcpyAsync(out_ps, B[8].ptr, C * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return DUET_OK;
+}
+
+}  // extern "C"

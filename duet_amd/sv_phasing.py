@@ -10,7 +10,8 @@ fields ...) and the Python path then takes over, so the observable behaviour is 
 Set DUET_NATIVE_INGEST=0 to force the Python path; DUET_DEVICE_ROWS=0 keeps the native path but formats the rows on
 the host instead of on the device.
 
-Two additive keyword arguments (upstream's five positionals are unchanged): `device` = HIP device index of a
+Three additive keyword arguments (upstream's five positionals are unchanged): `thresholds` = a vector of the decision's
+T1-T5 constants (duet_amd/tune.py; native single-GPU path only), `device` = HIP device index of a
 single-GPU run, `gpus` = N > 1 shards the contigs over N GPUs of the node, one process per GPU
 (duet_amd/multi.py: longest-processing-time-first on mark counts, the three kernels per rank, ONE all-gather of the
 (pred, ps) records over RCCL, rank 0 writes phased_sv.vcf).
@@ -90,16 +91,49 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
     return True
 
 
-def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, device=0, gpus=1):
+def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, vec):
+    """The native path with the decision's constants taken from `vec` (duet_amd/tune.py): ingest, the feature export, a sweep
+    of one vector that keeps its (pred, ps), the rows."""
+    from duet_amd import tune
+    ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf)
+    if ing is None:
+        raise RuntimeError('--thresholds needs the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
+    try:
+        write_header(ing, include_all_ctgs, out_vcf)
+        log_ingest(ing, chrom_list)
+        logging.info('integrate read weight information')
+        logging.info('calculate read weight statistics')
+        logging.info('predict SV haplotypes in the callset')
+        logging.info('  thresholds: ' + ', '.join('%s=%r' % (n, float(v)) for n, v in zip(tune.NAMES, vec)))
+        body = b''
+        if ing.soa.n_cands:
+            feat = ctx.features_host(ing.soa, svlen_thres, suppread_thres)
+            pred, ps = tune.apply(dict(feat=feat), vec, ctx=ctx)
+            body = ing.emit_rows(pred, ps)
+        logging.info('write phased callset into .vcf file')
+    finally:
+        ing.close()
+    with open(out_vcf, 'ab') as out:
+        out.write(body)
+
+
+def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, device=0, gpus=1, thresholds=None):
     logging.info('%s SV PHASING STARTED %s' % (_BAR, _BAR))
     t0 = time.time()
     caller_vcf = home + '/sv_calling/variants.vcf'
     out_vcf = home + '/phased_sv.vcf'
     logging.info('create output .vcf file')
     done = False
+    if thresholds is not None:
+        # (additive: T1-T5 constants of the caller's own, duet_amd/tune.py -- single GPU, native ingest only)
+        if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise ValueError('thresholds: single-GPU path only')
+        _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf,
+                           engine.default_context(int(device)), thresholds)
+        done = True
     # (DUET_FORCE_RANKS=1: the one-process-per-GPU path even with one GPU -- rank 0 of 1 over RCCL; tests use it to take the
     # collective through the real backend on a one-GPU box)
-    if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+    if not done and (int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1'):
         from duet_amd import multi
         done = multi.sv_phasing_sharded(home, svlen_thres, suppread_thres, thread, include_all_ctgs, int(gpus))
     if not done:

@@ -46,6 +46,9 @@ def build_parser():
     ap.add_argument('--device', type=int, default=0, help='HIP device index for SV phasing [%(default)s]')
     ap.add_argument('--gpus', type=int, default=1,
                     help='number of GPUs for SV phasing: contigs are sharded over them, one process per GPU [%(default)s]')
+    ap.add_argument('--thresholds', type=str, default=None,
+                    help='JSON object of T1-T5 threshold values (duet_amd/tune.py names; the others keep their defaults) for the '
+                         'SV phasing decision; single-GPU native path only')
     for name, text in _POSITIONALS:
         ap.add_argument(name, type=str, help=text)
     return ap

@@ -343,6 +343,97 @@ typedef struct duet_eval_counts {
 DUET_API int duet_eval_run_host(duet_ctx *ctx, const duet_eval_problem *prob, duet_eval_counts *counts);
 
 /* ---------------------------------------------------------------------------------------------
+ * Threshold sweep (duet_tune.hip): the T1-T5 tree of predict_hp (src/duet/sv_phasing_fn.py:142-183) with its constants
+ * replaced by a vector of binary64 values, applied to K vectors at once and scored against a truth set.
+ *
+ * duet_tune_thresholds: 14 binary64 fields in this fixed order, each named after the reference line it replaces; the
+ * defaults (DUET_TUNE_DEFAULTS) are the reference's constants.  Every comparison is the reference's, made in binary64 on
+ * the binary64 features Python computes (hapread_ratio = allhap / deg, a1, a2, sv_ratio, totsc_ratio; an integer compared
+ * with a double converts exactly), so NaN and +-inf behave as Python's <=, >=, > do.  Fixed, not in the vector: the
+ * `sv_ratio == 1` test of :146, the PC cap 8100 and ps_sr (they change classes and seed sets, not the tree) and the dead
+ * `sv_num >= 20` test of :157.
+ * ---------------------------------------------------------------------------------------------------------------------------- */
+typedef struct duet_tune_thresholds {
+    double c0_min_sv_num;           /* 4      :146  sv_num >= . (class 0) */
+    double c2_min_sv_ratio;         /* 0.72   :149  sv_ratio >= . */
+    double c2_max_avgsc_diff;       /* 1369.5 :150  hap_avgsc_diff <= . */
+    double c2_min_sv_num;           /* 3      :151  sv_num >= . */
+    double c2_min_hap0;             /* 6      :154  hap0 >= . */
+    double c1_onehap_sv_ratio_lo;   /* 0.24   :160  sv_ratio <= . */
+    double c1_onehap_sv_ratio_hi;   /* 0.9    :162  sv_ratio <= . */
+    double c1_hapread_ratio;        /* 0.75   :163, :166 all four uses: hapread_ratio <= . / > . */
+    double c1_max_avgsc_diff;       /* 2400   :163, :166  hap_avgsc_diff <= . */
+    double c1_twohap_sv_ratio_1;    /* 0.3    :169  sv_ratio <= . */
+    double c1_twohap_sv_ratio_2;    /* 0.45   :171  sv_ratio <= . */
+    double c1_max_ref_num;          /* 10     :172  ref_num > . */
+    double c1_twohap_sv_ratio_3;    /* 0.75   :176  sv_ratio <= . */
+    double c1_max_totsc_ratio;      /* 9.72   :177  totsc_ratio <= . */
+} duet_tune_thresholds;
+#define DUET_TUNE_DEFAULTS {4.0, 0.72, 1369.5, 3.0, 6.0, 0.24, 0.9, 0.75, 2400.0, 0.3, 0.45, 10.0, 0.75, 9.72}
+
+/* One candidate's features (56 bytes), in callset order.  `kept`: the filter of :189-190 holds; `eligible`: kept and the
+ * candidate's contig has a non-empty seed set (:209-210) -- only eligible candidates reach predict_hp.  cls is the PS-class
+ * (0 / 1 / 2, :191-194) of a kept candidate (0 otherwise).  The vote (hap1, hap2, hap0, allhap, t1, t2 = the PC sums, ps = the PS
+ * predict_hp returns) is that of get_phase_info (:70-111) and is filled in for eligible candidates only (0 otherwise); deg is
+ * the mark count, svread / refread the candidate's columns, for every candidate. */
+typedef struct duet_tune_feature {
+    uint64_t t1, t2;
+    uint32_t hap1, hap2, hap0, allhap;
+    uint32_t deg, svread, refread, ps;
+    uint8_t eligible, kept, cls, reserved0;
+    uint32_t reserved1;
+} duet_tune_feature;
+
+/* Runs E/F on the problem (device arrays as for duet_ef_run_device) for its seed sets, then one new kernel writes out[C]
+ * (device).  Synchronises `stream`; returns what duet_ef_check would for the same problem (e.g. DUET_ERR_DIV_ZERO: the records
+ * are written all the same).  _host: host arrays as for duet_ef_run_host, out[C] host. */
+DUET_API int duet_ef_features_device(duet_ctx *ctx, const duet_ef_problem *prob, duet_tune_feature *out, void *stream);
+DUET_API int duet_ef_features_host(duet_ctx *ctx, const duet_ef_problem *prob, duet_tune_feature *out);
+
+/* A truth set prepared for the candidates (host work, once, independent of the thresholds; duet_amd/tune.py): the call a
+ * candidate would be written as, read through the evaluator's own parser, matched once to its nearest truth record
+ * (src/scripts/evaluation.py:99-159).  Per candidate c:
+ *   cand_flags[c]  bit 12: the call is in the evaluator's call list; bit 13: it is, but the truth list of its (contig, type)
+ *                  is empty (upstream raises IndexError when such a call is emitted); bit 14: it matches cand_uid[c];
+ *                  bits 3 (p - 1) + {0, 1, 2}, p = pred 1..3: with that HP the match counts for genotyping / is "same" /
+ *                  is "flip" (:131-142)
+ *   cand_group[c]  the call's phase-set group (< n_groups) when bit 12 is set
+ *   cand_uid[c]    the matched truth id (< n_uid) when bit 14 is set
+ *   cand_pair[c]   dense id (< n_pairs) of the (group, uid) pair when bit 14 is set; pairs are numbered group-major:
+ *                  group g owns pairs group_pair_off[g] .. group_pair_off[g + 1], pair_uid[] gives their truth ids. */
+#define DUET_TUNE_IN_CALLS 0x1000u
+#define DUET_TUNE_RAISES 0x2000u
+#define DUET_TUNE_MATCHED 0x4000u
+typedef struct duet_tune_truth {
+    uint32_t n_uid, n_groups, n_pairs, reserved;
+    const uint16_t *cand_flags;     /* [C] */
+    const uint32_t *cand_group;     /* [C] */
+    const uint32_t *cand_uid;       /* [C] */
+    const uint32_t *cand_pair;      /* [C] */
+    const uint32_t *group_pair_off; /* [n_groups + 1] */
+    const uint32_t *pair_uid;       /* [n_pairs] */
+} duet_tune_truth;
+
+/* Per vector: what evaluation.py:99-159 reduces to its ten numbers.  n_calls = len(callinfo), n_groups = distinct phase-set
+ * groups among the emitted calls, the six set sizes of :100, n_raise = emitted calls for which upstream raises IndexError.
+ * Without a truth set only n_calls is filled in (then: every emitted candidate). */
+typedef struct duet_tune_counts {
+    uint32_t n_calls, n_groups, call_tp, base_tp, call_gt, base_gt, call_hp, base_hp, n_raise, reserved;
+} duet_tune_counts;
+
+/* K vectors over C candidates.  _device: feat[C], vec[K], the truth arrays (truth may be NULL), counts[K] (may be NULL when
+ * truth is NULL), out_pred[K * C] (vector-major, may be NULL) and out_ps[C] (may be NULL; = ps of eligible candidates, else 0,
+ * which is duet_ef_run_device's out_ps) are device memory; *truth itself is host memory.  Asynchronous on `stream` apart from
+ * the workspace (grown, never shrunk; the vectors are processed in batches that fit it).  _host: the same with host arrays;
+ * synchronises. */
+DUET_API int duet_tune_sweep_device(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *vec,
+                                    uint32_t n_vec, const duet_tune_truth *truth, duet_tune_counts *counts, uint8_t *out_pred,
+                                    uint32_t *out_ps, void *stream);
+DUET_API int duet_tune_sweep_host(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *vec,
+                                  uint32_t n_vec, const duet_tune_truth *truth, duet_tune_counts *counts, uint8_t *out_pred,
+                                  uint32_t *out_ps);
+
+/* ---------------------------------------------------------------------------------------------
  * The collective of the contig-sharded path: candidates shard by contig over the GPUs of one node,
  * one process and one context per GPU, and ONE all-gather of fixed-size record blocks reassembles the call set
  * (src/duet/sv_phasing_fn.py:15-18, 195-210: nothing crosses contigs before the final sort at :229).  RCCL over xGMI,
