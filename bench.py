@@ -2,10 +2,16 @@
 # coding=utf-8
 """bench.py -- throughput of Duet's step E/F hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   # started plainly: spawns one process per GPU itself
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   # started plainly: spawns one process per GPU itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch of synthetic input that is already resident in HBM.
+
+A plain run does only what the headline needs: it generates and uploads the input, warms up, times the K steps, writes
+--dump-outputs and prints the line (`metric`, `value`, `unit`, `ms_per_step`, ...; `roofline` too when the timed region
+itself sampled enough ef_classify launches).  Everything else described below -- parity against the C oracle, isolated
+per-kernel times, CPU baselines, the clustered pipeline, the larger sizes and their roofline points, the N > 1 line's
+1-GPU reference and extra points -- runs only with `--full` (about two minutes at N = 1).
 
 N = 1   BASELINE.json configs[1]: one contig, ~1.0 M SV support-read marks, 200 k reads, 100 k candidates
         (duet_amd.synth.bench_contig, seed 1); step = ef_classify -> ef_finalize_own (two launches up to 2048 tiles of 256 candidates and 64 contigs; beyond: ef_classify -> ef_seed_sort -> ef_finalize).  `value` is the phasing
@@ -29,7 +35,7 @@ per-candidate pred and ps a caller receives) as DIR/pred.npy and DIR/ps.npy (see
 Algorithmic bytes: ef_classify 12 B/mark + 22 B/candidate + 8 B/read per launch; the whole
 E/F step B_EF = 12 M + 27 C + 8 R; stage A0 18 B/mark.  Kernel durations come from HIP events on the kernel's own
 dispatch (duet_ctx_set_profiling), recorded inside the timed region.
-`cpu_baseline` times oracle/ef_oracle.c (scalar C port, 1 core) on the same arrays, rank 0, N = 1.
+`cpu_baseline` (--full) times oracle/ef_oracle.c (scalar C port, 1 core) on the same arrays, rank 0, N = 1.
 """
 
 import argparse
@@ -469,49 +475,83 @@ def sharded_run(args, ctx, torch, coll, rank, world, local_rank, one_gpu):
         preheat(ctx, dp, stream, torch)
         dt, prof, gg = timed_steps(ctx, dp, args.steps, args.warmup, world, torch, coll, 1)
         gathered = gg.last_job_blocks()
-        # --- outside the timed region: the pieces on their own ---------------------------------------------------
-        iso = step_kernels_profiled(ctx, dp, stream, torch, n=min(args.steps, 50))
-        n = max(10, min(args.steps, 50))
-        coll.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            dp.run(ctx, stream, 3)
-        torch.cuda.synchronize()
-        t_kern = (time.perf_counter() - t0) / n
-        src = dp.out_blocks[3]
-        dst = torch.empty(world * src.numel(), dtype=torch.uint8, device=src.device)
-        for _ in range(3):
-            coll.all_gather_into_tensor(dst, src)
-        torch.cuda.synchronize()
-        coll.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            coll.all_gather_into_tensor(dst, src)
-        torch.cuda.synchronize()
-        t_gather = (time.perf_counter() - t0) / n
+        if args.full:
+            # --- outside the timed region: the pieces on their own -----------------------------------------------
+            iso = step_kernels_profiled(ctx, dp, stream, torch, n=min(args.steps, 50))
+            n = max(10, min(args.steps, 50))
+            coll.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                dp.run(ctx, stream, 3)
+            torch.cuda.synchronize()
+            t_kern = (time.perf_counter() - t0) / n
+            src = dp.out_blocks[3]
+            dst = torch.empty(world * src.numel(), dtype=torch.uint8, device=src.device)
+            for _ in range(3):
+                coll.all_gather_into_tensor(dst, src)
+            torch.cuda.synchronize()
+            coll.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                coll.all_gather_into_tensor(dst, src)
+            torch.cuda.synchronize()
+            t_gather = (time.perf_counter() - t0) / n
     kms = float(prof.kernel_ms[0])
     ab = classify_bytes(sub)
     mine = {'rank': rank, 'contigs': [int(k) for k in owned[rank]], 'marks': sub.n_marks, 'candidates': sub.n_cands,
             'reads': sub.n_reads, 'ef_classify_ms': kms, 'ef_classify_launches_timed': int(prof.n_profiled_runs),
             'ef_classify_algorithmic_bytes': ab,
             'ef_classify_GBs': ab / (kms * 1e-3) / 1e9 if kms > 0 else 0.0,
-            'ef_classify_frac_of_8TBs': ab / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS if kms > 0 else 0.0,
-            'kernels_us_isolated': {k: round(float(iso.kernel_ms[i]) * 1e3, 2) for i, k in enumerate(('ef_classify', 'ef_seed_sort', 'ef_finalize'))},
-            'kernels_only_ms_per_step': t_kern * 1e3, 'gather_only_us': t_gather * 1e6}
+            'ef_classify_frac_of_8TBs': ab / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS if kms > 0 else 0.0}
+    if args.full:
+        mine.update({'kernels_us_isolated': {k: round(float(iso.kernel_ms[i]) * 1e3, 2) for i, k in enumerate(('ef_classify', 'ef_seed_sort', 'ef_finalize'))},
+                     'kernels_only_ms_per_step': t_kern * 1e3, 'gather_only_us': t_gather * 1e6})
     per_rank = coll.all_gather_object(mine)
     (dt,), _ = coll.reduce_max_sum([dt])
     topo = topology(torch, coll, rank, world, local_rank, one_gpu)
 
     out = None
-    same = None
     if rank == 0:
-        # the merged call set of the LAST timed problem against the C oracle on the unsharded problem
-        c_oracle = cpu_leg()
-        g = gathered.cpu().numpy()
-        got = dist.merge_results(soa, owned, [dist.unpack_block(g[r], n_max, sizes[r]) for r in range(world)])
+        got = None
+        if args.full or args.dump_outputs:
+            # the merged call set of the LAST timed problem
+            g = gathered.cpu().numpy()
+            got = dist.merge_results(soa, owned, [dist.unpack_block(g[r], n_max, sizes[r]) for r in range(world)])
         dumped = dump_outputs(args.dump_outputs, got[0], got[1]) if args.dump_outputs else None
+        slow = max(per_rank, key=lambda r: r['ef_classify_ms'])
+        loads = [r['marks'] for r in per_rank]
+        out = {
+            'metric': METRIC, 'value': soa.n_marks * args.steps / dt, 'unit': 'marks/s', 'n_gpus': world,
+            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True,
+            'scaling': 'strong', 'vs_baseline': None, 'dtype': DTYPE, 'data': 'synthetic',
+            'value_is': VALUE_IS.replace('value_clustered_and_phased', 'extra.fused_clustered_and_phased_sharded.marks_per_s'),
+            'plumbing_test_one_gpu': one_gpu,
+            'config': {'workload': 'BASELINE configs[2]: synthetic whole genome chr1-22,X,Y, %d SV marks / %d candidates / %d '
+                                   'tagged reads in %d contigs, resident in HBM, contigs LPT-sharded over %d GPUs; step = '
+                                   'classify[+seed_sort]+finalize per rank + ONE all-gather of the 5 B/candidate '
+                                   'records per problem (asynchronous, overlapping the next problem\'s kernels)'
+                                   % (soa.n_marks, soa.n_cands, soa.n_reads, soa.n_contigs, world),
+                       'marks': soa.n_marks, 'candidates': soa.n_cands, 'reads': soa.n_reads, 'contigs': soa.n_contigs,
+                       'parallelism': 'contig-sharded x%d (LPT on mark counts)' % world, 'svlen_thres': 50,
+                       'suppread_thres': 2},
+            'dumped_outputs': dumped,
+            'collective': coll.name,
+            'roofline': {'kernel': 'ef_classify', 'bound': 'hbm', 'achieved': slow['ef_classify_GBs'], 'peak': HBM_PEAK_GBS,
+                         'unit': 'GB/s', 'frac': slow['ef_classify_frac_of_8TBs'], 'traffic': None,
+                         'algorithmic_bytes_per_launch': slow['ef_classify_algorithmic_bytes'],
+                         'launch_ms': slow['ef_classify_ms'], 'launches_timed': slow['ef_classify_launches_timed'],
+                         'note': 'the rank whose ef_classify launch is longest (rank %d); every rank is in per_rank' % slow['rank']},
+            'sharding': {'lpt_imbalance_max_over_mean_marks': max(loads) / (sum(loads) / float(world)),
+                         'candidates_per_rank': sizes, 'record_bytes_per_rank': dist.record_bytes(n_max)},
+            'gather': {'collectives_per_problem': 1, 'bytes_contributed_per_rank': dist.record_bytes(n_max)},
+            'per_rank': per_rank,
+            'topology': topo,
+        }
+    if rank == 0 and args.full:
+        # the merged call set against the C oracle on the unsharded problem
+        c_oracle = cpu_leg()
         rc, want_pred, want_ps = c_oracle.ef(soa, 50, 2)
         parity = bool(rc == 0 and np.array_equal(got[0], want_pred) and np.array_equal(got[1], want_ps))
         # the SAME problem on this rank's GPU alone (the other ranks wait at the barrier below): the 1-GPU point of the
@@ -535,42 +575,13 @@ def sharded_run(args, ctx, torch, coll, rank, world, local_rank, one_gpu):
                 'note': 'no collective: one GPU holds the whole call set'}
         del dpf
         torch.cuda.empty_cache()
-        slow = max(per_rank, key=lambda r: r['ef_classify_ms'])
-        loads = [r['marks'] for r in per_rank]
-        out = {
-            'metric': METRIC, 'value': soa.n_marks * args.steps / dt, 'unit': 'marks/s', 'n_gpus': world,
-            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True,
-            'scaling': 'strong', 'vs_baseline': None, 'dtype': DTYPE, 'data': 'synthetic',
-            'value_is': VALUE_IS.replace('value_clustered_and_phased', 'extra.fused_clustered_and_phased_sharded.marks_per_s'),
-            'plumbing_test_one_gpu': one_gpu,
-            'config': {'workload': 'BASELINE configs[2]: synthetic whole genome chr1-22,X,Y, %d SV marks / %d candidates / %d '
-                                   'tagged reads in %d contigs, resident in HBM, contigs LPT-sharded over %d GPUs; step = '
-                                   'classify[+seed_sort]+finalize per rank + ONE all-gather of the 5 B/candidate '
-                                   'records per problem (asynchronous, overlapping the next problem\'s kernels)'
-                                   % (soa.n_marks, soa.n_cands, soa.n_reads, soa.n_contigs, world),
-                       'marks': soa.n_marks, 'candidates': soa.n_cands, 'reads': soa.n_reads, 'contigs': soa.n_contigs,
-                       'parallelism': 'contig-sharded x%d (LPT on mark counts)' % world, 'svlen_thres': 50,
-                       'suppread_thres': 2},
-            'parity_vs_oracle': parity,
-            'dumped_outputs': dumped,
-            'collective': coll.name,
-            'roofline': {'kernel': 'ef_classify', 'bound': 'hbm', 'achieved': slow['ef_classify_GBs'], 'peak': HBM_PEAK_GBS,
-                         'unit': 'GB/s', 'frac': slow['ef_classify_frac_of_8TBs'], 'traffic': None,
-                         'algorithmic_bytes_per_launch': slow['ef_classify_algorithmic_bytes'],
-                         'launch_ms': slow['ef_classify_ms'], 'launches_timed': slow['ef_classify_launches_timed'],
-                         'note': 'the rank whose ef_classify launch is longest (rank %d); every rank is in per_rank' % slow['rank']},
-            'sharding': {'lpt_imbalance_max_over_mean_marks': max(loads) / (sum(loads) / float(world)),
-                         'candidates_per_rank': sizes, 'record_bytes_per_rank': dist.record_bytes(n_max)},
-            'gather': {'collectives_per_problem': 1, 'bytes_contributed_per_rank': dist.record_bytes(n_max),
-                       'us_isolated_max_over_ranks': max(r['gather_only_us'] for r in per_rank),
-                       'kernels_only_ms_per_step_max_over_ranks': max(r['kernels_only_ms_per_step'] for r in per_rank)},
-            'per_rank': per_rank,
-            'topology': topo,
-            'same_problem_on_1_gpu': same,
-            # (what a scaling curve should be read against: the SAME call set on one GPU of this run -- the N = 1 line of
-            # bench.py is BASELINE configs[1], a different workload; its `scaling_point_1gpu` is this problem too)
-            'value_vs_1gpu_same_problem': (soa.n_marks * args.steps / dt) / same['marks_per_s'],
-        }
+        out['parity_vs_oracle'] = parity
+        out['gather'].update({'us_isolated_max_over_ranks': max(r['gather_only_us'] for r in per_rank),
+                              'kernels_only_ms_per_step_max_over_ranks': max(r['kernels_only_ms_per_step'] for r in per_rank)})
+        out['same_problem_on_1_gpu'] = same
+        # (what a scaling curve should be read against: the SAME call set on one GPU of this run -- the N = 1 line of
+        # bench.py is BASELINE configs[1], a different workload; its `scaling_point_1gpu` is this problem too)
+        out['value_vs_1gpu_same_problem'] = (soa.n_marks * args.steps / dt) / same['marks_per_s']
     coll.barrier()
     return out
 
@@ -765,8 +776,9 @@ def compact_line(full, detail_path=None):
         out['gather'] = full['gather']
     if 'per_rank' in full:
         pr = full['per_rank']
-        out['per_rank'] = {'marks': [r.get('marks') for r in pr], 'ef_classify_us': [round(r.get('ef_classify_ms', 0) * 1e3, 2) for r in pr],
-                           'kernels_only_us': [round(r.get('kernels_only_ms_per_step', 0) * 1e3, 2) for r in pr]}
+        out['per_rank'] = {'marks': [r.get('marks') for r in pr], 'ef_classify_us': [round(r.get('ef_classify_ms', 0) * 1e3, 2) for r in pr]}
+        if all('kernels_only_ms_per_step' in r for r in pr):           # (measured with --full only)
+            out['per_rank']['kernels_only_us'] = [round(r['kernels_only_ms_per_step'] * 1e3, 2) for r in pr]
     if 'topology' in full:
         tp = full['topology']
         out['topology'] = _pick(tp, ('backend', 'world_size', 'rccl_version', 'rccl_ranks_seen', 'comm_selftest', 'one_gpu_plumbing_mode', 'distinct_devices'))
@@ -848,7 +860,7 @@ def dump_outputs(out_dir, pred, ps):
 
 
 METRIC = 'SV support-read marks clustered+phased /sec; bit-exact phased_sv.vcf vs ref'
-VALUE_IS = 'phased_only (step E/F on pre-clustered candidates); the literal clustered+phased figure is value_clustered_and_phased'
+VALUE_IS = 'phased_only (step E/F on pre-clustered candidates); the literal clustered+phased figure is value_clustered_and_phased (--full)'
 DTYPE = 'u32/u64 integer + f64 threshold compares'
 
 
@@ -864,19 +876,16 @@ def single_gpu_run(args, ctx, torch):
         preheat_steps = preheat(ctx, dp, stream, torch)
         dt, prof, gg = timed_steps(ctx, dp, args.steps, args.warmup, 1, torch, None, 1)
         last_slot = gg.slot
-        iso = step_kernels_profiled(ctx, dp, stream, torch, n=max(min(args.steps, 100), 50))
+        iso = step_kernels_profiled(ctx, dp, stream, torch, n=max(min(args.steps, 100), 50)) if args.full else None
     pred, ps = dp.results(last_slot)
     dumped = dump_outputs(args.dump_outputs, pred, ps) if args.dump_outputs else None
-    c_oracle = cpu_leg()
-    rc, want_pred, want_ps = c_oracle.ef(soa, 50, 2)
-    parity = bool(rc == 0 and np.array_equal(pred, want_pred) and np.array_equal(ps, want_ps))
 
     kname = _lib.KERNEL_NAMES[0]
     # HIP events on ef_classify's own dispatch: inside the timed region every 8th step carries a pair; with fewer than 16
     # such launches (a short --steps) the serialised loop that follows the region (>= 50 launches, same kernel, same
-    # stream, same arguments) supplies the duration instead
+    # stream, same arguments; --full only) supplies the duration instead
     k_ms, k_n, k_src = float(prof.kernel_ms[0]), int(prof.n_profiled_runs), 'events on every 8th step inside the timed region'
-    if k_n < 16:
+    if k_n < 16 and args.full:
         k_ms, k_n, k_src = float(iso.kernel_ms[0]), int(iso.n_profiled_runs), \
             'events on every launch of the serialised loop right after the timed region (the region held only %d sampled launches)' % k_n
     out = {
@@ -888,7 +897,7 @@ def single_gpu_run(args, ctx, torch):
         'value_is': VALUE_IS,
         'config': {'workload': 'BASELINE configs[1]: synthetic 1 contig, %d SV marks / %d candidates / %d tagged reads, '
                                'resident in HBM; step = ef_classify + ef_finalize_own, two launches (phasing, E/F; ef_seed_sort 0: not launched at this size); the clustered+phased '
-                               'figure for the same marks is value_clustered_and_phased'
+                               'figure for the same marks is value_clustered_and_phased (--full)'
                                % (soa.n_marks, soa.n_cands, soa.n_reads),
                    'marks_per_gpu': soa.n_marks, 'candidates_per_gpu': soa.n_cands, 'reads_per_gpu': soa.n_reads,
                    'parallelism': 'contig-sharded x1', 'svlen_thres': 50, 'suppread_thres': 2,
@@ -896,13 +905,18 @@ def single_gpu_run(args, ctx, torch):
                    'generator_vs_SURVEY_8d': 'marks with no SAM line: 5 % (8d: 20 % of names absent); pc ~ geometric(1/2)*400 + '
                                              'U[0,400), mean ~600, capped at 8100 + 3 % U[8101,20000] (8d: exp mean 600); '
                                              'the reference sha256 in tests/golden/seeded.json pins exactly these inputs'},
-        'parity_vs_oracle': parity,
         'dumped_outputs': dumped,
-        'kernels_us_isolated': {n: round(float(iso.kernel_ms[i]) * 1e3, 2) for i, n in enumerate(_lib.KERNEL_NAMES)},
-        'roofline': roofline_block(kname, soa, k_ms, k_n, k_src,
-                                   note='config 2 is 15.5 MB per launch (~1.9 us at peak): launch-latency bound; '
-                                        'roofline_bandwidth_bound below is the same kernel at 2e8 marks'),
     }
+    if args.full or k_n >= 16:
+        out['roofline'] = roofline_block(kname, soa, k_ms, k_n, k_src,
+                                         note='config 2 is 15.5 MB per launch (~1.9 us at peak): launch-latency bound; '
+                                              'roofline_bandwidth_bound (--full) is the same kernel at 2e8 marks')
+    if not args.full:
+        return out
+    c_oracle = cpu_leg()
+    rc, want_pred, want_ps = c_oracle.ef(soa, 50, 2)
+    out['parity_vs_oracle'] = bool(rc == 0 and np.array_equal(pred, want_pred) and np.array_equal(ps, want_ps))
+    out['kernels_us_isolated'] = {n: round(float(iso.kernel_ms[i]) * 1e3, 2) for i, n in enumerate(_lib.KERNEL_NAMES)}
     if not args.no_extra:
         # the metric read literally: raw marks clustered (A0) AND phased (E/F) in one device pipeline
         fused = fused_point(ctx, torch, engine, synth, [contig])
@@ -965,14 +979,18 @@ def single_gpu_run(args, ctx, torch):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip the larger single-GPU roofline points')
-    ap.add_argument('--no-large', action='store_true', help='skip the 2e8-mark single-GPU point (about a minute of host-side generation)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also check the outputs against the C oracle and measure everything else: isolated '
+                         'per-kernel times, CPU baselines, the clustered pipeline, larger sizes and their roofline points (N = 1), '
+                         'the 1-GPU reference of the same problem and the extra points (N > 1); a plain run does none of it')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip the larger single-GPU roofline points')
+    ap.add_argument('--no-large', action='store_true', help='with --full: skip the 2e8-mark single-GPU point (about a minute of host-side generation)')
     ap.add_argument('--large', action='store_true', help='(default now; kept for round-1 command lines)')
     ap.add_argument('--genome-marks', type=int, default=20000000, help='N > 1: marks of the sharded whole-genome problem')
     ap.add_argument('--collective', choices=('duet', 'torch'), default='duet',
@@ -981,9 +999,14 @@ def main():
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last one computed (per candidate pred and ps) as DIR/<name>.npy')
     ap.add_argument('--launch-dry-run', action='store_true', help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
+
+
+def main():
+    args = parse_args()
 
     from duet_amd import launch
     if args.gpus > 1 and not launch.under_launcher():
@@ -1062,13 +1085,14 @@ def main():
         out = single_gpu_run(args, ctx, torch)
     else:
         out = sharded_run(args, ctx, torch, coll, rank, world, local_rank, one_gpu)
-        if not args.no_extra:
+        if args.full and not args.no_extra:
             weak = weak_grouped_run(args, ctx, torch, coll, rank, world, local_rank)
             fused = fused_sharded_run(args, ctx, torch, coll, rank, world, local_rank)
             if rank == 0:
                 out['extra'] = {'weak_grouped_config2_per_rank': weak, 'fused_clustered_and_phased_sharded': fused}
     if rank == 0:
-        path = write_detail(out, world)
+        # a plain run's record is its line; only --full writes the complete record beside it
+        path = write_detail(out, world) if args.full else None
         os.write(json_fd, (json.dumps(compact_line(out, path)) + '\n').encode())
     os.close(json_fd)
 

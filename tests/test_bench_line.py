@@ -109,3 +109,27 @@ def test_dump_outputs_exact_and_bounded(tmp_path, monkeypatch):
     assert np.array_equal(np.load(str(tmp_path / 'b' / 'ps.npy')), ps[idx].astype(np.float64))
     for f in ('pred.npy', 'ps.npy', 'sample_index.npy'):
         assert np.array_equal(np.load(str(tmp_path / 'b' / f)), np.load(str(tmp_path / 'c' / f)))
+
+
+def test_plain_run_is_the_default():
+    """Everything beyond the headline (oracle checks, isolated kernels, CPU baselines, other sizes) runs only with --full."""
+    a = bench.parse_args(['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 20, 5, False, None)
+    assert bench.parse_args(['--full']).full is True
+
+
+def test_plain_record_line():
+    """A plain run's record has the contract's keys and none of --full's blocks; the line carries it as it is."""
+    full = canned()
+    plain = {k: full[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better',
+                                  'scaling', 'vs_baseline', 'dtype', 'data', 'config')}
+    plain['value_is'] = bench.VALUE_IS
+    back = json.loads(json.dumps(bench.compact_line(plain, None)))
+    assert set(back) == set(plain)
+    for k in ('metric', 'unit', 'higher_is_better', 'dtype', 'steps', 'warmup'):
+        assert back[k] == plain[k], k
+    assert abs(back['value'] / plain['value'] - 1) < 1e-5 and abs(back['ms_per_step'] / plain['ms_per_step'] - 1) < 1e-5
+    # N > 1: per-rank figures without the isolated loops of --full
+    plain['per_rank'] = [{'rank': r, 'marks': 10 + r, 'ef_classify_ms': 0.01} for r in range(2)]
+    back = json.loads(json.dumps(bench.compact_line(plain, None)))
+    assert back['per_rank'] == {'marks': [10, 11], 'ef_classify_us': [10.0, 10.0]}

@@ -225,7 +225,7 @@ def test_bench_self_spawns_and_runs_the_sharded_genome(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
     env['DUET_BENCH_ONE_GPU'] = '1'
     out = subprocess.check_output([sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                                   '--genome-marks', '400000', '--no-extra'], env=env, timeout=600).decode()
+                                   '--genome-marks', '400000', '--full', '--no-extra'], env=env, timeout=600).decode()
     line = [l for l in out.splitlines() if l.startswith('{')][-1]
     assert len(line) < 8000                          # (the driver could not parse round 4's 22.5 kB line)
     d = json.loads(line)

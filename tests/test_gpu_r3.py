@@ -119,7 +119,7 @@ def test_bench_sharded_path_as_one_rank_over_rccl(collective):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
     env['DUET_BENCH_RCCL_SELF'] = '1'
     out = subprocess.check_output([sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2',
-                                   '--genome-marks', '2000000', '--collective', collective], env=env, timeout=900).decode()
+                                   '--genome-marks', '2000000', '--collective', collective, '--full'], env=env, timeout=900).decode()
     line = [l for l in out.splitlines() if l.startswith('{')][-1]
     assert len(line) < 8000
     d = json.loads(line)
