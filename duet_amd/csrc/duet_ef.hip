@@ -577,6 +577,8 @@ __device__ __forceinline__ void seeds_tile(const Params &p, TileShared &sh, uint
 // software pipeline.  The mark array is 16-byte aligned on this path, so an aligned 16-byte load that starts
 // inside it stays inside its last 16-byte granule even when M is not a multiple of 4; lanes past m_end read
 // a harmless in-range address.  stage_gather masks both cases when it finally consumes the indices.
+// (What the compiler makes of it is not that yet: in the gfx950 ISA the first pass's it = 0 load sits in a branch of its own and the
+// gather's `idx < n_reads` compare waits between the first and second index loads -- more than the one trip this intends.)
 __device__ __forceinline__ void stage_load_marks(const Params &p, uint4 (&r)[kStageIt], uint32_t cs, uint32_t m_end, uint32_t tid)
 {
 #pragma unroll
@@ -1509,8 +1511,8 @@ constexpr uint32_t kOwnMaxTiles = 2048;            // (measured, tools/own_sweep
 constexpr uint32_t kOwnTab = 2048;                 // hash-set slots (open addressing; the hash takes the product's top 11 bits)
 constexpr uint32_t kOwnKeys = 1024;                // distinct seeds kept in LDS
 
-// what the array-free walk needs of the kernel's arguments, by value: the walk is a rare path behind a real call, and a call that
-// took the 600-byte argument block by reference would make EVERY launch copy that block to scratch memory first
+// what the array-free walk needs of the kernel's arguments (the walk is a rare path, inlined behind its branch: ef_finalize_own makes
+// no calls and has no stack)
 struct OwnArgs {
     TileRecs recs;
     const uint64_t *seed_ent, *read_tag;
@@ -1566,7 +1568,7 @@ __device__ __forceinline__ void own_each_tag(const OwnArgs &a, uint32_t b, uint3
 }
 
 // one candidate of a contig whose seeds did not fit the LDS set (finalize_candidate's logic, array-free; the contig has seeds)
-__device__ __noinline__ void finalize_candidate_walk(OwnArgs a, uint32_t c, uint32_t code, uint32_t ps_in)
+__device__ __forceinline__ void finalize_candidate_walk(const OwnArgs &a, uint32_t c, uint32_t code, uint32_t ps_in)
 {
     if (code & kDivZero) {
         atomicOr(&a.status[0], 1u);
@@ -1610,9 +1612,10 @@ __device__ __noinline__ void finalize_candidate_walk(OwnArgs a, uint32_t c, uint
                 own_each_tag(a, mb, me, [&](uint64_t u) {
                     if (u == kUntagged || tag_pc(u) > kPcMax || tag_ps(u) != g) return;
                     ++n;
-                    const uint32_t hap = tag_hap(u);
-                    if (hap == 1) { ++n1; s1 += tag_pc(u); }
-                    else if (hap == 2) { ++n2; s2 += tag_pc(u); }
+                    const uint32_t hap = tag_hap(u), pc = tag_pc(u);
+                    // (selects, not a branch: the compiler turned the branch into a select of the counters' addresses -- a stack)
+                    n1 += hap == 1 ? 1u : 0u; s1 += hap == 1 ? pc : 0u;
+                    n2 += hap == 2 ? 1u : 0u; s2 += hap == 2 ? pc : 0u;
                 });
                 done_ps = g;
                 if (n > best) {                                // strict: the first-seen group wins ties (:101)
@@ -1651,7 +1654,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
 // (rare path of ef_finalize_own: candidates out of position order) the hash set's values, ascending, into s_one[0 .. u): compacted,
 // every wavefront orders blocks of 64 in its registers, a value's place is the sum of its lower bounds in all blocks (its own
 // included: the values are distinct) -- ef_seed_sort's scheme.  Every thread of the workgroup calls it.
-__device__ __noinline__ void own_sort_set(const uint32_t *s_tab, uint32_t *s_key, uint32_t *s_one, uint32_t *s_part, uint32_t u)
+__device__ __forceinline__ void own_sort_set(const uint32_t *s_tab, uint32_t *s_key, uint32_t *s_one, uint32_t *s_part, uint32_t u)
 {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     uint32_t mv[kOwnTab / 256u], cnt = 0;
@@ -1707,7 +1710,7 @@ __device__ __noinline__ void own_sort_set(const uint32_t *s_tab, uint32_t *s_key
 
 // (rare path of ef_finalize_own) the multi-PS vote of a candidate without a group summary, straight from its marks (:85-105,
 // class2_from_marks); "is this PS a seed" (:91) from the hash set in LDS
-__device__ __noinline__ void own_vote_from_marks(const uint32_t *mark_read, const uint64_t *read_tag, uint32_t mb, uint32_t me_,
+__device__ __forceinline__ void own_vote_from_marks(const uint32_t *mark_read, const uint64_t *read_tag, uint32_t mb, uint32_t me_,
                                                  const uint32_t *s_tab, Vote *vo, uint32_t *pso)
 {
     auto each = [&](auto f) {                                      // (eight marks' two dependent loads at a time, as for_each_tag)
@@ -1747,9 +1750,9 @@ __device__ __noinline__ void own_vote_from_marks(const uint32_t *mark_read, cons
         each([&](uint64_t u) {
             if (u == kUntagged || tag_pc(u) > kPcMax || tag_ps(u) != g) return;
             ++n;
-            const uint32_t hap = tag_hap(u);
-            if (hap == 1) { ++n1; s1 += tag_pc(u); }
-            else if (hap == 2) { ++n2; s2 += tag_pc(u); }
+            const uint32_t hap = tag_hap(u), pc = tag_pc(u);
+            n1 += hap == 1 ? 1u : 0u; s1 += hap == 1 ? pc : 0u;        // (selects: see finalize_candidate_walk)
+            n2 += hap == 2 ? 1u : 0u; s2 += hap == 2 ? pc : 0u;
         });
         done_ps = g;
         if (n > best) {                                            // strict: the first-seen group wins ties (:101)
@@ -1762,18 +1765,18 @@ __device__ __noinline__ void own_vote_from_marks(const uint32_t *mark_read, cons
     *pso = ps;
 }
 
-// ef_finalize_own's hash set, the probe sequence of `key` from slot h on: 1 when the key is new to the set, 0 when it is there already
-// (or the table is full).  ONE copy of this loop behind a call: inlined at the fourteen places that may need it, it was 2,000 of the
-// hot phase's 2,100 instructions.
-__device__ __noinline__ uint32_t own_insert_slow(uint32_t *s_tab, uint32_t key, uint32_t h)
+// ef_finalize_own's hash set, the probe sequence of `key` from slot h on: true when the key is new to the set, false when it is there
+// already (or the table is full).  Inlined: the kernel makes no calls (a call gives it a stack, and the compiler kept the records
+// that way in scratch memory).  The hot phase has ONE copy of it, after its groups' first probes (see `group`).
+__device__ __forceinline__ bool own_probe(uint32_t *s_tab, uint32_t key, uint32_t h)
 {
     for (uint32_t probes = 0; probes < kOwnTab; ++probes) {
         const uint32_t old = atomicCAS(&s_tab[h], kEmpty, key);
-        if (old == kEmpty) return 1u;
-        if (old == key) return 0u;
+        if (old == kEmpty) return true;
+        if (old == key) return false;
         h = (h + 1u) & (kOwnTab - 1u);
     }
-    return 0u;
+    return false;
 }
 
 constexpr uint32_t kOwnWin = 64;                   // seeds strictly inside the tile's range of asking positions that are kept as a list
@@ -1800,47 +1803,60 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
     const uint32_t tile = blockIdx.x;
     const uint32_t c0 = tile * 256u, c = c0 + tid;
     const bool live = c < n_cands;
+    const uint32_t cl = live ? c : n_cands - 1u;               // (a clamped address: every load of the first trip is unconditional)
     const uint32_t last = min(c0 + 255u, n_cands - 1);
+    const uint32_t keys_cap = (p.dbg & DUET_DBG_EF_OWN_SMALLTAB) ? 8u : kOwnKeys;
+    const uint32_t win_cap = (p.dbg & DUET_DBG_EF_OWN_SMALLTAB) ? 2u : kOwnWin;
+    const TileRecs recs{reinterpret_cast<const ulonglong4 *>(p.blk_rec)};
+    // ONE round trip in front of everything.  It carries the candidate's code, PS, position, mark range and read counts, up to four
+    // tiles' seed records of the tile's first contig, and the tile's own kC2Quota group-summary slots (3.5 KB: the candidates of this
+    // very tile put theirs there) -- whether or not anybody will look at them: what a multi-PS candidate needs (:85-105, :148-155)
+    // would otherwise be a SECOND, dependent trip, as its summary sits at a slot that only its PS word names.  Only a summary in the
+    // shared pool (a tile with more than 64 multi-PS candidates) is fetched once the slot is known.
+    // Every load below is unconditional, at a clamped address, and nothing is looked at before the last one has left: a conditional
+    // load is a branch, and the compiler waits for a load's value where it is first used -- both split the trip into several.
+    // The records stay in registers with constant indices only: a register array indexed at run time lives in scratch memory.
+    constexpr uint32_t kPre = 2;                               // records per thread that leave with the first trip: 512 tiles of a contig
+    static_assert(kPre == 2, "the overflow loop selects between rec[0] and rec[1]");
+    ulonglong4 rec[kPre], ext[kPre];                           // a tile's count + entries 0 .. 2; entries 3 .. 6
+    auto load_recs = [&](uint32_t b_lo, uint32_t b_hi) {       // (beyond b_hi: tile b_hi again; its count is masked where it is read)
+#pragma unroll
+        for (uint32_t i = 0; i < kPre; ++i) {
+            const uint32_t b = min(b_lo + tid + 256u * i, b_hi);
+            rec[i] = recs[b];
+            ext[i] = recs.second(b);
+        }
+    };
+    const uint32_t code_ld = p.out_pred[cl], ps_ld = p.out_ps[cl], pos_ld = p.cand_pos[cl];
+    const uint32_t o0_ld = p.cand_off[cl], o1_ld = p.cand_off[cl + 1u];
+    const uint32_t sv_ld = p.cand_svread[cl], rf_ld = p.cand_refread[cl];
+    constexpr uint32_t kPairs = kC2Quota * kC2Words / 2;       // 448 eight-byte pieces
+    const uint2 *c2src = reinterpret_cast<const uint2 *>(p.c2rec + (size_t)tile * kC2Quota * kC2Words);
+    const uint2 a0 = c2src[tid], a1 = c2src[tid + 256u < kPairs ? tid + 256u : tid];
+    // (the loads above leave before the contig search: its scalar loads of the kernel arguments are a dependent chain of their own)
     uint32_t lo = 0, hi = nK;                                  // the last k with coff(k) <= c0
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
         if (coff(mid) <= c0) lo = mid; else hi = mid;
     }
-    const uint32_t keys_cap = (p.dbg & DUET_DBG_EF_OWN_SMALLTAB) ? 8u : kOwnKeys;
-    const uint32_t win_cap = (p.dbg & DUET_DBG_EF_OWN_SMALLTAB) ? 2u : kOwnWin;
-    const TileRecs recs{reinterpret_cast<const ulonglong4 *>(p.blk_rec)};
-    // ONE round trip in front of everything: the candidate's code, PS and position (a candidate that needs the nearest seed would
-    // fetch its position one trip later) and up to four tiles' seed records of the tile's first contig
-    const uint32_t code = live ? (uint32_t)p.out_pred[c] : 0u;
-    const uint32_t ps_in = live ? p.out_ps[c] : 0;
-    const uint32_t c_pos = live ? p.cand_pos[c] : 0;
     uint32_t k_first = lo;
     while (k_first < nK && coff(k_first) == coff(k_first + 1)) ++k_first;       // (the tile's first contig with candidates)
-    constexpr uint32_t kPre = 2;                               // records per thread that leave with the first trip: 512 tiles of a contig
-    ulonglong4 rec[kPre] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, ext[kPre] = {{0, 0, 0, 0}, {0, 0, 0, 0}};      // a tile's count + entries 0 .. 2; entries 3 .. 6
-    auto load_recs = [&](uint32_t b_lo, uint32_t b_hi) {
-#pragma unroll
-        for (uint32_t i = 0; i < kPre; ++i) {
-            const uint32_t b = b_lo + tid + 256u * i;
-            rec[i].x = 0;
-            if (b <= b_hi) { rec[i] = recs[b]; ext[i] = recs.second(b); }
-        }
-    };
-    if (k_first < nK) load_recs(coff(k_first) / kCandPerBlock, (coff(k_first + 1) - 1) / kCandPerBlock);
-    // What a multi-PS candidate needs (:85-105, :148-155) would be a SECOND, dependent trip -- its group summary sits at a slot that
-    // only its PS word names.  The tile's own kC2Quota summary slots (3.5 KB: the candidates of this very tile put theirs there) and
-    // every candidate's own columns leave with the first trip instead, whether or not anybody will look at them; only a summary
-    // in the shared pool (a tile with more than 64 multi-PS candidates) is fetched once the slot is known.
-    const uint32_t c_o0 = live ? p.cand_off[c] : 0u, c_o1 = live ? p.cand_off[c + 1] : 0u;
-    const uint32_t c_svread = live ? p.cand_svread[c] : 0u, c_refread = live ? p.cand_refread[c] : 0u;
     {
-        constexpr uint32_t kPairs = kC2Quota * kC2Words / 2;                // 448 eight-byte pieces
-        const uint2 *src = reinterpret_cast<const uint2 *>(p.c2rec + (size_t)tile * kC2Quota * kC2Words);
+        const uint32_t kf = k_first < nK ? k_first : 0u;       // (no candidates in the tile: any records serve, nobody reads them)
+        load_recs(coff(kf) / kCandPerBlock, (coff(kf + 1) - 1) / kCandPerBlock);
+    }
+    // one wait for the columns and the summaries (the asm takes the values, so none of these loads is sunk to its first use); the
+    // records, issued last, are still on their way -- their wait is the insert phase's, behind the barrier
+    asm volatile("" ::"v"(code_ld), "v"(ps_ld), "v"(pos_ld), "v"(o0_ld), "v"(o1_ld), "v"(sv_ld), "v"(rf_ld), "v"(a0.x), "v"(a0.y),
+                 "v"(a1.x), "v"(a1.y));
+    {
         uint2 *dst = reinterpret_cast<uint2 *>(s_c2);
-        const uint2 a0 = src[tid], a1 = src[tid + 256u < kPairs ? tid + 256u : 0u];
         dst[tid] = a0;
         if (tid + 256u < kPairs) dst[tid + 256u] = a1;
     }
+    const uint32_t code = live ? code_ld : 0u, ps_in = live ? ps_ld : 0u, c_pos = live ? pos_ld : 0u;
+    const uint32_t c_o0 = live ? o0_ld : 0u, c_o1 = live ? o1_ld : 0u;
+    const uint32_t c_svread = live ? sv_ld : 0u, c_refread = live ? rf_ld : 0u;
     for (uint32_t k = lo; k < nK && coff(k) <= last; ++k) {
         const uint32_t c_lo = coff(k), c_hi = coff(k + 1);
         if (c_lo == c_hi) continue;
@@ -1859,6 +1875,11 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
         }
         lds_barrier();
         STAMP(2, 1);
+        // (the records are taken whole here: a half the code never reads -- the upper word of a count -- would otherwise be reused by
+        // the compiler while its load is in flight, which costs a wait in front of the barrier)
+        asm volatile("" ::"v"(rec[0].x), "v"(rec[1].x), "v"(rec[0].y), "v"(rec[1].y), "v"(rec[0].z), "v"(rec[1].z), "v"(rec[0].w),
+                     "v"(rec[1].w), "v"(ext[0].x), "v"(ext[1].x), "v"(ext[0].y), "v"(ext[1].y), "v"(ext[0].z), "v"(ext[1].z),
+                     "v"(ext[0].w), "v"(ext[1].w));
         // ---- every entry of the contig: into the hash set (is this PS a seed, :91), and -- in the same sweep, from the registers
         // it sits in -- what the tile needs to answer "which seed is nearest" for positions in [pmin, pmax]: the largest seed
         // <= pmin, the smallest seed >= pmax, and the seeds strictly inside (with position-ordered candidates a handful; repeats
@@ -1873,24 +1894,26 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
         uint32_t fresh = 0, leftp = 0, rinv = 0;
         static_assert(kOwnTab == 1u << 11, "the hash takes 11 bits");
         auto slot_of = [](uint32_t key) -> uint32_t { return (key * 2654435761u) >> (32u - 11u); };
-        auto is_new = [&](uint32_t key) {                                   // a seed new to the set: counted, and looked at once
-            ++fresh;
-            if (key <= pmin) leftp = max(leftp, key + 1u);
-            if (key >= pmax) rinv = max(rinv, ~key);
-            if (key > pmin && key < pmax) {
+        auto count_new = [&](bool nw, uint32_t key) {                       // a seed new to the set: counted, and looked at once
+            fresh += nw ? 1u : 0u;
+            leftp = max(leftp, (nw && key <= pmin) ? key + 1u : 0u);
+            rinv = max(rinv, (nw && key >= pmax) ? ~key : 0u);
+            if (nw && key > pmin && key < pmax) {
                 const uint32_t at = atomicAdd(&s_nwin, 1u);
                 if (at < kOwnWin) s_win[at] = key;
             }
         };
-        auto insert = [&](uint64_t e) {
+        auto insert = [&](uint64_t e) {                                     // (rare paths: the whole probe sequence on the spot)
             const uint32_t cc = (uint32_t)(e >> 32), key = (uint32_t)e;        // (a PS is at most 2^32 - 2: kEmpty is free)
-            if (cc >= c_lo && cc < c_hi && own_insert_slow(s_tab, key, slot_of(key))) is_new(key);
+            if (cc >= c_lo && cc < c_hi) count_new(own_probe(s_tab, key, slot_of(key)), key);
         };
         // The thread's up to 2 x 7 entries in four groups -- a tile's first three, its next four --, each group only when some lane
         // of the wavefront has one (most tiles have two or three entries, most wavefronts no second tile): a group's first probes
         // leave together, what comes back is looked at without a branch per entry (the branch per entry cost this phase 1,800
-        // instructions and 2 us: selects instead; only a collision and a seed inside the window are rare enough to branch for).
-        auto group = [&](const uint64_t (&e)[4], uint32_t first, uint32_t n_in, uint32_t cnt) {
+        // instructions and 2 us: selects instead).  A key whose first probe meets another key sets its bit in `coll` (bit 7 i + j:
+        // entry j of record i), and all of them go through ONE probe loop behind the groups.
+        uint32_t coll = 0;
+        auto group = [&](const uint64_t (&e)[4], uint32_t first, uint32_t n_in, uint32_t cnt, uint32_t bit0) {
             uint32_t key[4], old[4];
             bool ok[4];
 #pragma unroll
@@ -1905,16 +1928,8 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
                 if (ok[j]) old[j] = atomicCAS(&s_tab[slot_of(key[j])], kEmpty, key[j]);
 #pragma unroll
             for (uint32_t j = 0; j < 4; ++j) {
-                bool nw = ok[j] && old[j] == kEmpty;
-                if (ok[j] && old[j] != kEmpty && old[j] != key[j])          // (a collision: the probe sequence, behind a call)
-                    nw = own_insert_slow(s_tab, key[j], (slot_of(key[j]) + 1u) & (kOwnTab - 1u)) != 0u;
-                fresh += nw ? 1u : 0u;
-                leftp = max(leftp, (nw && key[j] <= pmin) ? key[j] + 1u : 0u);
-                rinv = max(rinv, (nw && key[j] >= pmax) ? ~key[j] : 0u);
-                if (nw && key[j] > pmin && key[j] < pmax) {
-                    const uint32_t at = atomicAdd(&s_nwin, 1u);
-                    if (at < kOwnWin) s_win[at] = key[j];
-                }
+                coll |= (ok[j] && old[j] != kEmpty && old[j] != key[j]) ? 1u << (bit0 + j) : 0u;
+                count_new(ok[j] && old[j] == kEmpty, key[j]);
             }
         };
 #pragma unroll
@@ -1922,12 +1937,28 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
             const uint32_t cnt = b_lo + tid + 256u * i <= b_hi ? (uint32_t)rec[i].x : 0u;
             if (__any(cnt > 0u)) {
                 const uint64_t e[4] = {rec[i].y, rec[i].z, rec[i].w, 0ull};
-                group(e, 0u, 3u, cnt);
+                group(e, 0u, 3u, cnt, 7u * i);
             }
             if (__any(cnt > 3u)) {
                 const uint64_t e[4] = {ext[i].x, ext[i].y, ext[i].z, ext[i].w};
-                group(e, 3u, 4u, cnt);
+                group(e, 3u, 4u, cnt, 7u * i + 3u);
             }
+        }
+        while (coll) {                                                      // (the collisions: their key picked by selects)
+            const uint32_t j = (uint32_t)__ffs(coll) - 1u;
+            coll &= coll - 1u;
+            uint32_t key = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < kPre; ++i) {
+                key = j == 7u * i + 0u ? (uint32_t)rec[i].y : key;
+                key = j == 7u * i + 1u ? (uint32_t)rec[i].z : key;
+                key = j == 7u * i + 2u ? (uint32_t)rec[i].w : key;
+                key = j == 7u * i + 3u ? (uint32_t)ext[i].x : key;
+                key = j == 7u * i + 4u ? (uint32_t)ext[i].y : key;
+                key = j == 7u * i + 5u ? (uint32_t)ext[i].z : key;
+                key = j == 7u * i + 6u ? (uint32_t)ext[i].w : key;
+            }
+            count_new(own_probe(s_tab, key, (slot_of(key) + 1u) & (kOwnTab - 1u)), key);
         }
         // A tile with more than seven entries -- candidates of a sparse type in stage A0's type-major order: a tile of 256 of them
         // spans a quarter of the contig and carries a hundred phase sets -- has the rest in its overflow slots: the WAVEFRONT takes
@@ -1958,21 +1989,24 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
                 for (uint32_t j = from + lane; j < cnt_h; j += 64u) insert(ov[j]);
             }
         };
+        // the overflow slots of the records above, then (a contig of more than 512 tiles) the others' records one more trip later
+        // (one loop: a single copy of the rare paths; the count of rec[i] by a select, not by a run-time index)
 #pragma unroll 1
-        for (uint32_t i = 0; i < kPre; ++i) {
-            const uint32_t b = b_lo + tid + 256u * i;
-            overflow(b, b <= b_hi ? (uint32_t)rec[i].x : 0u, 7u);
-        }
-        // (a contig of more than 512 tiles: the others' records one more trip later)
-        for (uint32_t b0 = b_lo + 256u * kPre; b0 <= b_hi; b0 += 256u) {
+        for (uint32_t i = 0, b0 = b_lo; b0 <= b_hi; ++i, b0 += 256u) {
             const uint32_t b = b0 + tid;
-            ulonglong4 r = {0, 0, 0, 0};
-            if (b <= b_hi) r = recs[b];
-            const uint32_t cnt = (uint32_t)r.x;
-            if (cnt > 0) insert(r.y);
-            if (cnt > 1) insert(r.z);
-            if (cnt > 2) insert(r.w);
-            overflow(b, cnt, 3u);
+            uint32_t cnt, from = 7u;
+            if (i < kPre) {
+                cnt = b <= b_hi ? (uint32_t)(i == 0 ? rec[0].x : rec[1].x) : 0u;
+            } else {
+                ulonglong4 r = {0, 0, 0, 0};
+                if (b <= b_hi) r = recs[b];
+                cnt = (uint32_t)r.x;
+                if (cnt > 0) insert(r.y);
+                if (cnt > 1) insert(r.z);
+                if (cnt > 2) insert(r.w);
+                from = 3u;
+            }
+            overflow(b, cnt, from);
         }
         {
             const uint32_t l = wave_max_u32(leftp), r = wave_max_u32(rinv), o = wave_sum(fresh);
@@ -1986,7 +2020,7 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
         const uint32_t n_win = s_nwin;
         const bool over = u > keys_cap;                                     // (a full table: u == kOwnTab > keys_cap)
         const bool sorted = !over && n_win > win_cap;                       // candidates out of position order: the whole set, ascending
-        if (sorted) own_sort_set(s_tab, s_key, s_one, s_part, u);      // (a call: rare, and its registers are not the hot path's)
+        if (sorted) own_sort_set(s_tab, s_key, s_one, s_part, u);      // (rare: inlined behind this branch)
         STAMP(2, 5);
         // ---- this tile's candidates of contig k ------------------------------------------------------
         // :107-111 -- ties go to the larger seed
@@ -2028,10 +2062,9 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
                 } else if (code & kClass2Slow) {                            // no group summary: the vote from the marks (:85-105)
                     Vote v;
                     uint32_t ps;
-                    const uint32_t mb = p.cand_off[c], me_ = p.cand_off[c + 1];
-                    own_vote_from_marks(p.mark_read, p.read_tag, mb, me_, s_tab, &v, &ps);
+                    own_vote_from_marks(p.mark_read, p.read_tag, c_o0, c_o1, s_tab, &v, &ps);
                     if (v.hap1 == 0 && v.hap2 == 0) ps = nearest(c_pos);    // :106
-                    p.out_pred[c] = (uint8_t)decide(2, v, me_ - mb, p.cand_svread[c], p.cand_refread[c]);
+                    p.out_pred[c] = (uint8_t)decide(2, v, c_o1 - c_o0, c_svread, c_refread);
                     p.out_ps[c] = ps;
                 } else if (code & kClass2) {                                // :85-105, :148-155 from the summary that is already here
                     uint32_t w[kC2Words];
