@@ -29,7 +29,8 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_ef_rows_run_host', 'duet_eval_run_host', 'duet_comm_unique_id', 'duet_comm_create', 'duet_comm_allgather_device',
            'duet_comm_allgather_host', 'duet_comm_destroy', 'duet_comm_set_timeout', 'duet_comm_block_bytes',
            'duet_comm_ef_allgather', 'duet_comm_rccl_version', 'duet_comm_info', 'duet_comm_selftest',
-           'duet_ef_features_device', 'duet_ef_features_host', 'duet_tune_sweep_device', 'duet_tune_sweep_host')
+           'duet_ef_features_device', 'duet_ef_features_host', 'duet_tune_sweep_device', 'duet_tune_sweep_host',
+           'duet_svim_vcf_rows_device', 'duet_svim_vcf_rows_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -67,6 +68,36 @@ class SvimProblem(ctypes.Structure):
                 ('n_reads', ctypes.c_uint32), ('n_contigs', ctypes.c_uint32), ('depth', ctypes.c_void_p),
                 ('depth_off', ctypes.c_void_p), ('depth_bin', ctypes.c_uint32), ('svlen_thres', ctypes.c_uint32),
                 ('suppread_thres', ctypes.c_uint32), ('reserved', ctypes.c_uint32)]
+
+
+class CallsetNames(ctypes.Structure):
+    _fields_ = [('mark_name', ctypes.c_void_p), ('name_off', ctypes.c_void_p), ('name_pool', ctypes.c_void_p),
+                ('n_names', ctypes.c_uint32), ('n_contigs', ctypes.c_uint32), ('chrom', ctypes.POINTER(ctypes.c_char_p))]
+
+
+def callset_bound(n_cands, n_marks, name_off, chrom_texts):
+    """The size duet_svim_vcf_rows_* can need at most (include/duet_ef.h): what the caller allocates for one call."""
+    longest = int(np.max(np.diff(np.asarray(name_off, dtype=np.int64)))) if len(name_off) > 1 else 0
+    chrom = max([len(c.encode()) for c in chrom_texts] + [0])
+    return int(n_cands) * (2 * chrom + 168) + int(n_marks) * (longest + 1) + 64
+
+
+def callset_names(mark_name, name_off, name_pool, chrom_texts, keep):
+    """-> CallsetNames over the given arrays (host or device pointers: ints are taken as device pointers); `keep` collects what
+    must outlive the call."""
+    n = CallsetNames()
+    for field, a in (('mark_name', mark_name), ('name_off', name_off), ('name_pool', name_pool)):
+        if isinstance(a, int):
+            setattr(n, field, a)
+        else:
+            keep.append(a)
+            setattr(n, field, a.ctypes.data if a.size else None)
+    n.n_names = int(len(name_off) if not isinstance(name_off, int) else 0)
+    texts = (ctypes.c_char_p * max(len(chrom_texts), 1))(*[c.encode() for c in chrom_texts])
+    keep.append(texts)
+    n.n_contigs = len(chrom_texts)
+    n.chrom = texts
+    return n
 
 
 class RowsProblem(ctypes.Structure):
@@ -183,6 +214,10 @@ def load():
                                          ctypes.POINTER(TuneTruth), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.duet_comm_destroy.restype = None
     lib.duet_comm_destroy.argtypes = [ctypes.c_void_p]
+    for fn in (lib.duet_svim_vcf_rows_device, lib.duet_svim_vcf_rows_host):
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult), ctypes.c_uint32,
+                       ctypes.POINTER(CallsetNames), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)] + \
+                      ([ctypes.c_void_p] if fn is lib.duet_svim_vcf_rows_device else [])
     _lib = lib
     return lib
 
@@ -342,9 +377,10 @@ class Context(object):
                     cand_type=out['cand_type'][:N], cand_pos=out['cand_pos'][:N], cand_span=out['cand_span'][:N])
 
     def svim_host(self, marks, read_tag, depth, depth_off, depth_bin, svlen_thres, suppread_thres, max_dist=0.9, part_gap=1000,
-                  part_max=100, normalizer=900.0):
+                  part_max=100, normalizer=900.0, want_order=False):
         """The fused SVIM-mode pipeline on host arrays (duet_svim_phase_host): raw marks dict(contig, type, pos, span, read) ->
-        dict(cand_off, cand_contig, cand_type, cand_pos, cand_span, pred, ps) trimmed to the candidate count."""
+        dict(cand_off, cand_contig, cand_type, cand_pos, cand_span, pred, ps) trimmed to the candidate count (want_order: and
+        the cluster order, order u32[M])."""
         arr = {k: np.ascontiguousarray(marks[k], dtype=dt) for k, dt in (('contig', np.uint16), ('type', np.uint8), ('pos', np.uint32),
                                                                         ('span', np.uint32), ('read', np.uint32))}
         read_tag = np.ascontiguousarray(read_tag, dtype=np.uint64)
@@ -375,14 +411,62 @@ class Context(object):
         res = ClusterResult()
         for k in out:
             setattr(res, k, out[k].ctypes.data)
-        res.order = None
+        order = np.zeros(max(M, 1), dtype=np.uint32) if want_order else None
+        res.order = order.ctypes.data if want_order else None
         res.n_cands = ctypes.addressof(n)
         rc = self.lib.duet_svim_phase_host(self.handle, ctypes.byref(p), ctypes.byref(res), _ptr(pred), _ptr(ps))
         if rc:
             self._raise(rc)
         N = n.value
-        return dict(cand_off=out['cand_off'][:N + 1], cand_contig=out['cand_contig'][:N], cand_type=out['cand_type'][:N],
-                    cand_pos=out['cand_pos'][:N], cand_span=out['cand_span'][:N], pred=pred[:N], ps=ps[:N])
+        got = dict(cand_off=out['cand_off'][:N + 1], cand_contig=out['cand_contig'][:N], cand_type=out['cand_type'][:N],
+                   cand_pos=out['cand_pos'][:N], cand_span=out['cand_span'][:N], pred=pred[:N], ps=ps[:N])
+        if want_order:
+            got['order'] = order[:M]
+        return got
+
+    def svim_vcf_rows_device(self, sv_problem, result, n_cands, names, out_ptr, cap, stream):
+        """duet_svim_vcf_rows_device on resident arrays (DeviceSvim.vcf_rows) -> bytes written."""
+        n = ctypes.c_uint64(0)
+        rc = self.lib.duet_svim_vcf_rows_device(self.handle, ctypes.byref(sv_problem), ctypes.byref(result), int(n_cands),
+                                                ctypes.byref(names), ctypes.c_void_p(out_ptr), ctypes.c_uint64(cap), ctypes.byref(n),
+                                                ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return n.value
+
+    def svim_vcf_rows_host(self, res, n_marks, mark_name, name_off, name_pool, depth, depth_off, depth_bin, chrom_texts):
+        """duet_svim_vcf_rows_host: the rows of sv_calling/variants.vcf for a cluster result (host arrays: order, cand_off,
+        cand_contig, cand_type, cand_pos, cand_span), the raw marks' names and the binned depth -> bytes."""
+        N = len(res['cand_pos'])
+        if N == 0:
+            return b''
+        arr = {k: np.ascontiguousarray(res[k], dtype=dt) for k, dt in (
+            ('order', np.uint32), ('cand_off', np.uint32), ('cand_contig', np.uint16), ('cand_type', np.uint8),
+            ('cand_pos', np.uint32), ('cand_span', np.uint32))}
+        r = ClusterResult()
+        for k in arr:
+            setattr(r, k, arr[k].ctypes.data)
+        depth = np.ascontiguousarray(depth, dtype=np.uint32)
+        depth_off = np.ascontiguousarray(depth_off, dtype=np.uint32)
+        p = SvimProblem()
+        p.marks.n_marks = int(n_marks)
+        p.n_contigs = len(depth_off) - 1
+        p.depth = depth.ctypes.data if depth.size else None
+        p.depth_off = depth_off.ctypes.data
+        p.depth_bin = int(depth_bin)
+        keep = []
+        name_off = np.ascontiguousarray(name_off, dtype=np.uint64)
+        nm = callset_names(np.ascontiguousarray(mark_name, dtype=np.uint32), name_off,
+                           np.ascontiguousarray(name_pool, dtype=np.uint8), chrom_texts, keep)
+        nm.n_names = len(name_off) - 1
+        cap = callset_bound(N, n_marks, name_off, chrom_texts)
+        out = np.empty(cap, dtype=np.uint8)
+        n = ctypes.c_uint64(0)
+        rc = self.lib.duet_svim_vcf_rows_host(self.handle, ctypes.byref(p), ctypes.byref(r), N, ctypes.byref(nm), out.ctypes.data,
+                                              ctypes.c_uint64(cap), ctypes.byref(n))
+        if rc:
+            self._raise(rc)
+        return out[:n.value].tobytes()
 
     def eval_counts(self, arrays, refdist, ratio):
         """duet_eval_run_host: `arrays` = dict of the flat host arrays (duet_amd/evaluation.py: flatten) -> EvalCounts."""

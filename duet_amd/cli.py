@@ -24,7 +24,7 @@ def pipeline(a):
             (stages.snp_calling, (a.OUTPUT, a.REFERENCE, a.BAM, a.min_allele_frequency, a.thread, a.include_all_ctgs)),
             (stages.snp_phasing, (a.OUTPUT, a.REFERENCE, a.BAM, a.thread)),
             (sv_phasing_from_bams, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs,
-                                    a.cluster_max_distance, a.device, a.gpus)),
+                                    a.cluster_max_distance, a.device, a.gpus, a.write_sv_calls)),
         )
     return (
         (stages.snp_calling, (a.OUTPUT, a.REFERENCE, a.BAM, a.min_allele_frequency, a.thread, a.include_all_ctgs)),
@@ -39,6 +39,9 @@ def pipeline(a):
 def main(argv):
     a = parse_args(argv)
     a.threshold_vector = None
+    if a.write_sv_calls and a.sv_caller != 'svim-gpu':
+        # (additive: the clustered calls exist only in the svim-gpu mode; every other caller writes sv_calling/variants.vcf itself)
+        raise SystemExit('duet: --write_sv_calls works with -b svim-gpu only')
     if a.thresholds is not None:
         # (additive: the decision's constants from a file -- checked before any stage runs)
         if a.gpus > 1 or a.sv_caller == 'svim-gpu' or os.environ.get('DUET_FORCE_RANKS') == '1':

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <string_view>
 #include <thread>
 #include <unordered_map>
 #include <vector>
@@ -280,6 +281,11 @@ struct duet_ingest {
     std::vector<std::vector<uint32_t>> depth;                   // per contig
     std::vector<uint32_t> depth_flat, depth_off, tag_off;
     std::vector<uint64_t> tag_flat;
+    // read names per raw mark (duet_ingest_keep_mark_names): m_name[i] indexes name_off; names interned per contig
+    bool keep_names = false;
+    std::vector<uint32_t> m_name;
+    std::vector<uint64_t> name_off{0};
+    std::string name_pool;
 };
 
 namespace {
@@ -789,7 +795,17 @@ int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int thread
         }
     }
     if (g->extract) {
+        // (names: one entry per distinct read of this contig, in order of first mark; the views point into `buf`, alive here)
+        std::unordered_map<std::string_view, uint32_t> interned;
         for (const Pend &m : pend) {
+            if (g->keep_names) {
+                auto it = interned.emplace(std::string_view(m.name, m.len), (uint32_t)(g->name_off.size() - 1));
+                if (it.second) {
+                    g->name_pool.append(m.name, m.len);
+                    g->name_off.push_back((uint64_t)g->name_pool.size());
+                }
+                g->m_name.push_back(it.first->second);
+            }
             const int id = tab.find_hashed(m.name, m.len, NameTable::hash(m.name, m.len));
             g->m_contig.push_back((uint16_t)contig);
             g->m_type.push_back(m.type);
@@ -1698,6 +1714,27 @@ int duet_ingest_set_extraction(duet_ingest *g, int enable, uint32_t min_sv_size,
     g->min_sv_size = min_sv_size;
     g->min_mapq = min_mapq;
     g->depth_bin = depth_bin;
+    return DUET_INGEST_OK;
+}
+
+int duet_ingest_keep_mark_names(duet_ingest *g, int enable)
+{
+    if (!g) return DUET_INGEST_INVALID;
+    if (!g->m_pos.empty()) { g->err = "duet_ingest_keep_mark_names after marks were extracted"; return DUET_INGEST_INVALID; }
+    g->keep_names = enable != 0;
+    return DUET_INGEST_OK;
+}
+
+int duet_ingest_get_mark_names(duet_ingest *g, duet_ingest_mark_names *o)
+{
+    if (!g || !o || !g->extract || !g->keep_names) return DUET_INGEST_INVALID;
+    if (g->name_off.size() - 1 > 0xFFFFFFFEull) return unsupported(g, "more than 2^32 - 2 distinct read names");
+    o->n_marks = (uint32_t)g->m_name.size();
+    o->n_names = (uint32_t)(g->name_off.size() - 1);
+    o->mark_name = g->m_name.data();
+    o->name_off = g->name_off.data();
+    o->name_pool = g->name_pool.data();
+    o->pool_bytes = (uint64_t)g->name_pool.size();
     return DUET_INGEST_OK;
 }
 

@@ -199,6 +199,35 @@ class DeviceSvim(DeviceCluster):
         self.n_found = n.value if wait else None
         return stream
 
+    def vcf_rows(self, ctx, names, chrom_texts, stream=None):
+        """Rows of sv_calling/variants.vcf for the last run_fused's candidates, formatted on the device from the resident
+        cluster result and depth (duet_svim_vcf_rows_device).  names: dict(mark_name, name_off, name_pool) of
+        NativeIngest.extract(..., names=True); chrom_texts: CHROM text per contig.  -> uint8 numpy array of the text."""
+        torch = self.torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.n_found is None:
+            self.n_found = self.n_cands()
+        N = self.n_found
+        if N == 0:
+            return np.zeros(0, dtype=np.uint8)
+
+        def up(a, dt):
+            a = np.ascontiguousarray(a, dtype=dt)
+            t = torch.zeros(a.nbytes + 64, dtype=torch.uint8, device=self.device)
+            if a.nbytes:
+                t[:a.nbytes] = torch.from_numpy(a.view(np.uint8).reshape(-1)).to(self.device)
+            return t
+
+        keep = [up(names['mark_name'], np.uint32), up(names['name_off'], np.uint64), up(names['name_pool'], np.uint8)]
+        hold = []
+        nm = _lib.callset_names(keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), chrom_texts, hold)
+        nm.n_names = len(names['name_off']) - 1
+        cap = _lib.callset_bound(N, self.M, names['name_off'], chrom_texts)
+        out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        n = ctx.svim_vcf_rows_device(self.sv_problem, self.result, N, nm, out.data_ptr(), cap, stream)
+        return out[:n].cpu().numpy()
+
     def fetch(self):
         """-> dict of the cluster arrays + pred/ps, trimmed to the candidate count (synchronises)."""
         if self.n_found is None:

@@ -21,7 +21,7 @@ EXPORTS = ('duet_ingest_create', 'duet_ingest_destroy', 'duet_ingest_error', 'du
            'duet_ingest_emit', 'duet_ingest_free', 'duet_ingest_header',
            'duet_ingest_get_rows', 'duet_ingest_set_extraction', 'duet_ingest_get_marks', 'duet_ingest_bam_has_alignments',
            'duet_ingest_vcf_precount', 'duet_ingest_set_owned', 'duet_ingest_count_kept', 'duet_ingest_emit_blocks',
-           'duet_ingest_cand_slots')
+           'duet_ingest_cand_slots', 'duet_ingest_keep_mark_names', 'duet_ingest_get_mark_names')
 
 
 class IngestArrays(ctypes.Structure):
@@ -42,6 +42,11 @@ class IngestMarks(ctypes.Structure):
                 ('depth_bin', ctypes.c_uint32)] + \
                [(n, ctypes.c_void_p) for n in ('mark_contig', 'mark_type', 'mark_pos', 'mark_span', 'mark_read', 'read_tag',
                                                'read_off', 'depth', 'depth_off')]
+
+
+class IngestMarkNames(ctypes.Structure):
+    _fields_ = [('n_marks', ctypes.c_uint32), ('n_names', ctypes.c_uint32), ('mark_name', ctypes.c_void_p),
+                ('name_off', ctypes.c_void_p), ('name_pool', ctypes.c_void_p), ('pool_bytes', ctypes.c_uint64)]
 
 
 _lib = None
@@ -72,6 +77,8 @@ def load():
         lib.duet_ingest_get_rows.argtypes = [ctypes.c_void_p, ctypes.POINTER(IngestRows)]
         lib.duet_ingest_set_extraction.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
         lib.duet_ingest_get_marks.argtypes = [ctypes.c_void_p, ctypes.POINTER(IngestMarks)]
+        lib.duet_ingest_keep_mark_names.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.duet_ingest_get_mark_names.argtypes = [ctypes.c_void_p, ctypes.POINTER(IngestMarkNames)]
         lib.duet_ingest_free.argtypes = [ctypes.c_void_p]
         lib.duet_ingest_free.restype = None
         lib.duet_ingest_bam_has_alignments.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -211,15 +218,16 @@ class NativeIngest(object):
         return cls(h, lib, soa, bam_contigs=with_bam)
 
     @classmethod
-    def extract(cls, sam_home, chrom_list, thread=4, min_sv_size=40, min_mapq=20, depth_bin=1000, only=None):
+    def extract(cls, sam_home, chrom_list, thread=4, min_sv_size=40, min_mapq=20, depth_bin=1000, only=None, names=False):
         """SVIM mode: the haplotagged BAMs alone -> raw SV marks (CIGAR insertions / deletions), tag tables, binned depth.
         -> (NativeIngest, dict(contig, type, pos, span, read, read_tag, read_off, depth, depth_off, depth_bin)) with
-        numpy COPIES of the arrays, or (None, reason)."""
+        numpy COPIES of the arrays, or (None, reason).  names=True: also the marks' read names (duet_ingest_keep_mark_names):
+        mark_name u32[M] into name_off u64[n_names + 1], name_pool u8[] (names interned per contig)."""
         lib = load()
         if lib is None:
             return None, 'libduet_ingest.so is missing'
-        names = (ctypes.c_char_p * len(chrom_list))(*[c.encode('utf-8') for c in chrom_list])
-        h = lib.duet_ingest_create(len(chrom_list), names)
+        labels = (ctypes.c_char_p * len(chrom_list))(*[c.encode('utf-8') for c in chrom_list])
+        h = lib.duet_ingest_create(len(chrom_list), labels)
         if not h:
             return None, 'duet_ingest_create failed'
 
@@ -229,6 +237,8 @@ class NativeIngest(object):
             return None, why
 
         if lib.duet_ingest_set_extraction(h, 1, int(min_sv_size), int(min_mapq), int(depth_bin)) != OK:
+            return decline()
+        if names and lib.duet_ingest_keep_mark_names(h, 1) != OK:
             return decline()
         for k, c in enumerate(chrom_list):
             if only is not None and k not in only:
@@ -249,6 +259,13 @@ class NativeIngest(object):
                    read_off=_view(m.read_off, K + 1, np.uint32).copy(),
                    depth=_view(m.depth, int(depth_off[-1]) if K else 0, np.uint32).copy(), depth_off=depth_off,
                    depth_bin=int(m.depth_bin))
+        if names:
+            nm = IngestMarkNames()
+            if lib.duet_ingest_get_mark_names(h, ctypes.byref(nm)) != OK:
+                return decline()
+            out['mark_name'] = _view(nm.mark_name, nm.n_marks, np.uint32).copy()
+            out['name_off'] = _view(nm.name_off, nm.n_names + 1, np.uint64).copy()
+            out['name_pool'] = _view(nm.name_pool, nm.pool_bytes, np.uint8).copy()
         return cls(h, lib, None), out
 
     def emit(self, pred, ps, include_all_ctgs):

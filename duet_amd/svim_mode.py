@@ -17,9 +17,11 @@ from duet_amd.native import NativeIngest
 from duet_amd.read_file import init_chrom_list
 
 
-def device_compute(ctx):
+def device_compute(ctx, chrom_texts=None):
     """-> compute(extracted arrays, svlen_thres, suppread_thres, max_dist, depth_bin) -> dict of result arrays, on ctx's GPU:
-    stage A0 -> adapter -> step E/F in one device pipeline (duet_svim_phase_device)."""
+    stage A0 -> adapter -> step E/F in one device pipeline (duet_svim_phase_device).  chrom_texts (CHROM text per contig): the
+    extracted arrays carry the marks' read names, and the result also holds `calls`, the rows of sv_calling/variants.vcf formatted
+    on the same resident arrays (duet_svim_vcf_rows_device)."""
     def compute(got, svlen_thres, suppread_thres, max_dist, depth_bin):
         from duet_amd.devmem import DeviceSvim
         ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, svlen_thres, suppread_thres,
@@ -27,38 +29,70 @@ def device_compute(ctx):
         ds.run_fused(ctx)
         ctx.check(ds.torch.cuda.current_stream(ds.device).cuda_stream)
         out = ds.fetch()
-        return dict(cand_contig=out['cand_contig'], cand_type=out['cand_type'], cand_pos=out['cand_pos'],
-                    cand_span=out['cand_span'], support=np.diff(out['cand_off'].astype(np.int64)), pred=out['pred'], ps=out['ps'])
+        res = dict(cand_contig=out['cand_contig'], cand_type=out['cand_type'], cand_pos=out['cand_pos'],
+                   cand_span=out['cand_span'], support=np.diff(out['cand_off'].astype(np.int64)), pred=out['pred'], ps=out['ps'])
+        if chrom_texts is not None:
+            res['calls'] = ds.vcf_rows(ctx, got, chrom_texts)
+        return res
     return compute
 
 
-def host_compute(ctx):
-    """The same through host arrays (duet_svim_phase_host): what a rank of `-b svim-gpu --gpus N` uses -- no torch in the process."""
+def host_compute(ctx, chrom_texts=None):
+    """The same through host arrays (duet_svim_phase_host, duet_svim_vcf_rows_host): what a rank of `-b svim-gpu --gpus N`
+    uses -- no torch in the process."""
     def compute(got, svlen_thres, suppread_thres, max_dist, depth_bin):
-        out = ctx.svim_host(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, svlen_thres, suppread_thres, max_dist=max_dist)
-        return dict(cand_contig=out['cand_contig'], cand_type=out['cand_type'], cand_pos=out['cand_pos'], cand_span=out['cand_span'],
-                    support=np.diff(out['cand_off'].astype(np.int64)), pred=out['pred'], ps=out['ps'])
+        out = ctx.svim_host(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, svlen_thres, suppread_thres, max_dist=max_dist,
+                            want_order=chrom_texts is not None)
+        res = dict(cand_contig=out['cand_contig'], cand_type=out['cand_type'], cand_pos=out['cand_pos'], cand_span=out['cand_span'],
+                   support=np.diff(out['cand_off'].astype(np.int64)), pred=out['pred'], ps=out['ps'])
+        if chrom_texts is not None:
+            res['calls'] = ctx.svim_vcf_rows_host(out, len(got['pos']), got['mark_name'], got['name_off'], got['name_pool'], got['depth'],
+                                                  got['depth_off'], depth_bin, chrom_texts)
+        return res
     return compute
+
+
+class ReadNameError(ValueError):
+    """A read name that READS= of sv_calling/variants.vcf cannot hold."""
+
+
+def check_read_names(got):
+    """A read name with ',' or ';' cannot be listed in READS= and read back: such a name fails the run (--write_sv_calls)."""
+    pool = got['name_pool']
+    bad = np.flatnonzero((pool == ord(',')) | (pool == ord(';')))
+    if bad.size:
+        j = int(np.searchsorted(got['name_off'], bad[0], side='right')) - 1
+        name = pool[int(got['name_off'][j]):int(got['name_off'][j + 1])].tobytes().decode('utf-8', 'replace')
+        raise ReadNameError('read name %r contains "," or ";": it cannot be listed in READS= of sv_calling/variants.vcf '
+                         '(--write_sv_calls)' % name)
 
 
 def phase_from_bams(home, svlen_thres=50, suppread_thres=2, thread=4, include_all_ctgs=False, max_dist=0.9,
-                    min_sv_size=40, min_mapq=20, depth_bin=1000, ctx=None, only=None, compute=None):
+                    min_sv_size=40, min_mapq=20, depth_bin=1000, ctx=None, only=None, compute=None, names=False):
     """-> dict(chroms, cand_contig u16[N], cand_type u8[N] (1 INS / 0 DEL), cand_pos, cand_span, support, pred, ps).
     only: the contig indices to read (a rank of a sharded run; the contig numbering stays the whole list's);
-    compute: what turns the extracted arrays into results (default: the GPU pipeline on ctx)."""
+    compute: what turns the extracted arrays into results (default: the GPU pipeline on ctx);
+    names (--write_sv_calls): the marks' read names are extracted and checked before anything runs on the device, and the
+    result also holds `calls`, the rows of sv_calling/variants.vcf (a compute made with chrom_texts)."""
     chroms = init_chrom_list(include_all_ctgs, home)
-    ing, got = NativeIngest.extract(home + '/snp_phasing/', chroms, thread, min_sv_size, min_mapq, depth_bin, only=only)
+    ing, got = NativeIngest.extract(home + '/snp_phasing/', chroms, thread, min_sv_size, min_mapq, depth_bin, only=only,
+                                    names=names)
     if ing is None:
         raise RuntimeError('signature extraction declined the input: %s' % got)
     ing.close()
+    if names:
+        check_read_names(got)
     N0 = dict(chroms=chroms, cand_contig=np.zeros(0, np.uint16), cand_type=np.zeros(0, np.uint8),
               cand_pos=np.zeros(0, np.uint32), cand_span=np.zeros(0, np.uint32), support=np.zeros(0, np.int64),
               pred=np.zeros(0, np.uint8), ps=np.zeros(0, np.uint32))
     N0['n_marks'] = 0
+    if names:
+        N0['calls'] = np.zeros(0, np.uint8)
     if len(got['pos']) == 0:
         return N0
     if compute is None:
-        compute = device_compute(ctx if ctx is not None else engine.default_context())
+        compute = device_compute(ctx if ctx is not None else engine.default_context(),
+                                 spelled_contigs(home, chroms) if names else None)
     out = compute(got, svlen_thres, suppread_thres, max_dist, depth_bin)
     return dict(out, chroms=chroms, n_marks=len(got['pos']))
 
@@ -92,10 +126,8 @@ def rows_text(home, res):
     return ''.join(out)
 
 
-def header_text(home, chroms):
-    """phased_sv.vcf header lines (write_file.py:19-45).  Upstream copies the ##contig lines of the caller VCF; this mode
-    has no caller VCF, so every listed contig that has a BAM contributes one line from the BAM's own reference list."""
-    from duet_amd.write_file import _COLS, _HEAD
+def contig_lines(home, chroms):
+    """The ##contig lines of this mode: one per listed contig that has a BAM, from the BAM's own reference list."""
     lines = []
     for c, name in zip(chroms, spelled_contigs(home, chroms)):
         bam = os.path.join(home, 'snp_phasing', name + '.bam')
@@ -105,7 +137,49 @@ def header_text(home, chroms):
             if ref == name:
                 lines.append('##contig=<ID=%s,length=%d>\n' % (ref, length))
                 break
-    return _HEAD + ''.join(lines) + _COLS
+    return ''.join(lines)
+
+
+def header_text(home, chroms):
+    """phased_sv.vcf header lines (write_file.py:19-45).  Upstream copies the ##contig lines of the caller VCF; this mode
+    has no caller VCF, so every listed contig that has a BAM contributes one line from the BAM's own reference list."""
+    from duet_amd.write_file import _COLS, _HEAD
+    return _HEAD + contig_lines(home, chroms) + _COLS
+
+
+# sv_calling/variants.vcf of this mode (--write_sv_calls; DESIGN.md section 15): the clustered candidates in the repository's own
+# dialect, modelled on SVIM's -- readable by read_file.parse_vcf (READS= / GT:DP:AD) and the native VCF ingest
+CALLSET_INFO = ''.join(line + '\n' for line in (
+    '##ALT=<ID=DEL,Description="Deletion">',
+    '##ALT=<ID=INS,Description="Insertion">',
+    '##ALT=<ID=INV,Description="Inversion">',
+    '##ALT=<ID=DUP,Description="Duplication">',
+    '##INFO=<ID=SVTYPE,Number=1,Type=String,Description="Type of structural variant">',
+    '##INFO=<ID=END,Number=1,Type=Integer,Description="End position of the variant described in this record">',
+    '##INFO=<ID=SVLEN,Number=1,Type=Integer,Description="Difference in length between REF and ALT alleles">',
+    '##INFO=<ID=SUPPORT,Number=1,Type=Integer,Description="Number of reads supporting this variant">',
+    '##INFO=<ID=READS,Number=.,Type=String,Description="Names of the supporting reads">',
+    '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">',
+    '##FORMAT=<ID=DP,Number=1,Type=Integer,Description="Read depth">',
+    '##FORMAT=<ID=AD,Number=R,Type=Integer,Description="Read depth for each allele">',
+))
+CALLSET_COLS = '\t'.join(('#CHROM', 'POS', 'ID', 'REF', 'ALT', 'QUAL', 'FILTER', 'INFO', 'FORMAT', 'SAMPLE')) + '\n'
+
+
+def callset_header_text(home, chroms):
+    return '##fileformat=VCFv4.2\n##source=duet_amd svim-gpu\n' + contig_lines(home, chroms) + CALLSET_INFO + CALLSET_COLS
+
+
+def callset_path(home):
+    return os.path.join(home, 'sv_calling', 'variants.vcf')
+
+
+def write_callset(home, chroms, rows):
+    """<home>/sv_calling/variants.vcf: header + the rows (bytes or a uint8 array), replacing any old file."""
+    os.makedirs(os.path.join(home, 'sv_calling'), exist_ok=True)
+    with open(callset_path(home), 'wb') as out:
+        out.write(callset_header_text(home, chroms).encode())
+        out.write(rows)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -147,30 +221,47 @@ def unpack_records(rec):
                 support=rec[:, 3].astype(np.int64), ps=rec[:, 4].copy())
 
 
+def part_path(home, rank):
+    """Where a rank of a sharded --write_sv_calls run leaves its contigs' callset rows for rank 0 (removed by rank 0)."""
+    return os.path.join(home, 'sv_calling', 'variants.vcf.rank%d.part' % rank)
+
+
 def rank_body(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist, rank, world, compute, to_device=None,
-              star=None, gather=None):
+              star=None, gather=None, write_sv_calls=False):
     """One rank of the sharded SVIM mode.  compute as in phase_from_bams.  Rank 0 appends the rows to the file that
     already holds the header.  -> exit code (5: division by zero on some rank).
     star / gather (duet_amd/comm.py; round 4): how many candidates a rank finds is a result, not an input, so the ranks first
     tell each other their counts -- 16 bytes each, a control message over the TCP star that also carried RCCL's id -- and then
     ONE all-gather (gather.allgather: RCCL inside libduet_ef.so, or the star in the one-GPU plumbing mode) moves the fixed-size
     candidate records.  Without them: torch.distributed's default group for both (the CPU tests over gloo, DUET_COMM=torch);
-    to_device: where its tensors live."""
+    to_device: where its tensors live.
+    write_sv_calls: every rank writes its contigs' callset rows (part_path) BEFORE the exchange of the counts; rank 0 then
+    writes phased_sv.vcf whole (the parent wrote no header) and assembles sv_calling/variants.vcf from the parts
+    (status 6: a read name that READS= cannot hold, on some rank -- nothing is written)."""
     from duet_amd import dist as D
     chroms = init_chrom_list(include_all_ctgs, home)
     owned = D.lpt_assign(bam_weights(home, chroms), world)
     status, res = 0, None
     try:
         res = phase_from_bams(home, svlen_thres, suppread_thres, max(1, int(thread) // world), include_all_ctgs,
-                              max_dist=max_dist, min_sv_size=max(int(svlen_thres), 1), only=set(owned[rank]), compute=compute)
+                              max_dist=max_dist, min_sv_size=max(int(svlen_thres), 1), only=set(owned[rank]), compute=compute,
+                              names=write_sv_calls)
     except ZeroDivisionError:
         status = 5
+    except ReadNameError as e:
+        logging.error(str(e))
+        status, res = 6, None
+    if write_sv_calls and status == 0:
+        os.makedirs(os.path.join(home, 'sv_calling'), exist_ok=True)
+        with open(part_path(home, rank), 'wb') as f:
+            f.write(res['calls'])
+    merge = lambda g, counts: _merge_and_write(home, chroms, g, counts, world, owned if write_sv_calls else None)
     rec = pack_records(res) if res is not None else np.zeros((0, REC_WORDS), dtype=np.uint32)
     if gather is not None:
         mine = np.array([len(rec), status, res['n_marks'] if res is not None else 0, 0], dtype=np.int32)
         counts = np.frombuffer(b''.join(star.allgather(mine.tobytes())), dtype=np.int32).reshape(world, 4)
         if int(counts[:, 1].max()) != 0:
-            return 5
+            return _failed(home, rank, world, counts, write_sv_calls)
         n_max = max(int(counts[:, 0].max()), 1)
         slot = np.zeros(n_max * REC_WORDS, dtype=np.uint32)
         slot[:rec.size] = rec.reshape(-1)
@@ -178,7 +269,7 @@ def rank_body(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_d
         if rank != 0:
             return 0
         g = np.ascontiguousarray(g).view(np.uint32).reshape(world, n_max, REC_WORDS)
-        return _merge_and_write(home, chroms, g, counts, world)
+        return merge(g, counts)
     import torch
     import torch.distributed as td
     dev = to_device if to_device is not None else torch.device('cpu')
@@ -187,7 +278,7 @@ def rank_body(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_d
     td.all_gather_into_tensor(counts, mine)                       # 16 bytes per rank: how large the records' slots must be
     counts = counts.cpu().numpy().reshape(world, 4)
     if int(counts[:, 1].max()) != 0:
-        return 5
+        return _failed(home, rank, world, counts, write_sv_calls)
     n_max = max(int(counts[:, 0].max()), 1)
     slot = torch.zeros(n_max * REC_WORDS, dtype=torch.int32, device=dev)
     if len(rec):
@@ -197,11 +288,49 @@ def rank_body(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_d
     if rank != 0:
         return 0
     g = gathered.cpu().numpy().view(np.uint32).reshape(world, n_max, REC_WORDS)
-    return _merge_and_write(home, chroms, g, counts, world)
+    return merge(g, counts)
 
 
-def _merge_and_write(home, chroms, g, counts, world):
-    """rank 0: the gathered records [world, n_max, REC_WORDS] -> rows appended to phased_sv.vcf"""
+def _failed(home, rank, world, counts, write_sv_calls):
+    """Some rank failed (status 5 or 6): rank 0 removes the callset parts every rank has written by now."""
+    if write_sv_calls and rank == 0:
+        for r in range(world):
+            if os.path.exists(part_path(home, r)):
+                os.remove(part_path(home, r))
+    return int(counts[:, 1].max())
+
+
+def _assemble_callset(home, chroms, owned, merged, world):
+    """rank 0: sv_calling/variants.vcf from the ranks' parts.  A part holds its rank's contigs in contig-list order, and the
+    first row of contig k is the one whose ID is svim_gpu.<CHROM>.1; the contigs are written in contig-list order."""
+    texts = spelled_contigs(home, chroms)
+    has_rows = np.bincount(merged['cand_contig'].astype(np.int64), minlength=len(chroms)) > 0
+    data, block = [], {}
+    for r in range(world):
+        with open(part_path(home, r), 'rb') as f:
+            data.append(f.read())
+        starts, at = [], 0
+        for k in sorted(owned[r]):
+            if has_rows[k]:
+                i = data[r].find(('\tsvim_gpu.%s.1\t' % texts[k]).encode(), at)
+                starts.append((k, data[r].rfind(b'\n', 0, i) + 1))
+                at = i + 1
+        for j, (k, s0) in enumerate(starts):
+            block[k] = (r, s0, starts[j + 1][1] if j + 1 < len(starts) else len(data[r]))
+    os.makedirs(os.path.join(home, 'sv_calling'), exist_ok=True)
+    with open(callset_path(home), 'wb') as out:
+        out.write(callset_header_text(home, chroms).encode())
+        for k in range(len(chroms)):
+            if k in block:
+                r, s0, e0 = block[k]
+                out.write(memoryview(data[r])[s0:e0])
+    for r in range(world):
+        os.remove(part_path(home, r))
+
+
+def _merge_and_write(home, chroms, g, counts, world, owned=None):
+    """rank 0: the gathered records [world, n_max, REC_WORDS] -> rows appended to phased_sv.vcf.  owned (--write_sv_calls): the
+    contig -> rank assignment; phased_sv.vcf is then written whole and sv_calling/variants.vcf assembled from the parts."""
     parts = [unpack_records(g[r, :int(counts[r, 0])]) for r in range(world)]
     merged = {k: np.concatenate([p_[k] for p_ in parts]) for k in parts[0]}
     # contigs are owned whole and a rank's candidates come contig-major: a stable sort by contig is the single-GPU order
@@ -211,6 +340,12 @@ def _merge_and_write(home, chroms, g, counts, world):
     logging.info('  %d SV marks clustered into %d candidates on %d GPUs, %d phased (clustering rule: parity unpinned)' % (
         int(counts[:, 2].sum()), len(merged['pred']), world, int(np.count_nonzero(merged['pred']))))
     logging.info('write phased callset into .vcf file')
+    if owned is not None:
+        with open(home + '/phased_sv.vcf', 'w') as out:
+            out.write(header_text(home, chroms) + rows_text(home, merged))
+        logging.info('write the clustered SV calls into sv_calling/variants.vcf')
+        _assemble_callset(home, chroms, owned, merged, world)
+        return 0
     with open(home + '/phased_sv.vcf', 'a') as out:
         out.write(rows_text(home, merged))
     return 0
@@ -221,6 +356,8 @@ def rank_main(argv):
     import datetime
     home, svlen_thres, suppread_thres, thread = argv[0], int(argv[1]), int(argv[2]), int(argv[3])
     all_ctgs, max_dist = argv[4] == '1', float(argv[5])
+    write_sv_calls = len(argv) > 6 and argv[6] == '1'
+    texts = spelled_contigs(home, init_chrom_list(all_ctgs, home)) if write_sv_calls else None
     rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
     one_gpu = os.environ.get('DUET_ONE_GPU') == '1'
     device_id = 0 if one_gpu else int(os.environ.get('LOCAL_RANK', rank))
@@ -236,8 +373,8 @@ def rank_main(argv):
         gather = None
         try:
             gather = comm.HostGather(star) if one_gpu else comm.RcclGather(ctx, star)
-            return rank_body(home, svlen_thres, suppread_thres, thread, all_ctgs, max_dist, rank, world, host_compute(ctx),
-                             star=star, gather=gather)
+            return rank_body(home, svlen_thres, suppread_thres, thread, all_ctgs, max_dist, rank, world, host_compute(ctx, texts),
+                             star=star, gather=gather, write_sv_calls=write_sv_calls)
         finally:
             if gather is not None:
                 gather.close()
@@ -256,31 +393,34 @@ def rank_main(argv):
         td.init_process_group('nccl', rank=rank, world_size=world, device_id=torch.device('cuda', device_id), timeout=limit)
     try:
         ctx = _lib.Context(device_id)                    # raises when libduet_ef.so / the GPU is missing: no fallback
-        return rank_body(home, svlen_thres, suppread_thres, thread, all_ctgs, max_dist, rank, world, device_compute(ctx),
-                         to_device=None if one_gpu else torch.device('cuda', device_id))
+        return rank_body(home, svlen_thres, suppread_thres, thread, all_ctgs, max_dist, rank, world, device_compute(ctx, texts),
+                         to_device=None if one_gpu else torch.device('cuda', device_id), write_sv_calls=write_sv_calls)
     finally:
         td.destroy_process_group()
 
 
 def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, cluster_max_distance=0.9, device=0,
-                         gpus=1):
+                         gpus=1, write_sv_calls=False):
     """`duet ... -b svim-gpu -c <max distance>`: SV calling (signatures + clustering, what `-b svim` delegates to the
     external `svim alignment ... --cluster_max_distance c`, sv_calling.py:13-15) AND SV phasing on the GPU, from the
     haplotagged BAMs of <home>/snp_phasing -> <home>/phased_sv.vcf.  The clustering half is this repository's own rule
-    (parity unpinned); step E/F is the pinned one."""
+    (parity unpinned); step E/F is the pinned one.
+    write_sv_calls (--write_sv_calls): also every clustered candidate -> <home>/sv_calling/variants.vcf (DESIGN.md section 15);
+    the marks' read names are extracted and checked first, and no file is written before they pass."""
     bar = '*' * 25
     logging.info('%s SV CALLING + PHASING (GPU, svim-gpu) STARTED %s' % (bar, bar))
     t0 = time.time()
-    logging.info('create output .vcf file')
     chroms = init_chrom_list(include_all_ctgs, home)
     out_vcf = home + '/phased_sv.vcf'
-    with open(out_vcf, 'w') as out:
-        out.write(header_text(home, chroms))
+    if not write_sv_calls:
+        logging.info('create output .vcf file')
+        with open(out_vcf, 'w') as out:
+            out.write(header_text(home, chroms))
     logging.info('extract SNP and SV signatures from the haplotagged alignments')
     if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':       # (see sv_phasing.py)
         from duet_amd import launch
         argv = ['-m', 'duet_amd.svim_mode', home, str(int(svlen_thres)), str(int(suppread_thres)), str(int(thread)),
-                '1' if include_all_ctgs else '0', repr(float(cluster_max_distance))]
+                '1' if include_all_ctgs else '0', repr(float(cluster_max_distance))] + (['1'] if write_sv_calls else [])
         env = {'PYTHONPATH': os.pathsep.join([os.path.dirname(os.path.dirname(os.path.abspath(__file__)))] +
                                              ([os.environ['PYTHONPATH']] if os.environ.get('PYTHONPATH') else []))}
         for h in logging.getLogger().handlers:
@@ -290,17 +430,34 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
         rc = launch.spawn_ranks(int(gpus), argv, extra_env=env, timeout=float(os.environ.get('DUET_RANK_TIMEOUT', '3600')))
         if rc == 5:
             raise ZeroDivisionError('division by zero')
+        if rc == 6:
+            raise ReadNameError('svim-gpu on %d GPUs: a read name contains "," or ";" and cannot be listed in READS= of '
+                             'sv_calling/variants.vcf (the rank that found it logged its name)' % int(gpus))
         if rc == 124:
             raise RuntimeError('svim-gpu on %d GPUs: the ranks did not finish within DUET_RANK_TIMEOUT; they were killed' % int(gpus))
         if rc:
             raise RuntimeError('svim-gpu on %d GPUs failed: a rank exited with code %d' % (int(gpus), rc))
         logging.info('%s SV CALLING + PHASING COMPLETED IN %ss %s' % (bar, round(time.time() - t0, 3), bar))
         return
-    res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
-                          min_sv_size=max(int(svlen_thres), 1), ctx=engine.default_context(int(device)))
+    if write_sv_calls:
+        # (the names are checked inside, before the device runs and before any file is written)
+        def compute(*args):
+            return device_compute(engine.default_context(int(device)), spelled_contigs(home, chroms))(*args)
+        res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
+                              min_sv_size=max(int(svlen_thres), 1), names=True, compute=compute)
+    else:
+        res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
+                              min_sv_size=max(int(svlen_thres), 1), ctx=engine.default_context(int(device)))
     logging.info('  %d SV marks clustered into %d candidates, %d phased (clustering rule: parity unpinned)' % (
         res['n_marks'], len(res['pred']), int(np.count_nonzero(res['pred']))))
     logging.info('write phased callset into .vcf file')
+    if write_sv_calls:
+        with open(out_vcf, 'w') as out:
+            out.write(header_text(home, chroms) + rows_text(home, res))
+        logging.info('write the clustered SV calls into sv_calling/variants.vcf')
+        write_callset(home, chroms, res['calls'])
+        logging.info('%s SV CALLING + PHASING COMPLETED IN %ss %s' % (bar, round(time.time() - t0, 3), bar))
+        return
     with open(out_vcf, 'a') as out:
         out.write(rows_text(home, res))
     logging.info('%s SV CALLING + PHASING COMPLETED IN %ss %s' % (bar, round(time.time() - t0, 3), bar))

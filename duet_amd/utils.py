@@ -49,6 +49,8 @@ def build_parser():
     ap.add_argument('--thresholds', type=str, default=None,
                     help='JSON object of T1-T5 threshold values (duet_amd/tune.py names; the others keep their defaults) for the '
                          'SV phasing decision; single-GPU native path only')
+    ap.add_argument('--write_sv_calls', action='store_true',
+                    help='with -b svim-gpu, also write the clustered SV calls to OUTPUT/sv_calling/variants.vcf')
     for name, text in _POSITIONALS:
         ap.add_argument(name, type=str, help=text)
     return ap

@@ -272,6 +272,40 @@ DUET_API int duet_svim_phase_host(duet_ctx *ctx, const duet_svim_problem *prob, 
                          uint8_t *out_pred, uint32_t *out_ps);
 
 /* ---------------------------------------------------------------------------------------------
+ * Rows of sv_calling/variants.vcf in the svim-gpu mode (duet_callset.hip): one row per candidate of a
+ * cluster result, in its order (contig-major, then type, then centre), phased or not -- this repository's own dialect modelled
+ * on SVIM's:
+ *     CHROM POS svim_gpu.<CHROM>.<i> N <T> . PASS SVTYPE=T;END=e;SVLEN=l;SUPPORT=n;READS=r1,...,rn GT:DP:AD gt:DP:ref,n
+ * i = the row's 1-based number within its contig; T = DEL, INS, INV, DUP for type codes 0-3 (any other code: DUET_ERR_INVALID);
+ * e = POS for INS, POS + span otherwise; l = -span for DEL, +span otherwise; n = member count; READS = the members' read names in
+ * cluster order (res->order); ref = max(depth(contig, POS) - n, 0) as the fused adapter computes it (bin min(POS / depth_bin,
+ * bins - 1), 0 on a contig without bins); DP = n + ref; gt = 1/1 if 5n >= 4 DP, else 0/1 if 5n >= DP, else 0/0.
+ * The header lines stay with the host.
+ * ---------------------------------------------------------------------------------------------------------------------- */
+typedef struct duet_callset_names {
+    const uint32_t *mark_name;      /* [M] per RAW mark (the order of prob->marks, like mark_read): index into name_off */
+    const uint64_t *name_off;       /* [n_names + 1] name j = name_pool[name_off[j] .. name_off[j + 1]) */
+    const char *name_pool;
+    uint32_t n_names;
+    uint32_t n_contigs;             /* must equal prob->n_contigs */
+    const char *const *chrom;       /* [K] HOST: the CHROM text of every contig, NUL-terminated */
+} duet_callset_names;
+
+/* From *prob: depth, depth_off (HOST), depth_bin, n_contigs, marks.n_marks; from *res: order, cand_off, cand_contig, cand_type,
+ * cand_pos, cand_span for n_cands candidates (res->n_cands is not read).
+ * _device: device arrays (as duet_svim_phase_device leaves them), out_text device; asynchronous on `stream` apart from one host
+ * round trip that learns the text's size.  _host: every array of *prob, *res and *names is HOST memory (res->order [M],
+ * cand_off [n_cands + 1]); uploads, runs the same kernels, copies the text to out_text (host), synchronises.
+ * Both: *out_len = the text's exact size; when out_cap is smaller nothing is written and the call returns DUET_ERR_INVALID.
+ * A bound the caller can compute from its inputs: n_cands * (2 * longest CHROM text + 168) + sum over the members of
+ * (name length + 1) -- e.g. M * (longest name + 1). */
+DUET_API int duet_svim_vcf_rows_device(duet_ctx *ctx, const duet_svim_problem *prob, const duet_cluster_result *res, uint32_t n_cands,
+                                       const duet_callset_names *names, char *out_text, uint64_t out_cap, uint64_t *out_len,
+                                       void *stream);
+DUET_API int duet_svim_vcf_rows_host(duet_ctx *ctx, const duet_svim_problem *prob, const duet_cluster_result *res, uint32_t n_cands,
+                                     const duet_callset_names *names, char *out_text, uint64_t out_cap, uint64_t *out_len);
+
+/* ---------------------------------------------------------------------------------------------
  * Rows of phased_sv.vcf on the device: from (pred, ps) to the text of the data rows.
  * Replaces, for the rows: the emission order of src/duet/sv_phasing_fn.py:204-228 (contig order, PS-class 0/1/2,
  * file order, pred 0 dropped), the stable sort of :229 (CHROM as text, POS as int), print_sv of

@@ -130,6 +130,21 @@ typedef struct duet_ingest_marks {      /* views into memory owned by the duet_i
 } duet_ingest_marks;
 int duet_ingest_get_marks(duet_ingest *ing, duet_ingest_marks *out);
 
+/* Read names of the raw marks (what sv_calling/variants.vcf lists in READS=; duet_svim_vcf_rows_* of duet_ef.h).  Opt-in: call
+ * duet_ingest_keep_mark_names(ing, 1) BEFORE the BAMs are added (DUET_INGEST_INVALID once marks exist); without it the extraction
+ * keeps no names and duet_ingest_get_mark_names returns DUET_INGEST_INVALID.  Names are interned per contig: mark_name[i] is the
+ * name of mark i of duet_ingest_get_marks (same order), an index into name_off; name n is name_pool[name_off[n] .. name_off[n + 1]).
+ * A read that supplies marks on two contigs has one entry per contig. */
+typedef struct duet_ingest_mark_names {  /* views into memory owned by the duet_ingest object */
+    uint32_t n_marks, n_names;
+    const uint32_t *mark_name;          /* [M] */
+    const uint64_t *name_off;           /* [n_names + 1] */
+    const char *name_pool;              /* [pool_bytes] */
+    uint64_t pool_bytes;
+} duet_ingest_mark_names;
+int duet_ingest_keep_mark_names(duet_ingest *ing, int enable);
+int duet_ingest_get_mark_names(duet_ingest *ing, duet_ingest_mark_names *out);
+
 #ifdef __cplusplus
 }
 #endif
