@@ -155,8 +155,9 @@ class DeviceSvim(DeviceCluster):
     """Fused SVIM-mode pipeline on resident inputs: raw marks (+ their read indices), read tags, binned depth."""
 
     def __init__(self, marks, read_tag, depth, depth_off, depth_bin=1000, svlen_thres=50, suppread_thres=2,
-                 max_dist=0.9, device='cuda:0'):
-        DeviceCluster.__init__(self, marks, max_dist=max_dist, device=device)
+                 max_dist=0.9, part_gap=1000, part_max=100, normalizer=900.0, device='cuda:0'):
+        DeviceCluster.__init__(self, marks, max_dist=max_dist, part_gap=part_gap, part_max=part_max, normalizer=normalizer,
+                               device=device)
         torch = self.torch
 
         def up(a, dt):

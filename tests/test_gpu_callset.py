@@ -70,12 +70,46 @@ def extracted(home, chroms):
     return got
 
 
+def host_rows(ctx, res, n_marks, names, depth, depth_off, depth_bin, texts, cap=None):
+    """duet_svim_vcf_rows_host on the given host arrays, the output pre-filled -> (rc, out_len, the whole buffer)."""
+    arr = {k: np.ascontiguousarray(res[k], dtype=dt) for k, dt in (
+        ('order', np.uint32), ('cand_off', np.uint32), ('cand_contig', np.uint16), ('cand_type', np.uint8),
+        ('cand_pos', np.uint32), ('cand_span', np.uint32))}
+    r = _lib.ClusterResult()
+    for k in arr:
+        setattr(r, k, arr[k].ctypes.data)
+    depth = np.ascontiguousarray(depth, dtype=np.uint32)
+    depth_off = np.ascontiguousarray(depth_off, dtype=np.uint32)
+    p = _lib.SvimProblem()
+    p.marks.n_marks = int(n_marks)
+    p.n_contigs = len(depth_off) - 1
+    p.depth = depth.ctypes.data if depth.size else None
+    p.depth_off, p.depth_bin = depth_off.ctypes.data, int(depth_bin)
+    hold = []
+    name_off = np.ascontiguousarray(names['name_off'], dtype=np.uint64)
+    nm = _lib.callset_names(np.ascontiguousarray(names['mark_name'], dtype=np.uint32), name_off,
+                            np.ascontiguousarray(names['name_pool'], dtype=np.uint8), texts, hold)
+    nm.n_names = len(name_off) - 1
+    N = len(arr['cand_pos'])
+    cap = _lib.callset_bound(N, n_marks, name_off, texts) if cap is None else cap
+    out = np.full(max(cap, 1) + 64, 0xAB, dtype=np.uint8)
+    n = ctypes.c_uint64(0)
+    rc = ctx.lib.duet_svim_vcf_rows_host(ctx.handle, ctypes.byref(p), ctypes.byref(r), N, ctypes.byref(nm), out.ctypes.data,
+                                         ctypes.c_uint64(cap), ctypes.byref(n))
+    return rc, n.value, out
+
+
 def check_both(ctx, res, got, texts, depth_bin=1000):
     want = callset_ref.rows(res, callset_ref.names_of(got), got['depth'], got['depth_off'], depth_bin, texts).encode()
     M = len(got['mark_name'])
+    # the bound a caller allocates (include/duet_ef.h) holds the text
+    assert len(want) <= _lib.callset_bound(len(res['cand_pos']), M, got['name_off'], texts)
     host = ctx.svim_vcf_rows_host(res, M, got['mark_name'], got['name_off'], got['name_pool'], got['depth'], got['depth_off'],
                                   depth_bin, texts)
     assert host == want
+    rc, n, out = host_rows(ctx, res, M, got, got['depth'], got['depth_off'], depth_bin, texts)
+    assert rc == 0 and n == len(want)
+    assert out[:n].tobytes() == want and (out[n:] == 0xAB).all()
     rc, n, out = device_rows(ctx, res, M, got, got['depth'], got['depth_off'], depth_bin, texts)
     assert rc == 0 and n == len(want)
     assert out[:n].tobytes() == want and (out[n:] == 0xAB).all()
@@ -194,3 +228,158 @@ def test_round_trip_through_the_vcf_path_and_sharded_run(ctx, tmp_path):
     assert open(svim_mode.callset_path(home), 'rb').read() == calls
     assert open(home + '/phased_sv.vcf', 'rb').read() == plain
     assert sorted(os.listdir(os.path.join(home, 'sv_calling'))) == ['variants.vcf']
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The rows at their extremes: hand-made cluster results (duet_svim_vcf_rows_* take any), no clustering.  Sizes covered: members
+# per row around cs_write's rounds of 64 names, name lengths around its 64-lane copy steps, numbers at digit boundaries, row
+# counts around kCsTile and the 32768-row step of the 8192-workgroup grid-stride loop.  NOT covered: a text of 4 GiB or more
+# (the 64-bit scan's high word, flag bit 1) -- it costs too much memory and time for this suite.
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def handmade(members, names, name_of=None, contig=None, types=None, pos=None, span=None, depth=None, depth_off=None, K=1, seed=1):
+    """Rows of members[i] marks each -> (res, got).  names: the read-name table (bytes); name_of(i, j) -> the name index of row
+    i's j-th member (default: round robin); order is a shuffle of the raw marks, so that the rows depend on it."""
+    rng = np.random.default_rng(seed)
+    members = np.asarray(members, dtype=np.int64)
+    N, M = len(members), int(members.sum())
+    off = np.concatenate([[0], np.cumsum(members)])
+    order = rng.permutation(M).astype(np.uint32)
+    by_slot = np.arange(M) % max(len(names), 1) if name_of is None else \
+        np.array([name_of(i, j) for i in range(N) for j in range(int(members[i]))], dtype=np.int64)
+    mark_name = np.zeros(M, dtype=np.uint32)
+    mark_name[order] = by_slot                                  # slot s of the cluster order holds raw mark order[s]
+    lens = np.array([len(x) for x in names], dtype=np.uint64)
+    got = dict(mark_name=mark_name, name_off=np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64),
+               name_pool=np.frombuffer(b''.join(names) + b'\0', dtype=np.uint8).copy()[:-1] if sum(map(len, names)) else np.zeros(0, np.uint8),
+               depth=np.asarray([30] * 8 if depth is None else depth, dtype=np.uint32),
+               depth_off=np.asarray([0] + [8] * K if depth_off is None else depth_off, dtype=np.uint32))
+    res = dict(order=order, cand_off=off.astype(np.uint32),
+               cand_contig=np.asarray(np.zeros(N) if contig is None else contig, dtype=np.uint16),
+               cand_type=np.asarray(np.arange(N) % 4 if types is None else types, dtype=np.uint8),
+               cand_pos=np.asarray(1000 + 10 * np.arange(N) if pos is None else pos, dtype=np.uint32),
+               cand_span=np.asarray(50 + np.arange(N) % 700 if span is None else span, dtype=np.uint32))
+    return res, got
+
+
+NAMES = [b'rd%d_%x' % (i, i * 2654435761 % 1000003) for i in range(300)]           # 5-14 bytes
+
+
+@pytest.mark.parametrize('n', [1, 63, 64, 65, 127, 128, 129, 200, 1000])
+def test_extreme_members_per_row(ctx, n):
+    """the header does not limit a row to part_max members: cs_write places the names 64 at a time"""
+    res, got = handmade([3, n, 2, n, 1], NAMES, seed=n)
+    want = check_both(ctx, res, got, ['chr1'])
+    assert want.count(b'\n') == 5 and want.split(b'\n')[1].count(b',') == n      # (n - 1 between the names, one in AD)
+    if n == 1000:
+        # out_cap one byte short on the largest row: nothing written, DUET_ERR_INVALID, the exact size reported -- by both entries
+        M = len(got['mark_name'])
+        for fn in (host_rows, device_rows):
+            rc, size, out = fn(ctx, res, M, got, got['depth'], got['depth_off'], 1000, ['chr1'], cap=len(want) - 1)
+            assert rc == _lib.DUET_ERR_INVALID and size == len(want) and (out == 0xAB).all(), fn.__name__
+
+
+@pytest.mark.parametrize('L', [0, 1, 63, 64, 65, 300])
+def test_extreme_name_lengths(ctx, L):
+    """names of L bytes between ordinary ones: the copy loops stride 64 lanes"""
+    names = NAMES[:7] + [bytes(97 + (i + k) % 26 for i in range(L)) for k in range(3)]
+    res, got = handmade([1, 2, 5, 70, 3], names, name_of=lambda i, j: (7 + j % 3) if (i + j) % 2 == 0 else j % 7, seed=L)
+    check_both(ctx, res, got, ['chr1'])
+
+
+def test_extreme_rows_of_empty_and_repeated_names(ctx):
+    names = [b'', b'ab', b'', b'read_twice']
+    pick = {0: lambda j: 0, 1: lambda j: 2 * (j % 2), 2: lambda j: 3, 3: lambda j: (0, 3, 3, 1, 0)[j % 5], 4: lambda j: 0}
+    res, got = handmade([1, 66, 2, 130, 5], names, name_of=lambda i, j: pick[i](j))
+    want = check_both(ctx, res, got, ['chr1']).split(b'\n')
+    assert b';READS=\t' in want[0] and b';READS=' + b',' * 65 + b'\t' in want[1] and b';READS=,,,,\t' in want[4]
+    assert b';READS=read_twice,read_twice\t' in want[2]
+
+
+def test_extreme_numbers_at_digit_boundaries(ctx):
+    big = 0xFFFFFFFF
+    pos = [0, 9, 10, 999999999, 1000000000, big, big, 5, 5]
+    span = [50, 50, 50, 50, 50, big, big, 0, 0]
+    types = [0, 1, 2, 3, 0, 0, 1, 0, 1]
+    res, got = handmade([2] * 9, NAMES, pos=pos, span=span, types=types)
+    want = check_both(ctx, res, got, ['chr1']).split(b'\n')
+    assert want[5].startswith(b'chr1\t4294967295\t') and b';END=8589934590;SVLEN=-4294967295;' in want[5]
+    assert b';END=4294967295;SVLEN=4294967295;' in want[6]
+    assert b'<DEL>' in want[7] and b';SVLEN=0;' in want[7] and b';SVLEN=0;' in want[8]
+    assert want[0].startswith(b'chr1\t0\t') and b';END=50;SVLEN=-50;' in want[0]
+
+
+def test_extreme_row_numbers_cross_their_digit_counts(ctx):
+    """9 -> 10, 99 -> 100, 99999 -> 100000 within one contig; the numbering restarts on the next occupied contig behind empty ones"""
+    N0 = 100003
+    contig = [0] * N0 + [3] * 12 + [4]
+    res, got = handmade([1] * len(contig), NAMES[:5], contig=contig, K=6)
+    want = check_both(ctx, res, got, ['c%d' % k for k in range(6)]).split(b'\n')
+    for i in (9, 10, 99, 100, 99999, 100000, N0):
+        assert b'\tsvim_gpu.c0.%d\t' % i in want[i - 1]
+    assert b'\tsvim_gpu.c3.1\t' in want[N0] and b'\tsvim_gpu.c3.10\t' in want[N0 + 9] and b'\tsvim_gpu.c4.1\t' in want[N0 + 12]
+
+
+def test_extreme_genotype_boundaries(ctx):
+    """(n, depth): 5n against 4 DP and against DP, one below / on / one above; depth below n, equal to n, 2^32 - 1"""
+    pairs = [(3, 4, b'0/1'), (4, 5, b'1/1'), (5, 6, b'1/1'),                   # 5n = 4 DP - 1, 4 DP, 4 DP + 1
+             (1, 6, b'0/0'), (1, 5, b'0/1'), (1, 4, b'0/1'),                   # 5n = DP - 1, DP, DP + 1
+             (7, 9, b'0/1'), (8, 10, b'1/1'), (9, 11, b'1/1'), (2, 11, b'0/0'), (2, 10, b'0/1'), (2, 9, b'0/1'),
+             (5, 2, b'1/1'), (5, 5, b'1/1'), (5, 0, b'1/1'), (3, 0xFFFFFFFF, b'0/0'), (64, 80, b'1/1'), (63, 79, b'0/1')]
+    for n, d, gt in pairs:                                                     # (the table itself, by the rule of the header)
+        dp = n + max(d - n, 0)
+        assert gt == (b'1/1' if 5 * n >= 4 * dp else (b'0/1' if 5 * n >= dp else b'0/0'))
+    res, got = handmade([n for n, _, _ in pairs], NAMES, pos=[7 * i + 3 for i in range(len(pairs))],
+                        depth=[d for _, d, _ in pairs], depth_off=[0, len(pairs)])
+    want = check_both(ctx, res, got, ['chr1'], depth_bin=7).split(b'\n')
+    for i, (n, d, gt) in enumerate(pairs):
+        dp = max(n, d)
+        assert want[i].endswith(b'\tGT:DP:AD\t%s:%d:%d,%d' % (gt, dp, dp - n, n)), (i, want[i][-40:])
+
+
+@pytest.mark.parametrize('depth_bin', [1, 7, 0xFFFFFFFF])
+def test_extreme_depth_bins(ctx, depth_bin):
+    """bins of 1 bp, 7 bp and 2^32 - 1 bp; POS / depth_bin beyond the contig's bins (the last bin counts); a contig without bins"""
+    nb = [5, 0, 3, 1]
+    depth = [11, 12, 13, 14, 99, 21, 22, 77, 55]
+    contig = [0] * 6 + [1] * 2 + [2] * 4 + [3] * 2
+    pos = [0, depth_bin - 1, depth_bin, 4 * min(depth_bin, 1 << 29), 5 * min(depth_bin, 1 << 29), 0xFFFFFFFF, 0, 0xFFFFFFFF,
+           0, 2 * min(depth_bin, 1 << 30), 3 * min(depth_bin, 1 << 30), 0xFFFFFFFF, 0, 0xFFFFFFFF]
+    res, got = handmade([2] * len(contig), NAMES, contig=contig, pos=pos, depth=depth, depth_off=np.concatenate([[0], np.cumsum(nb)]),
+                        K=4)
+    want = check_both(ctx, res, got, ['a', 'b', 'c', 'd'], depth_bin=depth_bin).split(b'\n')
+    wide = depth_bin == 0xFFFFFFFF                                               # (POS 2^32 - 1 is then in bin 1)
+    assert want[5].endswith(b':12:10,2' if wide else b':99:97,2')                # beyond contig a's five bins: its last one
+    assert want[6].endswith(b'1/1:2:0,2') and want[7].endswith(b'1/1:2:0,2')     # contig b has no bins
+    assert want[11].endswith(b':22:20,2' if wide else b':77:75,2') and want[13].endswith(b':55:53,2')
+
+
+def test_extreme_chrom_texts(ctx):
+    texts = ['', 'x', 'c' * 64, 'd' * 65, 'e' * 200, 'unused']
+    contig = [0, 0, 1, 1, 2, 2, 3, 3, 4, 4]
+    res, got = handmade([1, 2, 3, 64, 65, 1, 2, 3, 4, 5], NAMES, contig=contig, K=6)
+    want = check_both(ctx, res, got, texts).split(b'\n')
+    assert want[0].startswith(b'\t1000\tsvim_gpu..1\t') and want[9].startswith(b'e' * 200 + b'\t1090\tsvim_gpu.' + b'e' * 200 + b'.2\t')
+
+
+@pytest.mark.parametrize('N', [1, 2047, 2048, 2049, 32768, 32769, 40000])
+def test_extreme_row_counts(ctx, N):
+    """short rows across kCsTile (2048 rows per scan tile) and the 32768 rows one sweep of cs_write's 8192 workgroups takes"""
+    rng = np.random.default_rng(N)
+    contig = np.sort(rng.integers(0, 3, N))
+    res, got = handmade(1 + (np.arange(N) % 3 == 0), NAMES[:50], contig=contig, K=3, seed=N)
+    want = check_both(ctx, res, got, ['chr1', 'chr2', 'chrX'])
+    assert want.count(b'\n') == N
+
+
+def test_extreme_type_code_4_is_refused_by_both_entries(ctx):
+    for at in (0, 2500):
+        types = np.arange(3000) % 4
+        res, got = handmade([1] * 3000, NAMES[:9], types=types)
+        res['cand_type'][at] = 4
+        with pytest.raises(ValueError):
+            callset_ref.rows(res, callset_ref.names_of(got), got['depth'], got['depth_off'], 1000, ['chr1'])
+        M = len(got['mark_name'])
+        for fn in (host_rows, device_rows):
+            rc, n, out = fn(ctx, res, M, got, got['depth'], got['depth_off'], 1000, ['chr1'])
+            assert rc == _lib.DUET_ERR_INVALID and (out == 0xAB).all(), (fn.__name__, at)

@@ -12,32 +12,18 @@ import pytest
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from duet_amd import engine, launch, svim_mode, synth
-from oracle import c_oracle
+from duet_amd import launch, svim_mode, synth
 from tests import helpers as H
+from tests import svim_ref
 
 
 def oracle_compute(got, svlen_thres, suppread_thres, max_dist, depth_bin):
-    """The fused pipeline's contract (include/duet_ef.h: duet_svim_phase_device) on the CPU."""
-    K = len(got['depth_off']) - 1
-    cl = c_oracle.cluster(got['contig'], got['type'], got['pos'], got['span'], max_dist=max_dist)
-    N = len(cl['cand_pos'])
-    off = cl['cand_off'].astype(np.int64)
-    support = np.diff(off)
-    k = cl['cand_contig'].astype(np.int64)
-    depth, depth_off = got['depth'], got['depth_off'].astype(np.int64)
-    nb = np.diff(depth_off)[k]
-    bins = np.minimum(cl['cand_pos'].astype(np.int64) // depth_bin, np.maximum(nb - 1, 0))
-    d = np.where(nb > 0, depth[np.minimum(depth_off[k] + bins, max(len(depth) - 1, 0))] if len(depth) else 0, 0).astype(np.int64)
-    soa = engine.EfSoA(cand_ctg_off=np.searchsorted(k, np.arange(K + 1)), read_tag=got['read_tag'],
-                       cand_pos=cl['cand_pos'], cand_svlen=cl['cand_span'], cand_svread=support,
-                       cand_refread=np.maximum(d - support, 0), cand_gt_ok=np.ones(N, dtype=np.uint8),
-                       cand_off=off, mark_read=got['read'][cl['order']])
-    rc, pred, ps = c_oracle.ef(soa, svlen_thres, suppread_thres)
-    if rc:
+    """The fused pipeline's contract (include/duet_ef.h: duet_svim_phase_device) on the CPU: tests/svim_ref.py."""
+    want = svim_ref.fused(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, svlen_thres, suppread_thres,
+                          max_dist=max_dist)
+    if want['rc']:
         raise ZeroDivisionError('division by zero')
-    return dict(cand_contig=cl['cand_contig'], cand_type=cl['cand_type'], cand_pos=cl['cand_pos'], cand_span=cl['cand_span'],
-                support=support, pred=pred, ps=ps)
+    return {f: want[f] for f in ('cand_contig', 'cand_type', 'cand_pos', 'cand_span', 'support', 'pred', 'ps')}
 
 
 def _worker(rank, world, port, home, out_dir):
