@@ -30,7 +30,7 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_comm_allgather_host', 'duet_comm_destroy', 'duet_comm_set_timeout', 'duet_comm_block_bytes',
            'duet_comm_ef_allgather', 'duet_comm_rccl_version', 'duet_comm_info', 'duet_comm_selftest',
            'duet_ef_features_device', 'duet_ef_features_host', 'duet_tune_sweep_device', 'duet_tune_sweep_host',
-           'duet_svim_vcf_rows_device', 'duet_svim_vcf_rows_host')
+           'duet_svim_vcf_rows_device', 'duet_svim_vcf_rows_host', 'duet_svim_phased_rows_device', 'duet_svim_phased_rows_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -80,6 +80,17 @@ def callset_bound(n_cands, n_marks, name_off, chrom_texts):
     longest = int(np.max(np.diff(np.asarray(name_off, dtype=np.int64)))) if len(name_off) > 1 else 0
     chrom = max([len(c.encode()) for c in chrom_texts] + [0])
     return int(n_cands) * (2 * chrom + 168) + int(n_marks) * (longest + 1) + 64
+
+
+def chrom_bytes(chrom_texts):
+    """CHROM texts as the bytes the library compares and writes (str: UTF-8, whose byte order is Python's str order)."""
+    return [c if isinstance(c, bytes) else c.encode() for c in chrom_texts]
+
+
+def phased_rows_bound(n_rows, chrom_texts):
+    """The size duet_svim_phased_rows_* can need at most for n_rows rows (include/duet_ef.h): a row without CHROM is at most
+    95 bytes."""
+    return int(n_rows) * (max([len(c) for c in chrom_bytes(chrom_texts)] + [0]) + 96)
 
 
 def callset_names(mark_name, name_off, name_pool, chrom_texts, keep):
@@ -218,6 +229,11 @@ def load():
         fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult), ctypes.c_uint32,
                        ctypes.POINTER(CallsetNames), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)] + \
                       ([ctypes.c_void_p] if fn is lib.duet_svim_vcf_rows_device else [])
+    for fn in (lib.duet_svim_phased_rows_device, lib.duet_svim_phased_rows_host):
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ClusterResult), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_uint32, ctypes.POINTER(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_uint64,
+                       ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)] + \
+                      ([ctypes.c_void_p] if fn is lib.duet_svim_phased_rows_device else [])
     _lib = lib
     return lib
 
@@ -467,6 +483,39 @@ class Context(object):
         if rc:
             self._raise(rc)
         return out[:n.value].tobytes()
+
+    def svim_phased_rows_device(self, result, n_cands, pred_ptr, ps_ptr, chrom_texts, out_ptr, cap, stream):
+        """duet_svim_phased_rows_device on resident arrays (DeviceSvim.phased_rows) -> (bytes written, rows)."""
+        texts = chrom_bytes(chrom_texts)
+        arr = (ctypes.c_char_p * max(len(texts), 1))(*texts)
+        n, rows = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        rc = self.lib.duet_svim_phased_rows_device(self.handle, ctypes.byref(result), int(n_cands), ctypes.c_void_p(pred_ptr),
+                                                   ctypes.c_void_p(ps_ptr), len(texts), arr, ctypes.c_void_p(out_ptr),
+                                                   ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(rows), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return n.value, rows.value
+
+    def svim_phased_rows_host(self, res, chrom_texts):
+        """duet_svim_phased_rows_host: the rows of phased_sv.vcf for host arrays (dict: cand_contig, cand_type, cand_pos, cand_span,
+        pred, ps -- e.g. the merged records of a sharded run) -> (bytes, rows)."""
+        arr = {k: np.ascontiguousarray(res[k], dtype=dt) for k, dt in (
+            ('cand_contig', np.uint16), ('cand_type', np.uint8), ('cand_pos', np.uint32), ('cand_span', np.uint32),
+            ('pred', np.uint8), ('ps', np.uint32))}
+        N = len(arr['pred'])
+        r = ClusterResult()
+        for k in ('cand_contig', 'cand_type', 'cand_pos', 'cand_span'):
+            setattr(r, k, arr[k].ctypes.data if N else None)
+        texts = chrom_bytes(chrom_texts)
+        chrom = (ctypes.c_char_p * max(len(texts), 1))(*texts)
+        cap = phased_rows_bound(int(np.count_nonzero(arr['pred'])), texts)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        n, rows = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        rc = self.lib.duet_svim_phased_rows_host(self.handle, ctypes.byref(r), N, _ptr(arr['pred']), _ptr(arr['ps']), len(texts), chrom,
+                                                 out.ctypes.data, ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(rows))
+        if rc:
+            self._raise(rc)
+        return out[:n.value].tobytes(), rows.value
 
     def eval_counts(self, arrays, refdist, ratio):
         """duet_eval_run_host: `arrays` = dict of the flat host arrays (duet_amd/evaluation.py: flatten) -> EvalCounts."""

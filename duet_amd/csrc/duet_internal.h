@@ -81,6 +81,7 @@ struct duet_ctx {
     bool pending_check = false;
     DuetOwnedBufs tune_ws;                 // threshold sweep (duet_tune.hip): E/F outputs of the feature export, sweep workspace, host-run staging
     DuetOwnedBufs callset_ws;              // svim-gpu callset rows (duet_callset.hip): workspace 0-4, host-run staging 5-14, text 15
+    DuetOwnedBufs svim_rows_ws;            // svim-gpu rows of phased_sv.vcf (duet_svim_rows.hip): workspace 0-8, host-run staging 9-14, text 15
 };
 
 extern thread_local std::string duet_g_last_error;

@@ -229,6 +229,24 @@ class DeviceSvim(DeviceCluster):
         n = ctx.svim_vcf_rows_device(self.sv_problem, self.result, N, nm, out.data_ptr(), cap, stream)
         return out[:n].cpu().numpy()
 
+    def phased_rows(self, ctx, chrom_texts, stream=None):
+        """Rows of phased_sv.vcf for the last run_fused's candidates, sorted and formatted on the device from the resident
+        cluster result and (pred, ps) (duet_svim_phased_rows_device).  chrom_texts: CHROM text per contig.
+        -> (uint8 numpy array of the text, number of rows)."""
+        torch = self.torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.n_found is None:
+            self.n_found = self.n_cands()
+        N = self.n_found
+        if N == 0:
+            return np.zeros(0, dtype=np.uint8), 0
+        cap = _lib.phased_rows_bound(N, chrom_texts)
+        out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        n, n_rows = ctx.svim_phased_rows_device(self.result, N, self.out_pred.data_ptr(), self.out_ps.data_ptr(), chrom_texts,
+                                                out.data_ptr(), cap, stream)
+        return out[:n].cpu().numpy(), n_rows
+
     def fetch(self):
         """-> dict of the cluster arrays + pred/ps, trimmed to the candidate count (synchronises)."""
         if self.n_found is None:

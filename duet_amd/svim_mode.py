@@ -17,11 +17,12 @@ from duet_amd.native import NativeIngest
 from duet_amd.read_file import init_chrom_list
 
 
-def device_compute(ctx, chrom_texts=None):
+def device_compute(ctx, chrom_texts=None, row_texts=None):
     """-> compute(extracted arrays, svlen_thres, suppread_thres, max_dist, depth_bin) -> dict of result arrays, on ctx's GPU:
     stage A0 -> adapter -> step E/F in one device pipeline (duet_svim_phase_device).  chrom_texts (CHROM text per contig): the
     extracted arrays carry the marks' read names, and the result also holds `calls`, the rows of sv_calling/variants.vcf formatted
-    on the same resident arrays (duet_svim_vcf_rows_device)."""
+    on the same resident arrays (duet_svim_vcf_rows_device).  row_texts (CHROM text per contig): the result also holds `rows` /
+    `n_rows`, the data rows of phased_sv.vcf sorted and formatted on the resident arrays (duet_svim_phased_rows_device)."""
     def compute(got, svlen_thres, suppread_thres, max_dist, depth_bin):
         from duet_amd.devmem import DeviceSvim
         ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, svlen_thres, suppread_thres,
@@ -31,6 +32,8 @@ def device_compute(ctx, chrom_texts=None):
         out = ds.fetch()
         res = dict(cand_contig=out['cand_contig'], cand_type=out['cand_type'], cand_pos=out['cand_pos'],
                    cand_span=out['cand_span'], support=np.diff(out['cand_off'].astype(np.int64)), pred=out['pred'], ps=out['ps'])
+        if row_texts is not None:
+            res['rows'], res['n_rows'] = ds.phased_rows(ctx, row_texts)
         if chrom_texts is not None:
             res['calls'] = ds.vcf_rows(ctx, got, chrom_texts)
         return res
@@ -73,7 +76,8 @@ def phase_from_bams(home, svlen_thres=50, suppread_thres=2, thread=4, include_al
     only: the contig indices to read (a rank of a sharded run; the contig numbering stays the whole list's);
     compute: what turns the extracted arrays into results (default: the GPU pipeline on ctx);
     names (--write_sv_calls): the marks' read names are extracted and checked before anything runs on the device, and the
-    result also holds `calls`, the rows of sv_calling/variants.vcf (a compute made with chrom_texts)."""
+    result also holds `calls`, the rows of sv_calling/variants.vcf (a compute made with chrom_texts).  A compute made with
+    row_texts adds `rows` / `n_rows`: the data rows of phased_sv.vcf, sorted and formatted on the device."""
     chroms = init_chrom_list(include_all_ctgs, home)
     ing, got = NativeIngest.extract(home + '/snp_phasing/', chroms, thread, min_sv_size, min_mapq, depth_bin, only=only,
                                     names=names)
@@ -227,7 +231,7 @@ def part_path(home, rank):
 
 
 def rank_body(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist, rank, world, compute, to_device=None,
-              star=None, gather=None, write_sv_calls=False):
+              star=None, gather=None, write_sv_calls=False, format_rows=None):
     """One rank of the sharded SVIM mode.  compute as in phase_from_bams.  Rank 0 appends the rows to the file that
     already holds the header.  -> exit code (5: division by zero on some rank).
     star / gather (duet_amd/comm.py; round 4): how many candidates a rank finds is a result, not an input, so the ranks first
@@ -237,7 +241,9 @@ def rank_body(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_d
     to_device: where its tensors live.
     write_sv_calls: every rank writes its contigs' callset rows (part_path) BEFORE the exchange of the counts; rank 0 then
     writes phased_sv.vcf whole (the parent wrote no header) and assembles sv_calling/variants.vcf from the parts
-    (status 6: a read name that READS= cannot hold, on some rank -- nothing is written)."""
+    (status 6: a read name that READS= cannot hold, on some rank -- nothing is written).
+    format_rows: (merged result dict, CHROM text per contig) -> the bytes of phased_sv.vcf's data rows, what rank 0 writes
+    (rank_main: duet_svim_phased_rows_host on the rank's context); default: rows_text."""
     from duet_amd import dist as D
     chroms = init_chrom_list(include_all_ctgs, home)
     owned = D.lpt_assign(bam_weights(home, chroms), world)
@@ -255,7 +261,7 @@ def rank_body(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_d
         os.makedirs(os.path.join(home, 'sv_calling'), exist_ok=True)
         with open(part_path(home, rank), 'wb') as f:
             f.write(res['calls'])
-    merge = lambda g, counts: _merge_and_write(home, chroms, g, counts, world, owned if write_sv_calls else None)
+    merge = lambda g, counts: _merge_and_write(home, chroms, g, counts, world, owned if write_sv_calls else None, format_rows)
     rec = pack_records(res) if res is not None else np.zeros((0, REC_WORDS), dtype=np.uint32)
     if gather is not None:
         mine = np.array([len(rec), status, res['n_marks'] if res is not None else 0, 0], dtype=np.int32)
@@ -328,9 +334,10 @@ def _assemble_callset(home, chroms, owned, merged, world):
         os.remove(part_path(home, r))
 
 
-def _merge_and_write(home, chroms, g, counts, world, owned=None):
+def _merge_and_write(home, chroms, g, counts, world, owned=None, format_rows=None):
     """rank 0: the gathered records [world, n_max, REC_WORDS] -> rows appended to phased_sv.vcf.  owned (--write_sv_calls): the
-    contig -> rank assignment; phased_sv.vcf is then written whole and sv_calling/variants.vcf assembled from the parts."""
+    contig -> rank assignment; phased_sv.vcf is then written whole and sv_calling/variants.vcf assembled from the parts.
+    format_rows: see rank_body."""
     parts = [unpack_records(g[r, :int(counts[r, 0])]) for r in range(world)]
     merged = {k: np.concatenate([p_[k] for p_ in parts]) for k in parts[0]}
     # contigs are owned whole and a rank's candidates come contig-major: a stable sort by contig is the single-GPU order
@@ -340,15 +347,28 @@ def _merge_and_write(home, chroms, g, counts, world, owned=None):
     logging.info('  %d SV marks clustered into %d candidates on %d GPUs, %d phased (clustering rule: parity unpinned)' % (
         int(counts[:, 2].sum()), len(merged['pred']), world, int(np.count_nonzero(merged['pred']))))
     logging.info('write phased callset into .vcf file')
-    if owned is not None:
+    if format_rows is not None:
+        rows = format_rows(merged, spelled_contigs(home, chroms))
+        with open(home + '/phased_sv.vcf', 'wb' if owned is not None else 'ab') as out:
+            if owned is not None:
+                out.write(header_text(home, chroms).encode())
+            out.write(rows)
+    elif owned is not None:
         with open(home + '/phased_sv.vcf', 'w') as out:
             out.write(header_text(home, chroms) + rows_text(home, merged))
+    else:
+        with open(home + '/phased_sv.vcf', 'a') as out:
+            out.write(rows_text(home, merged))
+    if owned is not None:
         logging.info('write the clustered SV calls into sv_calling/variants.vcf')
         _assemble_callset(home, chroms, owned, merged, world)
-        return 0
-    with open(home + '/phased_sv.vcf', 'a') as out:
-        out.write(rows_text(home, merged))
     return 0
+
+
+def device_format_rows(ctx):
+    """-> rank_body's format_rows for a rank process: rank 0 sorts and formats the merged records on its GPU
+    (duet_svim_phased_rows_host)."""
+    return lambda merged, row_texts: ctx.svim_phased_rows_host(merged, row_texts)[0]
 
 
 def rank_main(argv):
@@ -374,7 +394,7 @@ def rank_main(argv):
         try:
             gather = comm.HostGather(star) if one_gpu else comm.RcclGather(ctx, star)
             return rank_body(home, svlen_thres, suppread_thres, thread, all_ctgs, max_dist, rank, world, host_compute(ctx, texts),
-                             star=star, gather=gather, write_sv_calls=write_sv_calls)
+                             star=star, gather=gather, write_sv_calls=write_sv_calls, format_rows=device_format_rows(ctx))
         finally:
             if gather is not None:
                 gather.close()
@@ -394,7 +414,8 @@ def rank_main(argv):
     try:
         ctx = _lib.Context(device_id)                    # raises when libduet_ef.so / the GPU is missing: no fallback
         return rank_body(home, svlen_thres, suppread_thres, thread, all_ctgs, max_dist, rank, world, device_compute(ctx, texts),
-                         to_device=None if one_gpu else torch.device('cuda', device_id), write_sv_calls=write_sv_calls)
+                         to_device=None if one_gpu else torch.device('cuda', device_id), write_sv_calls=write_sv_calls,
+                         format_rows=device_format_rows(ctx))
     finally:
         td.destroy_process_group()
 
@@ -439,27 +460,32 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
             raise RuntimeError('svim-gpu on %d GPUs failed: a rank exited with code %d' % (int(gpus), rc))
         logging.info('%s SV CALLING + PHASING COMPLETED IN %ss %s' % (bar, round(time.time() - t0, 3), bar))
         return
-    if write_sv_calls:
-        # (the names are checked inside, before the device runs and before any file is written)
-        def compute(*args):
-            return device_compute(engine.default_context(int(device)), spelled_contigs(home, chroms))(*args)
-        res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
-                              min_sv_size=max(int(svlen_thres), 1), names=True, compute=compute)
-    else:
-        res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
-                              min_sv_size=max(int(svlen_thres), 1), ctx=engine.default_context(int(device)))
+    # (--write_sv_calls: the names are checked inside, before the device runs and before any file is written)
+    ctx = None if write_sv_calls else engine.default_context(int(device))
+
+    def compute(*args):
+        texts = spelled_contigs(home, chroms)
+        return device_compute(ctx if ctx is not None else engine.default_context(int(device)), texts if write_sv_calls else None,
+                              row_texts=texts)(*args)
+    res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
+                          min_sv_size=max(int(svlen_thres), 1), names=bool(write_sv_calls), compute=compute)
+    # the data rows come sorted and formatted from the device; without a single mark nothing ran and there are none
+    if 'rows' not in res and len(res['pred']):
+        raise RuntimeError('svim-gpu: the device pipeline returned candidates without the rows of phased_sv.vcf')
+    rows, n_rows = res.get('rows', b''), int(res.get('n_rows', 0))
     logging.info('  %d SV marks clustered into %d candidates, %d phased (clustering rule: parity unpinned)' % (
-        res['n_marks'], len(res['pred']), int(np.count_nonzero(res['pred']))))
+        res['n_marks'], len(res['pred']), n_rows))
     logging.info('write phased callset into .vcf file')
     if write_sv_calls:
-        with open(out_vcf, 'w') as out:
-            out.write(header_text(home, chroms) + rows_text(home, res))
+        with open(out_vcf, 'wb') as out:
+            out.write(header_text(home, chroms).encode())
+            out.write(rows)
         logging.info('write the clustered SV calls into sv_calling/variants.vcf')
         write_callset(home, chroms, res['calls'])
         logging.info('%s SV CALLING + PHASING COMPLETED IN %ss %s' % (bar, round(time.time() - t0, 3), bar))
         return
-    with open(out_vcf, 'a') as out:
-        out.write(rows_text(home, res))
+    with open(out_vcf, 'ab') as out:
+        out.write(rows)
     logging.info('%s SV CALLING + PHASING COMPLETED IN %ss %s' % (bar, round(time.time() - t0, 3), bar))
 
 

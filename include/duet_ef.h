@@ -306,6 +306,34 @@ DUET_API int duet_svim_vcf_rows_host(duet_ctx *ctx, const duet_svim_problem *pro
                                      const duet_callset_names *names, char *out_text, uint64_t out_cap, uint64_t *out_len);
 
 /* ---------------------------------------------------------------------------------------------
+ * Rows of phased_sv.vcf in the svim-gpu mode (duet_svim_rows.hip): from a cluster result and its
+ * (pred, ps) to the text of the data rows, as duet_amd/svim_mode.py rows_text writes them.
+ *     CHROM POS Duet.<n> N <T> . PASS SVLEN=v;SVTYPE=<T> HP:PS hp:ps        (tab-separated, one '\n' behind each row)
+ * Kept: the candidates with pred != 0.  Order: stable, by CHROM text (unsigned byte order, the shorter text first on a common
+ * prefix -- how Python compares the strings) then POS; ties keep candidate order.  The library ranks the n_contigs texts itself,
+ * on the host; two contigs with the same text share a rank.  n = the row's 1-based number after the sort; T = DEL, INS, INV, DUP
+ * for type & 3 = 0, 1, 2, 3; v = span for INS and DUP, -span otherwise (a span of 0 prints 0); hp = 1|0, 0|1, 1|1 for pred 1, 2,
+ * 3; POS, n, span and ps are full unsigned 32-bit values in decimal.  The header lines stay with the host.
+ *
+ * Reads res->cand_contig, cand_type, cand_pos, cand_span for n_cands candidates (order, cand_off, n_cands of *res are not read),
+ * pred[n_cands], ps[n_cands].  chrom: [n_contigs] HOST, NUL-terminated CHROM text of every contig (each at most 1 MiB).
+ * _device: device arrays (as duet_svim_phase_device leaves them), out_text device; asynchronous on `stream` apart from ONE host
+ * round trip that learns the row count and the text's size.  _host: everything HOST; uploads, runs the same kernels, copies the
+ * text back, synchronises.
+ * Both: *n_rows = the row count, *out_len = the text's exact size; when out_cap is smaller nothing is written and the call
+ * returns DUET_ERR_INVALID with *out_len still exact.  n_rows * (longest CHROM text + 96) always suffices: a row without CHROM is
+ * at most 95 bytes.  Row offsets are 64-bit: a text of 4 GiB or more is legal.
+ * DUET_ERR_INVALID, nothing written, duet_last_error names the case: a NULL array with n_cands > 0; n_contigs of 0 or more than
+ * 65535; a NULL chrom[k]; a kept candidate with pred > 3; a kept candidate with cand_contig >= n_contigs.
+ * n_cands == 0, or no kept candidate: DUET_OK, zero rows, zero bytes. */
+DUET_API int duet_svim_phased_rows_device(duet_ctx *ctx, const duet_cluster_result *res, uint32_t n_cands, const uint8_t *pred,
+                                          const uint32_t *ps, uint32_t n_contigs, const char *const *chrom, char *out_text,
+                                          uint64_t out_cap, uint64_t *out_len, uint32_t *n_rows, void *stream);
+DUET_API int duet_svim_phased_rows_host(duet_ctx *ctx, const duet_cluster_result *res, uint32_t n_cands, const uint8_t *pred,
+                                        const uint32_t *ps, uint32_t n_contigs, const char *const *chrom, char *out_text,
+                                        uint64_t out_cap, uint64_t *out_len, uint32_t *n_rows);
+
+/* ---------------------------------------------------------------------------------------------
  * Rows of phased_sv.vcf on the device: from (pred, ps) to the text of the data rows.
  * Replaces, for the rows: the emission order of src/duet/sv_phasing_fn.py:204-228 (contig order, PS-class 0/1/2,
  * file order, pred 0 dropped), the stable sort of :229 (CHROM as text, POS as int), print_sv of
