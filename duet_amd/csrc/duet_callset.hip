@@ -5,7 +5,7 @@
 // Pipeline (one stream):
 //   cs_first        first candidate of every contig (the row numbers of the ID column count per contig)
 //   cs_len          per candidate: decimal digit counts + CHROM twice + the members' name lengths (order -> mark_name -> name_off)
-//   64-bit scan     cs_scan_reduce (tile sums) -> cs_scan_spine (one workgroup) -> cs_scan_apply: row offsets and the total
+//   64-bit scan     cs_scan_reduce (tile sums) -> scan_spine_u64 (one workgroup) -> cs_scan_apply: row offsets and the total
 //   (one host round trip: the total and the type-code check)
 //   cs_write        one wavefront per row: lane 0 formats the numeric pieces into LDS, the lanes copy the pieces and the names
 //                   (consecutive lanes on consecutive bytes)
@@ -20,6 +20,8 @@
 #include "duet_internal.h"
 
 namespace {
+
+#include "duet_text.hip.h"
 
 constexpr uint32_t kCsThreads = 256, kCsItems = 8, kCsTile = kCsThreads * kCsItems;
 
@@ -44,23 +46,6 @@ struct CsParams {
     char *out;
     uint64_t cap;
 };
-
-__device__ __forceinline__ uint32_t digits_u64(uint64_t v)
-{
-    uint32_t d = 1;
-    while (v >= 10u) { v /= 10u; ++d; }
-    return d;
-}
-
-__device__ __forceinline__ uint32_t put_u64(char *dst, uint64_t v)
-{
-    const uint32_t n = digits_u64(v);
-    for (uint32_t i = n; i-- > 0;) {
-        dst[i] = (char)('0' + (uint32_t)(v % 10u));
-        v /= 10u;
-    }
-    return n;
-}
 
 // the numbers of a row
 struct CsRow {
@@ -131,18 +116,6 @@ __global__ __launch_bounds__(256) void cs_len(const CsParams p)
 }
 
 // 64-bit exclusive scan of len[] (row lengths are 32-bit, their sums are not)
-__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, uint32_t d)
-{
-    const uint32_t lo = __shfl_up((uint32_t)v, d, 64), hi = __shfl_up((uint32_t)(v >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, uint32_t d)
-{
-    const uint32_t lo = __shfl_xor((uint32_t)v, d, 64), hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 __global__ __launch_bounds__(kCsThreads) void cs_scan_reduce(const CsParams p)
 {
     __shared__ uint64_t s_w[kCsThreads / 64];
@@ -151,37 +124,10 @@ __global__ __launch_bounds__(kCsThreads) void cs_scan_reduce(const CsParams p)
 #pragma unroll
     for (uint32_t j = 0; j < kCsItems; ++j)
         if (base + j < p.N) acc += p.len[base + j];
-#pragma unroll
-    for (uint32_t d = 32; d > 0; d >>= 1) acc += shfl_xor_u64(acc, d);
+    acc = wave_sum(acc);
     if ((tid & 63u) == 0) s_w[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) p.part[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-// one workgroup: part[0..nb) <- exclusive sums (each thread a contiguous run), *total <- the sum of everything
-__global__ __launch_bounds__(1024) void cs_scan_spine(const CsParams p, uint32_t nb)
-{
-    __shared__ uint64_t s_w[16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t per = (nb + 1023u) / 1024u, lo = min(nb, tid * per), hi = min(nb, lo + per);
-    uint64_t acc = 0;
-    for (uint32_t i = lo; i < hi; ++i) acc += p.part[i];
-    uint64_t x = acc;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint64_t y = shfl_up_u64(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) s_w[wave] = x;
-    __syncthreads();
-    uint64_t run = x - acc;
-    for (uint32_t w = 0; w < wave; ++w) run += s_w[w];
-    if (tid == 1023) *p.total = run + acc;
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint64_t v = p.part[i];
-        p.part[i] = run;
-        run += v;
-    }
 }
 
 __global__ __launch_bounds__(kCsThreads) void cs_scan_apply(const CsParams p)
@@ -196,12 +142,7 @@ __global__ __launch_bounds__(kCsThreads) void cs_scan_apply(const CsParams p)
         v[j] = base + j < p.N ? p.len[base + j] : 0u;
         acc += v[j];
     }
-    uint64_t x = acc;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint64_t y = shfl_up_u64(x, d);
-        if (lane >= d) x += y;
-    }
+    const uint64_t x = wave_scan(acc, lane);
     if (lane == 63) s_w[wave] = x;
     __syncthreads();
     uint64_t run = p.part[blockIdx.x] + x - acc;
@@ -214,13 +155,6 @@ __global__ __launch_bounds__(kCsThreads) void cs_scan_apply(const CsParams p)
 }
 
 __device__ __constant__ const char kTypes[4][4] = {"DEL", "INS", "INV", "DUP"};
-
-__device__ __forceinline__ uint32_t put_str(char *dst, const char *s)
-{
-    uint32_t n = 0;
-    while (s[n]) { dst[n] = s[n]; ++n; }
-    return n;
-}
 
 __global__ __launch_bounds__(256) void cs_write(const CsParams p)
 {
@@ -272,9 +206,7 @@ __global__ __launch_bounds__(256) void cs_write(const CsParams p)
             e[q++] = '\n';
             s_len[wave][2] = q;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        wave_publish();
         const uint32_t la = s_len[wave][0], lb = s_len[wave][1], lc = s_len[wave][2];
         const uint32_t c0 = p.chrom_off[k], L = p.chrom_off[k + 1] - c0;
         uint64_t cur = p.row_off[c];
@@ -285,13 +217,13 @@ __global__ __launch_bounds__(256) void cs_write(const CsParams p)
             continue;
         }
         char *out = p.out;
-        for (uint32_t i = lane; i < L; i += 64) out[cur + i] = p.chrom_pool[c0 + i];               // CHROM
+        wave_copy(out + cur, p.chrom_pool + c0, L, lane);                                         // CHROM
         cur += L;
-        for (uint32_t i = lane; i < la; i += 64) out[cur + i] = s_a[wave][i];                      // \t POS \t svim_gpu.
+        wave_copy(out + cur, s_a[wave], la, lane);                                                // \t POS \t svim_gpu.
         cur += la;
-        for (uint32_t i = lane; i < L; i += 64) out[cur + i] = p.chrom_pool[c0 + i];               // CHROM
+        wave_copy(out + cur, p.chrom_pool + c0, L, lane);                                         // CHROM
         cur += L;
-        for (uint32_t i = lane; i < lb; i += 64) out[cur + i] = s_b[wave][i];                      // .i ... ;READS=
+        wave_copy(out + cur, s_b[wave], lb, lane);                                                // .i ... ;READS=
         cur += lb;
         // the members' names in cluster order, 64 at a time: each lane looks one up, a wave scan places them, then all lanes
         // copy each name (consecutive lanes on consecutive bytes)
@@ -305,24 +237,19 @@ __global__ __launch_bounds__(256) void cs_write(const CsParams p)
                 ln = (uint32_t)(p.name_off[nm + 1] - src);
                 w = ln + (j + 1 < n ? 1u : 0u);
             }
-            uint32_t x = w;
-#pragma unroll
-            for (uint32_t d = 1; d < 64; d <<= 1) {
-                const uint32_t y = __shfl_up(x, d, 64);
-                if (lane >= d) x += y;
-            }
+            const uint32_t x = wave_scan(w, lane);
             const uint32_t at = x - w;
             const uint32_t cnt = n - j0 < 64u ? n - j0 : 64u;
             for (uint32_t q = 0; q < cnt; ++q) {
                 const uint32_t lo = __shfl((uint32_t)src, q, 64), hi = __shfl((uint32_t)(src >> 32), q, 64);
                 const uint32_t qln = __shfl(ln, q, 64), qat = __shfl(at, q, 64);
                 const uint64_t qsrc = ((uint64_t)hi << 32) | lo;
-                for (uint32_t i = lane; i < qln; i += 64) out[cur + qat + i] = p.name_pool[qsrc + i];
+                wave_copy(out + cur + qat, p.name_pool + qsrc, qln, lane);
                 if (lane == 0 && j0 + q + 1 < n) out[cur + qat + qln] = ',';
             }
             cur += __shfl(x, 63, 64);
         }
-        for (uint32_t i = lane; i < lc; i += 64) out[cur + i] = s_c[wave][i];                      // \tGT:DP:AD\t ... \n
+        wave_copy(out + cur, s_c[wave], lc, lane);                                                // \tGT:DP:AD\t ... \n
         __builtin_amdgcn_wave_barrier();                                                          // before lane 0 rewrites the LDS pieces
     }
 }
@@ -345,13 +272,10 @@ struct CsInputs {
 int cs_plan(duet_ctx *ctx, const CsInputs &in, CsParams &p, hipStream_t st, uint64_t *need)
 {
     const uint32_t N = in.N, K = in.K;
-    std::vector<uint32_t> chrom_off(K + 1, 0);
-    std::string chrom_pool;
-    for (uint32_t k = 0; k < K; ++k) {
+    for (uint32_t k = 0; k < K; ++k)
         if (!in.chrom[k]) return duet_fail(ctx, DUET_ERR_INVALID, "null CHROM text");
-        chrom_pool += in.chrom[k];
-        chrom_off[k + 1] = (uint32_t)chrom_pool.size();
-    }
+    const DuetChromTable ct = duet_chrom_table(in.chrom, K, false);
+    const std::string &chrom_pool = ct.pool;
     const uint32_t nb = (N + kCsTile - 1) / kCsTile;
     const size_t small = 64 + ((size_t)K + 1) * 8 + chrom_pool.size() + 64;
     const size_t sizes[5] = {(size_t)K * 4 + 64, (size_t)N * 4, (size_t)N * 8, (size_t)nb * 8 + 64, small};
@@ -363,7 +287,7 @@ int cs_plan(duet_ctx *ctx, const CsInputs &in, CsParams &p, hipStream_t st, uint
     char *d_chrom = (char *)(d_chrom_off + (K + 1));
     HIP_TRY(ctx, hipMemsetAsync(sm, 0, 64, st));
     HIP_TRY(ctx, hipMemcpyAsync(d_depth_off, in.depth_off_host, ((size_t)K + 1) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_chrom_off, chrom_off.data(), ((size_t)K + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_chrom_off, ct.off.data(), ((size_t)K + 1) * 4, hipMemcpyHostToDevice, st));
     if (!chrom_pool.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_chrom, chrom_pool.data(), chrom_pool.size(), hipMemcpyHostToDevice, st));
     memset(&p, 0, sizeof(p));
     p.N = N; p.K = K; p.depth_bin = in.depth_bin;
@@ -380,7 +304,7 @@ int cs_plan(duet_ctx *ctx, const CsInputs &in, CsParams &p, hipStream_t st, uint
     hipLaunchKernelGGL(cs_first, dim3(g), dim3(256), 0, st, p);
     hipLaunchKernelGGL(cs_len, dim3(g), dim3(256), 0, st, p);
     hipLaunchKernelGGL(cs_scan_reduce, dim3(nb), dim3(kCsThreads), 0, st, p);
-    hipLaunchKernelGGL(cs_scan_spine, dim3(1), dim3(1024), 0, st, p, nb);
+    hipLaunchKernelGGL(scan_spine_u64, dim3(1), dim3(1024), 0, st, p.part, nb, p.total);
     hipLaunchKernelGGL(cs_scan_apply, dim3(nb), dim3(kCsThreads), 0, st, p);
     HIP_TRY(ctx, hipGetLastError());
     uint64_t fin[2] = {0, 0};
@@ -463,12 +387,7 @@ int duet_svim_vcf_rows_host(duet_ctx *ctx, const duet_svim_problem *prob, const 
     const size_t bytes[10] = {((size_t)N + 1) * 4, (size_t)M * 4, (size_t)N * 2, (size_t)N, (size_t)N * 4, (size_t)N * 4,
                               (size_t)M * 4, ((size_t)names->n_names + 1) * 8, (size_t)pool_bytes, (size_t)n_bins * 4};
     void *dev[10];
-    for (int i = 0; i < 10; ++i) {
-        DevBuf &b = ctx->callset_ws.b[5 + i];
-        if ((rc = duet_reserve(ctx, b, bytes[i] + 64))) return rc;
-        if (bytes[i]) HIP_TRY(ctx, hipMemcpyAsync(b.ptr, src[i], bytes[i], hipMemcpyHostToDevice, s));
-        dev[i] = b.ptr;
-    }
+    if ((rc = duet_stage_arrays(ctx, ctx->callset_ws.b + 5, src, bytes, 10, s, dev))) return rc;
     CsInputs in = {N, M, K, prob->depth_bin, (const uint32_t *)dev[0], (const uint32_t *)dev[1], (const uint16_t *)dev[2],
                    (const uint8_t *)dev[3], (const uint32_t *)dev[4], (const uint32_t *)dev[5], (const uint32_t *)dev[6],
                    (const uint64_t *)dev[7], (const char *)dev[8], (const uint32_t *)dev[9], prob->depth_off, names->chrom};

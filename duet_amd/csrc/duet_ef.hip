@@ -2653,21 +2653,19 @@ int duet_ef_upload(duet_ctx *ctx, const duet_ef_problem *pr, duet_ef_problem *d,
     const size_t bytes[8] = {(size_t)R * 8, (size_t)C * 4, (size_t)C * 4, (size_t)C * 4, (size_t)C * 4,
                              (size_t)C, ((size_t)C + 1) * 4, (size_t)M * 4};
     int rc;
-    for (int i = 0; i < 8; ++i) {
-        if ((rc = reserve(ctx, ctx->h_in[i], bytes[i] ? bytes[i] : 16))) return rc;
-        if (bytes[i]) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_in[i].ptr, src[i], bytes[i], hipMemcpyHostToDevice, s));
-    }
+    void *dev[8];
+    if ((rc = duet_stage_arrays(ctx, ctx->h_in, src, bytes, 8, s, dev))) return rc;
     if ((rc = reserve(ctx, ctx->h_out[0], C ? C : 16))) return rc;
     if ((rc = reserve(ctx, ctx->h_out[1], C ? (size_t)C * 4 : 16))) return rc;
     *d = *pr;
-    d->read_tag = (const uint64_t *)ctx->h_in[0].ptr;
-    d->cand_pos = (const uint32_t *)ctx->h_in[1].ptr;
-    d->cand_svlen = (const uint32_t *)ctx->h_in[2].ptr;
-    d->cand_svread = (const uint32_t *)ctx->h_in[3].ptr;
-    d->cand_refread = (const uint32_t *)ctx->h_in[4].ptr;
-    d->cand_gt_ok = (const uint8_t *)ctx->h_in[5].ptr;
-    d->cand_off = (const uint32_t *)ctx->h_in[6].ptr;
-    d->mark_read = (const uint32_t *)ctx->h_in[7].ptr;
+    d->read_tag = (const uint64_t *)dev[0];
+    d->cand_pos = (const uint32_t *)dev[1];
+    d->cand_svlen = (const uint32_t *)dev[2];
+    d->cand_svread = (const uint32_t *)dev[3];
+    d->cand_refread = (const uint32_t *)dev[4];
+    d->cand_gt_ok = (const uint8_t *)dev[5];
+    d->cand_off = (const uint32_t *)dev[6];
+    d->mark_read = (const uint32_t *)dev[7];
     return DUET_OK;
 }
 

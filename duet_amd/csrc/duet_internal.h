@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -128,6 +130,55 @@ inline int duet_reserve(duet_ctx *ctx, DevBuf &b, size_t bytes)
     HIP_TRY(ctx, hipMalloc(&b.ptr, want));
     b.cap = want;
     return DUET_OK;
+}
+
+// host arrays -> the staging buffers bufs[0..n): each reserved (with 64 spare bytes, so an empty array still has a readable
+// address), copied on s when it has bytes; dev[i] = its device address
+inline int duet_stage_arrays(duet_ctx *ctx, DevBuf *bufs, const void *const *src, const size_t *bytes, int n, hipStream_t s, void **dev)
+{
+    for (int i = 0; i < n; ++i) {
+        int rc = duet_reserve(ctx, bufs[i], bytes[i] + 64);
+        if (rc) return rc;
+        if (bytes[i]) HIP_TRY(ctx, hipMemcpyAsync(bufs[i].ptr, src[i], bytes[i], hipMemcpyHostToDevice, s));
+        dev[i] = bufs[i].ptr;
+    }
+    return DUET_OK;
+}
+
+// The CHROM texts of K contigs (NUL-terminated, none null) in one pool, contig k at off[k] .. off[k + 1].  With want_rank also
+// rank[k] = the text's rank among the distinct texts in unsigned byte order, the shorter text first on a common prefix (how
+// Python compares the strings; equal texts share a rank), and n_texts = the number of distinct texts.
+struct DuetChromTable {
+    std::string pool;
+    std::vector<uint32_t> off;
+    std::vector<uint16_t> rank;
+    uint32_t n_texts = 0;
+};
+
+inline DuetChromTable duet_chrom_table(const char *const *chrom, uint32_t K, bool want_rank)
+{
+    DuetChromTable t;
+    t.off.assign((size_t)K + 1, 0);
+    for (uint32_t k = 0; k < K; ++k) {
+        t.pool += chrom[k];
+        t.off[k + 1] = (uint32_t)t.pool.size();
+    }
+    if (!want_rank) return t;
+    std::vector<uint32_t> by_text(K);
+    for (uint32_t k = 0; k < K; ++k) by_text[k] = k;
+    auto less = [&](uint32_t a, uint32_t b) {
+        const size_t la = t.off[a + 1] - t.off[a], lb = t.off[b + 1] - t.off[b];
+        const int c = memcmp(t.pool.data() + t.off[a], t.pool.data() + t.off[b], la < lb ? la : lb);
+        return c ? c < 0 : la < lb;
+    };
+    std::sort(by_text.begin(), by_text.end(), less);
+    t.rank.assign(K, 0);
+    for (uint32_t i = 0; i < K; ++i) {
+        if (i && less(by_text[i - 1], by_text[i])) ++t.n_texts;
+        t.rank[by_text[i]] = (uint16_t)t.n_texts;
+    }
+    ++t.n_texts;
+    return t;
 }
 
 #endif

@@ -30,6 +30,7 @@
 namespace {
 
 #include "duet_prims.hip.h"
+#include "duet_text.hip.h"
 
 constexpr uint32_t kAbsentRead = 0xFFFFFFFFu;
 
@@ -52,23 +53,6 @@ struct RowParams {
     uint64_t cap;
     uint32_t *overflow;
 };
-
-struct LoadKeep {
-    const uint8_t *pred;
-    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return pred[i] != 0 ? 1u : 0u; }
-};
-struct StoreCompact {
-    uint32_t *idx;
-    __device__ __forceinline__ void operator()(uint32_t i, uint32_t v, uint32_t in) const { if (in) idx[v] = i; }
-};
-
-__device__ __forceinline__ uint32_t digits_u32(uint32_t v)
-{
-    uint32_t d = 1;
-    d += v >= 10u; d += v >= 100u; d += v >= 1000u; d += v >= 10000u; d += v >= 100000u;
-    d += v >= 1000000u; d += v >= 10000000u; d += v >= 100000000u; d += v >= 1000000000u;
-    return d;
-}
 
 __global__ void rows_keys(const RowParams p, const uint32_t *idx, uint64_t *keys, uint32_t *vals)
 {
@@ -114,16 +98,6 @@ struct LoadRowLen {
     }
 };
 
-__device__ __forceinline__ uint32_t put_u32(char *dst, uint32_t v)
-{
-    const uint32_t n = digits_u32(v);
-    for (uint32_t i = n; i-- > 0;) {
-        dst[i] = (char)('0' + v % 10u);
-        v /= 10u;
-    }
-    return n;
-}
-
 __global__ __launch_bounds__(256) void rows_write(const RowParams p)
 {
     __shared__ char s_a[4][32], s_b[4][40], s_c[4][32];
@@ -162,9 +136,7 @@ __global__ __launch_bounds__(256) void rows_write(const RowParams p)
             q[n++] = '\n';
             s_len[wave][2] = n;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        wave_publish();
         const uint32_t la = s_len[wave][0], lb = s_len[wave][1], lc = s_len[wave][2];
         uint64_t cur = p.row_off[j];
         const uint64_t total = (uint64_t)(o4 - o0) + la + 1 + lb + lc;
@@ -174,21 +146,21 @@ __global__ __launch_bounds__(256) void rows_write(const RowParams p)
             continue;
         }
         char *out = p.out;
-        for (uint32_t i = lane; i < o1 - o0; i += 64) out[cur + i] = p.pool[o0 + i];          // CHROM
+        wave_copy(out + cur, p.pool + o0, o1 - o0, lane);                                    // CHROM
         cur += o1 - o0;
-        for (uint32_t i = lane; i < la; i += 64) out[cur + i] = s_a[wave][i];                 // \t POS \t Duet.N \t
+        wave_copy(out + cur, s_a[wave], la, lane);                                           // \t POS \t Duet.N \t
         cur += la;
-        for (uint32_t i = lane; i < o2 - o1; i += 64) out[cur + i] = p.pool[o1 + i];          // REF
+        wave_copy(out + cur, p.pool + o1, o2 - o1, lane);                                    // REF
         cur += o2 - o1;
         if (lane == 0) out[cur] = '\t';
         cur += 1;
-        for (uint32_t i = lane; i < o3 - o2; i += 64) out[cur + i] = p.pool[o2 + i];          // ALT
+        wave_copy(out + cur, p.pool + o2, o3 - o2, lane);                                    // ALT
         cur += o3 - o2;
-        for (uint32_t i = lane; i < lb; i += 64) out[cur + i] = s_b[wave][i];                 // \t.\tPASS\tSVLEN=..;SVTYPE=<
+        wave_copy(out + cur, s_b[wave], lb, lane);                                           // \t.\tPASS\tSVLEN=..;SVTYPE=<
         cur += lb;
-        for (uint32_t i = lane; i < o4 - o3; i += 64) out[cur + i] = p.pool[o3 + i];          // SVTYPE
+        wave_copy(out + cur, p.pool + o3, o4 - o3, lane);                                    // SVTYPE
         cur += o4 - o3;
-        for (uint32_t i = lane; i < lc; i += 64) out[cur + i] = s_c[wave][i];                 // >\tHP:PS\t hp:ps \n
+        wave_copy(out + cur, s_c[wave], lc, lane);                                           // >\tHP:PS\t hp:ps \n
         __builtin_amdgcn_wave_barrier();                                                     // before lane 0 rewrites the LDS pieces
     }
 }
@@ -293,10 +265,8 @@ int duet_ef_rows_run_host(duet_ctx *ctx, const duet_ef_problem *pr, const duet_r
     const uint64_t cap = rows->pool_bytes + 96ull * C + 64;
     const void *src[4] = {rows->pool, rows->str_off, rows->cand_chrom_rank, rows->cand_plus};
     const size_t bytes[4] = {(size_t)rows->pool_bytes, ((size_t)4 * C + 1) * 4, (size_t)C * 2, (size_t)C};
-    for (int i = 0; i < 4; ++i) {
-        if ((rc = duet_reserve(ctx, ctx->rows_in[i], bytes[i] ? bytes[i] : 16))) return rc;
-        if (bytes[i]) HIP_TRY(ctx, hipMemcpyAsync(ctx->rows_in[i].ptr, src[i], bytes[i], hipMemcpyHostToDevice, s));
-    }
+    void *dev[4];
+    if ((rc = duet_stage_arrays(ctx, ctx->rows_in, src, bytes, 4, s, dev))) return rc;
     if ((rc = duet_reserve(ctx, ctx->rows_in[4], cap))) return rc;
     if ((rc = duet_ef_check(ctx, s))) return rc;                  // division by zero etc. surfaces here, before any row
     duet_rows_problem r = *rows;
@@ -304,10 +274,10 @@ int duet_ef_rows_run_host(duet_ctx *ctx, const duet_ef_problem *pr, const duet_r
     r.cand_ctg_off = pr->cand_ctg_off;
     r.pred = d_pred; r.ps = d_ps;
     r.cand_pos = d.cand_pos; r.cand_svlen = d.cand_svlen;
-    r.pool = (const char *)ctx->rows_in[0].ptr;
-    r.str_off = (const uint32_t *)ctx->rows_in[1].ptr;
-    r.cand_chrom_rank = (const uint16_t *)ctx->rows_in[2].ptr;
-    r.cand_plus = (const uint8_t *)ctx->rows_in[3].ptr;
+    r.pool = (const char *)dev[0];
+    r.str_off = (const uint32_t *)dev[1];
+    r.cand_chrom_rank = (const uint16_t *)dev[2];
+    r.cand_plus = (const uint8_t *)dev[3];
     r.cand_off = d.cand_off; r.mark_read = d.mark_read; r.read_tag = d.read_tag;
     uint64_t len = 0;
     if ((rc = duet_rows_run_device(ctx, &r, (char *)ctx->rows_in[4].ptr, cap, &len, n_rows, s))) return rc;

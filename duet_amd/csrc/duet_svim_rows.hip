@@ -13,7 +13,7 @@
 //   add up to a number the host knows from n_rows alone, so the text's exact size is known here, before the sort.)
 //   sr_keys               key = rank(CHROM text) << pos_bits | POS, value = the candidate
 //   radix sort            stable LSD over exactly the bits in use
-//   sr_tile_len           bytes of every tile of 64 consecutive rows -> sr_tile_scan (one workgroup, 64-bit) -> tile offsets
+//   sr_tile_len           bytes of every tile of 64 consecutive rows -> scan_spine_u64 (one workgroup, 64-bit) -> tile offsets
 //   sr_write              one workgroup per tile; see there
 //
 // CHROM's byte-order rank among the distinct texts is computed by the host once per call (equal texts share a rank).
@@ -31,6 +31,7 @@
 namespace {
 
 #include "duet_prims.hip.h"
+#include "duet_text.hip.h"
 
 constexpr uint32_t kSrRows = 64;                // rows per tile of sr_write: one wavefront stages them, a lane each
 constexpr uint32_t kSrThreads = 256;
@@ -47,29 +48,12 @@ struct SrParams {
     const uint16_t *chrom_rank;                 // [K]
     const char *chrom_pool;
     const uint32_t *sorted;                     // candidate of each row
-    uint64_t *tile_off;                         // [tiles] bytes of each tile, then (sr_tile_scan) its offset in the text
+    uint64_t *tile_off;                         // [tiles] bytes of each tile, then (scan_spine_u64) its offset in the text
     uint64_t *sum;                              // status block: [0] the rows' bytes without their row numbers
     uint32_t *flag, *max_pos;                   //               bit 0 pred > 3, bit 1 contig >= K, bit 2 a tile past out_cap
     char *out;
     uint64_t cap;
 };
-
-struct LoadKeep {
-    const uint8_t *pred;
-    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return pred[i] != 0 ? 1u : 0u; }
-};
-struct StoreCompact {
-    uint32_t *idx;
-    __device__ __forceinline__ void operator()(uint32_t i, uint32_t v, uint32_t in) const { if (in) idx[v] = i; }
-};
-
-__device__ __forceinline__ uint32_t digits_u32(uint32_t v)
-{
-    uint32_t d = 1;
-    d += v >= 10u; d += v >= 100u; d += v >= 1000u; d += v >= 10000u; d += v >= 100000u;
-    d += v >= 1000000u; d += v >= 10000000u; d += v >= 100000000u; d += v >= 1000000000u;
-    return d;
-}
 
 // The row behind CHROM, every number at its full ten digits and the sign present: 95 bytes.
 //     \t PPPPPPPPPP \tDuet. NNNNNNNNNN \tN\t< TTT >\t.\tPASS\tSVLEN= - SSSSSSSSSS ;SVTYPE=< TTT >\tHP:PS\t h|h : QQQQQQQQQQ \n
@@ -158,18 +142,6 @@ __device__ __forceinline__ SrRow sr_row(const SrParams &p, uint32_t j)
     return r;
 }
 
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, uint32_t d)
-{
-    const uint32_t lo = __shfl_xor((uint32_t)v, d, 64), hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, uint32_t d)
-{
-    const uint32_t lo = __shfl_up((uint32_t)v, d, 64), hi = __shfl_up((uint32_t)(v >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 __global__ __launch_bounds__(256) void sr_check_len(const SrParams p)
 {
     __shared__ uint64_t s_sum[4];
@@ -223,35 +195,8 @@ __global__ __launch_bounds__(256) void sr_tile_len(const SrParams p, uint32_t n_
     const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (tile >= n_tiles) return;
     const uint32_t j = tile * kSrRows + lane;
-    uint32_t len = j < p.N ? sr_row(p, j).len : 0u;
-#pragma unroll
-    for (uint32_t d = 32; d > 0; d >>= 1) len += __shfl_xor(len, d, 64);
+    const uint32_t len = wave_sum(j < p.N ? sr_row(p, j).len : 0u);
     if (lane == 0) p.tile_off[tile] = len;
-}
-
-// one workgroup: tile_off[0..nb) <- exclusive sums (each thread a contiguous run)
-__global__ __launch_bounds__(1024) void sr_tile_scan(const SrParams p, uint32_t nb)
-{
-    __shared__ uint64_t s_w[16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t per = (nb + 1023u) / 1024u, lo = min(nb, tid * per), hi = min(nb, lo + per);
-    uint64_t acc = 0;
-    for (uint32_t i = lo; i < hi; ++i) acc += p.tile_off[i];
-    uint64_t x = acc;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint64_t y = shfl_up_u64(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) s_w[wave] = x;
-    __syncthreads();
-    uint64_t run = x - acc;
-    for (uint32_t w = 0; w < wave; ++w) run += s_w[w];
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint64_t v = p.tile_off[i];
-        p.tile_off[i] = run;
-        run += v;
-    }
 }
 
 // what sr_write keeps in LDS: the tile's rows (a field per array: lanes on neighbouring rows read neighbouring words) and the tables
@@ -329,12 +274,7 @@ __global__ __launch_bounds__(kSrThreads) void sr_write(const SrParams p)
         SrRow r;
         r.len = r.L = r.choff = r.pos = r.span = r.ps = r.pk = 0u;
         if (tid < nr) r = sr_row(p, j0 + tid);
-        uint32_t x = r.len;
-#pragma unroll
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d, 64);
-            if (tid >= d) x += y;
-        }
+        const uint32_t x = wave_scan(r.len, tid);
         s.start[tid] = x - r.len;
         if (tid == kSrRows - 1u) s.start[kSrRows] = x;
         s.L[tid] = r.L; s.choff[tid] = r.choff; s.pos[tid] = r.pos; s.span[tid] = r.span; s.ps[tid] = r.ps; s.pk[tid] = r.pk;
@@ -418,32 +358,13 @@ int sr_run(duet_ctx *ctx, const SrInputs &in, char *out_text, uint64_t out_cap, 
 {
     const uint32_t C = in.C, K = in.K;
     // CHROM: the texts in one pool, and each contig's rank among the distinct texts in unsigned byte order
-    std::vector<uint32_t> by_text(K);
-    for (uint32_t k = 0; k < K; ++k) by_text[k] = k;
-    auto cmp = [&](uint32_t a, uint32_t b) {
-        const char *x = in.chrom[a], *y = in.chrom[b];
-        const size_t lx = strlen(x), ly = strlen(y);
-        const int c = memcmp(x, y, lx < ly ? lx : ly);
-        return c ? c < 0 : lx < ly;
-    };
-    std::sort(by_text.begin(), by_text.end(), cmp);
+    const DuetChromTable ct = duet_chrom_table(in.chrom, K, true);
+    const uint32_t n_texts = ct.n_texts;
     const size_t off_bytes = ((size_t)K + 1) * 4, rank_bytes = ((size_t)K * 2 + 3) & ~(size_t)3;
-    std::vector<char> small(off_bytes + rank_bytes);
-    uint32_t *h_off = (uint32_t *)small.data();
-    uint16_t *h_rank = (uint16_t *)(small.data() + off_bytes);
-    uint32_t n_texts = 0;
-    for (uint32_t i = 0; i < K; ++i) {
-        if (i && cmp(by_text[i - 1], by_text[i])) ++n_texts;
-        h_rank[by_text[i]] = (uint16_t)n_texts;
-    }
-    ++n_texts;
-    h_off[0] = 0;
-    for (uint32_t k = 0; k < K; ++k) {
-        const size_t l = strlen(in.chrom[k]);
-        small.insert(small.end(), in.chrom[k], in.chrom[k] + l);
-        h_off = (uint32_t *)small.data();
-        h_off[k + 1] = h_off[k] + (uint32_t)l;
-    }
+    std::vector<char> small(off_bytes + rank_bytes + ct.pool.size());                 // one upload: offsets | ranks | pool
+    memcpy(small.data(), ct.off.data(), off_bytes);
+    memcpy(small.data() + off_bytes, ct.rank.data(), (size_t)K * 2);
+    memcpy(small.data() + off_bytes + rank_bytes, ct.pool.data(), ct.pool.size());
 
     const uint32_t nb_rx = (C + kRxTile - 1) / kRxTile, nb_sc = (C + kScanTile - 1) / kScanTile;
     const uint32_t nb_hs = (256u * nb_rx + kScanTile - 1) / kScanTile;
@@ -508,7 +429,7 @@ int sr_run(duet_ctx *ctx, const SrInputs &in, char *out_text, uint64_t out_cap, 
     p.cap = need;
     const uint32_t n_tiles = (N + kSrRows - 1) / kSrRows;
     hipLaunchKernelGGL(sr_tile_len, dim3((n_tiles + 3) / 4), dim3(256), 0, st, p, n_tiles);
-    hipLaunchKernelGGL(sr_tile_scan, dim3(1), dim3(1024), 0, st, p, n_tiles);
+    hipLaunchKernelGGL(scan_spine_u64, dim3(1), dim3(1024), 0, st, p.tile_off, n_tiles, (uint64_t *)nullptr);
     hipLaunchKernelGGL(sr_write, dim3(n_tiles), dim3(kSrThreads), 0, st, p);
     HIP_TRY(ctx, hipGetLastError());
     if (!to_host) return DUET_OK;
@@ -549,12 +470,7 @@ int duet_svim_phased_rows_host(duet_ctx *ctx, const duet_cluster_result *res, ui
     const void *src[6] = {res->cand_contig, res->cand_type, res->cand_pos, res->cand_span, pred, ps};
     const size_t bytes[6] = {N * 2, N, N * 4, N * 4, N, N * 4};
     void *dev[6];
-    for (int i = 0; i < 6; ++i) {
-        DevBuf &b = ctx->svim_rows_ws.b[9 + i];
-        if ((rc = duet_reserve(ctx, b, bytes[i] + 64))) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(b.ptr, src[i], bytes[i], hipMemcpyHostToDevice, s));
-        dev[i] = b.ptr;
-    }
+    if ((rc = duet_stage_arrays(ctx, ctx->svim_rows_ws.b + 9, src, bytes, 6, s, dev))) return rc;
     const SrInputs in = {n_cands, n_contigs, (const uint16_t *)dev[0], (const uint8_t *)dev[1], (const uint32_t *)dev[2],
                          (const uint32_t *)dev[3], (const uint8_t *)dev[4], (const uint32_t *)dev[5], chrom};
     return sr_run(ctx, in, out_text, out_cap, out_len, n_rows, s, true);

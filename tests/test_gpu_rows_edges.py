@@ -1,0 +1,233 @@
+# coding=utf-8
+"""-m gpu: duet_rows_run_device at its edge shapes -- hand-made candidates with (pred, ps) given, against a plain formatter
+of the row layout in the head comment of duet_rows.hip:
+    CHROM POS Duet.<n> REF ALT . PASS SVLEN=<signed>;SVTYPE=<T> HP:PS <hp>:<ps>
+sorted stably by (CHROM text, POS, contig, PS-class).  The whole-pipeline cases are in test_gpu_rows.py."""
+import numpy as np
+import pytest
+
+from duet_amd import _lib, engine
+
+pytestmark = pytest.mark.gpu
+
+CANARY = 0xAB
+BIG = 0xFFFFFFFF
+ABSENT = None                                  # a mark without a read
+HP = {1: b'1|0', 2: b'0|1', 3: b'1|1'}
+COLUMNS = ('contig', 'chrom', 'pos', 'ref', 'alt', 'svtype', 'svlen', 'plus', 'pred', 'ps', 'marks')
+
+
+@pytest.fixture(scope='module')
+def ctx():
+    return engine.default_context(0)
+
+
+def cands(C, **over):
+    """C candidates, a list per column; a column given as one value holds it for every candidate.  Defaults: contig 0,
+    CHROM chr<contig + 1>, one mark per candidate (so PS-class 1)."""
+    d = dict(contig=0, chrom=None, pos=1000, ref=b'N', alt=b'<INS>', svtype=b'INS', svlen=50, plus=1, pred=1, ps=7, marks=None)
+    d.update(over)
+    for k in COLUMNS:
+        v = d[k]
+        if isinstance(v, np.ndarray):
+            v = v.tolist()
+        d[k] = list(v) if isinstance(v, (list, tuple)) else [v] * C
+        assert len(d[k]) == C, k
+    d['chrom'] = [b'chr%d' % (k + 1) if t is None else t for t, k in zip(d['chrom'], d['contig'])]
+    d['marks'] = [[i % 5] if m is None else m for i, m in enumerate(d['marks'])]
+    assert d['contig'] == sorted(d['contig'])                                # candidates come contig-major
+    return d
+
+
+def ps_class(marks):
+    return min(len(set(t for t in marks if t is not ABSENT)), 2)
+
+
+def rows_of(d):
+    """The reference: the kept candidates in their final order, formatted."""
+    kept = [i for i, p in enumerate(d['pred']) if p]
+    kept.sort(key=lambda i: (d['chrom'][i], d['pos'][i], d['contig'][i], ps_class(d['marks'][i])))
+    out = []
+    for n, i in enumerate(kept, 1):
+        svlen = d['svlen'][i] if d['plus'][i] else -d['svlen'][i]
+        out.append(b'%s\t%d\tDuet.%d\t%s\t%s\t.\tPASS\tSVLEN=%d;SVTYPE=<%s>\tHP:PS\t%s:%d\n' % (
+            d['chrom'][i], d['pos'][i], n, d['ref'][i], d['alt'][i], svlen, d['svtype'][i], HP[d['pred'][i]], d['ps'][i]))
+    return b''.join(out), len(kept)
+
+
+class Resident(object):
+    """The candidates as a RowsProblem over torch tensors."""
+
+    def __init__(self, d, max_pos=None):
+        import torch
+        self.torch = torch
+        self.dev = torch.device('cuda:0')
+        self.keep = []
+        C = len(d['pred'])
+        K = max(d['contig']) + 1 if C else 1
+        texts = [t for i in range(C) for t in (d['chrom'][i], d['ref'][i], d['alt'][i], d['svtype'][i])]
+        str_off = np.zeros(4 * C + 1, dtype=np.uint32)
+        np.cumsum([len(t) for t in texts], out=str_off[1:])
+        pool = np.frombuffer(b''.join(texts), dtype=np.uint8).copy()
+        distinct = sorted(set(d['chrom']))
+        rank = {t: r for r, t in enumerate(distinct)}
+        cand_off = np.zeros(C + 1, dtype=np.uint32)
+        np.cumsum([len(m) for m in d['marks']], out=cand_off[1:])
+        tags = [t for m in d['marks'] for t in m]                            # a read per mark
+        mark_read = [_lib.MARK_ABSENT if t is ABSENT else r for r, t in enumerate(tags)]
+        read_tag = [0 if t is ABSENT else t for t in tags]
+        self.ctg_off = np.searchsorted(np.asarray(d['contig'], dtype=np.int64), np.arange(K + 1)).astype(np.uint32)
+        p = _lib.RowsProblem()
+        p.n_contigs, p.n_cands = K, C
+        p.cand_ctg_off = self.ctg_off.ctypes.data
+        p.pred, p.ps = self.up(d['pred'], np.uint8), self.up(d['ps'], np.uint32)
+        p.cand_pos, p.cand_svlen = self.up(d['pos'], np.uint32), self.up(d['svlen'], np.uint32)
+        p.cand_plus = self.up(d['plus'], np.uint8)
+        p.cand_chrom_rank = self.up([rank[t] for t in d['chrom']], np.uint16)
+        p.n_chrom_texts = max(len(distinct), 1)
+        p.max_pos = (max(d['pos']) if C else 0) if max_pos is None else max_pos
+        p.pool, p.pool_bytes, p.str_off = self.up(pool, np.uint8), len(pool), self.up(str_off, np.uint32)
+        p.cand_off, p.mark_read, p.read_tag = self.up(cand_off, np.uint32), self.up(mark_read, np.uint32), self.up(read_tag, np.uint64)
+        self.p = p
+        self.bound = len(pool) + 96 * C
+
+    def up(self, a, dt):
+        a = np.ascontiguousarray(np.asarray(a, dtype=dt))
+        t = self.torch.zeros(a.nbytes + 64, dtype=self.torch.uint8, device=self.dev)
+        if a.nbytes:
+            t[:a.nbytes] = self.torch.from_numpy(a.view(np.uint8).reshape(-1)).to(self.dev)
+        self.keep.append(t)
+        return t.data_ptr()
+
+    def run(self, ctx, cap):
+        """-> (out_len, n_rows) or the library's error, and the whole buffer: cap bytes and a pre-filled tail of 64."""
+        torch = self.torch
+        out = torch.full((cap + 64,), CANARY, dtype=torch.uint8, device=self.dev)
+        try:
+            got = ctx.rows_device(self.p, out.data_ptr(), cap, torch.cuda.current_stream(self.dev).cuda_stream)
+        except _lib.DuetLibraryError as e:
+            got = e
+        torch.cuda.synchronize(self.dev)
+        return got, out.cpu().numpy()
+
+
+def check(ctx, d, max_pos=None):
+    want, n_rows = rows_of(d)
+    r = Resident(d, max_pos)
+    assert len(want) <= r.bound
+    got, out = r.run(ctx, r.bound)
+    assert got == (len(want), n_rows), got
+    assert out[:len(want)].tobytes() == want and (out[r.bound:] == CANARY).all()
+    return want
+
+
+# rows_write: 4 rows per workgroup, the grid capped at 8,192 workgroups -- 32,769 rows take the grid-stride loop
+@pytest.mark.parametrize('N', [0, 1, 3, 4, 5, 255, 256, 257, 32767, 32768, 32769])
+def test_kept_rows(ctx, N):
+    rng = np.random.default_rng(N)
+    C = N + N // 3 + 2
+    pred = np.zeros(C, dtype=np.int64)
+    pred[rng.choice(C, N, replace=False)] = rng.integers(1, 4, N)
+    d = cands(C, contig=np.sort(rng.integers(0, 3, C)), pos=rng.integers(0, 3_000_000, C), svlen=rng.integers(0, 20000, C),
+              plus=rng.integers(0, 2, C), pred=pred, ps=rng.integers(0, 3_000_000, C),
+              ref=[b'ACGT'[:1 + i % 4] for i in range(C)], svtype=[(b'INS', b'DEL', b'DUP')[i % 3] for i in range(C)])
+    want = check(ctx, d)
+    assert want.count(b'\n') == N
+
+
+EDGES = sorted(set([0, BIG] + [10 ** k - 1 for k in range(1, 10)] + [10 ** k for k in range(1, 10)]))
+
+
+def test_decimal_boundaries_of_pos_svlen_and_ps(ctx):
+    """0, every 10^k - 1 / 10^k and 2^32 - 1 in each number while the others vary"""
+    E = len(EDGES)
+    idx = np.arange(3 * E)
+    v = np.array(EDGES, dtype=np.int64)
+    d = cands(3 * E, pos=np.where(idx // E == 0, v[idx % E], v[(idx * 7 + 3) % E]),
+              svlen=np.where(idx // E == 1, v[idx % E], v[(idx * 5 + 1) % E]), plus=idx % 2,
+              ps=np.where(idx // E == 2, v[idx % E], v[(idx * 11 + 2) % E]), pred=1 + idx % 3)
+    want = check(ctx, d).decode()
+    for e in EDGES:
+        assert 'chr1\t%d\t' % e in want and ':%d\n' % e in want and ('SVLEN=%d;' % e in want or 'SVLEN=-%d;' % e in want)
+    check(ctx, d, max_pos=0)                                                     # POS bound unknown: 32 key bits
+    # the longest numeric pieces: every number at ten digits, the sign present
+    want = check(ctx, cands(3, pos=BIG, svlen=BIG, ps=BIG, plus=0, pred=3, svtype=b'DEL'))
+    assert want.startswith(b'chr1\t4294967295\tDuet.1\tN\t<INS>\t.\tPASS\tSVLEN=-4294967295;SVTYPE=<DEL>\tHP:PS\t1|1:4294967295\n')
+
+
+def test_row_numbers_cross_their_digit_counts(ctx):
+    """10,001 kept rows among dropped ones: Duet.9 -> Duet.10, Duet.99 -> Duet.100, Duet.9999 -> Duet.10000"""
+    C = 12000
+    rng = np.random.default_rng(5)
+    pred = np.ones(C, dtype=np.int64)
+    pred[rng.choice(C, C - 10001, replace=False)] = 0
+    d = cands(C, contig=np.sort(rng.integers(0, 2, C)), pos=rng.integers(0, 1_000_000, C), pred=pred)
+    want = check(ctx, d).split(b'\n')
+    assert len(want) == 10002
+    for n in (1, 9, 10, 99, 100, 999, 1000, 9999, 10000, 10001):
+        assert b'\tDuet.%d\t' % n in want[n - 1]
+
+
+def test_ref_and_alt_lengths_around_the_64_lane_copy(ctx):
+    lens = (1, 63, 64, 65, 300)
+    text = bytes(bytearray(65 + i % 26 for i in range(300)))
+    pairs = [(a, b) for a in lens for b in lens]
+    d = cands(len(pairs), pos=np.arange(len(pairs)), ref=[text[:a] for a, _ in pairs], alt=[text[300 - b:] for _, b in pairs])
+    want = check(ctx, d).split(b'\n')[:-1]
+    assert [(len(l.split(b'\t')[3]), len(l.split(b'\t')[4])) for l in want] == pairs
+
+
+def test_two_chrom_spellings_within_one_contig(ctx):
+    C = 200
+    rng = np.random.default_rng(2)
+    d = cands(C, contig=np.arange(C) // 100, chrom=[(b'chr1', b'1')[i % 2] if i < 100 else (b'chr2', b'2')[i % 3 == 0] for i in range(C)],
+              pos=rng.integers(0, 40, C), ps=np.arange(C), pred=1 + np.arange(C) % 3)
+    want = check(ctx, d).split(b'\n')[:-1]
+    first = [l.split(b'\t')[0] for l in want]
+    assert first == sorted(first) and set(first) == {b'1', b'2', b'chr1', b'chr2'}
+
+
+def test_sign_of_svlen_and_the_haplotypes(ctx):
+    """cand_plus 0 and 1 with SVLEN 0 and not (no -0); pred 1, 2, 3"""
+    plus, svlen, pred = zip(*[(a, b, c) for a in (0, 1) for b in (0, 37) for c in (1, 2, 3)])
+    d = cands(12, pos=np.arange(12), plus=plus, svlen=svlen, pred=pred)
+    want = check(ctx, d).decode()
+    assert '-0' not in want
+    assert want.count('SVLEN=0;') == 6 and want.count('SVLEN=-37;') == 3 and want.count('SVLEN=37;') == 3
+    assert [l.rsplit('\t', 1)[1].split(':')[0] for l in want.split('\n')[:-1]] == ['1|0', '0|1', '1|1'] * 4
+
+
+def test_ties_across_ps_classes_and_contigs_stay_in_file_order(ctx):
+    """equal (CHROM, POS): contig first, then PS-class 0 / 1 / 2, then file order"""
+    kinds = ([ABSENT], [4], [4, 9], [4, ABSENT, 4], [ABSENT, ABSENT], [9, 4, 4])                 # classes 0 1 2 1 0 2
+    C = 48
+    d = cands(C, contig=np.arange(C) // 24, chrom=b'chr1', pos=[(500, 20)[(i // 12) % 2] for i in range(C)],
+              marks=[kinds[(i * 5) % 6] for i in range(C)], ps=np.arange(C), pred=1 + np.arange(C) % 3)
+    want = check(ctx, d).split(b'\n')[:-1]
+    got = [int(l.rsplit(b':', 1)[1]) for l in want]
+    assert got == [i for p in (20, 500) for k in (0, 1) for c in (0, 1, 2) for i in range(C)
+                   if d['pos'][i] == p and d['contig'][i] == k and ps_class(d['marks'][i]) == c]
+
+
+def test_chrom_texts_sort_as_text(ctx):
+    C = 90
+    d = cands(C, contig=np.arange(C) // 30, chrom=[(b'1', b'10', b'2')[i // 30] for i in range(C)],
+              pos=np.random.default_rng(3).integers(0, 30, C), ps=np.arange(C))
+    want = check(ctx, d).split(b'\n')[:-1]
+    assert [l.split(b'\t')[0] for l in want] == [b'1'] * 30 + [b'10'] * 30 + [b'2'] * 30
+
+
+def test_out_cap(ctx):
+    """the exact size works; one byte less is refused; the bytes behind out_cap stay as they were in both"""
+    rng = np.random.default_rng(8)
+    C = 3000
+    d = cands(C, contig=np.sort(rng.integers(0, 3, C)), pos=rng.integers(0, 3_000_000, C), pred=rng.integers(0, 4, C),
+              svlen=rng.integers(0, 20000, C), plus=rng.integers(0, 2, C), ps=rng.integers(0, 3_000_000, C))
+    want, n_rows = rows_of(d)
+    r = Resident(d)
+    got, out = r.run(ctx, len(want))
+    assert got == (len(want), n_rows)
+    assert out[:len(want)].tobytes() == want and (out[len(want):] == CANARY).all()
+    got, out = r.run(ctx, len(want) - 1)
+    assert isinstance(got, _lib.DuetLibraryError) and 'output buffer too small' in str(got)
+    assert (out[len(want) - 1:] == CANARY).all()

@@ -101,8 +101,9 @@ def test_svim_rows_kernels_use_no_scratch_and_make_no_call(tmp_path):
     r = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     found = re.findall(r'Function Name: (\S+) \[.*?\n(?:.*\n){0,8}?.*ScratchSize \[bytes/lane\]: (\d+)', r.stderr)
-    # every kernel of the unit: its own (sr_*) and the scan / radix instances it takes from duet_prims.hip.h
-    own = {n: int(v) for n, v in found if 'sr_' in n}
+    # every kernel of the unit: its own (sr_*), the 64-bit spine scan it takes from duet_text.hip.h and the scan / radix
+    # instances it takes from duet_prims.hip.h
+    own = {n: int(v) for n, v in found if 'sr_' in n or 'scan_spine_u64' in n}
     assert len(own) == 5, found
     assert len(found) >= 5 + 5 and all(int(v) == 0 for _, v in found), found
     with open(asm) as f:
