@@ -30,7 +30,8 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_comm_allgather_host', 'duet_comm_destroy', 'duet_comm_set_timeout', 'duet_comm_block_bytes',
            'duet_comm_ef_allgather', 'duet_comm_rccl_version', 'duet_comm_info', 'duet_comm_selftest',
            'duet_ef_features_device', 'duet_ef_features_host', 'duet_tune_sweep_device', 'duet_tune_sweep_host',
-           'duet_svim_vcf_rows_device', 'duet_svim_vcf_rows_host', 'duet_svim_phased_rows_device', 'duet_svim_phased_rows_host')
+           'duet_svim_vcf_rows_device', 'duet_svim_vcf_rows_host', 'duet_svim_phased_rows_device', 'duet_svim_phased_rows_host',
+           'duet_svim_features_device', 'duet_svim_features_host', 'duet_tune_truth_build_device', 'duet_tune_truth_build_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -149,6 +150,26 @@ class TuneTruth(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ('cand_flags', 'cand_group', 'cand_uid', 'cand_pair', 'group_pair_off', 'pair_uid')]
 
 
+TUNE_KEY_NONE, TUNE_KEY_SKIP = 0xFFFFFFFE, 0xFFFFFFFF
+
+
+class TuneTruthProblem(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ('n_cands', 'n_keys', 'n_base', 'n_base_uid', 'n_chrom', 'n_contigs', 'refdist',
+                                               'reserved')] + [('ratio', ctypes.c_double)] + \
+               [(n, ctypes.c_void_p) for n in ('feat', 'cand_pos', 'cand_len', 'cand_key', 'cand_chrom', 'cand_contig', 'cand_type',
+                                               'key_table', 'chrom_id', 'bed_off', 'bed_lo', 'bed_hi', 'base_off', 'base_pos',
+                                               'base_len', 'base_uid', 'base_hp')]
+
+
+# the arrays of a TuneTruthProblem and their element types: per candidate (either form), the tables, the truth side
+TRUTH_PROBLEM_ARRAYS = (('cand_pos', np.uint32), ('cand_len', np.uint32), ('cand_key', np.uint32), ('cand_chrom', np.uint32),
+                        ('cand_contig', np.uint16), ('cand_type', np.uint8), ('key_table', np.uint32), ('chrom_id', np.uint32),
+                        ('bed_off', np.uint32), ('bed_lo', np.uint32), ('bed_hi', np.uint32), ('base_off', np.uint32),
+                        ('base_pos', np.uint32), ('base_len', np.uint32), ('base_uid', np.uint32), ('base_hp', np.uint8))
+TRUTH_ARRAYS = (('cand_flags', np.uint16), ('cand_group', np.uint32), ('cand_uid', np.uint32), ('cand_pair', np.uint32),
+                ('group_pair_off', np.uint32), ('pair_uid', np.uint32))
+
+
 class DuetLibraryError(RuntimeError):
     pass
 
@@ -234,6 +255,12 @@ def load():
                        ctypes.c_uint32, ctypes.POINTER(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_uint64,
                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)] + \
                       ([ctypes.c_void_p] if fn is lib.duet_svim_phased_rows_device else [])
+    lib.duet_svim_features_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult),
+                                              ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+    lib.duet_svim_features_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult), ctypes.c_void_p]
+    lib.duet_tune_truth_build_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(TuneTruthProblem), ctypes.POINTER(TuneTruth),
+                                                 ctypes.c_void_p]
+    lib.duet_tune_truth_build_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(TuneTruthProblem), ctypes.POINTER(TuneTruth)]
     _lib = lib
     return lib
 
@@ -392,11 +419,9 @@ class Context(object):
         return dict(order=out['order'][:M], cand_off=out['cand_off'][:N + 1], cand_contig=out['cand_contig'][:N],
                     cand_type=out['cand_type'][:N], cand_pos=out['cand_pos'][:N], cand_span=out['cand_span'][:N])
 
-    def svim_host(self, marks, read_tag, depth, depth_off, depth_bin, svlen_thres, suppread_thres, max_dist=0.9, part_gap=1000,
-                  part_max=100, normalizer=900.0, want_order=False):
-        """The fused SVIM-mode pipeline on host arrays (duet_svim_phase_host): raw marks dict(contig, type, pos, span, read) ->
-        dict(cand_off, cand_contig, cand_type, cand_pos, cand_span, pred, ps) trimmed to the candidate count (want_order: and
-        the cluster order, order u32[M])."""
+    def _svim_host_problem(self, marks, read_tag, depth, depth_off, depth_bin, svlen_thres, suppread_thres, max_dist, part_gap,
+                           part_max, normalizer, want_order):
+        """-> (SvimProblem, ClusterResult, result arrays, order or None, n_cands word, keepalive) over host arrays."""
         arr = {k: np.ascontiguousarray(marks[k], dtype=dt) for k, dt in (('contig', np.uint16), ('type', np.uint8), ('pos', np.uint32),
                                                                         ('span', np.uint32), ('read', np.uint32))}
         read_tag = np.ascontiguousarray(read_tag, dtype=np.uint64)
@@ -422,7 +447,6 @@ class Context(object):
         out = dict(cand_off=np.zeros(M + 1, dtype=np.uint32), cand_contig=np.zeros(max(M, 1), dtype=np.uint16),
                    cand_type=np.zeros(max(M, 1), dtype=np.uint8), cand_pos=np.zeros(max(M, 1), dtype=np.uint32),
                    cand_span=np.zeros(max(M, 1), dtype=np.uint32))
-        pred, ps = np.zeros(max(M, 1), dtype=np.uint8), np.zeros(max(M, 1), dtype=np.uint32)
         n = ctypes.c_uint32(0)
         res = ClusterResult()
         for k in out:
@@ -430,15 +454,43 @@ class Context(object):
         order = np.zeros(max(M, 1), dtype=np.uint32) if want_order else None
         res.order = order.ctypes.data if want_order else None
         res.n_cands = ctypes.addressof(n)
+        return p, res, out, order, n, (arr, read_tag, depth, depth_off)
+
+    @staticmethod
+    def _svim_trim(out, N):
+        return dict(cand_off=out['cand_off'][:N + 1], cand_contig=out['cand_contig'][:N], cand_type=out['cand_type'][:N],
+                    cand_pos=out['cand_pos'][:N], cand_span=out['cand_span'][:N])
+
+    def svim_host(self, marks, read_tag, depth, depth_off, depth_bin, svlen_thres, suppread_thres, max_dist=0.9, part_gap=1000,
+                  part_max=100, normalizer=900.0, want_order=False):
+        """The fused SVIM-mode pipeline on host arrays (duet_svim_phase_host): raw marks dict(contig, type, pos, span, read) ->
+        dict(cand_off, cand_contig, cand_type, cand_pos, cand_span, pred, ps) trimmed to the candidate count (want_order: and
+        the cluster order, order u32[M])."""
+        p, res, out, order, n, keep = self._svim_host_problem(marks, read_tag, depth, depth_off, depth_bin, svlen_thres, suppread_thres,
+                                                              max_dist, part_gap, part_max, normalizer, want_order)
+        M = p.marks.n_marks
+        pred, ps = np.zeros(max(M, 1), dtype=np.uint8), np.zeros(max(M, 1), dtype=np.uint32)
         rc = self.lib.duet_svim_phase_host(self.handle, ctypes.byref(p), ctypes.byref(res), _ptr(pred), _ptr(ps))
+        del keep
         if rc:
             self._raise(rc)
         N = n.value
-        got = dict(cand_off=out['cand_off'][:N + 1], cand_contig=out['cand_contig'][:N], cand_type=out['cand_type'][:N],
-                   cand_pos=out['cand_pos'][:N], cand_span=out['cand_span'][:N], pred=pred[:N], ps=ps[:N])
+        got = dict(self._svim_trim(out, N), pred=pred[:N], ps=ps[:N])
         if want_order:
             got['order'] = order[:M]
         return got
+
+    def svim_features_host(self, marks, read_tag, depth, depth_off, depth_bin, svlen_thres, suppread_thres, max_dist=0.9,
+                           part_gap=1000, part_max=100, normalizer=900.0):
+        """duet_svim_features_host: like svim_host, with the candidates' features (FEATURE_DTYPE[N]) in place of pred / ps."""
+        p, res, out, _, n, keep = self._svim_host_problem(marks, read_tag, depth, depth_off, depth_bin, svlen_thres, suppread_thres,
+                                                          max_dist, part_gap, part_max, normalizer, False)
+        feat = np.zeros(max(p.marks.n_marks, 1), dtype=FEATURE_DTYPE)
+        rc = self.lib.duet_svim_features_host(self.handle, ctypes.byref(p), ctypes.byref(res), _ptr(feat))
+        del keep
+        if rc:
+            self._raise(rc)
+        return dict(self._svim_trim(out, n.value), feat=feat[:n.value])
 
     def svim_vcf_rows_device(self, sv_problem, result, n_cands, names, out_ptr, cap, stream):
         """duet_svim_vcf_rows_device on resident arrays (DeviceSvim.vcf_rows) -> bytes written."""
@@ -571,6 +623,66 @@ class Context(object):
         if rc:
             self._raise(rc)
         return counts, pred, ps
+
+    def truth_build_host(self, feat, arrays, refdist, ratio):
+        """duet_tune_truth_build_host: feat FEATURE_DTYPE[C]; arrays = dict of the host arrays of a TuneTruthProblem (cand_pos,
+        cand_len, then cand_key + cand_chrom or cand_contig + cand_type + key_table + chrom_id [+ bed_off, bed_lo, bed_hi]; the truth
+        side base_off, base_pos, base_len, base_uid, base_hp) and the words n_base_uid, n_chrom
+        -> dict of the six truth arrays trimmed to their sizes, n_uid, n_groups, n_pairs (what tune.prepare_truth returns)."""
+        feat = np.ascontiguousarray(feat, dtype=FEATURE_DTYPE)
+        C = len(feat)
+        p, keep = TuneTruthProblem(), [feat]
+        p.feat = feat.ctypes.data if C else None
+        for name, dt in TRUTH_PROBLEM_ARRAYS:
+            if arrays.get(name) is None:
+                continue
+            a = np.ascontiguousarray(arrays[name], dtype=dt)
+            keep.append(a)
+            setattr(p, name, a.ctypes.data if a.size else None)
+        p.n_cands, p.n_keys, p.n_base = C, len(arrays['base_off']) - 1, len(arrays['base_pos'])
+        p.n_base_uid, p.n_chrom = int(arrays['n_base_uid']), int(arrays['n_chrom'])
+        p.n_contigs = len(arrays['chrom_id']) if arrays.get('chrom_id') is not None else 0
+        p.refdist, p.ratio = clamp_u32(refdist), float(ratio)
+        out = {name: np.zeros(C + (1 if name == 'group_pair_off' else 0), dtype=dt) for name, dt in TRUTH_ARRAYS}
+        t = TuneTruth()
+        for name, _ in TRUTH_ARRAYS:
+            setattr(t, name, out[name].ctypes.data if out[name].size else None)
+        rc = self.lib.duet_tune_truth_build_host(self.handle, ctypes.byref(p), ctypes.byref(t))
+        del keep
+        if rc:
+            self._raise(rc)
+        out['group_pair_off'] = out['group_pair_off'][:t.n_groups + 1]
+        out['pair_uid'] = out['pair_uid'][:t.n_pairs]
+        out.update(n_uid=t.n_uid, n_groups=t.n_groups, n_pairs=t.n_pairs)
+        return out
+
+    def truth_build_device(self, prob, truth, stream=0):
+        """duet_tune_truth_build_device on resident arrays (devmem.DeviceTune): fills truth.n_groups / n_pairs."""
+        rc = self.lib.duet_tune_truth_build_device(self.handle, ctypes.byref(prob), ctypes.byref(truth), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+
+    def features_device(self, prob, out_ptr, stream=0):
+        """duet_ef_features_device; raises ZeroDivisionError where E/F would (the records are written all the same)."""
+        rc = self.lib.duet_ef_features_device(self.handle, ctypes.byref(prob), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+
+    def svim_features_device(self, sv_problem, result, out_ptr, stream=0):
+        """duet_svim_features_device -> the candidate count."""
+        n = ctypes.c_uint32(0)
+        rc = self.lib.duet_svim_features_device(self.handle, ctypes.byref(sv_problem), ctypes.byref(result), ctypes.c_void_p(out_ptr),
+                                                ctypes.byref(n), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return n.value
+
+    def sweep_device(self, feat_ptr, n_cands, vec_ptr, n_vec, truth, counts_ptr, stream=0):
+        rc = self.lib.duet_tune_sweep_device(self.handle, ctypes.c_void_p(feat_ptr), int(n_cands), ctypes.c_void_p(vec_ptr), int(n_vec),
+                                             ctypes.byref(truth) if truth is not None else None, ctypes.c_void_p(counts_ptr), None, None,
+                                             ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
 
     def seed_ps(self, contig, cap=1 << 20):
         out = np.zeros(cap, dtype=np.uint32)

@@ -3621,5 +3621,130 @@ int duet_svim_phase_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_
     return DUET_OK;
 }
 
+// The fused pipeline up to the adapted E/F problem, then the features of that problem (duet_tune.hip) instead of its decisions: the
+// host-planned branch of duet_svim_phase_device with duet_ef_features_device in place of duet_ef_run_device.  (That entry stays
+// as it is -- its asynchronous branch has no counterpart here -- so the set-up in front of the clustering is restated.)
+int duet_svim_features_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat,
+                              uint32_t *n_cands_host, void *stream_)
+{
+    if (!ctx) return duet_fail(nullptr, DUET_ERR_INVALID, "null context");
+    if (!pr || !res || !out_feat || !n_cands_host) return duet_fail(ctx, DUET_ERR_INVALID, "null argument");
+    if (!pr->depth_off || pr->depth_bin == 0 || pr->n_contigs == 0 || pr->n_contigs > 65535)
+        return duet_fail(ctx, DUET_ERR_INVALID, "bad depth / contig description");
+    hipStream_t st = (hipStream_t)stream_;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t M = pr->marks.n_marks, K = pr->n_contigs;
+    *n_cands_host = 0;
+    if (M == 0) {
+        if (res->n_cands) HIP_TRY(ctx, hipMemsetAsync(res->n_cands, 0, 4, st));
+        return DUET_OK;
+    }
+    if (!pr->mark_read || !pr->depth) return duet_fail(ctx, DUET_ERR_INVALID, "null array");
+    int rc;
+    const size_t sz[5] = {((size_t)K + 1) * 4 * 2, (size_t)M * 4, (size_t)M * 4, (size_t)M, (size_t)M * 4};
+    for (int i = 0; i < 5; ++i)
+        if ((rc = duet_reserve(ctx, ctx->sv_ws[i], sz[i]))) return rc;
+    uint32_t *d_ctg_off = (uint32_t *)ctx->sv_ws[0].ptr, *d_depth_off = d_ctg_off + (K + 1);
+    // (the depth offsets are uploaded only when they change, ordered as duet_svim_phase_device orders them)
+    if (ctx->sv_depth_off_at != (void *)d_depth_off || ctx->sv_depth_off.size() != (size_t)K + 1 || ctx->sv_depth_off_stream != st ||
+        memcmp(ctx->sv_depth_off.data(), pr->depth_off, ((size_t)K + 1) * 4) != 0) {
+        if (!ctx->sv_depth_off_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->sv_depth_off_ev, hipEventDisableTiming));
+        if (ctx->sv_depth_off_at) HIP_TRY(ctx, hipEventSynchronize(ctx->sv_depth_off_ev));
+        ctx->sv_depth_off.assign(pr->depth_off, pr->depth_off + K + 1);
+        HIP_TRY(ctx, hipMemcpyAsync(d_depth_off, ctx->sv_depth_off.data(), ((size_t)K + 1) * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipEventRecord(ctx->sv_depth_off_ev, st));
+        ctx->sv_depth_off_at = (void *)d_depth_off;
+        ctx->sv_depth_off_stream = st;
+    }
+    SvExtra sv;
+    sv.mark_in = pr->mark_read; sv.depth = pr->depth; sv.depth_off = d_depth_off; sv.depth_bin = pr->depth_bin;
+    sv.mark_out = (uint32_t *)ctx->sv_ws[4].ptr; sv.svread = (uint32_t *)ctx->sv_ws[1].ptr;
+    sv.refread = (uint32_t *)ctx->sv_ws[2].ptr; sv.gt = (uint8_t *)ctx->sv_ws[3].ptr;
+    sv.ef_ctg_off = nullptr; sv.ef_zero = nullptr; sv.n_contigs = K;
+    if ((rc = cluster_run(ctx, &pr->marks, res, st, &sv))) return rc;
+    hipLaunchKernelGGL(sv_contig_offsets, dim3((K + 1 + 255) / 256), dim3(256), 0, st, (const uint16_t *)res->cand_contig,
+                       (const uint32_t *)res->n_cands, K, d_ctg_off);
+    std::vector<uint32_t> ctg_off(K + 1);
+    HIP_TRY(ctx, hipMemcpyAsync(ctg_off.data(), d_ctg_off, ((size_t)K + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));             // candidates per contig
+    const uint32_t N = ctg_off[K];
+    *n_cands_host = N;
+    if (N == 0) return DUET_OK;
+    duet_ef_problem ef;
+    memset(&ef, 0, sizeof(ef));
+    ef.n_contigs = K; ef.n_cands = N; ef.n_marks = M; ef.n_reads = pr->n_reads;
+    ef.cand_ctg_off = ctg_off.data();
+    ef.read_tag = pr->read_tag;
+    ef.cand_pos = res->cand_pos; ef.cand_svlen = res->cand_span; ef.cand_svread = sv.svread; ef.cand_refread = sv.refread;
+    ef.cand_gt_ok = sv.gt; ef.cand_off = res->cand_off; ef.mark_read = sv.mark_out;
+    ef.svlen_thres = pr->svlen_thres; ef.suppread_thres = pr->suppread_thres;
+    return duet_ef_features_device(ctx, &ef, out_feat, st);
+}
+
+int duet_svim_features_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat)
+{
+    if (!ctx) return duet_fail(nullptr, DUET_ERR_INVALID, "null context");
+    if (!pr || !res || !res->n_cands || !out_feat) return duet_fail(ctx, DUET_ERR_INVALID, "null argument");
+    if (!pr->depth_off || pr->n_contigs == 0) return duet_fail(ctx, DUET_ERR_INVALID, "bad depth / contig description");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t M = pr->marks.n_marks;
+    *res->n_cands = 0;
+    if (M == 0) return DUET_OK;
+    // (host arrays: what the device entry has to trust is checked, as in duet_svim_phase_host)
+    if (!res->cand_off || !res->cand_contig || !res->cand_type || !res->cand_pos || !res->cand_span)
+        return duet_fail(ctx, DUET_ERR_INVALID, "null result array");
+    for (uint32_t k = 0; k < pr->n_contigs; ++k)
+        if (pr->depth_off[k] > pr->depth_off[k + 1]) return duet_fail(ctx, DUET_ERR_INVALID, "depth_off must be non-decreasing");
+    if (!pr->marks.mark_contig) return duet_fail(ctx, DUET_ERR_INVALID, "null array");
+    for (uint32_t i = 0; i < M; ++i)
+        if (pr->marks.mark_contig[i] >= pr->n_contigs)
+            return duet_fail(ctx, DUET_ERR_INVALID, "a mark's contig id is not below n_contigs (the depth description's contig count)");
+    hipStream_t s = ctx->own_stream;
+    int rc;
+    const size_t n_depth = pr->depth_off[pr->n_contigs];
+    const void *src[7] = {pr->marks.mark_contig, pr->marks.mark_type, pr->marks.mark_pos, pr->marks.mark_span, pr->mark_read, pr->read_tag, pr->depth};
+    const size_t ib[7] = {(size_t)M * 2, (size_t)M, (size_t)M * 4, (size_t)M * 4, (size_t)M * 4, (size_t)pr->n_reads * 8, n_depth * 4};
+    DevBuf *in[7] = {&ctx->cl_in[0], &ctx->cl_in[1], &ctx->cl_in[2], &ctx->cl_in[3], &ctx->sv_in[0], &ctx->sv_in[1], &ctx->sv_in[2]};
+    for (int i = 0; i < 7; ++i) {
+        if (!src[i] && ib[i]) return duet_fail(ctx, DUET_ERR_INVALID, "null array");
+        if ((rc = duet_reserve(ctx, *in[i], ib[i] + 16))) return rc;
+        if (ib[i]) HIP_TRY(ctx, hipMemcpyAsync(in[i]->ptr, src[i], ib[i], hipMemcpyHostToDevice, s));
+    }
+    const size_t ob[6] = {(size_t)M * 4, ((size_t)M + 1) * 4 + 16, (size_t)M * 2, (size_t)M, (size_t)M * 4, (size_t)M * 4};
+    for (int i = 0; i < 6; ++i)
+        if ((rc = duet_reserve(ctx, ctx->cl_out[i], ob[i]))) return rc;
+    DevBuf &bf = ctx->tune_ws.b[2];                     // (the feature staging of duet_ef_features_host)
+    if ((rc = duet_reserve(ctx, bf, (size_t)M * sizeof(duet_tune_feature)))) return rc;
+    duet_svim_problem d = *pr;
+    d.marks.mark_contig = (const uint16_t *)ctx->cl_in[0].ptr;
+    d.marks.mark_type = (const uint8_t *)ctx->cl_in[1].ptr;
+    d.marks.mark_pos = (const uint32_t *)ctx->cl_in[2].ptr;
+    d.marks.mark_span = (const uint32_t *)ctx->cl_in[3].ptr;
+    d.mark_read = (const uint32_t *)ctx->sv_in[0].ptr;
+    d.read_tag = (const uint64_t *)ctx->sv_in[1].ptr;
+    d.depth = (const uint32_t *)ctx->sv_in[2].ptr;
+    duet_cluster_result r;
+    r.order = (uint32_t *)ctx->cl_out[0].ptr;
+    r.cand_off = (uint32_t *)ctx->cl_out[1].ptr;
+    r.cand_contig = (uint16_t *)ctx->cl_out[2].ptr;
+    r.cand_type = (uint8_t *)ctx->cl_out[3].ptr;
+    r.cand_pos = (uint32_t *)ctx->cl_out[4].ptr;
+    r.cand_span = (uint32_t *)ctx->cl_out[5].ptr;
+    r.n_cands = (uint32_t *)((char *)ctx->cl_out[1].ptr + ((size_t)M + 1) * 4);        // spare word after cand_off
+    uint32_t n = 0;
+    rc = duet_svim_features_device(ctx, &d, &r, (duet_tune_feature *)bf.ptr, &n, s);
+    if (rc && rc != DUET_ERR_DIV_ZERO) return rc;
+    const std::string msg = ctx->err;
+    *res->n_cands = n;
+    if (res->order) HIP_TRY(ctx, hipMemcpy(res->order, r.order, (size_t)M * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(res->cand_off, r.cand_off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(res->cand_contig, r.cand_contig, (size_t)n * 2, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(res->cand_type, r.cand_type, (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(res->cand_pos, r.cand_pos, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(res->cand_span, r.cand_span, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out_feat, bf.ptr, (size_t)n * sizeof(duet_tune_feature), hipMemcpyDeviceToHost));
+    if (rc) ctx->err = msg;
+    return rc;
+}
 
 }  // extern "C"

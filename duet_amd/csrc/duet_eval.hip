@@ -28,6 +28,8 @@
 
 namespace {
 
+#include "duet_prims.hip.h"
+
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 
 struct EvalParams {
@@ -58,20 +60,9 @@ __global__ __launch_bounds__(256) void eval_match(const EvalParams p)
         const uint32_t lo0 = p.base_off[key], n = p.base_off[key + 1] - lo0;
         const uint32_t *bp = p.base_pos + lo0;
         const uint32_t pos = p.call_pos[c];
-        uint32_t lo = 0, hi = n;                                        // np.searchsorted(..., side='left')
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (bp[mid] < pos) lo = mid + 1; else hi = mid;
-        }
-        uint32_t j;                                                      // :118-125
-        if (lo == n) j = lo - 1;
-        else if (lo > 0 && llabs((long long)pos - (long long)bp[lo]) > llabs((long long)pos - (long long)bp[lo - 1])) j = lo - 1;
-        else j = lo;
+        const uint32_t j = nearest_truth(bp, n, pos);                  // :117-125
         const uint32_t b = lo0 + j;
-        const uint32_t cl = p.call_len[c], bl = p.base_len[b];
-        const uint32_t mn = cl < bl ? cl : bl, mx = cl < bl ? bl : cl;
-        const bool ok = (uint64_t)llabs((long long)pos - (long long)bp[j]) <= (uint64_t)p.refdist &&
-                        (double)mn / (double)mx >= p.ratio;             // :126-127
+        const bool ok = truth_accepts(pos, bp[j], p.call_len[c], p.base_len[b], p.refdist, p.ratio);   // :126-127
         if (ok) {
             m = b;
             const uint8_t ch = p.call_hp[c], bh = p.base_hp[b];

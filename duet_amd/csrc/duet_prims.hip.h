@@ -11,6 +11,29 @@ constexpr int kScanThreads = 256;
 constexpr int kScanItems = 8;
 constexpr int kScanTile = kScanThreads * kScanItems;
 
+// The evaluator's nearest truth record (src/scripts/evaluation.py:117-125) among the n >= 1 ascending positions bp[]:
+// np.searchsorted(..., side='left'); the left neighbour when the insertion point is the end or when it is strictly nearer, a
+// tie goes to the right one; among equal positions the first.  Shared by the evaluator (duet_eval.hip) and the sweep's truth
+// build (duet_tune_truth.hip).
+__device__ __forceinline__ uint32_t nearest_truth(const uint32_t *bp, uint32_t n, uint32_t pos)
+{
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (bp[mid] < pos) lo = mid + 1; else hi = mid;
+    }
+    if (lo == n) return lo - 1;
+    if (lo > 0 && llabs((long long)pos - (long long)bp[lo]) > llabs((long long)pos - (long long)bp[lo - 1])) return lo - 1;
+    return lo;
+}
+
+// ... and its acceptance test (:126-127): the length quotient in binary64, as numpy divides
+__device__ __forceinline__ bool truth_accepts(uint32_t pos, uint32_t bpos, uint32_t cl, uint32_t bl, uint32_t refdist, double ratio)
+{
+    const uint32_t mn = cl < bl ? cl : bl, mx = cl < bl ? bl : cl;
+    return (uint64_t)llabs((long long)pos - (long long)bpos) <= (uint64_t)refdist && (double)mn / (double)mx >= ratio;
+}
+
 // 1024 threads per 4096-key tile (the tile of rx_scatter): four keys per thread, so that a small input -- one tile per CU at
 // 1 M keys -- still has 16 wavefronts per CU loading
 constexpr int kRxHistThreads = 1024;

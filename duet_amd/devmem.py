@@ -200,6 +200,15 @@ class DeviceSvim(DeviceCluster):
         self.n_found = n.value if wait else None
         return stream
 
+    def run_features(self, ctx, feat_ptr, stream=None):
+        """duet_svim_features_device: clusters, adapts and writes the candidates' features to feat_ptr (room for M records);
+        the cluster result stays in self.result.  -> the candidate count.  Raises ZeroDivisionError where E/F would."""
+        if stream is None:
+            stream = self.torch.cuda.current_stream(self.device).cuda_stream
+        self.n_found = None
+        self.n_found = ctx.svim_features_device(self.sv_problem, self.result, feat_ptr, stream)
+        return self.n_found
+
     def vcf_rows(self, ctx, names, chrom_texts, stream=None):
         """Rows of sv_calling/variants.vcf for the last run_fused's candidates, formatted on the device from the resident
         cluster result and depth (duet_svim_vcf_rows_device).  names: dict(mark_name, name_off, name_pool) of
@@ -257,3 +266,79 @@ class DeviceSvim(DeviceCluster):
                     cand_contig=g('cand_contig', np.uint16, N), cand_type=g('cand_type', np.uint8, N),
                     cand_pos=g('cand_pos', np.uint32, N), cand_span=g('cand_span', np.uint32, N),
                     pred=self.out_pred[:N].cpu().numpy(), ps=self.out_ps[:N].cpu().numpy().view(np.uint32))
+
+
+class DeviceTune(object):
+    """What a sweep over settings (duet_amd/tune.py: sweep_settings) keeps in HBM: the truth side, the per-candidate key columns or
+    the per-contig tables, the feature records, the six truth arrays, the vectors and the counts.  Features and truth arrays never
+    leave the device; counts() brings the K count records back."""
+
+    def __init__(self, n_max, base, refdist, ratio, vectors, device='cuda:0'):
+        """n_max: the most candidates any setting can have; base: the truth side (tune.truth_side); vectors: float64[K, 14]."""
+        import torch
+        self.torch = torch
+        self.device = torch.device(device)
+        self.n_max = int(n_max)
+        self.keep = {}
+        p = _lib.TuneTruthProblem()
+        for name, dt in _lib.TRUTH_PROBLEM_ARRAYS[-5:]:
+            setattr(p, name, self._up(name, base[name], dt))
+        p.n_keys, p.n_base, p.n_base_uid = len(base['base_off']) - 1, len(base['base_pos']), int(base['n_base_uid'])
+        p.refdist, p.ratio = _lib.clamp_u32(refdist), float(ratio)
+        self.problem = p
+        n = max(self.n_max, 1)
+        self.feat = torch.zeros(n * _lib.FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        t = _lib.TuneTruth()
+        for name, dt in _lib.TRUTH_ARRAYS:
+            self.keep[name] = torch.zeros((n + 1) * np.dtype(dt).itemsize, dtype=torch.uint8, device=self.device)
+            setattr(t, name, self.keep[name].data_ptr())
+        self.truth = t
+        vec = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1, len(_lib.TUNE_NAMES))
+        self.K = len(vec)
+        self.vec_ptr = self._up('vectors', vec, np.float64)
+        self.counts = torch.zeros(max(self.K, 1) * _lib.COUNTS_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+
+    def _up(self, name, a, dt):
+        a = np.ascontiguousarray(a, dtype=dt)
+        t = self.torch.zeros(a.nbytes + 64, dtype=self.torch.uint8, device=self.device)
+        if a.nbytes:
+            t[:a.nbytes] = self.torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(self.device)
+        self.keep[name] = t
+        return t.data_ptr()
+
+    def stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def set_candidates(self, cand_pos, cand_len, cand_key, cand_chrom, n_chrom):
+        """The per-candidate form: the columns of a callset, uploaded once."""
+        p = self.problem
+        for name, a in (('cand_pos', cand_pos), ('cand_len', cand_len), ('cand_key', cand_key), ('cand_chrom', cand_chrom)):
+            setattr(p, name, self._up(name, a, np.uint32))
+        p.n_chrom = int(n_chrom)
+
+    def set_tables(self, key_table, chrom_id, n_chrom, bed=None):
+        """The table form (a cluster result): per contig the four list keys and the CHROM id; bed = (bed_off, bed_lo, bed_hi)."""
+        p = self.problem
+        p.cand_key, p.cand_chrom = None, None
+        p.key_table, p.chrom_id = self._up('key_table', key_table, np.uint32), self._up('chrom_id', chrom_id, np.uint32)
+        p.n_contigs, p.n_chrom = len(chrom_id), int(n_chrom)
+        if bed is not None:
+            p.bed_off, p.bed_lo, p.bed_hi = (self._up(k, a, np.uint32) for k, a in zip(('bed_off', 'bed_lo', 'bed_hi'), bed))
+
+    def build(self, ctx, n_cands, result=None):
+        """The truth arrays of the features in self.feat (duet_tune_truth_build_device).  result: the ClusterResult whose
+        candidate columns the table form reads."""
+        p = self.problem
+        p.n_cands, p.feat = int(n_cands), self.feat.data_ptr()
+        if result is not None:
+            p.cand_contig, p.cand_type, p.cand_pos, p.cand_len = result.cand_contig, result.cand_type, result.cand_pos, result.cand_span
+        ctx.truth_build_device(p, self.truth, self.stream())
+
+    def sweep(self, ctx, n_cands):
+        """The K vectors over the features and truth arrays of the last build -> COUNTS_DTYPE[K] on the host."""
+        ctx.sweep_device(self.feat.data_ptr(), int(n_cands), self.vec_ptr, self.K, self.truth, self.counts.data_ptr(), self.stream())
+        return self.counts[:self.K * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).copy()
+
+    def features_host(self, n_cands):
+        """(--features) the feature records of the last setting, on the host."""
+        return self.feat[:int(n_cands) * _lib.FEATURE_DTYPE.itemsize].cpu().numpy().view(_lib.FEATURE_DTYPE).copy()

@@ -3,17 +3,22 @@
 
     features(home, ...)                    per-candidate features of a Duet work directory (duet_ef_features_host)
     sweep(home, truth_vcf, grid, ...)      one row per threshold vector: the 14 values and evaluation.py's ten numbers
-    python -m duet_amd.tune WORKDIR TRUTH.vcf --grid GRID.json [...]
+    sweep_settings(home, truth_vcf, grid, svlen_thres=(..), suppread_thres=(..), cluster_max_distance=(..), from_bams=..)
+                                           the same for every setting of -s, -r and (svim-gpu mode, from the BAMs) -c
+    python -m duet_amd.tune WORKDIR TRUTH.vcf --grid GRID.json [-s 30,50 -r 2,3 [--from_bams -c 0.5,0.9]] [...]
 
 The vector's 14 fields, their order and defaults are include/duet_ef.h's duet_tune_thresholds (NAMES, DEFAULTS).  A grid is
 either a list of partial vectors (dicts) or a dict of name -> list of values, expanded as a Cartesian product; names left out
 take the defaults, unknown names are an error.  Values may be numbers or the strings 'nan', 'inf', '-inf'.
 
-The truth set is prepared once on the host (prepare_truth): every candidate that can be emitted is written as the row
-phased_sv.vcf would hold (write_file's format), read back through duet_amd/evaluation.parse_vcf -- so the evaluator's own rules
-decide which calls it sees and with which (contig, type, pos, len, phase-set group) -- and matched once to its nearest truth
-record by the evaluator's rule.  The device then applies the K vectors and counts (duet_tune_sweep_host); the ten numbers are
-the evaluator's binary64 quotients of those counts.  Where upstream would raise (ZeroDivisionError: no calls, or precision +
+What the evaluator's parser makes of a candidate's row does not depend on -s, -r, -c or the thresholds: it is derived once per
+work directory on the host (candidate_keys, contig_tables: every candidate -- or, without per-candidate text, every (contig, type)
+-- written as the row phased_sv.vcf would hold and read back through duet_amd/evaluation.parse_vcf, so the evaluator's own rules
+decide which calls it sees and under which (contig, type, phase-set group)).  Per setting the device then computes the features,
+matches every call to its nearest truth record by the evaluator's rule and numbers the groups and pairs
+(duet_tune_truth_build_device), applies the K vectors and counts (duet_tune_sweep_device); the ten numbers are the evaluator's
+binary64 quotients of those counts.  prepare_truth is the same truth match on the host, in the evaluator's own terms: the
+normative text the device build is tested against.  Where upstream would raise (ZeroDivisionError: no calls, or precision +
 recall == 0; IndexError: an emitted call whose (contig, type) has no truth record) the row's ten numbers are nan.
 """
 
@@ -190,6 +195,101 @@ def prepare_truth(cands, truth_vcf, refdist=1000, pctsim=0.0, bed='', skip_phasi
                 n_uid=len(base_uid), n_groups=G, n_pairs=len(pairs), n_base=len(baseinfo))
 
 
+def truth_side(truth_vcf, bed='', skip_phasing=False):
+    """The truth set as include/duet_ef.h's duet_eval_problem carries it (evaluation.flatten), plus n_base = len(baseinfo)."""
+    baseinfo = evaluation.parse_vcf(truth_vcf, skip_phasing, bed or '')
+    a = evaluation.flatten(baseinfo, [])
+    return dict(base_off=np.asarray(a['base_off'], dtype=np.uint32), base_pos=np.asarray(a['base_pos'], dtype=np.uint32),
+                base_len=np.asarray(a['base_len'], dtype=np.uint32), base_uid=np.asarray(a['base_uid'], dtype=np.uint32),
+                base_hp=np.asarray(a['base_hp'], dtype=np.uint8), n_base_uid=int(a['n_base_uid']), n_base=len(baseinfo))
+
+
+_LIST_KEY = {(c, t): 2 * k + j for k, c in enumerate(evaluation.CHROMS) for j, t in enumerate(('INS', 'DEL'))}
+
+
+def _parsed_rows(rows, bed, skip_phasing):
+    """rows: (chrom, pos, ref, alt, svtype) -> per row (list key | KEY_NONE | KEY_SKIP, CHROM text), through evaluation.parse_vcf.
+    The row's length is written as 50 (the parser's own length test stays with the caller: cand_len >= 50), its HP as 1|0 and its
+    PS as 0: none of them changes what else the parser does with the row."""
+    fd, path = tempfile.mkstemp(suffix='.vcf')
+    try:
+        with os.fdopen(fd, 'w') as f:
+            for i, (chrom, pos, ref, alt, svtype) in enumerate(rows):
+                f.write(row_text(chrom, int(pos), i + 1, ref, alt, 50, svtype, '1|0', 0))
+        recs = evaluation.parse_vcf(path, skip_phasing, bed or '')
+    finally:
+        os.remove(path)
+    key = np.full(len(rows), _lib.TUNE_KEY_SKIP, dtype=np.uint32)
+    for rec in recs:
+        i = int(rec['id'][5:len(rec['id']) - len(rec['chr']) - len(str(rec['pos']))]) - 1       # id = 'Duet.<i + 1>' + CHROM + POS
+        key[i] = _LIST_KEY.get((rec['chr'], rec['type']), _lib.TUNE_KEY_NONE)
+    return key
+
+
+def _dense_ids(texts):
+    ids = {}
+    return np.array([ids.setdefault(t, len(ids)) for t in texts], dtype=np.uint32), max(len(ids), 1)
+
+
+def candidate_keys(cands, bed='', skip_phasing=False):
+    """Per candidate of a callset: cand_key, cand_chrom of include/duet_ef.h's duet_tune_truth_problem, and n_chrom.  With a
+    BED file the evaluator's position test is part of it (a candidate outside the ranges is dropped: KEY_SKIP)."""
+    C = len(cands['pos'])
+    key = _parsed_rows([(cands['chrom'][c], cands['pos'][c], cands['ref'][c], cands['alt'][c], cands['svtype'][c]) for c in range(C)],
+                       bed, skip_phasing)
+    chrom, n_chrom = _dense_ids(cands['chrom'])
+    return key, chrom, n_chrom
+
+
+def contig_tables(chrom_texts, skip_phasing=False):
+    """The table form for a cluster result (svim-gpu mode: no per-candidate text): key_table[4 * contig + type] from one row per
+    (contig, type) as svim_mode.rows_text writes it, chrom_id[contig], n_chrom.  (INV comes out as KEY_SKIP.)"""
+    from duet_amd.svim_mode import SV_TYPE_NAMES
+    rows = [(text, 1, 'N', '<%s>' % t, t) for text in chrom_texts for t in SV_TYPE_NAMES]
+    chrom_id, n_chrom = _dense_ids(chrom_texts)
+    return _parsed_rows(rows, '', skip_phasing), chrom_id, n_chrom
+
+
+def merge_ranges(ranges):
+    """Closed integer ranges -> the same set of positions as sorted, disjoint closed ranges within 0 .. 2^32 - 1."""
+    out = []
+    for a, b in sorted((max(int(a), 0), min(int(b), 0xFFFFFFFF)) for a, b in ranges if int(b) >= max(int(a), 0) and int(a) <= 0xFFFFFFFF):
+        if out and a <= out[-1][1] + 1:
+            out[-1][1] = max(out[-1][1], b)
+        else:
+            out.append([a, b])
+    return [(a, b) for a, b in out]
+
+
+def bed_tables(bed, chrom_texts):
+    """-> (bed_off[K + 1], bed_lo, bed_hi): per contig the merged ranges evaluation.parse_vcf tests its positions against -- those
+    of the label CHROM[3:], whatever the first three characters are."""
+    spans = evaluation.parse_bed(bed)
+    off, lo, hi = [0], [], []
+    for text in chrom_texts:
+        for a, b in merge_ranges(spans.get(text[3:], [])):
+            lo.append(a)
+            hi.append(b)
+        off.append(len(lo))
+    return np.array(off, dtype=np.uint32), np.array(lo, dtype=np.uint32), np.array(hi, dtype=np.uint32)
+
+
+def _match_limits(refdist, pctsim):
+    """(refdist, ratio) for the device: abs(...) <= a negative refdist never holds, which a ratio of +inf says as well."""
+    return (0, math.inf) if refdist < 0 else (int(refdist), float(pctsim))
+
+
+def build_truth(cands, truth_vcf, refdist=1000, pctsim=0.0, bed='', skip_phasing=False, ctx=None):
+    """prepare_truth's arrays from the device build (duet_tune_truth_build_host); groups and pairs may be numbered differently."""
+    ctx = ctx or engine.default_context()
+    base = truth_side(truth_vcf, bed, skip_phasing)
+    key, chrom, n_chrom = candidate_keys(cands, bed, skip_phasing)
+    arrays = dict(base, cand_pos=cands['pos'], cand_len=cands['svlen'], cand_key=key, cand_chrom=chrom, n_chrom=n_chrom)
+    out = ctx.truth_build_host(cands['feat'], arrays, *_match_limits(refdist, pctsim))
+    out['n_base'] = base['n_base']
+    return out
+
+
 def scores(counts, n_base):
     """evaluation.evaluation's ten numbers from one vector's counts (binary64, the same expressions); nan where it raises."""
     n_calls, n_groups = int(counts['n_calls']), int(counts['n_groups'])
@@ -216,13 +316,128 @@ def sweep(home, truth_vcf, grid, refdist=1000, pctsim=0.0, bed='', skip_phasing=
     ctx = ctx or engine.default_context()
     if cands is None:
         cands = features(home, svlen_thres, suppread_thres, include_all_ctgs, thread, ctx=ctx)
-    truth = prepare_truth(cands, truth_vcf, refdist, pctsim, bed, skip_phasing)
+    truth = build_truth(cands, truth_vcf, refdist, pctsim, bed, skip_phasing, ctx=ctx)
     counts, _, _ = ctx.sweep_host(cands['feat'], vecs, truth)
+    return _rows(vecs, counts, truth['n_base'])
+
+
+def _rows(vecs, counts, n_base, lead=None):
+    """One dict per vector: the leading setting columns (if any), the 14 thresholds, the ten numbers (counts None: nan)."""
     out = []
-    for v, cnt in zip(vecs, counts):
-        row = dict(zip(NAMES, (float(x) for x in v)))
-        row.update(zip(SCORES, scores(cnt, truth['n_base'])))
+    for k, v in enumerate(vecs):
+        row = dict(lead or {})
+        row.update(zip(NAMES, (float(x) for x in v)))
+        row.update(zip(SCORES, scores(counts[k], n_base) if counts is not None else (math.nan,) * 10))
         out.append(row)
+    return out
+
+
+def _int_list(name, v):
+    vals = [v] if isinstance(v, (int, np.integer)) else list(v)
+    if not vals or any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 0 for x in vals):
+        raise ValueError('%s: a non-empty list of non-negative integers, not %r' % (name, v))
+    return [int(x) for x in vals]
+
+
+def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,), cluster_max_distance=None, from_bams=False,
+                   refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False, thread=4, ctx=None, on_features=None):
+    """sweep() for every setting of -s (svlen_thres), -r (suppread_thres) and, with from_bams, -c (cluster_max_distance; default
+    (0.9,)): -> list of rows, settings outermost in the order c, s, r, each row a dict of svlen_thres, suppread_thres
+    [, cluster_max_distance], the 14 thresholds and the ten numbers.  from_bams: the candidates come from <home>/snp_phasing/*.bam
+    through the fused svim-gpu pipeline (duet_svim_features_device) instead of from sv_calling/variants.vcf.
+    The work directory is ingested once (from_bams: once per distinct -s, whose max(s, 1) is the extraction's minimum size, as in
+    svim_mode.sv_phasing_from_bams) and uploaded once; per setting the device computes the features, builds the truth arrays and
+    applies the vectors -- only the K count records come back.  A setting for which E/F reports a division by zero (upstream
+    raises there) yields nan rows.  on_features(setting, cands): called per setting with the features brought to the host
+    (cands as features() returns them, without ref / alt / soa in the from_bams mode)."""
+    vecs = grid if isinstance(grid, np.ndarray) else expand_grid(grid)
+    ss, rs = _int_list('svlen_thres', svlen_thres), _int_list('suppread_thres', suppread_thres)
+    if cluster_max_distance is not None and not from_bams:
+        raise ValueError('cluster_max_distance only acts on candidates clustered from the BAMs: it needs from_bams')
+    ctx = ctx or engine.default_context()
+    base = truth_side(truth_vcf, bed, skip_phasing)
+    if from_bams:
+        cs = [float(c) for c in (cluster_max_distance if cluster_max_distance is not None else (0.9,))]
+        if not cs:
+            raise ValueError('cluster_max_distance: an empty list')
+        return _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features)
+    from duet_amd.devmem import DeviceProblem, DeviceTune
+    soa, txt = _candidates(home, ss[0], rs[0], include_all_ctgs, thread)
+    cands = dict(pos=soa.cand_pos, svlen=soa.cand_svlen, **txt)
+    key, chrom, n_chrom = candidate_keys(cands, bed, skip_phasing)
+    device = 'cuda:%d' % ctx.device_id
+    C = soa.n_cands
+    dt = DeviceTune(C, base, *_match_limits(refdist, pctsim), vectors=vecs, device=device)
+    dt.set_candidates(soa.cand_pos, soa.cand_svlen, key, chrom, n_chrom)
+    dp = DeviceProblem(soa, ss[0], rs[0], device=device) if C else None
+    out = []
+    for s_ in ss:
+        for r_ in rs:
+            lead = dict(svlen_thres=s_, suppread_thres=r_)
+            counts = None
+            try:
+                if C:
+                    dp.problem.svlen_thres, dp.problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
+                    ctx.features_device(dp.problem, dt.feat.data_ptr(), dt.stream())
+                dt.build(ctx, C)
+                counts = dt.sweep(ctx, C)
+            except ZeroDivisionError:
+                pass
+            if on_features is not None:
+                on_features(lead, dict(cands, feat=dt.features_host(C)))
+            out.extend(_rows(vecs, counts, base['n_base'], lead))
+    return out
+
+
+def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features):
+    from duet_amd import svim_mode
+    from duet_amd.devmem import DeviceSvim, DeviceTune
+    from duet_amd.native import NativeIngest
+    from duet_amd.read_file import init_chrom_list
+    chroms = init_chrom_list(include_all_ctgs, home)
+    texts = svim_mode.spelled_contigs(home, chroms)
+    key_table, chrom_id, n_chrom = contig_tables(texts, skip_phasing)
+    bed_t = bed_tables(bed, texts) if bed else None
+    device = 'cuda:%d' % ctx.device_id
+    depth_bin = 1000                                        # (phase_from_bams's defaults)
+    done = {}
+    for s_ in sorted(set(ss)):
+        ing, got = NativeIngest.extract(home + '/snp_phasing/', chroms, thread, max(s_, 1), 20, depth_bin)
+        if ing is None:
+            raise RuntimeError('signature extraction declined the input: %s' % got)
+        ing.close()
+        M = len(got['pos'])
+        dt = DeviceTune(M, base, *_match_limits(refdist, pctsim), vectors=vecs, device=device)
+        dt.set_tables(key_table, chrom_id, n_chrom, bed_t)
+        ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, s_, rs[0], max_dist=cs[0], device=device) if M else None
+        for c_ in cs:
+            for r_ in rs:
+                if (c_, s_, r_) in done:
+                    continue
+                counts, N = None, 0
+                try:
+                    if M:
+                        ds.sv_problem.marks.max_dist = c_
+                        ds.sv_problem.svlen_thres, ds.sv_problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
+                        N = ds.run_features(ctx, dt.feat.data_ptr())
+                    dt.build(ctx, N, ds.result if M else None)
+                    counts = dt.sweep(ctx, N)
+                except ZeroDivisionError:
+                    pass
+                done[(c_, s_, r_)] = counts
+                if on_features is not None:
+                    if M and ds.n_found is None:
+                        ds.n_found = ds.n_cands()           # (a division by zero: the records are written all the same)
+                    res = ds.fetch() if M else dict(cand_contig=[], cand_type=[], cand_pos=[], cand_span=[])
+                    on_features(dict(cluster_max_distance=c_, svlen_thres=s_, suppread_thres=r_), dict(
+                        feat=dt.features_host(len(res['cand_pos'])), chrom=[texts[int(k)] for k in res['cand_contig']],
+                        pos=res['cand_pos'], svlen=res['cand_span'],
+                        svtype=[svim_mode.SV_TYPE_NAMES[int(t) & 3] for t in res['cand_type']]))
+    out = []
+    for c_ in cs:
+        for s_ in ss:
+            for r_ in rs:
+                out.extend(_rows(vecs, done[(c_, s_, r_)], base['n_base'], dict(cluster_max_distance=c_, svlen_thres=s_, suppread_thres=r_)))
     return out
 
 
@@ -249,37 +464,77 @@ def _write_tsv(path, names, rows):
             f.write('\t'.join(repr(x) if isinstance(x, float) else str(x) for x in r) + '\n')
 
 
+def _csv(kind, what):
+    def parse(text):
+        try:
+            vals = [kind(x) for x in text.split(',')]
+        except ValueError:
+            raise argparse.ArgumentTypeError('%s: %r is not a comma-separated list' % (what, text))
+        if not vals or any(v < 0 for v in vals):
+            raise argparse.ArgumentTypeError('%s: %r holds a negative value' % (what, text))
+        return vals
+    return parse
+
+
 def parse_args(argv):
     ap = argparse.ArgumentParser(description='score many T1-T5 threshold vectors of the SV phasing decision against a truth set')
     ap.add_argument('workdir', help='Duet work directory (sv_calling/variants.vcf, snp_phasing/*.bam)')
     ap.add_argument('truthset', help='VCF of the phased truth set')
     ap.add_argument('--grid', required=True, help='JSON: a list of partial vectors, or an object of name -> list of values')
-    ap.add_argument('-s', '--sv_min_size', type=int, default=50, help='minimum SV size [%(default)s]')
-    ap.add_argument('-r', '--min_support_read', type=int, default=2, help='minimum number of supporting reads [%(default)s]')
+    ap.add_argument('-s', '--sv_min_size', type=_csv(int, '-s'), default=[50],
+                    help='minimum SV size; a comma-separated list sweeps it [50]')
+    ap.add_argument('-r', '--min_support_read', type=_csv(int, '-r'), default=[2],
+                    help='minimum number of supporting reads; a comma-separated list sweeps it [2]')
+    ap.add_argument('--from_bams', action='store_true',
+                    help='take the candidates from snp_phasing/*.bam through the svim-gpu pipeline, not from sv_calling/variants.vcf')
+    ap.add_argument('-c', '--cluster_max_distance', type=_csv(float, '-c'), default=None,
+                    help='with --from_bams: maximum span-position distance of the clustering; a comma-separated list sweeps it [0.9]')
     ap.add_argument('-a', '--include_all_ctgs', action='store_true', help='all contigs, not only chr{1..22,X,Y}')
     ap.add_argument('-t', '--thread', type=int, default=4, help='threads of the ingest [%(default)s]')
     ap.add_argument('--refdist', type=int, default=1000, help="the evaluator's --refdist [%(default)s]")
     ap.add_argument('--pctsim', type=float, default=0, help="the evaluator's --pctsim [%(default)s]")
     ap.add_argument('--bed_file', type=str, default='', help="the evaluator's --bed_file")
     ap.add_argument('--skip_phasing', action='store_true', help="the evaluator's --skip_phasing")
-    ap.add_argument('--out', default='sweep.tsv', help='one row per vector [%(default)s]')
-    ap.add_argument('--features', default='', help='also write the per-candidate features here (TSV)')
+    ap.add_argument('--out', default='sweep.tsv', help='one row per setting and vector [%(default)s]')
+    ap.add_argument('--features', default='', help='also write the per-candidate features here (TSV; with several settings one '
+                                                   'file per setting, the setting in its name)')
     ap.add_argument('--device', type=int, default=0, help='HIP device index [%(default)s]')
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.cluster_max_distance is not None and not a.from_bams:
+        ap.error('-c / --cluster_max_distance needs --from_bams: it only acts on candidates clustered from the BAMs')
+    return a
+
+
+LEAD = ('svlen_thres', 'suppread_thres', 'cluster_max_distance')      # the setting columns in front of a row, in this order
+
+
+def features_path(path, setting):
+    """--features with several settings: FILE.ext -> FILE[.c<c>].s<s>.r<r>.ext"""
+    root, ext = os.path.splitext(path)
+    tag = ''.join('.%s%s' % (t, setting[n]) for t, n in (('c', 'cluster_max_distance'), ('s', 'svlen_thres'), ('r', 'suppread_thres'))
+                  if n in setting)
+    return root + tag + ext
 
 
 def main(argv):
     a = parse_args(argv)
     vecs = load_grid(a.grid)
     ctx = engine.default_context(a.device)
-    cands = features(a.workdir, a.sv_min_size, a.min_support_read, a.include_all_ctgs, a.thread, ctx=ctx)
-    if a.features:
+    cs = a.cluster_max_distance if a.from_bams else None
+    plain = not a.from_bams and len(a.sv_min_size) == 1 and len(a.min_support_read) == 1
+
+    def write_features(setting, cands):
         f = cands['feat']
         cols = ('chrom', 'pos', 'svtype', 'svlen') + tuple(n for n in _lib.FEATURE_DTYPE.names if not n.startswith('reserved'))
-        _write_tsv(a.features, cols, ([cands['chrom'][c], int(cands['pos'][c]), cands['svtype'][c], int(cands['svlen'][c])] +
-                                      [int(f[n][c]) for n in cols[4:]] for c in range(len(f))))
-    rows = sweep(a.workdir, a.truthset, vecs, a.refdist, a.pctsim, a.bed_file, a.skip_phasing, ctx=ctx, cands=cands)
-    _write_tsv(a.out, NAMES + SCORES, ([r[n] for n in NAMES + SCORES] for r in rows))
+        _write_tsv(a.features if plain else features_path(a.features, setting), cols,
+                   ([cands['chrom'][c], int(cands['pos'][c]), cands['svtype'][c], int(cands['svlen'][c])] +
+                    [int(f[n][c]) for n in cols[4:]] for c in range(len(f))))
+
+    rows = sweep_settings(a.workdir, a.truthset, vecs, a.sv_min_size, a.min_support_read, cs, a.from_bams, a.refdist, a.pctsim,
+                          a.bed_file, a.skip_phasing, a.include_all_ctgs, a.thread, ctx=ctx,
+                          on_features=write_features if a.features else None)
+    lead = () if plain else tuple(n for n in LEAD if n in rows[0])
+    _write_tsv(a.out, lead + NAMES + SCORES, ([r[n] for n in lead + NAMES + SCORES] for r in rows))
     best = max(range(len(rows)), key=lambda i: -1.0 if math.isnan(rows[i]['hp_f1']) else rows[i]['hp_f1'])
     print('%d vectors scored -> %s; best phasing F1 %r at vector %d' % (len(rows), a.out, rows[best]['hp_f1'], best))
 

@@ -495,6 +495,66 @@ DUET_API int duet_tune_sweep_host(duet_ctx *ctx, const duet_tune_feature *feat, 
                                   uint32_t n_vec, const duet_tune_truth *truth, duet_tune_counts *counts, uint8_t *out_pred,
                                   uint32_t *out_ps);
 
+/* The features of the fused pipeline's candidates (for a sweep over -c, -s and -r without a callset file): clusters and adapts
+ * as duet_svim_phase_device does with n_cands_host given, then runs E/F and the feature kernel on the adapted problem
+ * (duet_ef_features_device) -- out_feat[M] in place of out_pred / out_ps, indexed like the cluster result's candidate arrays, which
+ * stay in *res for duet_tune_truth_build_device's table form.  n_cands_host is mandatory.  Synchronises `stream`; the status is
+ * duet_ef_features_device's (DUET_ERR_DIV_ZERO: the records are written all the same).  _host: arrays as for
+ * duet_svim_phase_host, out_feat[M] host. */
+DUET_API int duet_svim_features_device(duet_ctx *ctx, const duet_svim_problem *prob, const duet_cluster_result *res,
+                                       duet_tune_feature *out_feat, uint32_t *n_cands_host, void *stream);
+DUET_API int duet_svim_features_host(duet_ctx *ctx, const duet_svim_problem *prob, const duet_cluster_result *res,
+                                     duet_tune_feature *out_feat);
+
+/* The truth arrays built on the device (duet_tune_truth.hip) -- what duet_amd/tune.py's prepare_truth computes on the host, which
+ * stays the normative text.  Per candidate the caller says how the evaluator's parser sees the row the candidate would be
+ * written as, which does not depend on -s, -r or the thresholds:
+ *   cand_key[c]    the truth list key 2 * contig + type as in duet_eval_problem (< n_keys), or DUET_TUNE_KEY_NONE: the parser keeps
+ *                  the row but no truth list can match it, or DUET_TUNE_KEY_SKIP: the parser drops the row (any other value
+ *                  >= n_keys is taken as DUET_TUNE_KEY_NONE)
+ *   cand_chrom[c]  dense id (< n_chrom) of the row's CHROM text; equal texts share an id
+ *   cand_len[c]    abs(SVLEN): the parser also drops a row with a length below 50
+ * or, with cand_key == NULL and cand_chrom == NULL (a cluster result: no per-candidate text exists), tables per contig:
+ *   cand_contig[c] (< n_contigs), cand_type[c] (0..3: DEL, INS, INV, DUP; anything else is dropped), key_table[4 * contig + type]
+ *   = the candidate's cand_key, chrom_id[contig] = its cand_chrom and, when bed_off != NULL, per contig the merged, sorted,
+ *   closed ranges bed_lo[j] <= pos <= bed_hi[j], j in bed_off[contig] .. bed_off[contig + 1]: a candidate outside every range of
+ *   its contig is DUET_TUNE_KEY_SKIP.
+ * Of feat[c] `eligible` and `ps` are read.  The truth side is duet_eval_problem's: base_off[n_keys + 1], base_pos / base_len /
+ * base_uid / base_hp [n_base] (position-sorted inside a list, base_uid < n_base_uid, base_hp codes 0 '1|0', 1 '0|1', 2 '1|1',
+ * >= 3 anything else), refdist and ratio (the quotient min(len) / max(len) is taken in binary64).
+ *
+ * A candidate is in the call list iff it is eligible, not dropped and cand_len >= 50; every output of any other candidate is 0.
+ * Groups are the distinct (cand_chrom, ps) among the calls, pairs the distinct (group, uid) among the matched calls.  The
+ * numbering is that of one stable sort by (cand_chrom, ps, uid): it does not depend on the order in which anything arrives. */
+#define DUET_TUNE_KEY_NONE 0xFFFFFFFEu
+#define DUET_TUNE_KEY_SKIP 0xFFFFFFFFu
+typedef struct duet_tune_truth_problem {
+    uint32_t n_cands, n_keys, n_base, n_base_uid;
+    uint32_t n_chrom;                   /* CHROM ids are < n_chrom */
+    uint32_t n_contigs;                 /* table form only */
+    uint32_t refdist;
+    uint32_t reserved;
+    double ratio;
+    const duet_tune_feature *feat;      /* [C] */
+    const uint32_t *cand_pos, *cand_len;/* [C] */
+    const uint32_t *cand_key, *cand_chrom;      /* [C], or both NULL: the table form */
+    const uint16_t *cand_contig;        /* [C] */
+    const uint8_t *cand_type;           /* [C] */
+    const uint32_t *key_table;          /* [4 * n_contigs] */
+    const uint32_t *chrom_id;           /* [n_contigs] */
+    const uint32_t *bed_off, *bed_lo, *bed_hi;  /* [n_contigs + 1], [bed_off[n_contigs]] x 2; bed_off NULL: no BED file */
+    const uint32_t *base_off, *base_pos, *base_len, *base_uid;
+    const uint8_t *base_hp;
+} duet_tune_truth_problem;
+
+/* Fills the six arrays *truth points to -- the caller's buffers, cand_* with room for C entries, group_pair_off for C + 1,
+ * pair_uid for C -- and truth->n_uid (= n_base_uid), n_groups, n_pairs; *truth can then go to duet_tune_sweep_device as it is.
+ * _device: every array of *prob and *truth is device memory; asynchronous on `stream` apart from ONE host round trip at the end
+ * that learns n_groups and n_pairs.  _host: everything host memory; uploads, runs the same kernels, downloads, synchronises.
+ * DUET_ERR_INVALID: a NULL array that is needed, or more key bits than 64 (bits of n_chrom - 1, 32 of ps, bits of n_base_uid, 1). */
+DUET_API int duet_tune_truth_build_device(duet_ctx *ctx, const duet_tune_truth_problem *prob, duet_tune_truth *truth, void *stream);
+DUET_API int duet_tune_truth_build_host(duet_ctx *ctx, const duet_tune_truth_problem *prob, duet_tune_truth *truth);
+
 /* ---------------------------------------------------------------------------------------------
  * The collective of the contig-sharded path: candidates shard by contig over the GPUs of one node,
  * one process and one context per GPU, and ONE all-gather of fixed-size record blocks reassembles the call set
