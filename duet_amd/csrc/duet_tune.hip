@@ -455,16 +455,22 @@ int duet_tune_sweep_device(duet_ctx *ctx, const duet_tune_feature *feat, uint32_
     if (!ctx) return fail(nullptr, DUET_ERR_INVALID, "null context");
     if (n_cands && !feat) return fail(ctx, DUET_ERR_INVALID, "null feature array");
     if (n_vec && !vec) return fail(ctx, DUET_ERR_INVALID, "null threshold vectors");
-    if (truth && !counts) return fail(ctx, DUET_ERR_INVALID, "a truth set needs the counts array");
+    if (truth && n_vec && !counts) return fail(ctx, DUET_ERR_INVALID, "a truth set needs the counts array");
     if (truth && n_cands && (!truth->cand_flags || !truth->cand_group || !truth->cand_uid || !truth->cand_pair ||
                              !truth->group_pair_off || (truth->n_pairs && !truth->pair_uid)))
         return fail(ctx, DUET_ERR_INVALID, "null truth array");
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (counts && n_vec) HIP_TRY(ctx, hipMemsetAsync(counts, 0, (size_t)n_vec * sizeof(duet_tune_counts), stream));
-    if (n_cands == 0 || n_vec == 0) return DUET_OK;
+    if (n_cands == 0 || (n_vec == 0 && !out_ps)) return DUET_OK;
     SweepArgs a;
     memset(&a, 0, sizeof(a));
+    if (n_vec == 0) {                            // no vector: out_ps is still owed (one row of tune_decide, whose vector loop is empty)
+        a.feat = feat; a.C = n_cands; a.out_ps = out_ps;
+        hipLaunchKernelGGL(tune_decide, dim3((n_cands + 255) / 256, 1), dim3(256), 0, stream, a);
+        HIP_TRY(ctx, hipGetLastError());
+        return DUET_OK;
+    }
     a.feat = feat; a.C = n_cands; a.vec = vec; a.counts = counts; a.out_pred = out_pred; a.out_ps = out_ps;
     size_t per_vec = 0;
     if (truth) {
@@ -478,13 +484,15 @@ int duet_tune_sweep_device(duet_ctx *ctx, const duet_tune_feature *feat, uint32_
         if (per_vec > 0xFFFFFFFFull) return fail(ctx, DUET_ERR_INVALID, "truth set too large");
         a.ws_words = (uint32_t)per_vec;
     }
-    // vectors per batch: what the workspace budget holds (at least one), and what one grid dimension takes
+    // vectors per batch: what the workspace budget holds (at least one), and what gridDim.y takes -- tune_decide runs one row of
+    // workgroups per kVecPerBlock vectors, tune_groups and tune_popcount (truth set only) one row per vector
     uint32_t batch = n_vec;
     if (per_vec) {
         const size_t fit = kWsBudget / (per_vec * 4);
         if (fit < batch) batch = fit ? (uint32_t)fit : 1u;
     }
     if (batch > 65535u * kVecPerBlock) batch = 65535u * kVecPerBlock;
+    if (per_vec && batch > 65535u) batch = 65535u;
     int rc;
     if (per_vec && (rc = duet_reserve(ctx, ctx->tune_ws.b[3], (size_t)batch * per_vec * 4))) return rc;
     a.ws = (uint32_t *)ctx->tune_ws.b[3].ptr;

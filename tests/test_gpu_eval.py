@@ -8,8 +8,10 @@ import os
 import numpy as np
 import pytest
 
+from duet_amd import engine
 from duet_amd import evaluation as E
 from duet_amd import synth
+from tests import eval_ref
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -66,6 +68,10 @@ def test_matches_the_numpy_restatement(seed, n_truth, n_calls, refdist, ratio):
     want = E.evaluation(truth, calls, refdist, ratio)
     got = E.evaluation_gpu(truth, calls, refdist, ratio)
     assert [float(x) for x in got] == [float(x) for x in want]
+    # the six integers themselves, against the plain restatement (tests/eval_ref.py)
+    a = E.flatten(truth, calls)
+    n = engine.default_context().eval_counts(a, refdist, ratio)
+    assert tuple(getattr(n, f) for f in eval_ref.NAMES) == eval_ref.counts(a, refdist, ratio)
 
 
 def test_empty_truth_list_raises_like_upstream():
