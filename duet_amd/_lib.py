@@ -31,7 +31,9 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_comm_ef_allgather', 'duet_comm_rccl_version', 'duet_comm_info', 'duet_comm_selftest',
            'duet_ef_features_device', 'duet_ef_features_host', 'duet_tune_sweep_device', 'duet_tune_sweep_host',
            'duet_svim_vcf_rows_device', 'duet_svim_vcf_rows_host', 'duet_svim_phased_rows_device', 'duet_svim_phased_rows_host',
-           'duet_svim_features_device', 'duet_svim_features_host', 'duet_tune_truth_build_device', 'duet_tune_truth_build_host')
+           'duet_svim_features_device', 'duet_svim_features_host', 'duet_tune_truth_build_device', 'duet_tune_truth_build_host',
+           'duet_tune_strata_build_device', 'duet_tune_strata_build_host', 'duet_tune_sweep_strata_device',
+           'duet_tune_sweep_strata_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -151,6 +153,13 @@ class TuneTruth(ctypes.Structure):
 
 
 TUNE_KEY_NONE, TUNE_KEY_SKIP = 0xFFFFFFFE, 0xFFFFFFFF
+TUNE_MAX_STRATA = 64
+
+
+class TuneStrata(ctypes.Structure):
+    """duet_tune_strata; uid_off is host memory in both forms."""
+    _fields_ = [('n_strata', ctypes.c_uint32), ('reserved', ctypes.c_uint32)] + \
+               [(n, ctypes.c_void_p) for n in ('cand_stratum', 'group_stratum', 'uid_off')]
 
 
 class TuneTruthProblem(ctypes.Structure):
@@ -261,6 +270,12 @@ def load():
     lib.duet_tune_truth_build_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(TuneTruthProblem), ctypes.POINTER(TuneTruth),
                                                  ctypes.c_void_p]
     lib.duet_tune_truth_build_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(TuneTruthProblem), ctypes.POINTER(TuneTruth)]
+    lib.duet_tune_strata_build_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(TuneTruthProblem), ctypes.POINTER(TuneTruth),
+                                                  ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.duet_tune_strata_build_host.argtypes = lib.duet_tune_strata_build_device.argtypes[:-1]
+    lib.duet_tune_sweep_strata_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                                  ctypes.POINTER(TuneTruth), ctypes.POINTER(TuneStrata), ctypes.c_void_p, ctypes.c_void_p]
+    lib.duet_tune_sweep_strata_host.argtypes = lib.duet_tune_sweep_strata_device.argtypes[:-1]
     _lib = lib
     return lib
 
@@ -655,6 +670,77 @@ class Context(object):
         out['pair_uid'] = out['pair_uid'][:t.n_pairs]
         out.update(n_uid=t.n_uid, n_groups=t.n_groups, n_pairs=t.n_pairs)
         return out
+
+    def strata_build_host(self, arrays, truth, chrom_stratum, n_strata):
+        """duet_tune_strata_build_host: arrays = the CHROM ids of a TuneTruthProblem's candidates (cand_chrom, or cand_contig +
+        chrom_id) and n_chrom; truth = the truth arrays of the same candidates (cand_flags, cand_group, n_groups); chrom_stratum
+        u8[n_chrom] -> (cand_stratum u8[C], group_stratum u8[n_groups])"""
+        flags = np.ascontiguousarray(truth['cand_flags'], dtype=np.uint16)
+        group = np.ascontiguousarray(truth['cand_group'], dtype=np.uint32)
+        C = len(flags)
+        p, keep = TuneTruthProblem(), []
+        for name, dt in (('cand_chrom', np.uint32), ('cand_contig', np.uint16), ('chrom_id', np.uint32)):
+            if arrays.get(name) is None:
+                continue
+            a = np.ascontiguousarray(arrays[name], dtype=dt)
+            keep.append(a)
+            setattr(p, name, a.ctypes.data if a.size else None)
+        p.n_cands, p.n_chrom = C, int(arrays['n_chrom'])
+        p.n_contigs = len(arrays['chrom_id']) if arrays.get('chrom_id') is not None else 0
+        t = TuneTruth()
+        t.n_groups = int(truth['n_groups'])
+        t.cand_flags, t.cand_group = (a.ctypes.data if C else None for a in (flags, group))
+        cs = np.ascontiguousarray(chrom_stratum, dtype=np.uint8)
+        assert len(cs) >= p.n_chrom or C == 0, 'chrom_stratum holds one entry per CHROM id'
+        cand, grp = np.zeros(C, dtype=np.uint8), np.zeros(C, dtype=np.uint8)
+        rc = self.lib.duet_tune_strata_build_host(self.handle, ctypes.byref(p), ctypes.byref(t), _ptr(cs), int(n_strata), _ptr(cand),
+                                                  _ptr(grp))
+        del keep
+        if rc:
+            self._raise(rc)
+        return cand, grp[:t.n_groups].copy()
+
+    def sweep_strata_host(self, feat, vectors, truth, strata):
+        """duet_tune_sweep_strata_host: feat, vectors, truth as for sweep_host; strata = dict(n_strata, cand_stratum u8[C],
+        group_stratum u8[n_groups], uid_off u32[S + 1]) -> counts COUNTS_DTYPE[K, S]"""
+        feat = np.ascontiguousarray(feat, dtype=FEATURE_DTYPE)
+        vec = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1, len(TUNE_NAMES))
+        C, K, S = len(feat), len(vec), int(strata['n_strata'])
+        t, keep = TuneTruth(), []
+        t.n_uid, t.n_groups, t.n_pairs = int(truth['n_uid']), int(truth['n_groups']), int(truth['n_pairs'])
+        for name, dt in TRUTH_ARRAYS:
+            a = np.ascontiguousarray(truth[name], dtype=dt)
+            keep.append(a)
+            setattr(t, name, a.ctypes.data if a.size else None)
+        st = TuneStrata()
+        st.n_strata = S if 0 <= S <= 0xFFFFFFFF else 0xFFFFFFFF
+        for name, dt in (('cand_stratum', np.uint8), ('group_stratum', np.uint8), ('uid_off', np.uint32)):
+            a = np.ascontiguousarray(strata[name], dtype=dt)
+            keep.append(a)
+            setattr(st, name, a.ctypes.data if a.size else None)
+        assert not 1 <= S <= TUNE_MAX_STRATA or len(keep[-1]) == S + 1, 'uid_off holds n_strata + 1 entries'
+        counts = np.zeros((K, S if 1 <= S <= TUNE_MAX_STRATA else 1), dtype=COUNTS_DTYPE)
+        rc = self.lib.duet_tune_sweep_strata_host(self.handle, _ptr(feat), C, _ptr(vec), K, ctypes.byref(t), ctypes.byref(st),
+                                                  _ptr(counts))
+        del keep
+        if rc:
+            self._raise(rc)
+        return counts
+
+    def strata_build_device(self, prob, truth, chrom_stratum_ptr, n_strata, cand_stratum_ptr, group_stratum_ptr, stream=0):
+        """duet_tune_strata_build_device on resident arrays (devmem.DeviceTune), after truth_build_device on the same prob / truth."""
+        rc = self.lib.duet_tune_strata_build_device(self.handle, ctypes.byref(prob), ctypes.byref(truth), ctypes.c_void_p(chrom_stratum_ptr),
+                                                    int(n_strata), ctypes.c_void_p(cand_stratum_ptr), ctypes.c_void_p(group_stratum_ptr),
+                                                    ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+
+    def sweep_strata_device(self, feat_ptr, n_cands, vec_ptr, n_vec, truth, strata, counts_ptr, stream=0):
+        rc = self.lib.duet_tune_sweep_strata_device(self.handle, ctypes.c_void_p(feat_ptr), int(n_cands), ctypes.c_void_p(vec_ptr),
+                                                    int(n_vec), ctypes.byref(truth), ctypes.byref(strata), ctypes.c_void_p(counts_ptr),
+                                                    ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
 
     def truth_build_device(self, prob, truth, stream=0):
         """duet_tune_truth_build_device on resident arrays (devmem.DeviceTune): fills truth.n_groups / n_pairs."""

@@ -339,6 +339,48 @@ class DeviceTune(object):
         ctx.sweep_device(self.feat.data_ptr(), int(n_cands), self.vec_ptr, self.K, self.truth, self.counts.data_ptr(), self.stream())
         return self.counts[:self.K * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).copy()
 
+    def set_strata(self, chrom_stratum, uid_off, base_uid=None):
+        """One stratified pass (tune.truth_side(strata=...), tune.chrom_strata): chrom_stratum u8[n_chrom], uid_off u32[S + 1] and
+        the truth side's base_uid numbered per (stratum, id text).  -> the pass, for build() and sweep_strata(); its arrays stay
+        resident like the rest, and several passes can be set side by side."""
+        torch = self.torch
+        uid_off = np.ascontiguousarray(uid_off, dtype=np.uint32)
+        S, n = len(uid_off) - 1, max(self.n_max, 1)
+        i = len([k for k in self.keep if k.startswith('chrom_stratum')])
+        st = _lib.TuneStrata()
+        st.n_strata = S
+        for name in ('cand_stratum', 'group_stratum'):
+            self.keep['%s%d' % (name, i)] = t = torch.zeros(n + 64, dtype=torch.uint8, device=self.device)
+            setattr(st, name, t.data_ptr())
+        st.uid_off = uid_off.ctypes.data
+        p = dict(strata=st, uid_off=uid_off, n_base_uid=int(uid_off[-1]),
+                 chrom_stratum=self._up('chrom_stratum%d' % i, chrom_stratum, np.uint8),
+                 base_uid=self._up('base_uid%d' % i, base_uid, np.uint32) if base_uid is not None else self.problem.base_uid,
+                 counts=torch.zeros(max(self.K * S, 1) * _lib.COUNTS_DTYPE.itemsize, dtype=torch.uint8, device=self.device))
+        self.strata = p
+        return p
+
+    def build_strata(self, ctx, n_cands, result=None, strata=None):
+        """build() with the pass's truth-id numbering, then the strata of the candidates and groups
+        (duet_tune_strata_build_device).  The truth arrays are the pass's from here on: a plain sweep() goes before it."""
+        s, p = strata or self.strata, self.problem
+        plain = p.base_uid, p.n_base_uid
+        p.base_uid, p.n_base_uid = s['base_uid'], s['n_base_uid']
+        try:
+            self.build(ctx, n_cands, result)
+        finally:
+            p.base_uid, p.n_base_uid = plain
+        ctx.strata_build_device(p, self.truth, s['chrom_stratum'], s['strata'].n_strata, s['strata'].cand_stratum,
+                                s['strata'].group_stratum, self.stream())
+
+    def sweep_strata(self, ctx, n_cands, strata=None):
+        """The K vectors over the features and the truth arrays of the last build_strata -> COUNTS_DTYPE[K, S] on the host."""
+        s = strata or self.strata
+        S = s['strata'].n_strata
+        ctx.sweep_strata_device(self.feat.data_ptr(), int(n_cands), self.vec_ptr, self.K, self.truth, s['strata'], s['counts'].data_ptr(),
+                                self.stream())
+        return s['counts'][:self.K * S * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).reshape(self.K, S).copy()
+
     def features_host(self, n_cands):
         """(--features) the feature records of the last setting, on the host."""
         return self.feat[:int(n_cands) * _lib.FEATURE_DTYPE.itemsize].cpu().numpy().view(_lib.FEATURE_DTYPE).copy()

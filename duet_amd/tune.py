@@ -5,7 +5,10 @@
     sweep(home, truth_vcf, grid, ...)      one row per threshold vector: the 14 values and evaluation.py's ten numbers
     sweep_settings(home, truth_vcf, grid, svlen_thres=(..), suppread_thres=(..), cluster_max_distance=(..), from_bams=..)
                                            the same for every setting of -s, -r and (svim-gpu mode, from the BAMs) -c
-    python -m duet_amd.tune WORKDIR TRUTH.vcf --grid GRID.json [-s 30,50 -r 2,3 [--from_bams -c 0.5,0.9]] [...]
+    strata_by_contig(), strata_holdout(texts)   strata (sets of CHROM texts) for sweep_settings(holdout=.., by_contig=..): every
+                                           vector scored per stratum in one pass over the candidates (duet_tune_sweep_strata_device)
+    python -m duet_amd.tune WORKDIR TRUTH.vcf --grid GRID.json [-s 30,50 -r 2,3 [--from_bams -c 0.5,0.9]]
+                                           [--holdout chr20,chr21 --by_contig FILE.tsv] [...]
 
 The vector's 14 fields, their order and defaults are include/duet_ef.h's duet_tune_thresholds (NAMES, DEFAULTS).  A grid is
 either a list of partial vectors (dicts) or a dict of name -> list of values, expanded as a Cartesian product; names left out
@@ -20,6 +23,12 @@ matches every call to its nearest truth record by the evaluator's rule and numbe
 binary64 quotients of those counts.  prepare_truth is the same truth match on the host, in the evaluator's own terms: the
 normative text the device build is tested against.  Where upstream would raise (ZeroDivisionError: no calls, or precision +
 recall == 0; IndexError: an emitted call whose (contig, type) has no truth record) the row's ten numbers are nan.
+
+Strata.  A stratum is a set of CHROM texts; the ten numbers of (vector, stratum) are what the unmodified evaluator returns when the
+callset and the truth set are both restricted to the rows with those CHROM texts -- it matches, fills its id sets and groups the
+phase sets inside `for ch in range(24)`, so restricting the rows is all it takes, and a stratum is nan exactly where the restricted
+evaluator would raise.  A truth id is the text ID + CHROM + POS, which rows of two contigs can share: truth_side(strata=..) numbers
+the ids per (stratum, id text), so that such an id counts once in a stratum that holds both rows and once in each otherwise.
 """
 
 import argparse
@@ -195,13 +204,55 @@ def prepare_truth(cands, truth_vcf, refdist=1000, pctsim=0.0, bed='', skip_phasi
                 n_uid=len(base_uid), n_groups=G, n_pairs=len(pairs), n_base=len(baseinfo))
 
 
-def truth_side(truth_vcf, bed='', skip_phasing=False):
-    """The truth set as include/duet_ef.h's duet_eval_problem carries it (evaluation.flatten), plus n_base = len(baseinfo)."""
+def strata_by_contig():
+    """One stratum per scored contig (evaluation.CHROMS) and `other` for any CHROM text the parser keeps that is none of them."""
+    return dict(names=tuple(evaluation.CHROMS) + ('other',), index={c: i for i, c in enumerate(evaluation.CHROMS)}, default=len(evaluation.CHROMS))
+
+
+def strata_holdout(texts):
+    """`test`: the listed CHROM texts; `train`: every other text."""
+    texts = [str(t) for t in texts]
+    if not texts or not all(texts):
+        raise ValueError('holdout: a non-empty list of CHROM texts, not %r' % (texts,))
+    return dict(names=('train', 'test'), index=dict.fromkeys(texts, 1), default=0)
+
+
+def stratum_of(strata, text):
+    return strata['index'].get(text, strata['default'])
+
+
+def chrom_strata(texts, strata):
+    """chrom_stratum u8[n_chrom] for the dense CHROM ids _dense_ids gives the same texts (equal texts share an id)."""
+    return np.array([stratum_of(strata, t) for t in dict.fromkeys(texts)], dtype=np.uint8)
+
+
+def truth_side(truth_vcf, bed='', skip_phasing=False, strata=None):
+    """The truth set as include/duet_ef.h's duet_eval_problem carries it (evaluation.flatten), plus n_base = len(baseinfo).
+    With strata: base_uid is numbered per (stratum, id text), stratum-major, stratum s owning uid_off[s] .. uid_off[s + 1] with
+    every offset a multiple of 32 (n_base_uid = uid_off[S]); n_base_strata[s] = the truth records of stratum s, those outside
+    every list (CHROM not 'chr' + label) included."""
     baseinfo = evaluation.parse_vcf(truth_vcf, skip_phasing, bed or '')
+    if strata is not None:
+        of = [stratum_of(strata, r['chr']) for r in baseinfo]
+        baseinfo = [dict(r, id=(s, r['id'])) for r, s in zip(baseinfo, of)]
     a = evaluation.flatten(baseinfo, [])
-    return dict(base_off=np.asarray(a['base_off'], dtype=np.uint32), base_pos=np.asarray(a['base_pos'], dtype=np.uint32),
-                base_len=np.asarray(a['base_len'], dtype=np.uint32), base_uid=np.asarray(a['base_uid'], dtype=np.uint32),
-                base_hp=np.asarray(a['base_hp'], dtype=np.uint8), n_base_uid=int(a['n_base_uid']), n_base=len(baseinfo))
+    out = dict(base_off=np.asarray(a['base_off'], dtype=np.uint32), base_pos=np.asarray(a['base_pos'], dtype=np.uint32),
+               base_len=np.asarray(a['base_len'], dtype=np.uint32), base_uid=np.asarray(a['base_uid'], dtype=np.uint32),
+               base_hp=np.asarray(a['base_hp'], dtype=np.uint8), n_base_uid=int(a['n_base_uid']), n_base=len(baseinfo))
+    if strata is not None:
+        S = len(strata['names'])
+        first_seen = list(dict.fromkeys(r['id'] for r in baseinfo))         # flatten's numbering: (stratum, id text) as first seen
+        n_ids = np.bincount([s for s, _ in first_seen], minlength=S)
+        uid_off = np.concatenate([[0], np.cumsum((n_ids + 31) // 32 * 32)]).astype(np.int64)
+        if uid_off[-1] > 0xFFFFFFFF:
+            raise ValueError('too many truth ids')
+        nxt, renumber = uid_off[:-1].copy(), np.zeros(len(first_seen), dtype=np.uint32)
+        for i, (s, _) in enumerate(first_seen):
+            renumber[i] = nxt[s]
+            nxt[s] += 1
+        out.update(base_uid=renumber[out['base_uid']] if len(out['base_uid']) else out['base_uid'], n_base_uid=int(uid_off[-1]),
+                   uid_off=uid_off.astype(np.uint32), n_base_strata=[int(x) for x in np.bincount(of, minlength=S)])
+    return out
 
 
 _LIST_KEY = {(c, t): 2 * k + j for k, c in enumerate(evaluation.CHROMS) for j, t in enumerate(('INS', 'DEL'))}
@@ -332,6 +383,37 @@ def _rows(vecs, counts, n_base, lead=None):
     return out
 
 
+def _strata_passes(truth_vcf, bed, skip_phasing, holdout, by_contig):
+    """The stratified passes a sweep was asked for: (kind, strata, the truth side numbered for them)."""
+    passes = []
+    if holdout is not None:
+        passes.append(('holdout', strata_holdout(holdout)))
+    if by_contig is not None:
+        passes.append(('by_contig', strata_by_contig()))
+    return [(kind, st, truth_side(truth_vcf, bed, skip_phasing, strata=st)) for kind, st in passes]
+
+
+COUNTS = tuple(n for n in _lib.COUNTS_NAMES if n != 'reserved')
+
+
+def _strata_rows(rows, contig_rows, vecs, strata_counts, passes, lead):
+    """Per setting: train_ / test_ scores onto its K rows (holdout); one row per vector and stratum that has a call or a truth
+    record to contig_rows (by_contig).  strata_counts[kind] is COUNTS_DTYPE[K, S], or None where the setting's rows are nan."""
+    for kind, st, base_s in passes:
+        counts, n_base = strata_counts.get(kind), base_s['n_base_strata']
+        for k in range(len(vecs)):
+            for s, name in enumerate(st['names']):
+                rec = counts[k, s] if counts is not None else np.zeros((), dtype=_lib.COUNTS_DTYPE)
+                ten = scores(rec, n_base[s]) if counts is not None else (math.nan,) * 10
+                if kind == 'holdout':
+                    rows[k].update(('%s_%s' % (name, n), x) for n, x in zip(SCORES, ten))
+                elif int(rec['n_calls']) or n_base[s]:
+                    row = dict(lead, vector=k, contig=name, n_base=n_base[s])
+                    row.update((n, int(rec[n])) for n in COUNTS)
+                    row.update(zip(SCORES, ten))
+                    contig_rows.append(row)
+
+
 def _int_list(name, v):
     vals = [v] if isinstance(v, (int, np.integer)) else list(v)
     if not vals or any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 0 for x in vals):
@@ -340,7 +422,8 @@ def _int_list(name, v):
 
 
 def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,), cluster_max_distance=None, from_bams=False,
-                   refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False, thread=4, ctx=None, on_features=None):
+                   refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False, thread=4, ctx=None, on_features=None,
+                   holdout=None, by_contig=None):
     """sweep() for every setting of -s (svlen_thres), -r (suppread_thres) and, with from_bams, -c (cluster_max_distance; default
     (0.9,)): -> list of rows, settings outermost in the order c, s, r, each row a dict of svlen_thres, suppread_thres
     [, cluster_max_distance], the 14 thresholds and the ten numbers.  from_bams: the candidates come from <home>/snp_phasing/*.bam
@@ -349,18 +432,25 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     svim_mode.sv_phasing_from_bams) and uploaded once; per setting the device computes the features, builds the truth arrays and
     applies the vectors -- only the K count records come back.  A setting for which E/F reports a division by zero (upstream
     raises there) yields nan rows.  on_features(setting, cands): called per setting with the features brought to the host
-    (cands as features() returns them, without ref / alt / soa in the from_bams mode)."""
+    (cands as features() returns them, without ref / alt / soa in the from_bams mode).
+    holdout: a list of CHROM texts -- every row gains train_<score> (every other text) and test_<score> (the listed texts) for the
+    ten SCORES.  by_contig: a list that receives one row per setting, vector and stratum of strata_by_contig() with a call or a
+    truth record: the setting, vector, contig, the nine counts, n_base and the ten scores.  Each is one stratified pass per
+    setting (truth arrays with the pass's id numbering, duet_tune_sweep_strata_device) beside the plain sweep, whose rows do
+    not change."""
     vecs = grid if isinstance(grid, np.ndarray) else expand_grid(grid)
     ss, rs = _int_list('svlen_thres', svlen_thres), _int_list('suppread_thres', suppread_thres)
     if cluster_max_distance is not None and not from_bams:
         raise ValueError('cluster_max_distance only acts on candidates clustered from the BAMs: it needs from_bams')
     ctx = ctx or engine.default_context()
     base = truth_side(truth_vcf, bed, skip_phasing)
+    passes = _strata_passes(truth_vcf, bed, skip_phasing, holdout, by_contig)
     if from_bams:
         cs = [float(c) for c in (cluster_max_distance if cluster_max_distance is not None else (0.9,))]
         if not cs:
             raise ValueError('cluster_max_distance: an empty list')
-        return _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features)
+        return _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features,
+                           passes, by_contig)
     from duet_amd.devmem import DeviceProblem, DeviceTune
     soa, txt = _candidates(home, ss[0], rs[0], include_all_ctgs, thread)
     cands = dict(pos=soa.cand_pos, svlen=soa.cand_svlen, **txt)
@@ -370,26 +460,33 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     dt = DeviceTune(C, base, *_match_limits(refdist, pctsim), vectors=vecs, device=device)
     dt.set_candidates(soa.cand_pos, soa.cand_svlen, key, chrom, n_chrom)
     dp = DeviceProblem(soa, ss[0], rs[0], device=device) if C else None
+    resident = {kind: dt.set_strata(chrom_strata(cands['chrom'], st), b['uid_off'], b['base_uid']) for kind, st, b in passes}
     out = []
     for s_ in ss:
         for r_ in rs:
             lead = dict(svlen_thres=s_, suppread_thres=r_)
-            counts = None
+            counts, strata_counts = None, {}
             try:
                 if C:
                     dp.problem.svlen_thres, dp.problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
                     ctx.features_device(dp.problem, dt.feat.data_ptr(), dt.stream())
                 dt.build(ctx, C)
                 counts = dt.sweep(ctx, C)
+                for kind, p in resident.items():
+                    dt.build_strata(ctx, C, strata=p)
+                    strata_counts[kind] = dt.sweep_strata(ctx, C, p)
             except ZeroDivisionError:
                 pass
             if on_features is not None:
                 on_features(lead, dict(cands, feat=dt.features_host(C)))
-            out.extend(_rows(vecs, counts, base['n_base'], lead))
+            rows = _rows(vecs, counts, base['n_base'], lead)
+            _strata_rows(rows, by_contig, vecs, strata_counts, passes, lead)
+            out.extend(rows)
     return out
 
 
-def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features):
+def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features,
+                passes=(), by_contig=None):
     from duet_amd import svim_mode
     from duet_amd.devmem import DeviceSvim, DeviceTune
     from duet_amd.native import NativeIngest
@@ -409,12 +506,13 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
         M = len(got['pos'])
         dt = DeviceTune(M, base, *_match_limits(refdist, pctsim), vectors=vecs, device=device)
         dt.set_tables(key_table, chrom_id, n_chrom, bed_t)
+        resident = {kind: dt.set_strata(chrom_strata(texts, st), b['uid_off'], b['base_uid']) for kind, st, b in passes}
         ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, s_, rs[0], max_dist=cs[0], device=device) if M else None
         for c_ in cs:
             for r_ in rs:
                 if (c_, s_, r_) in done:
                     continue
-                counts, N = None, 0
+                counts, N, strata_counts = None, 0, {}
                 try:
                     if M:
                         ds.sv_problem.marks.max_dist = c_
@@ -422,9 +520,12 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
                         N = ds.run_features(ctx, dt.feat.data_ptr())
                     dt.build(ctx, N, ds.result if M else None)
                     counts = dt.sweep(ctx, N)
+                    for kind, p in resident.items():
+                        dt.build_strata(ctx, N, ds.result if M else None, p)
+                        strata_counts[kind] = dt.sweep_strata(ctx, N, p)
                 except ZeroDivisionError:
                     pass
-                done[(c_, s_, r_)] = counts
+                done[(c_, s_, r_)] = counts, strata_counts
                 if on_features is not None:
                     if M and ds.n_found is None:
                         ds.n_found = ds.n_cands()           # (a division by zero: the records are written all the same)
@@ -437,7 +538,11 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
     for c_ in cs:
         for s_ in ss:
             for r_ in rs:
-                out.extend(_rows(vecs, done[(c_, s_, r_)], base['n_base'], dict(cluster_max_distance=c_, svlen_thres=s_, suppread_thres=r_)))
+                lead = dict(cluster_max_distance=c_, svlen_thres=s_, suppread_thres=r_)
+                counts, strata_counts = done[(c_, s_, r_)]
+                rows = _rows(vecs, counts, base['n_base'], lead)
+                _strata_rows(rows, by_contig, vecs, strata_counts, passes, lead)
+                out.extend(rows)
     return out
 
 
@@ -498,10 +603,17 @@ def parse_args(argv):
     ap.add_argument('--out', default='sweep.tsv', help='one row per setting and vector [%(default)s]')
     ap.add_argument('--features', default='', help='also write the per-candidate features here (TSV; with several settings one '
                                                    'file per setting, the setting in its name)')
+    ap.add_argument('--holdout', type=lambda t: [x for x in t.split(',')], default=None,
+                    help='comma-separated CHROM texts held out: every row gains train_<score> (all other texts) and test_<score> '
+                         '(these texts) for the ten scores')
+    ap.add_argument('--by_contig', default='', help='also write one row per setting, vector and contig (chr1..chrY, other) that has '
+                                                    'a call or a truth record here (TSV): counts, n_base and the ten scores')
     ap.add_argument('--device', type=int, default=0, help='HIP device index [%(default)s]')
     a = ap.parse_args(argv)
     if a.cluster_max_distance is not None and not a.from_bams:
         ap.error('-c / --cluster_max_distance needs --from_bams: it only acts on candidates clustered from the BAMs')
+    if a.holdout is not None and (not a.holdout or not all(a.holdout)):
+        ap.error('--holdout: an empty list (or an empty CHROM text in it)')
     return a
 
 
@@ -530,11 +642,19 @@ def main(argv):
                    ([cands['chrom'][c], int(cands['pos'][c]), cands['svtype'][c], int(cands['svlen'][c])] +
                     [int(f[n][c]) for n in cols[4:]] for c in range(len(f))))
 
+    contig_rows = []
     rows = sweep_settings(a.workdir, a.truthset, vecs, a.sv_min_size, a.min_support_read, cs, a.from_bams, a.refdist, a.pctsim,
                           a.bed_file, a.skip_phasing, a.include_all_ctgs, a.thread, ctx=ctx,
-                          on_features=write_features if a.features else None)
+                          on_features=write_features if a.features else None, holdout=a.holdout,
+                          by_contig=contig_rows if a.by_contig else None)
     lead = () if plain else tuple(n for n in LEAD if n in rows[0])
-    _write_tsv(a.out, lead + NAMES + SCORES, ([r[n] for n in lead + NAMES + SCORES] for r in rows))
+    cols = lead + NAMES + SCORES
+    if a.holdout is not None:
+        cols += tuple('%s_%s' % (part, n) for part in ('train', 'test') for n in SCORES)
+    _write_tsv(a.out, cols, ([r[n] for n in cols] for r in rows))
+    if a.by_contig:
+        cols = lead + ('vector', 'contig') + COUNTS + ('n_base',) + SCORES
+        _write_tsv(a.by_contig, cols, ([r[n] for n in cols] for r in contig_rows))
     best = max(range(len(rows)), key=lambda i: -1.0 if math.isnan(rows[i]['hp_f1']) else rows[i]['hp_f1'])
     print('%d vectors scored -> %s; best phasing F1 %r at vector %d' % (len(rows), a.out, rows[best]['hp_f1'], best))
 

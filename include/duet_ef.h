@@ -555,6 +555,54 @@ typedef struct duet_tune_truth_problem {
 DUET_API int duet_tune_truth_build_device(duet_ctx *ctx, const duet_tune_truth_problem *prob, duet_tune_truth *truth, void *stream);
 DUET_API int duet_tune_truth_build_host(duet_ctx *ctx, const duet_tune_truth_problem *prob, duet_tune_truth *truth);
 
+/* Strata: the sweep scored per set of CHROM texts in one pass.  A stratum is a set of CHROM texts; every row of the callset and
+ * of the truth file belongs to exactly one stratum, by its CHROM text alone.  The record of (vector v, stratum s) is what
+ * evaluation.py:99-159 forms when callset and truth set are both restricted to the rows whose CHROM text is in s -- the
+ * evaluator matches, fills its six id sets and picks each phase-set group's labelling inside `for ch in range(24)`, so nothing
+ * crosses a CHROM text.  A truth id is the text ID + CHROM + POS (:53), which two rows of different contigs can share ('.' at
+ * chr1:2345678 and at chr12:345678): the restricted evaluator counts such an id once in a stratum that holds both contigs and
+ * once in each stratum that holds one.  The caller therefore numbers the truth ids per (stratum, id text), stratum-major:
+ * stratum s owns the ids uid_off[s] .. uid_off[s + 1], every offset a multiple of 32 (ids that name no record fill a range up),
+ * so that a 32-bit word of the sweep's id sets belongs to one stratum.
+ *   cand_stratum[c]   stratum (< n_strata) of candidate c; read for the candidates in the call list only
+ *   group_stratum[g]  stratum of phase-set group g (all calls of a group share a CHROM id); read for groups with a call only */
+#define DUET_TUNE_MAX_STRATA 64
+typedef struct duet_tune_strata {
+    uint32_t n_strata;              /* S, 1 .. DUET_TUNE_MAX_STRATA */
+    uint32_t reserved;
+    const uint8_t *cand_stratum;    /* [C] */
+    const uint8_t *group_stratum;   /* [n_groups] */
+    const uint32_t *uid_off;        /* [S + 1] HOST memory in both forms: uid_off[0] = 0, nondecreasing, every entry a multiple of 32,
+                                       uid_off[S] == truth->n_uid */
+} duet_tune_strata;
+
+/* cand_stratum and group_stratum from the CHROM ids of a truth problem: runs after duet_tune_truth_build_* on the same *prob and
+ * *truth.  The CHROM id of candidate c is prob->cand_chrom[c] (per-candidate form) or prob->chrom_id[prob->cand_contig[c]] (table
+ * form); cand_stratum[c] = chrom_stratum[id] for every candidate and, for every call (DUET_TUNE_IN_CALLS in truth->cand_flags),
+ * group_stratum[truth->cand_group[c]] too.  chrom_stratum[prob->n_chrom]; cand_stratum and group_stratum with room for C entries.
+ * _device: every array is device memory; one kernel on `stream`, then the stream is synchronised for the kernel's status word
+ * (4 bytes) -- a chrom_stratum entry >= n_strata, or a CHROM id >= n_chrom, writes stratum 0 and reports DUET_ERR_INVALID, it
+ * never indexes past an array.  _host: host arrays; uploads, runs the same kernel, downloads cand_stratum[C] and
+ * group_stratum[truth->n_groups].  DUET_ERR_INVALID also for n_strata of 0 or above DUET_TUNE_MAX_STRATA and for a NULL array
+ * that is needed. */
+DUET_API int duet_tune_strata_build_device(duet_ctx *ctx, const duet_tune_truth_problem *prob, const duet_tune_truth *truth,
+                                           const uint8_t *chrom_stratum, uint32_t n_strata, uint8_t *cand_stratum,
+                                           uint8_t *group_stratum, void *stream);
+DUET_API int duet_tune_strata_build_host(duet_ctx *ctx, const duet_tune_truth_problem *prob, const duet_tune_truth *truth,
+                                         const uint8_t *chrom_stratum, uint32_t n_strata, uint8_t *cand_stratum, uint8_t *group_stratum);
+
+/* K vectors over C candidates, one duet_tune_counts record per (vector, stratum): counts[v * S + s].  truth and strata are
+ * mandatory (pred and ps come from duet_tune_sweep_*); batching, workspace and the asynchrony of the _device form are
+ * duet_tune_sweep_device's.  n_vec == 0 or n_cands == 0: DUET_OK, the counts zeroed.  DUET_ERR_INVALID: n_strata out of range,
+ * uid_off not as described above, a NULL array that is needed and, in the _host form (which can read them), a cand_stratum entry
+ * of a call or a group_stratum entry >= n_strata. */
+DUET_API int duet_tune_sweep_strata_device(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *vec,
+                                           uint32_t n_vec, const duet_tune_truth *truth, const duet_tune_strata *strata,
+                                           duet_tune_counts *counts, void *stream);
+DUET_API int duet_tune_sweep_strata_host(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *vec,
+                                         uint32_t n_vec, const duet_tune_truth *truth, const duet_tune_strata *strata,
+                                         duet_tune_counts *counts);
+
 /* ---------------------------------------------------------------------------------------------
  * The collective of the contig-sharded path: candidates shard by contig over the GPUs of one node,
  * one process and one context per GPU, and ONE all-gather of fixed-size record blocks reassembles the call set
