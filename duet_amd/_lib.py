@@ -33,7 +33,7 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_svim_vcf_rows_device', 'duet_svim_vcf_rows_host', 'duet_svim_phased_rows_device', 'duet_svim_phased_rows_host',
            'duet_svim_features_device', 'duet_svim_features_host', 'duet_tune_truth_build_device', 'duet_tune_truth_build_host',
            'duet_tune_strata_build_device', 'duet_tune_strata_build_host', 'duet_tune_sweep_strata_device',
-           'duet_tune_sweep_strata_host')
+           'duet_tune_sweep_strata_host', 'duet_tune_line_device', 'duet_tune_line_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -276,6 +276,10 @@ def load():
     lib.duet_tune_sweep_strata_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                                   ctypes.POINTER(TuneTruth), ctypes.POINTER(TuneStrata), ctypes.c_void_p, ctypes.c_void_p]
     lib.duet_tune_sweep_strata_host.argtypes = lib.duet_tune_sweep_strata_device.argtypes[:-1]
+    lib.duet_tune_line_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                          ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+                                          ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+    lib.duet_tune_line_host.argtypes = lib.duet_tune_line_device.argtypes[:-1]
     _lib = lib
     return lib
 
@@ -767,6 +771,39 @@ class Context(object):
         rc = self.lib.duet_tune_sweep_device(self.handle, ctypes.c_void_p(feat_ptr), int(n_cands), ctypes.c_void_p(vec_ptr), int(n_vec),
                                              ctypes.byref(truth) if truth is not None else None, ctypes.c_void_p(counts_ptr), None, None,
                                              ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+
+    def line_host(self, feat, base, axis, max_values=0):
+        """duet_tune_line_host: feat FEATURE_DTYPE[C], base float64[14] -> (vectors float64[n_vec, 14], n_distinct): the line of
+        field `axis` (its index in TUNE_NAMES) through `base`.  Raises ZeroDivisionError where a compared feature is not finite."""
+        feat = np.ascontiguousarray(feat, dtype=FEATURE_DTYPE)
+        base = np.ascontiguousarray(base, dtype=np.float64).reshape(len(TUNE_NAMES))
+        out = np.zeros((len(feat) + 1, len(TUNE_NAMES)), dtype=np.float64)
+        n_vec, n_distinct = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        rc = self.lib.duet_tune_line_host(self.handle, _ptr(feat), len(feat), _ptr(base), clamp_u32(axis), int(max_values), _ptr(out),
+                                          ctypes.byref(n_vec), ctypes.byref(n_distinct))
+        if rc:
+            self._raise(rc)
+        return out[:n_vec.value].copy(), n_distinct.value
+
+    def line_device(self, feat_ptr, n_cands, base, axis, max_values, out_vec_ptr, stream=0):
+        """duet_tune_line_device on resident arrays (devmem.DeviceTune.line); base float64[14] on the host
+        -> (n_vec, n_distinct)."""
+        base = np.ascontiguousarray(base, dtype=np.float64).reshape(len(TUNE_NAMES))
+        n_vec, n_distinct = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        rc = self.lib.duet_tune_line_device(self.handle, ctypes.c_void_p(feat_ptr), int(n_cands), _ptr(base), clamp_u32(axis),
+                                            int(max_values), ctypes.c_void_p(out_vec_ptr), ctypes.byref(n_vec), ctypes.byref(n_distinct),
+                                            ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return n_vec.value, n_distinct.value
+
+    def apply_device(self, feat_ptr, n_cands, vec_ptr, pred_ptr, ps_ptr, stream=0):
+        """duet_tune_sweep_device with one vector and no truth set: pred u8[C] and ps u32[C] on the device, what
+        duet_ef_run_device writes with the built-in constants."""
+        rc = self.lib.duet_tune_sweep_device(self.handle, ctypes.c_void_p(feat_ptr), int(n_cands), ctypes.c_void_p(vec_ptr), 1, None, None,
+                                             ctypes.c_void_p(pred_ptr), ctypes.c_void_p(ps_ptr), ctypes.c_void_p(stream))
         if rc:
             self._raise(rc)
 

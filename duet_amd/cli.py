@@ -24,7 +24,8 @@ def pipeline(a):
             (stages.snp_calling, (a.OUTPUT, a.REFERENCE, a.BAM, a.min_allele_frequency, a.thread, a.include_all_ctgs)),
             (stages.snp_phasing, (a.OUTPUT, a.REFERENCE, a.BAM, a.thread)),
             (sv_phasing_from_bams, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs,
-                                    a.cluster_max_distance, a.device, a.gpus, a.write_sv_calls)),
+                                    a.cluster_max_distance, a.device, a.gpus, a.write_sv_calls,
+                                    getattr(a, 'threshold_vector', None))),
         )
     return (
         (stages.snp_calling, (a.OUTPUT, a.REFERENCE, a.BAM, a.min_allele_frequency, a.thread, a.include_all_ctgs)),
@@ -44,7 +45,8 @@ def main(argv):
         raise SystemExit('duet: --write_sv_calls works with -b svim-gpu only')
     if a.thresholds is not None:
         # (additive: the decision's constants from a file -- checked before any stage runs)
-        if a.gpus > 1 or a.sv_caller == 'svim-gpu' or os.environ.get('DUET_FORCE_RANKS') == '1':
+        # (-b svim-gpu on one GPU takes a vector too: one fitted on the BAM path, `tune --from_bams --fit`, is usable on it)
+        if a.gpus > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
             raise SystemExit('duet: --thresholds works on the single-GPU path with an external SV caller only '
                              '(not with --gpus > 1 or -b svim-gpu)')
         from duet_amd import tune

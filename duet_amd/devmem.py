@@ -209,6 +209,21 @@ class DeviceSvim(DeviceCluster):
         self.n_found = ctx.svim_features_device(self.sv_problem, self.result, feat_ptr, stream)
         return self.n_found
 
+    def run_thresholds(self, ctx, thresholds, stream=None):
+        """run_fused with the decision's 14 constants taken from `thresholds` (float64[14]): the candidates' features
+        (duet_svim_features_device), then the one vector applied to them (duet_tune_sweep_device) into out_pred / out_ps.
+        Raises ZeroDivisionError where the fused run would."""
+        torch = self.torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        vec = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(len(_lib.TUNE_NAMES))
+        feat = torch.zeros(max(self.M, 1) * _lib.FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        d_vec = torch.from_numpy(vec.copy()).to(self.device)
+        N = self.run_features(ctx, feat.data_ptr(), stream)
+        ctx.apply_device(feat.data_ptr(), N, d_vec.data_ptr(), self.out_pred.data_ptr(), self.out_ps.data_ptr(), stream)
+        torch.cuda.current_stream(self.device).synchronize()       # (feat and d_vec are released when this returns)
+        return stream
+
     def vcf_rows(self, ctx, names, chrom_texts, stream=None):
         """Rows of sv_calling/variants.vcf for the last run_fused's candidates, formatted on the device from the resident
         cluster result and depth (duet_svim_vcf_rows_device).  names: dict(mark_name, name_off, name_pool) of
@@ -288,11 +303,7 @@ class DeviceTune(object):
         self.problem = p
         n = max(self.n_max, 1)
         self.feat = torch.zeros(n * _lib.FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-        t = _lib.TuneTruth()
-        for name, dt in _lib.TRUTH_ARRAYS:
-            self.keep[name] = torch.zeros((n + 1) * np.dtype(dt).itemsize, dtype=torch.uint8, device=self.device)
-            setattr(t, name, self.keep[name].data_ptr())
-        self.truth = t
+        self.truth = self._truth_arrays('')
         vec = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1, len(_lib.TUNE_NAMES))
         self.K = len(vec)
         self.vec_ptr = self._up('vectors', vec, np.float64)
@@ -305,6 +316,14 @@ class DeviceTune(object):
             t[:a.nbytes] = self.torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(self.device)
         self.keep[name] = t
         return t.data_ptr()
+
+    def _truth_arrays(self, tag):
+        """A TuneTruth over six resident arrays of their own, sized for n_max candidates."""
+        n, t = max(self.n_max, 1), _lib.TuneTruth()
+        for name, dt in _lib.TRUTH_ARRAYS:
+            self.keep[name + tag] = self.torch.zeros((n + 1) * np.dtype(dt).itemsize, dtype=self.torch.uint8, device=self.device)
+            setattr(t, name, self.keep[name + tag].data_ptr())
+        return t
 
     def stream(self):
         return self.torch.cuda.current_stream(self.device).cuda_stream
@@ -325,24 +344,25 @@ class DeviceTune(object):
         if bed is not None:
             p.bed_off, p.bed_lo, p.bed_hi = (self._up(k, a, np.uint32) for k, a in zip(('bed_off', 'bed_lo', 'bed_hi'), bed))
 
-    def build(self, ctx, n_cands, result=None):
+    def build(self, ctx, n_cands, result=None, truth=None):
         """The truth arrays of the features in self.feat (duet_tune_truth_build_device).  result: the ClusterResult whose
-        candidate columns the table form reads."""
+        candidate columns the table form reads.  truth: the arrays to fill (a pass's own, see set_strata) instead of self.truth."""
         p = self.problem
         p.n_cands, p.feat = int(n_cands), self.feat.data_ptr()
         if result is not None:
             p.cand_contig, p.cand_type, p.cand_pos, p.cand_len = result.cand_contig, result.cand_type, result.cand_pos, result.cand_span
-        ctx.truth_build_device(p, self.truth, self.stream())
+        ctx.truth_build_device(p, truth if truth is not None else self.truth, self.stream())
 
     def sweep(self, ctx, n_cands):
         """The K vectors over the features and truth arrays of the last build -> COUNTS_DTYPE[K] on the host."""
         ctx.sweep_device(self.feat.data_ptr(), int(n_cands), self.vec_ptr, self.K, self.truth, self.counts.data_ptr(), self.stream())
         return self.counts[:self.K * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).copy()
 
-    def set_strata(self, chrom_stratum, uid_off, base_uid=None):
+    def set_strata(self, chrom_stratum, uid_off, base_uid=None, own_truth=False):
         """One stratified pass (tune.truth_side(strata=...), tune.chrom_strata): chrom_stratum u8[n_chrom], uid_off u32[S + 1] and
         the truth side's base_uid numbered per (stratum, id text).  -> the pass, for build() and sweep_strata(); its arrays stay
-        resident like the rest, and several passes can be set side by side."""
+        resident like the rest, and several passes can be set side by side.  own_truth: build_strata fills truth arrays of the
+        pass's own, so that plain and stratified sweeps can alternate after one build of each (the fit)."""
         torch = self.torch
         uid_off = np.ascontiguousarray(uid_off, dtype=np.uint32)
         S, n = len(uid_off) - 1, max(self.n_max, 1)
@@ -357,29 +377,73 @@ class DeviceTune(object):
                  chrom_stratum=self._up('chrom_stratum%d' % i, chrom_stratum, np.uint8),
                  base_uid=self._up('base_uid%d' % i, base_uid, np.uint32) if base_uid is not None else self.problem.base_uid,
                  counts=torch.zeros(max(self.K * S, 1) * _lib.COUNTS_DTYPE.itemsize, dtype=torch.uint8, device=self.device))
+        if own_truth:
+            p['truth'] = self._truth_arrays('_strata%d' % i)
         self.strata = p
         return p
 
     def build_strata(self, ctx, n_cands, result=None, strata=None):
         """build() with the pass's truth-id numbering, then the strata of the candidates and groups
-        (duet_tune_strata_build_device).  The truth arrays are the pass's from here on: a plain sweep() goes before it."""
+        (duet_tune_strata_build_device).  The truth arrays are the pass's from here on: a plain sweep() goes before it -- unless
+        the pass has truth arrays of its own (set_strata(own_truth=True))."""
         s, p = strata or self.strata, self.problem
+        truth = s.get('truth', self.truth)
         plain = p.base_uid, p.n_base_uid
         p.base_uid, p.n_base_uid = s['base_uid'], s['n_base_uid']
         try:
-            self.build(ctx, n_cands, result)
+            self.build(ctx, n_cands, result, truth)
         finally:
             p.base_uid, p.n_base_uid = plain
-        ctx.strata_build_device(p, self.truth, s['chrom_stratum'], s['strata'].n_strata, s['strata'].cand_stratum,
+        ctx.strata_build_device(p, truth, s['chrom_stratum'], s['strata'].n_strata, s['strata'].cand_stratum,
                                 s['strata'].group_stratum, self.stream())
 
     def sweep_strata(self, ctx, n_cands, strata=None):
         """The K vectors over the features and the truth arrays of the last build_strata -> COUNTS_DTYPE[K, S] on the host."""
         s = strata or self.strata
         S = s['strata'].n_strata
-        ctx.sweep_strata_device(self.feat.data_ptr(), int(n_cands), self.vec_ptr, self.K, self.truth, s['strata'], s['counts'].data_ptr(),
-                                self.stream())
+        ctx.sweep_strata_device(self.feat.data_ptr(), int(n_cands), self.vec_ptr, self.K, s.get('truth', self.truth), s['strata'],
+                                s['counts'].data_ptr(), self.stream())
         return s['counts'][:self.K * S * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).reshape(self.K, S).copy()
+
+    # -- the line of one axis (tune.fit): a block of n_max + 2 vectors next to the grid's, made on the device --------------------
+    VEC_BYTES = 8 * len(_lib.TUNE_NAMES)
+
+    def line(self, ctx, n_cands, base, axis, max_values=0):
+        """The line of `axis` through `base` (float64[14], host) from the resident features (duet_tune_line_device) into the
+        line block, and `base` itself behind its n_vec vectors, so that one sweep scores the current vector in the same batch.
+        -> (n_vec, n_distinct).  Raises ZeroDivisionError where a compared feature is not finite."""
+        torch = self.torch
+        if getattr(self, 'line_vec', None) is None:
+            n = self.n_max + 2
+            self.line_vec = torch.zeros(n * self.VEC_BYTES, dtype=torch.uint8, device=self.device)
+            self.line_counts = torch.zeros(n * _lib.COUNTS_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        base = np.ascontiguousarray(base, dtype=np.float64).reshape(len(_lib.TUNE_NAMES))
+        n_vec, n_distinct = ctx.line_device(self.feat.data_ptr(), int(n_cands), base, axis, max_values, self.line_vec.data_ptr(),
+                                            self.stream())
+        self.line_vec[n_vec * self.VEC_BYTES:(n_vec + 1) * self.VEC_BYTES] = torch.from_numpy(base.view(np.uint8).copy()).to(self.device)
+        return n_vec, n_distinct
+
+    def line_value(self, i, axis):
+        """The value of field `axis` (index) in vector i of the line block."""
+        at = i * self.VEC_BYTES + 8 * int(axis)
+        return float(self.line_vec[at:at + 8].cpu().numpy().view(np.float64)[0])
+
+    def sweep_line(self, ctx, n_cands, first, K):
+        """Vectors first .. first + K of the line block over the features and truth arrays of the last build
+        -> COUNTS_DTYPE[K] on the host."""
+        ctx.sweep_device(self.feat.data_ptr(), int(n_cands), self.line_vec.data_ptr() + first * self.VEC_BYTES, K, self.truth,
+                         self.line_counts.data_ptr(), self.stream())
+        return self.line_counts[:K * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).copy()
+
+    def sweep_line_strata(self, ctx, n_cands, first, K, strata=None):
+        """The same per stratum, over the truth arrays of the last build_strata -> COUNTS_DTYPE[K, S] on the host."""
+        s = strata or self.strata
+        S, rec = s['strata'].n_strata, _lib.COUNTS_DTYPE.itemsize
+        if s.get('line_counts') is None:
+            s['line_counts'] = self.torch.zeros((self.n_max + 2) * S * rec, dtype=self.torch.uint8, device=self.device)
+        ctx.sweep_strata_device(self.feat.data_ptr(), int(n_cands), self.line_vec.data_ptr() + first * self.VEC_BYTES, K,
+                                s.get('truth', self.truth), s['strata'], s['line_counts'].data_ptr(), self.stream())
+        return s['line_counts'][:K * S * rec].cpu().numpy().view(_lib.COUNTS_DTYPE).reshape(K, S).copy()
 
     def features_host(self, n_cands):
         """(--features) the feature records of the last setting, on the host."""

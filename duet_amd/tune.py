@@ -9,6 +9,10 @@
                                            vector scored per stratum in one pass over the candidates (duet_tune_sweep_strata_device)
     python -m duet_amd.tune WORKDIR TRUTH.vcf --grid GRID.json [-s 30,50 -r 2,3 [--from_bams -c 0.5,0.9]]
                                            [--holdout chr20,chr21 --by_contig FILE.tsv] [...]
+    fit(home, truth_vcf, objective, ...)   coordinate descent over exact lines: per axis one vector per distinct value of the feature
+                                           the axis is compared with (duet_tune_line_device), scored by the same sweep
+    python -m duet_amd.tune WORKDIR TRUTH.vcf --fit hp_f1 [--start VEC.json --axes a,b --rounds N --max_values N --holdout ..]
+                                           --out_vector best.json [--trace fit.tsv]
 
 The vector's 14 fields, their order and defaults are include/duet_ef.h's duet_tune_thresholds (NAMES, DEFAULTS).  A grid is
 either a list of partial vectors (dicts) or a dict of name -> list of values, expanded as a Cartesian product; names left out
@@ -23,6 +27,14 @@ matches every call to its nearest truth record by the evaluator's rule and numbe
 binary64 quotients of those counts.  prepare_truth is the same truth match on the host, in the evaluator's own terms: the
 normative text the device build is tested against.  Where upstream would raise (ZeroDivisionError: no calls, or precision +
 recall == 0; IndexError: an emitted call whose (contig, type) has no truth record) the row's ten numbers are nan.
+
+Fit.  With the other 13 constants fixed, every count of a sweep is a piecewise-constant function of one constant: it changes only
+where the constant crosses a value of the feature it is compared with that some candidate has.  The line of an axis -- those
+distinct values and one sentinel (-inf in front for the <= and > axes, +inf behind for the >= axes) -- therefore holds every
+behaviour of the axis, and the best vector on it is the exact optimum of the axis, not the best of a guessed grid.  fit() walks the
+axes round by round; an axis moves only to a strictly better objective, and then to the line's lowest-index value that attains it,
+so the objective never decreases, and a round without a move ends the fit.  The line is made on the device from the resident
+features; only count records (and the one chosen value) come back.
 
 Strata.  A stratum is a set of CHROM texts; the ten numbers of (vector, stratum) are what the unmodified evaluator returns when the
 callset and the truth set are both restricted to the rows with those CHROM texts -- it matches, fills its id sets and groups the
@@ -423,7 +435,7 @@ def _int_list(name, v):
 
 def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,), cluster_max_distance=None, from_bams=False,
                    refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False, thread=4, ctx=None, on_features=None,
-                   holdout=None, by_contig=None):
+                   holdout=None, by_contig=None, _each=None):
     """sweep() for every setting of -s (svlen_thres), -r (suppread_thres) and, with from_bams, -c (cluster_max_distance; default
     (0.9,)): -> list of rows, settings outermost in the order c, s, r, each row a dict of svlen_thres, suppread_thres
     [, cluster_max_distance], the 14 thresholds and the ten numbers.  from_bams: the candidates come from <home>/snp_phasing/*.bam
@@ -437,7 +449,10 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     ten SCORES.  by_contig: a list that receives one row per setting, vector and stratum of strata_by_contig() with a call or a
     truth record: the setting, vector, contig, the nine counts, n_base and the ten scores.  Each is one stratified pass per
     setting (truth arrays with the pass's id numbering, duet_tune_sweep_strata_device) beside the plain sweep, whose rows do
-    not change."""
+    not change.
+    _each (fit): called per setting as _each(setting, dt, n_cands, passes) in place of the sweeps, with the features, the plain truth
+    arrays and every pass's own truth arrays and strata built and resident in dt (a DeviceTune); dt None: the setting's features
+    report a division by zero.  The rows returned are then nan."""
     vecs = grid if isinstance(grid, np.ndarray) else expand_grid(grid)
     ss, rs = _int_list('svlen_thres', svlen_thres), _int_list('suppread_thres', suppread_thres)
     if cluster_max_distance is not None and not from_bams:
@@ -450,7 +465,7 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
         if not cs:
             raise ValueError('cluster_max_distance: an empty list')
         return _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features,
-                           passes, by_contig)
+                           passes, by_contig, _each)
     from duet_amd.devmem import DeviceProblem, DeviceTune
     soa, txt = _candidates(home, ss[0], rs[0], include_all_ctgs, thread)
     cands = dict(pos=soa.cand_pos, svlen=soa.cand_svlen, **txt)
@@ -460,7 +475,8 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     dt = DeviceTune(C, base, *_match_limits(refdist, pctsim), vectors=vecs, device=device)
     dt.set_candidates(soa.cand_pos, soa.cand_svlen, key, chrom, n_chrom)
     dp = DeviceProblem(soa, ss[0], rs[0], device=device) if C else None
-    resident = {kind: dt.set_strata(chrom_strata(cands['chrom'], st), b['uid_off'], b['base_uid']) for kind, st, b in passes}
+    resident = {kind: dt.set_strata(chrom_strata(cands['chrom'], st), b['uid_off'], b['base_uid'], own_truth=_each is not None)
+                for kind, st, b in passes}
     out = []
     for s_ in ss:
         for r_ in rs:
@@ -471,12 +487,17 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
                     dp.problem.svlen_thres, dp.problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
                     ctx.features_device(dp.problem, dt.feat.data_ptr(), dt.stream())
                 dt.build(ctx, C)
-                counts = dt.sweep(ctx, C)
+                if _each is None:
+                    counts = dt.sweep(ctx, C)
                 for kind, p in resident.items():
                     dt.build_strata(ctx, C, strata=p)
-                    strata_counts[kind] = dt.sweep_strata(ctx, C, p)
+                    if _each is None:
+                        strata_counts[kind] = dt.sweep_strata(ctx, C, p)
+                if _each is not None:
+                    _each(lead, dt, C, resident)
             except ZeroDivisionError:
-                pass
+                if _each is not None:
+                    _each(lead, None, 0, resident)
             if on_features is not None:
                 on_features(lead, dict(cands, feat=dt.features_host(C)))
             rows = _rows(vecs, counts, base['n_base'], lead)
@@ -486,7 +507,7 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
 
 
 def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features,
-                passes=(), by_contig=None):
+                passes=(), by_contig=None, _each=None):
     from duet_amd import svim_mode
     from duet_amd.devmem import DeviceSvim, DeviceTune
     from duet_amd.native import NativeIngest
@@ -506,7 +527,8 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
         M = len(got['pos'])
         dt = DeviceTune(M, base, *_match_limits(refdist, pctsim), vectors=vecs, device=device)
         dt.set_tables(key_table, chrom_id, n_chrom, bed_t)
-        resident = {kind: dt.set_strata(chrom_strata(texts, st), b['uid_off'], b['base_uid']) for kind, st, b in passes}
+        resident = {kind: dt.set_strata(chrom_strata(texts, st), b['uid_off'], b['base_uid'], own_truth=_each is not None)
+                    for kind, st, b in passes}
         ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, s_, rs[0], max_dist=cs[0], device=device) if M else None
         for c_ in cs:
             for r_ in rs:
@@ -519,12 +541,17 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
                         ds.sv_problem.svlen_thres, ds.sv_problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
                         N = ds.run_features(ctx, dt.feat.data_ptr())
                     dt.build(ctx, N, ds.result if M else None)
-                    counts = dt.sweep(ctx, N)
+                    if _each is None:
+                        counts = dt.sweep(ctx, N)
                     for kind, p in resident.items():
                         dt.build_strata(ctx, N, ds.result if M else None, p)
-                        strata_counts[kind] = dt.sweep_strata(ctx, N, p)
+                        if _each is None:
+                            strata_counts[kind] = dt.sweep_strata(ctx, N, p)
+                    if _each is not None:
+                        _each(dict(cluster_max_distance=c_, svlen_thres=s_, suppread_thres=r_), dt, N, resident)
                 except ZeroDivisionError:
-                    pass
+                    if _each is not None:
+                        _each(dict(cluster_max_distance=c_, svlen_thres=s_, suppread_thres=r_), None, 0, resident)
                 done[(c_, s_, r_)] = counts, strata_counts
                 if on_features is not None:
                     if M and ds.n_found is None:
@@ -544,6 +571,147 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
                 _strata_rows(rows, by_contig, vecs, strata_counts, passes, lead)
                 out.extend(rows)
     return out
+
+
+TRACE = ('round', 'axis', 'n_distinct', 'n_vec', 'exact', 'old', 'new', 'objective_before', 'objective_after')
+
+
+def _axes(axes):
+    """--axes: names (or indices) of the vector's fields -> indices, in the order given; None: all 14 in field order."""
+    if axes is None:
+        return list(range(len(NAMES)))
+    out = []
+    for a in axes:
+        if isinstance(a, str) and a in NAMES:
+            out.append(NAMES.index(a))
+        elif isinstance(a, (int, np.integer)) and not isinstance(a, bool) and 0 <= a < len(NAMES):
+            out.append(int(a))
+        else:
+            raise ValueError('axes: %r is not a threshold name' % (a,))
+    if not out:
+        raise ValueError('axes: an empty list')
+    return out
+
+
+def _better(x, best):
+    """Is objective x strictly greater than best?  nan never wins, and anything with a number beats nan."""
+    return not math.isnan(x) and (math.isnan(best) or x > best)
+
+
+def _fit_setting(ctx, dt, n_cands, start, axes, rounds, max_values, score_of, n_base, hold=None, n_base_hold=None):
+    """Coordinate descent for one setting on the resident features and truth arrays of dt -> (vector, trace rows).
+    hold: the holdout pass (its stratum 0 is `train`, whose score is the objective; stratum 1 `test` is only reported)."""
+    cur = np.array(start, dtype=np.float64)
+    memo = {}
+
+    def ten(rec, nb):
+        key = (rec.tobytes(), nb)
+        if key not in memo:
+            memo[key] = scores(rec, nb)
+        return memo[key]
+
+    trace = []
+    for rnd in range(1, rounds + 1):
+        moved = False
+        for ax in axes:
+            n_vec, n_distinct = dt.line(ctx, n_cands, cur, ax, max_values)
+            K = n_vec + 1                                    # (the line's vectors, then the current vector)
+            if hold is not None:
+                sc = dt.sweep_line_strata(ctx, n_cands, 0, K, hold)
+                objs = [ten(sc[k, 0], n_base_hold[0])[score_of] for k in range(K)]
+            else:
+                pc = dt.sweep_line(ctx, n_cands, 0, K)
+                objs = [ten(pc[k], n_base)[score_of] for k in range(K)]
+            before, best, pick = objs[n_vec], objs[n_vec], n_vec
+            for i in range(n_vec):
+                if _better(objs[i], best):
+                    best, pick = objs[i], i
+            old = float(cur[ax])
+            if pick != n_vec:
+                cur[ax] = dt.line_value(pick, ax)
+                moved = True
+            row = dict(round=rnd, axis=NAMES[ax], n_distinct=n_distinct, n_vec=n_vec, exact=int(n_vec == n_distinct + 1), old=old,
+                       new=float(cur[ax]), objective_before=before, objective_after=objs[pick])
+            plain = dt.sweep_line(ctx, n_cands, pick, 1)[0] if hold is not None else pc[pick]
+            row.update(zip(SCORES, ten(plain, n_base)))
+            if hold is not None:
+                for s_i, part in enumerate(('train', 'test')):
+                    row.update(('%s_%s' % (part, n), x) for n, x in zip(SCORES, ten(sc[pick, s_i], n_base_hold[s_i])))
+            trace.append(row)
+        if not moved:
+            break
+    return cur, trace
+
+
+def _nan_row(holdout):
+    row = dict(zip(TRACE, (0, '', 0, 0, 0) + (math.nan,) * 4))
+    row.update(dict.fromkeys(SCORES, math.nan))
+    if holdout:
+        row.update(('%s_%s' % (part, n), math.nan) for part in ('train', 'test') for n in SCORES)
+    return row
+
+
+def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max_values=0, svlen_thres=(50,), suppread_thres=(2,),
+        cluster_max_distance=None, from_bams=False, refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False,
+        thread=4, ctx=None, holdout=None):
+    """Fit the vector to the truth set by exact per-threshold line search (see the module text), per setting of -s, -r and -c as
+    sweep_settings takes them.  objective: one of SCORES (with holdout: the `train` stratum's; `test` is reported, never used);
+    start: a vector, a partial vector (dict) or None for the defaults; axes: names of the fields to move, in this order (None: all,
+    in field order); rounds: at most this many passes over the axes; max_values: 0 for the whole line of every axis, N >= 2 for
+    at most N of its values (both ends among them).
+    -> dict(fits = one dict(setting, vector (None: no fit), objective, scores, trace) per setting in c, s, r order,
+            best = the fit with the greatest final objective (ties: the earlier setting; None when no setting has a fit),
+            trace = every setting's rows, each the setting's columns, TRACE, the ten SCORES of the new vector and, with holdout,
+            its train_ / test_ scores).
+    A setting whose features or line report a division by zero, or whose objective never has a number, has no fit: its vector is
+    None and (division by zero) its trace is one row of nan."""
+    if objective not in SCORES:
+        raise ValueError('objective: %r is not one of %s' % (objective, ', '.join(SCORES)))
+    rounds, max_values = int(rounds), int(max_values)
+    if rounds < 1:
+        raise ValueError('rounds: at least 1')
+    if max_values < 0 or max_values == 1:
+        raise ValueError('max_values: 0 (all) or at least 2')
+    v0 = vector(start) if start is None or isinstance(start, dict) else np.array(start, dtype=np.float64).reshape(len(NAMES))
+    ax = _axes(axes)
+    score_of = SCORES.index(objective)
+    ctx = ctx or engine.default_context()
+    n_base = truth_side(truth_vcf, bed, skip_phasing)['n_base']
+    n_base_hold = None
+    if holdout is not None:
+        n_base_hold = truth_side(truth_vcf, bed, skip_phasing, strata=strata_holdout(holdout))['n_base_strata']
+    fits = {}
+
+    def each(setting, dt, n_cands, resident):
+        key = tuple(setting[n] for n in LEAD if n in setting)
+        if key in fits:
+            return
+        vec, trace = None, None
+        if dt is not None:
+            try:
+                vec, trace = _fit_setting(ctx, dt, n_cands, v0, ax, rounds, max_values, score_of, n_base, resident.get('holdout'),
+                                          n_base_hold)
+            except ZeroDivisionError:
+                pass
+        if trace is None:
+            fits[key] = dict(setting=dict(setting), vector=None, objective=math.nan, scores=dict.fromkeys(SCORES, math.nan),
+                             trace=[dict(setting, **_nan_row(holdout is not None))])
+            return
+        last = trace[-1]
+        obj = last['objective_after']
+        fits[key] = dict(setting=dict(setting), vector=None if math.isnan(obj) else vec, objective=obj,
+                         scores={n: last[n] for n in last if n in SCORES or n.startswith(('train_', 'test_'))},
+                         trace=[dict(setting, **r) for r in trace])
+
+    rows = sweep_settings(home, truth_vcf, v0[None, :], svlen_thres, suppread_thres, cluster_max_distance, from_bams, refdist, pctsim, bed,
+                          skip_phasing, include_all_ctgs, thread, ctx=ctx, holdout=holdout, _each=each)
+    # (sweep_settings' rows come settings outermost, in c, s, r order)
+    out = [fits[k] for k in dict.fromkeys(tuple(r[n] for n in LEAD if n in r) for r in rows)]
+    best = None
+    for f in out:
+        if f['vector'] is not None and (best is None or f['objective'] > best['objective']):
+            best = f
+    return dict(fits=out, best=best, trace=[r for f in out for r in f['trace']])
 
 
 def apply(cands, thresholds, ctx=None):
@@ -585,7 +753,21 @@ def parse_args(argv):
     ap = argparse.ArgumentParser(description='score many T1-T5 threshold vectors of the SV phasing decision against a truth set')
     ap.add_argument('workdir', help='Duet work directory (sv_calling/variants.vcf, snp_phasing/*.bam)')
     ap.add_argument('truthset', help='VCF of the phased truth set')
-    ap.add_argument('--grid', required=True, help='JSON: a list of partial vectors, or an object of name -> list of values')
+    ap.add_argument('--grid', default=None, help='JSON: a list of partial vectors, or an object of name -> list of values '
+                                                 '(required without --fit)')
+    ap.add_argument('--fit', choices=SCORES, default=None, metavar='SCORE',
+                    help='fit the vector instead of scoring a grid: coordinate descent over the exact line of every axis, maximising '
+                         'this score (one of %s); with --holdout the score of the train part' % ', '.join(SCORES))
+    ap.add_argument('--start', default=None, help='with --fit: JSON object, the (partial) vector the fit starts from [the defaults]')
+    ap.add_argument('--axes', type=lambda t: [x for x in t.split(',')], default=None,
+                    help='with --fit: comma-separated threshold names to move, in this order [all 14, in field order]')
+    ap.add_argument('--rounds', type=int, default=8, help='with --fit: at most this many passes over the axes [%(default)s]')
+    ap.add_argument('--max_values', type=int, default=0,
+                    help='with --fit: at most this many values of an axis per line, both ends among them; 0 = every distinct value '
+                         '(exact) [%(default)s]')
+    ap.add_argument('--out_vector', default='best.json', help='with --fit: the fitted vector, a JSON object that duet --thresholds '
+                                                              'reads [%(default)s]')
+    ap.add_argument('--trace', default='', help='with --fit: one row per setting, round and axis here (TSV)')
     ap.add_argument('-s', '--sv_min_size', type=_csv(int, '-s'), default=[50],
                     help='minimum SV size; a comma-separated list sweeps it [50]')
     ap.add_argument('-r', '--min_support_read', type=_csv(int, '-r'), default=[2],
@@ -610,6 +792,14 @@ def parse_args(argv):
                                                     'a call or a truth record here (TSV): counts, n_base and the ten scores')
     ap.add_argument('--device', type=int, default=0, help='HIP device index [%(default)s]')
     a = ap.parse_args(argv)
+    if a.fit is not None and a.grid is not None:
+        ap.error('--fit and --grid exclude each other')
+    if a.fit is None and a.grid is None:
+        ap.error('the following arguments are required: --grid')
+    if a.fit is not None and (a.by_contig or a.features):
+        ap.error('--fit writes --out_vector and --trace: --by_contig and --features belong to --grid')
+    if a.fit is not None and (a.rounds < 1 or a.max_values < 0 or a.max_values == 1):
+        ap.error('--rounds is at least 1; --max_values is 0 (every value) or at least 2')
     if a.cluster_max_distance is not None and not a.from_bams:
         ap.error('-c / --cluster_max_distance needs --from_bams: it only acts on candidates clustered from the BAMs')
     if a.holdout is not None and (not a.holdout or not all(a.holdout)):
@@ -628,8 +818,37 @@ def features_path(path, setting):
     return root + tag + ext
 
 
+def main_fit(a):
+    """--fit: the fitted vector -> --out_vector, the trace -> --trace, the best setting and its scores on stdout (one line)."""
+    try:
+        start = load_vector(a.start) if a.start else None
+        _axes(a.axes)
+    except ValueError as e:
+        raise SystemExit('tune: %s' % e)
+    got = fit(a.workdir, a.truthset, a.fit, start, a.axes, a.rounds, a.max_values, a.sv_min_size, a.min_support_read,
+              a.cluster_max_distance if a.from_bams else None, a.from_bams, a.refdist, a.pctsim, a.bed_file, a.skip_phasing,
+              a.include_all_ctgs, a.thread, ctx=engine.default_context(a.device), holdout=a.holdout)
+    if a.trace:
+        lead = tuple(n for n in LEAD if n in got['trace'][0])
+        cols = lead + TRACE + SCORES
+        if a.holdout is not None:
+            cols += tuple('%s_%s' % (part, n) for part in ('train', 'test') for n in SCORES)
+        _write_tsv(a.trace, cols, ([r[n] for n in cols] for r in got['trace']))
+    best = got['best']
+    if best is None:
+        raise SystemExit('tune: no setting has a fit (%s is nan for every vector tried, or the features report a division by zero); '
+                         '%s is not written' % (a.fit, a.out_vector))
+    with open(a.out_vector, 'w') as f:
+        json.dump(dict(zip(NAMES, (float(x) for x in best['vector']))), f, indent=1)
+        f.write('\n')
+    print('fit %s=%r at %s; %s -> %s' % (a.fit, best['objective'], ' '.join('%s=%s' % (n, best['setting'][n]) for n in LEAD if n in best['setting']),
+                                        ' '.join('%s=%r' % (n, best['scores'][n]) for n in best['scores']), a.out_vector))
+
+
 def main(argv):
     a = parse_args(argv)
+    if a.fit is not None:
+        return main_fit(a)
     vecs = load_grid(a.grid)
     ctx = engine.default_context(a.device)
     cs = a.cluster_max_distance if a.from_bams else None

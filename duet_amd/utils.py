@@ -48,7 +48,7 @@ def build_parser():
                     help='number of GPUs for SV phasing: contigs are sharded over them, one process per GPU [%(default)s]')
     ap.add_argument('--thresholds', type=str, default=None,
                     help='JSON object of T1-T5 threshold values (duet_amd/tune.py names; the others keep their defaults) for the '
-                         'SV phasing decision; single-GPU native path only')
+                         'SV phasing decision; one GPU only (the native path, or -b svim-gpu)')
     ap.add_argument('--write_sv_calls', action='store_true',
                     help='with -b svim-gpu, also write the clustered SV calls to OUTPUT/sv_calling/variants.vcf')
     for name, text in _POSITIONALS:

@@ -603,6 +603,30 @@ DUET_API int duet_tune_sweep_strata_host(duet_ctx *ctx, const duet_tune_feature 
                                          uint32_t n_vec, const duet_tune_truth *truth, const duet_tune_strata *strata,
                                          duet_tune_counts *counts);
 
+/* The line of one axis (duet_tune_line.hip): with the other 13 constants fixed, every count of a sweep is a piecewise-constant
+ * function of one constant and changes only where it crosses a value of the feature it is compared with, so one vector per
+ * distinct value plus one sentinel covers every behaviour of the axis.  axis = the field's index in duet_tune_thresholds.  The
+ * compared feature (binary64, the expressions of the sweep's own tree) and who takes part -- eligible candidates only:
+ *   0 svread, class 0 (>=)      1 sv_ratio, 2 avgsc_diff, 3 svread, 4 hap0: class 2 (>=, <=, >=, >=)
+ *   5, 6 sv_ratio, 7 hapread_ratio, 8 avgsc_diff: class 1 with one voting haplotype (<=; 7 also >)
+ *   9, 10, 12 sv_ratio, 11 refread, 13 totsc_ratio: class 1 otherwise (<=; 11 >)
+ * The participants do not depend on *base: a value no candidate is tested against under *base only adds a vector that scores like
+ * its neighbour.  With x_1 < .. < x_D the distinct values, the line is -inf, x_1 .. x_D for the <= and > axes and x_1 .. x_D, +inf
+ * for the >= axes: D + 1 values; out_vec[i] = *base with the axis field replaced by the i-th of them.  max_values = N >= 2 and
+ * D + 1 > N: only the line's entries floor(i * D / (N - 1)), i = 0 .. N - 1, are written (both ends among them); 0: all.
+ * *n_distinct = D, *n_vec = the vectors written.  n_cands == 0 or no participant: one vector, with the sentinel.
+ * _device: feat[C] and out_vec (room for n_cands + 1 vectors) are device memory; base, n_vec and n_distinct host memory.  One host
+ * round trip (D and the status word), then the vectors are written asynchronously on `stream`; the workspace is grown, never
+ * shrunk.  _host: the same with host arrays; synchronises.
+ * DUET_ERR_INVALID: axis > 13, max_values == 1, a NULL array that is needed.  DUET_ERR_DIV_ZERO: a participant's feature is not
+ * finite (deg == 0, or svread + refread == 0 where duet_ef_features_device reports the same); no vector is written. */
+DUET_API int duet_tune_line_device(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *base,
+                                   uint32_t axis, uint32_t max_values, duet_tune_thresholds *out_vec, uint32_t *n_vec,
+                                   uint32_t *n_distinct, void *stream);
+DUET_API int duet_tune_line_host(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *base,
+                                 uint32_t axis, uint32_t max_values, duet_tune_thresholds *out_vec, uint32_t *n_vec,
+                                 uint32_t *n_distinct);
+
 /* ---------------------------------------------------------------------------------------------
  * The collective of the contig-sharded path: candidates shard by contig over the GPUs of one node,
  * one process and one context per GPU, and ONE all-gather of fixed-size record blocks reassembles the call set
