@@ -19,6 +19,8 @@ DUET_ERR_INVALID = -1
 DUET_ERR_DIV_ZERO = -5
 DUET_ERR_TIMEOUT = -6
 MARK_ABSENT = 0xFFFFFFFF
+PC_MAX = 8100                   # DUET_PC_MAX: the reference's PC cap (sv_phasing_fn.py:76,88,201)
+PC_CAP_MAX = (1 << 30) - 3      # the largest cap the *_cap entries take: the tag word saturates pc at 2^30 - 2
 N_KERNELS = 3
 KERNEL_NAMES = ('ef_classify', 'ef_seed_sort', 'ef_finalize')
 
@@ -33,7 +35,8 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_svim_vcf_rows_device', 'duet_svim_vcf_rows_host', 'duet_svim_phased_rows_device', 'duet_svim_phased_rows_host',
            'duet_svim_features_device', 'duet_svim_features_host', 'duet_tune_truth_build_device', 'duet_tune_truth_build_host',
            'duet_tune_strata_build_device', 'duet_tune_strata_build_host', 'duet_tune_sweep_strata_device',
-           'duet_tune_sweep_strata_host', 'duet_tune_line_device', 'duet_tune_line_host')
+           'duet_tune_sweep_strata_host', 'duet_tune_line_device', 'duet_tune_line_host',
+           'duet_ef_features_cap_device', 'duet_ef_features_cap_host', 'duet_svim_features_cap_device', 'duet_svim_features_cap_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -280,6 +283,12 @@ def load():
                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
     lib.duet_tune_line_host.argtypes = lib.duet_tune_line_device.argtypes[:-1]
+    lib.duet_ef_features_cap_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(EfProblem), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    lib.duet_ef_features_cap_host.argtypes = lib.duet_ef_features_cap_device.argtypes[:-1]
+    lib.duet_svim_features_cap_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult),
+                                                  ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+    lib.duet_svim_features_cap_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult),
+                                                ctypes.c_uint32, ctypes.c_void_p]
     _lib = lib
     return lib
 
@@ -500,12 +509,17 @@ class Context(object):
         return got
 
     def svim_features_host(self, marks, read_tag, depth, depth_off, depth_bin, svlen_thres, suppread_thres, max_dist=0.9,
-                           part_gap=1000, part_max=100, normalizer=900.0):
-        """duet_svim_features_host: like svim_host, with the candidates' features (FEATURE_DTYPE[N]) in place of pred / ps."""
+                           part_gap=1000, part_max=100, normalizer=900.0, pc_cap=None):
+        """duet_svim_features_host: like svim_host, with the candidates' features (FEATURE_DTYPE[N]) in place of pred / ps.
+        pc_cap: duet_svim_features_cap_host with that PC cap."""
+        cap = check_pc_cap(pc_cap)
         p, res, out, _, n, keep = self._svim_host_problem(marks, read_tag, depth, depth_off, depth_bin, svlen_thres, suppread_thres,
                                                           max_dist, part_gap, part_max, normalizer, False)
         feat = np.zeros(max(p.marks.n_marks, 1), dtype=FEATURE_DTYPE)
-        rc = self.lib.duet_svim_features_host(self.handle, ctypes.byref(p), ctypes.byref(res), _ptr(feat))
+        if cap is None:
+            rc = self.lib.duet_svim_features_host(self.handle, ctypes.byref(p), ctypes.byref(res), _ptr(feat))
+        else:
+            rc = self.lib.duet_svim_features_cap_host(self.handle, ctypes.byref(p), ctypes.byref(res), cap, _ptr(feat))
         del keep
         if rc:
             self._raise(rc)
@@ -608,11 +622,16 @@ class Context(object):
             self._raise(rc)
         return out
 
-    def features_host(self, soa, svlen_thres, suppread_thres):
-        """duet_ef_features_host -> structured array of FEATURE_DTYPE[C].  Raises ZeroDivisionError where E/F would."""
+    def features_host(self, soa, svlen_thres, suppread_thres, pc_cap=None):
+        """duet_ef_features_host -> structured array of FEATURE_DTYPE[C].  Raises ZeroDivisionError where E/F would.
+        pc_cap: duet_ef_features_cap_host with that PC cap (None: the reference's 8100 through the entry above)."""
+        cap = check_pc_cap(pc_cap)
         prob, keep = problem_from_arrays(soa, svlen_thres, suppread_thres)
         out = np.zeros(soa.n_cands, dtype=FEATURE_DTYPE)
-        rc = self.lib.duet_ef_features_host(self.handle, ctypes.byref(prob), _ptr(out))
+        if cap is None:
+            rc = self.lib.duet_ef_features_host(self.handle, ctypes.byref(prob), _ptr(out))
+        else:
+            rc = self.lib.duet_ef_features_cap_host(self.handle, ctypes.byref(prob), cap, _ptr(out))
         del keep
         if rc:
             self._raise(rc)
@@ -752,17 +771,28 @@ class Context(object):
         if rc:
             self._raise(rc)
 
-    def features_device(self, prob, out_ptr, stream=0):
-        """duet_ef_features_device; raises ZeroDivisionError where E/F would (the records are written all the same)."""
-        rc = self.lib.duet_ef_features_device(self.handle, ctypes.byref(prob), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream))
+    def features_device(self, prob, out_ptr, stream=0, pc_cap=None):
+        """duet_ef_features_device; raises ZeroDivisionError where E/F would (the records are written all the same).
+        pc_cap: duet_ef_features_cap_device with that PC cap."""
+        cap = check_pc_cap(pc_cap)
+        if cap is None:
+            rc = self.lib.duet_ef_features_device(self.handle, ctypes.byref(prob), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream))
+        else:
+            rc = self.lib.duet_ef_features_cap_device(self.handle, ctypes.byref(prob), cap, ctypes.c_void_p(out_ptr),
+                                                      ctypes.c_void_p(stream))
         if rc:
             self._raise(rc)
 
-    def svim_features_device(self, sv_problem, result, out_ptr, stream=0):
-        """duet_svim_features_device -> the candidate count."""
+    def svim_features_device(self, sv_problem, result, out_ptr, stream=0, pc_cap=None):
+        """duet_svim_features_device (pc_cap: duet_svim_features_cap_device with that PC cap) -> the candidate count."""
+        cap = check_pc_cap(pc_cap)
         n = ctypes.c_uint32(0)
-        rc = self.lib.duet_svim_features_device(self.handle, ctypes.byref(sv_problem), ctypes.byref(result), ctypes.c_void_p(out_ptr),
-                                                ctypes.byref(n), ctypes.c_void_p(stream))
+        if cap is None:
+            rc = self.lib.duet_svim_features_device(self.handle, ctypes.byref(sv_problem), ctypes.byref(result), ctypes.c_void_p(out_ptr),
+                                                    ctypes.byref(n), ctypes.c_void_p(stream))
+        else:
+            rc = self.lib.duet_svim_features_cap_device(self.handle, ctypes.byref(sv_problem), ctypes.byref(result), cap,
+                                                        ctypes.c_void_p(out_ptr), ctypes.byref(n), ctypes.c_void_p(stream))
         if rc:
             self._raise(rc)
         return n.value
@@ -813,6 +843,15 @@ class Context(object):
         if n < 0:
             self._raise(n)
         return out[:min(n, cap)].copy()
+
+
+def check_pc_cap(pc_cap):
+    """A PC cap argument: None (the entry without a cap), or an integer in 0 .. PC_CAP_MAX -> int; else ValueError."""
+    if pc_cap is None:
+        return None
+    if isinstance(pc_cap, bool) or not isinstance(pc_cap, (int, np.integer)) or not 0 <= int(pc_cap) <= PC_CAP_MAX:
+        raise ValueError('pc_cap: an integer in 0 .. 2^30 - 3 (%d), not %r' % (PC_CAP_MAX, pc_cap))
+    return int(pc_cap)
 
 
 def clamp_u32(v):

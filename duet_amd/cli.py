@@ -25,7 +25,7 @@ def pipeline(a):
             (stages.snp_phasing, (a.OUTPUT, a.REFERENCE, a.BAM, a.thread)),
             (sv_phasing_from_bams, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs,
                                     a.cluster_max_distance, a.device, a.gpus, a.write_sv_calls,
-                                    getattr(a, 'threshold_vector', None))),
+                                    getattr(a, 'threshold_vector', None), getattr(a, 'pc_cap_value', None))),
         )
     return (
         (stages.snp_calling, (a.OUTPUT, a.REFERENCE, a.BAM, a.min_allele_frequency, a.thread, a.include_all_ctgs)),
@@ -33,13 +33,13 @@ def pipeline(a):
                              a.min_support_read)),
         (stages.snp_phasing, (a.OUTPUT, a.REFERENCE, a.BAM, a.thread)),
         (sv_phasing, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs, a.device, a.gpus,
-                      a.threshold_vector)),
+                      a.threshold_vector, a.pc_cap_value)),
     )
 
 
 def main(argv):
     a = parse_args(argv)
-    a.threshold_vector = None
+    a.threshold_vector, a.pc_cap_value = None, None
     if a.write_sv_calls and a.sv_caller != 'svim-gpu':
         # (additive: the clustered calls exist only in the svim-gpu mode; every other caller writes sv_calling/variants.vcf itself)
         raise SystemExit('duet: --write_sv_calls works with -b svim-gpu only')
@@ -50,7 +50,13 @@ def main(argv):
             raise SystemExit('duet: --thresholds works on the single-GPU path with an external SV caller only '
                              '(not with --gpus > 1 or -b svim-gpu)')
         from duet_amd import tune
-        a.threshold_vector = tune.load_vector(a.thresholds)
+        a.threshold_vector, a.pc_cap_value = tune.load_vector(a.thresholds, with_cap=True)
+    if a.pc_cap is not None:
+        # (additive: the PC cap of the vote, sv_phasing_fn.py:76,88,201 -- the flag wins over a pc_cap key of the thresholds file;
+        # without --thresholds the vector is the defaults)
+        if a.gpus > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise SystemExit('duet: --pc_cap works on the single-GPU path only (not with --gpus > 1)')
+        a.pc_cap_value = a.pc_cap
     check_envs(a.REFERENCE, a.BAM)
     os.makedirs(a.OUTPUT, exist_ok=True)
     set_logging(a.OUTPUT)

@@ -3624,10 +3624,12 @@ int duet_svim_phase_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_
 // The fused pipeline up to the adapted E/F problem, then the features of that problem (duet_tune.hip) instead of its decisions: the
 // host-planned branch of duet_svim_phase_device with duet_ef_features_device in place of duet_ef_run_device.  (That entry stays
 // as it is -- its asynchronous branch has no counterpart here -- so the set-up in front of the clustering is restated.)
-int duet_svim_features_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat,
-                              uint32_t *n_cands_host, void *stream_)
+// (pc_cap == nullptr: the reference's cap through duet_ef_features_device; else duet_ef_features_cap_device with *pc_cap)
+static int svim_features_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat,
+                                uint32_t *n_cands_host, void *stream_, const uint32_t *pc_cap)
 {
     if (!ctx) return duet_fail(nullptr, DUET_ERR_INVALID, "null context");
+    if (pc_cap && *pc_cap > (1u << 30) - 3u) return duet_fail(ctx, DUET_ERR_INVALID, "pc_cap is above 2^30 - 3 (the tag word saturates pc at 2^30 - 2)");
     if (!pr || !res || !out_feat || !n_cands_host) return duet_fail(ctx, DUET_ERR_INVALID, "null argument");
     if (!pr->depth_off || pr->depth_bin == 0 || pr->n_contigs == 0 || pr->n_contigs > 65535)
         return duet_fail(ctx, DUET_ERR_INVALID, "bad depth / contig description");
@@ -3678,12 +3680,26 @@ int duet_svim_features_device(duet_ctx *ctx, const duet_svim_problem *pr, const 
     ef.cand_pos = res->cand_pos; ef.cand_svlen = res->cand_span; ef.cand_svread = sv.svread; ef.cand_refread = sv.refread;
     ef.cand_gt_ok = sv.gt; ef.cand_off = res->cand_off; ef.mark_read = sv.mark_out;
     ef.svlen_thres = pr->svlen_thres; ef.suppread_thres = pr->suppread_thres;
-    return duet_ef_features_device(ctx, &ef, out_feat, st);
+    return pc_cap ? duet_ef_features_cap_device(ctx, &ef, *pc_cap, out_feat, st) : duet_ef_features_device(ctx, &ef, out_feat, st);
 }
 
-int duet_svim_features_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat)
+int duet_svim_features_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat,
+                              uint32_t *n_cands_host, void *stream_)
+{
+    return svim_features_device(ctx, pr, res, out_feat, n_cands_host, stream_, nullptr);
+}
+
+int duet_svim_features_cap_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, uint32_t pc_cap,
+                                  duet_tune_feature *out_feat, uint32_t *n_cands_host, void *stream_)
+{
+    return svim_features_device(ctx, pr, res, out_feat, n_cands_host, stream_, &pc_cap);
+}
+
+static int svim_features_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat,
+                              const uint32_t *pc_cap)
 {
     if (!ctx) return duet_fail(nullptr, DUET_ERR_INVALID, "null context");
+    if (pc_cap && *pc_cap > (1u << 30) - 3u) return duet_fail(ctx, DUET_ERR_INVALID, "pc_cap is above 2^30 - 3 (the tag word saturates pc at 2^30 - 2)");
     if (!pr || !res || !res->n_cands || !out_feat) return duet_fail(ctx, DUET_ERR_INVALID, "null argument");
     if (!pr->depth_off || pr->n_contigs == 0) return duet_fail(ctx, DUET_ERR_INVALID, "bad depth / contig description");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3732,7 +3748,7 @@ int duet_svim_features_host(duet_ctx *ctx, const duet_svim_problem *pr, const du
     r.cand_span = (uint32_t *)ctx->cl_out[5].ptr;
     r.n_cands = (uint32_t *)((char *)ctx->cl_out[1].ptr + ((size_t)M + 1) * 4);        // spare word after cand_off
     uint32_t n = 0;
-    rc = duet_svim_features_device(ctx, &d, &r, (duet_tune_feature *)bf.ptr, &n, s);
+    rc = svim_features_device(ctx, &d, &r, (duet_tune_feature *)bf.ptr, &n, s, pc_cap);
     if (rc && rc != DUET_ERR_DIV_ZERO) return rc;
     const std::string msg = ctx->err;
     *res->n_cands = n;
@@ -3745,6 +3761,17 @@ int duet_svim_features_host(duet_ctx *ctx, const duet_svim_problem *pr, const du
     HIP_TRY(ctx, hipMemcpy(out_feat, bf.ptr, (size_t)n * sizeof(duet_tune_feature), hipMemcpyDeviceToHost));
     if (rc) ctx->err = msg;
     return rc;
+}
+
+int duet_svim_features_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat)
+{
+    return svim_features_host(ctx, pr, res, out_feat, nullptr);
+}
+
+int duet_svim_features_cap_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, uint32_t pc_cap,
+                                duet_tune_feature *out_feat)
+{
+    return svim_features_host(ctx, pr, res, out_feat, &pc_cap);
 }
 
 }  // extern "C"

@@ -19,195 +19,23 @@
 
 namespace {
 
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-constexpr uint64_t kUntagged = ~0ull;
-constexpr int kStage = 1024;                  // tune_features: voter words staged in LDS per pass over a candidate's marks (8 KiB)
 constexpr int kVecPerBlock = 32;              // tune_decide: vectors applied to one tile of candidates
 constexpr size_t kWsBudget = (size_t)256 << 20;   // sweep workspace per batch of vectors
 
 int fail(duet_ctx *ctx, int code, const char *msg) { return duet_fail(ctx, code, msg); }
 
-// the tag word's fields (include/duet_ef.h: DUET_TAG)
-__device__ __forceinline__ uint32_t tg_ps(uint64_t t) { return (uint32_t)t; }
-__device__ __forceinline__ uint32_t tg_pc(uint64_t t) { return (uint32_t)(t >> 32) & 0x3FFFFFFFu; }
-__device__ __forceinline__ uint32_t tg_hap(uint64_t t) { return (uint32_t)(t >> 62); }
+#include "duet_tune_feat.hip.h"            // FeatArgs, features_body(): the feature record (shared with duet_tune_cap.hip)
 
-__device__ __forceinline__ uint32_t lower_bound(const uint32_t *a, uint32_t n, uint32_t key)
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// sv_phasing_fn.py:107-111 -- the nearest seed, ties to the larger one (n >= 1)
-__device__ __forceinline__ uint32_t nearest_seed(const uint32_t *a, uint32_t n, uint32_t pos)
-{
-    const uint32_t i = lower_bound(a, n, pos);
-    const uint32_t lo = i > 0 ? i - 1 : 0;
-    const uint32_t hi = i < n - 1 ? i : n - 1;
-    const int64_t dl = llabs((int64_t)pos - (int64_t)a[lo]);
-    const int64_t dh = llabs((int64_t)pos - (int64_t)a[hi]);
-    return dl < dh ? a[lo] : a[hi];
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_max64(uint64_t v)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t w = __shfl_xor(v, o);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-struct FeatArgs {
-    uint32_t C, K, n_reads, svlen_thres, suppread_thres;
-    const uint64_t *read_tag;
-    const uint32_t *cand_pos, *cand_svlen, *cand_svread, *cand_refread, *cand_off, *mark_read;
-    const uint8_t *cand_gt_ok;
-    const uint32_t *ctg_off, *n_one, *onebuf;     // the E/F workspace: contig offsets, seed counts, ascending seed arrays
-    duet_tune_feature *out;
+// the seed source of tune_features: the reference's cap, and what the E/F kernels of the same context left in their workspace
+struct EfSeeds {
+    static constexpr bool kSeedPass = false;
+    __device__ __forceinline__ uint32_t cap() const { return DUET_PC_MAX; }
+    __device__ __forceinline__ uint32_t count(const FeatArgs &a, uint32_t k) const { return a.n_one[k]; }
+    __device__ __forceinline__ const uint32_t *seeds(const FeatArgs &a, uint32_t k) const { return a.onebuf + a.ctg_off[k] + k + 1; }
+    __device__ __forceinline__ void div_zero() const {}          // (E/F's own status word reports it: duet_ef_check)
 };
 
-// the tag of mark m, kUntagged for a mark whose read has no tag
-__device__ __forceinline__ uint64_t mark_tag(const FeatArgs &a, uint32_t m)
-{
-    const uint32_t r = a.mark_read[m];
-    return (r == kEmpty || r >= a.n_reads) ? kUntagged : a.read_tag[r];
-}
-__device__ __forceinline__ bool is_voter(uint64_t t) { return t != kUntagged && tg_pc(t) <= DUET_PC_MAX; }
-
-// One candidate per workgroup of one wavefront: every walk over the marks goes 64 at a time, so a candidate of any degree and any
-// number of phase sets takes the same code.  The multi-PS winner (:85-105): among voters whose PS is a seed, the PS with the most
-// voters, ties to the one seen first -- i.e. the largest (count, -first index) over the first occurrences.
-__global__ __launch_bounds__(64) void tune_features(const FeatArgs a)
-{
-    __shared__ uint64_t s_w[kStage];
-    const uint32_t lane = threadIdx.x;
-    for (uint32_t c = blockIdx.x; c < a.C; c += gridDim.x) {
-        const uint32_t b = a.cand_off[c], e = a.cand_off[c + 1];
-        const uint32_t svread = a.cand_svread[c], refread = a.cand_refread[c];
-        duet_tune_feature f;
-        memset(&f, 0, sizeof(f));
-        f.deg = e - b;
-        f.svread = svread;
-        f.refread = refread;
-        const bool kept = a.cand_svlen[c] >= a.svlen_thres && svread >= a.suppread_thres && a.cand_gt_ok[c] != 0;
-        f.kept = kept ? 1 : 0;
-        if (kept) {
-            // PS-class: distinct PS among ALL tagged marks (no PC test, :192-194)
-            uint32_t p0 = 0;
-            bool have = false, multi = false;
-            for (uint32_t m0 = b; m0 < e && !multi; m0 += 64) {
-                const uint32_t m = m0 + lane;
-                const uint64_t t = m < e ? mark_tag(a, m) : kUntagged;
-                const bool tagged = t != kUntagged;
-                const uint64_t bal = __ballot(tagged);
-                if (!have && bal) {
-                    p0 = __shfl(tg_ps(t), __ffsll((unsigned long long)bal) - 1);
-                    have = true;
-                }
-                if (have) multi = __any(tagged && tg_ps(t) != p0);
-            }
-            f.cls = multi ? 2 : (have ? 1 : 0);
-            // the contig and its seed set
-            uint32_t lo = 0, hi = a.K;
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (a.ctg_off[mid] <= c) lo = mid; else hi = mid;
-            }
-            const uint32_t n_seed = a.n_one[lo];
-            const uint32_t *seeds = a.onebuf + a.ctg_off[lo] + lo + 1;
-            if (n_seed) {
-                f.eligible = 1;
-                uint32_t hap1 = 0, hap2 = 0, allhap = 0, ps = 0;
-                uint64_t t1 = 0, t2 = 0;
-                if (f.cls == 1) {                                   // :74-84
-                    for (uint32_t m0 = b; m0 < e; m0 += 64) {
-                        const uint32_t m = m0 + lane;
-                        const uint64_t t = m < e ? mark_tag(a, m) : kUntagged;
-                        if (is_voter(t)) {
-                            if (tg_hap(t) == 1) { ++hap1; t1 += tg_pc(t); }
-                            else if (tg_hap(t) == 2) { ++hap2; t2 += tg_pc(t); }
-                        }
-                    }
-                    hap1 = wave_sum(hap1); hap2 = wave_sum(hap2);
-                    t1 = wave_sum64(t1); t2 = wave_sum64(t2);
-                    allhap = hap1 + hap2;
-                    ps = p0;                                        // every voter carries the one PS
-                } else if (f.cls == 2) {                            // :85-105
-                    uint64_t best = 0;                              // (count << 32) | ~(index of the first occurrence)
-                    for (uint32_t i0 = b; i0 < e; i0 += 64) {
-                        const uint32_t i = i0 + lane;
-                        const uint64_t t = i < e ? mark_tag(a, i) : kUntagged;
-                        const bool voter = is_voter(t);
-                        allhap += voter ? 1u : 0u;
-                        const uint64_t my = voter ? ((1ull << 32) | tg_ps(t)) : 0ull;
-                        const uint32_t ni = n_seed;
-                        bool cand = false;
-                        if (voter) {
-                            const uint32_t at = lower_bound(seeds, ni, tg_ps(t));
-                            cand = at < ni && seeds[at] == tg_ps(t);     // :91
-                        }
-                        if (!__any(cand)) continue;
-                        uint32_t n = 0;
-                        bool first = cand;
-                        for (uint32_t j0 = b; j0 < e; j0 += kStage) {
-                            const uint32_t cnt = e - j0 < (uint32_t)kStage ? e - j0 : (uint32_t)kStage;
-                            __syncthreads();
-                            for (uint32_t jj = lane; jj < cnt; jj += 64) {
-                                const uint64_t u = mark_tag(a, j0 + jj);
-                                s_w[jj] = is_voter(u) ? ((1ull << 32) | tg_ps(u)) : 0ull;
-                            }
-                            __syncthreads();
-                            if (cand)
-                                for (uint32_t jj = 0; jj < cnt; ++jj)
-                                    if (s_w[jj] == my) {
-                                        ++n;
-                                        if (j0 + jj < i) first = false;
-                                    }
-                        }
-                        const uint64_t key = (cand && first) ? (((uint64_t)n << 32) | (uint64_t)(~(i - b))) : 0ull;
-                        const uint64_t w = wave_max64(key);
-                        best = w > best ? w : best;
-                    }
-                    allhap = wave_sum(allhap);
-                    if (best) {
-                        const uint32_t at = b + ~(uint32_t)best;
-                        const uint32_t win = tg_ps(mark_tag(a, at));
-                        for (uint32_t m0 = b; m0 < e; m0 += 64) {
-                            const uint32_t m = m0 + lane;
-                            const uint64_t t = m < e ? mark_tag(a, m) : kUntagged;
-                            if (is_voter(t) && tg_ps(t) == win) {
-                                if (tg_hap(t) == 1) { ++hap1; t1 += tg_pc(t); }
-                                else if (tg_hap(t) == 2) { ++hap2; t2 += tg_pc(t); }
-                            }
-                        }
-                        hap1 = wave_sum(hap1); hap2 = wave_sum(hap2);
-                        t1 = wave_sum64(t1); t2 = wave_sum64(t2);
-                        f.hap0 = allhap - hap1 - hap2;              // only with a winner (:105)
-                        ps = win;
-                    }
-                }
-                if (f.cls == 0 || (hap1 == 0 && hap2 == 0)) ps = nearest_seed(seeds, n_seed, a.cand_pos[c]);   // :106-111
-                f.hap1 = hap1; f.hap2 = hap2; f.allhap = allhap; f.t1 = t1; f.t2 = t2; f.ps = ps;
-            }
-        }
-        if (lane == 0) a.out[c] = f;
-    }
-}
+__global__ __launch_bounds__(64) void tune_features(const FeatArgs a) { features_body(a, EfSeeds{}); }
 
 #include "duet_tune_derive.hip.h"          // Derived, derive(): what the tree compares (shared with duet_tune_line.hip)
 

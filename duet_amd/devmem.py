@@ -200,26 +200,27 @@ class DeviceSvim(DeviceCluster):
         self.n_found = n.value if wait else None
         return stream
 
-    def run_features(self, ctx, feat_ptr, stream=None):
+    def run_features(self, ctx, feat_ptr, stream=None, pc_cap=None):
         """duet_svim_features_device: clusters, adapts and writes the candidates' features to feat_ptr (room for M records);
-        the cluster result stays in self.result.  -> the candidate count.  Raises ZeroDivisionError where E/F would."""
+        the cluster result stays in self.result.  -> the candidate count.  Raises ZeroDivisionError where E/F would.
+        pc_cap: the features under that PC cap (duet_svim_features_cap_device)."""
         if stream is None:
             stream = self.torch.cuda.current_stream(self.device).cuda_stream
         self.n_found = None
-        self.n_found = ctx.svim_features_device(self.sv_problem, self.result, feat_ptr, stream)
+        self.n_found = ctx.svim_features_device(self.sv_problem, self.result, feat_ptr, stream, pc_cap=pc_cap)
         return self.n_found
 
-    def run_thresholds(self, ctx, thresholds, stream=None):
+    def run_thresholds(self, ctx, thresholds, stream=None, pc_cap=None):
         """run_fused with the decision's 14 constants taken from `thresholds` (float64[14]): the candidates' features
-        (duet_svim_features_device), then the one vector applied to them (duet_tune_sweep_device) into out_pred / out_ps.
-        Raises ZeroDivisionError where the fused run would."""
+        (duet_svim_features_device; pc_cap: under that PC cap), then the one vector applied to them (duet_tune_sweep_device) into
+        out_pred / out_ps.  Raises ZeroDivisionError where the fused run would."""
         torch = self.torch
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         vec = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(len(_lib.TUNE_NAMES))
         feat = torch.zeros(max(self.M, 1) * _lib.FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
         d_vec = torch.from_numpy(vec.copy()).to(self.device)
-        N = self.run_features(ctx, feat.data_ptr(), stream)
+        N = self.run_features(ctx, feat.data_ptr(), stream, pc_cap=pc_cap)
         ctx.apply_device(feat.data_ptr(), N, d_vec.data_ptr(), self.out_pred.data_ptr(), self.out_ps.data_ptr(), stream)
         torch.cuda.current_stream(self.device).synchronize()       # (feat and d_vec are released when this returns)
         return stream

@@ -10,8 +10,9 @@ fields ...) and the Python path then takes over, so the observable behaviour is 
 Set DUET_NATIVE_INGEST=0 to force the Python path; DUET_DEVICE_ROWS=0 keeps the native path but formats the rows on
 the host instead of on the device.
 
-Three additive keyword arguments (upstream's five positionals are unchanged): `thresholds` = a vector of the decision's
-T1-T5 constants (duet_amd/tune.py; native single-GPU path only), `device` = HIP device index of a
+Four additive keyword arguments (upstream's five positionals are unchanged): `thresholds` = a vector of the decision's
+T1-T5 constants (duet_amd/tune.py; native single-GPU path only), `pc_cap` = the PC cap of the vote in place of 8100 (the same
+path; without `thresholds` the vector is the defaults), `device` = HIP device index of a
 single-GPU run, `gpus` = N > 1 shards the contigs over N GPUs of the node, one process per GPU
 (duet_amd/multi.py: longest-processing-time-first on mark counts, the three kernels per rank, ONE all-gather of the
 (pred, ps) records over RCCL, rank 0 writes phased_sv.vcf).
@@ -91,13 +92,13 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
     return True
 
 
-def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, vec):
-    """The native path with the decision's constants taken from `vec` (duet_amd/tune.py): ingest, the feature export, a sweep
-    of one vector that keeps its (pred, ps), the rows."""
+def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, vec, pc_cap=None):
+    """The native path with the decision's constants taken from `vec` (duet_amd/tune.py): ingest, the feature export (pc_cap:
+    under that PC cap, duet_ef_features_cap_host), a sweep of one vector that keeps its (pred, ps), the rows."""
     from duet_amd import tune
     ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf)
     if ing is None:
-        raise RuntimeError('--thresholds needs the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
+        raise RuntimeError('--thresholds / --pc_cap need the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
     try:
         write_header(ing, include_all_ctgs, out_vcf)
         log_ingest(ing, chrom_list)
@@ -105,9 +106,11 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
         logging.info('calculate read weight statistics')
         logging.info('predict SV haplotypes in the callset')
         logging.info('  thresholds: ' + ', '.join('%s=%r' % (n, float(v)) for n, v in zip(tune.NAMES, vec)))
+        if pc_cap is not None:
+            logging.info('  pc_cap: %d' % pc_cap)
         body = b''
         if ing.soa.n_cands:
-            feat = ctx.features_host(ing.soa, svlen_thres, suppread_thres)
+            feat = ctx.features_host(ing.soa, svlen_thres, suppread_thres, pc_cap=pc_cap)
             pred, ps = tune.apply(dict(feat=feat), vec, ctx=ctx)
             body = ing.emit_rows(pred, ps)
         logging.info('write phased callset into .vcf file')
@@ -117,7 +120,15 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
         out.write(body)
 
 
-def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, device=0, gpus=1, thresholds=None):
+def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, device=0, gpus=1, thresholds=None, pc_cap=None):
+    if pc_cap is not None:
+        # (additive: the PC cap of the vote -- refused before anything is opened; the route is that of `thresholds`)
+        from duet_amd import _lib, tune
+        pc_cap = _lib.check_pc_cap(pc_cap)
+        if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise ValueError('pc_cap: single-GPU path only')
+        if thresholds is None:
+            thresholds = tune.vector()
     logging.info('%s SV PHASING STARTED %s' % (_BAR, _BAR))
     t0 = time.time()
     caller_vcf = home + '/sv_calling/variants.vcf'
@@ -129,7 +140,7 @@ def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, devi
         if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
             raise ValueError('thresholds: single-GPU path only')
         _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf,
-                           engine.default_context(int(device)), thresholds)
+                           engine.default_context(int(device)), thresholds, pc_cap)
         done = True
     # (DUET_FORCE_RANKS=1: the one-process-per-GPU path even with one GPU -- rank 0 of 1 over RCCL; tests use it to take the
     # collective through the real backend on a one-GPU box)

@@ -17,20 +17,21 @@ from duet_amd.native import NativeIngest
 from duet_amd.read_file import init_chrom_list
 
 
-def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None):
+def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_cap=None):
     """-> compute(extracted arrays, svlen_thres, suppread_thres, max_dist, depth_bin) -> dict of result arrays, on ctx's GPU:
     stage A0 -> adapter -> step E/F in one device pipeline (duet_svim_phase_device).  chrom_texts (CHROM text per contig): the
     extracted arrays carry the marks' read names, and the result also holds `calls`, the rows of sv_calling/variants.vcf formatted
     on the same resident arrays (duet_svim_vcf_rows_device).  row_texts (CHROM text per contig): the result also holds `rows` /
     `n_rows`, the data rows of phased_sv.vcf sorted and formatted on the resident arrays (duet_svim_phased_rows_device).
     thresholds (float64[14], --thresholds): the decision is made with this vector -- the candidates' features
-    (duet_svim_features_device) and one vector applied to them (duet_tune_sweep_device) in place of the fused run's E/F."""
+    (duet_svim_features_device; pc_cap: under that PC cap, duet_svim_features_cap_device) and one vector applied to them
+    (duet_tune_sweep_device) in place of the fused run's E/F."""
     def compute(got, svlen_thres, suppread_thres, max_dist, depth_bin):
         from duet_amd.devmem import DeviceSvim
         ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, svlen_thres, suppread_thres,
                         max_dist=max_dist, device='cuda:%d' % ctx.device_id)
         if thresholds is not None:
-            ds.run_thresholds(ctx, thresholds)
+            ds.run_thresholds(ctx, thresholds, pc_cap=pc_cap)
         else:
             ds.run_fused(ctx)
             ctx.check(ds.torch.cuda.current_stream(ds.device).cuda_stream)
@@ -426,7 +427,7 @@ def rank_main(argv):
 
 
 def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, cluster_max_distance=0.9, device=0,
-                         gpus=1, write_sv_calls=False, thresholds=None):
+                         gpus=1, write_sv_calls=False, thresholds=None, pc_cap=None):
     """`duet ... -b svim-gpu -c <max distance>`: SV calling (signatures + clustering, what `-b svim` delegates to the
     external `svim alignment ... --cluster_max_distance c`, sv_calling.py:13-15) AND SV phasing on the GPU, from the
     haplotagged BAMs of <home>/snp_phasing -> <home>/phased_sv.vcf.  The clustering half is this repository's own rule
@@ -434,7 +435,16 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
     write_sv_calls (--write_sv_calls): also every clustered candidate -> <home>/sv_calling/variants.vcf (DESIGN.md section 15);
     the marks' read names are extracted and checked first, and no file is written before they pass.
     thresholds (--thresholds): a vector of the decision's 14 constants (duet_amd/tune.py: vector) in place of the built-in ones;
-    single-GPU path only."""
+    single-GPU path only.
+    pc_cap (--pc_cap): the PC cap of the vote in place of 8100, on the same route (without thresholds the vector is the defaults);
+    the clustered calls of --write_sv_calls do not depend on it."""
+    if pc_cap is not None:
+        from duet_amd import _lib, tune
+        pc_cap = _lib.check_pc_cap(pc_cap)
+        if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise ValueError('pc_cap: single-GPU path only')
+        if thresholds is None:
+            thresholds = tune.vector()
     if thresholds is not None and (int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1'):
         raise ValueError('thresholds: single-GPU path only')
     bar = '*' * 25
@@ -449,6 +459,8 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
     if thresholds is not None:
         from duet_amd import tune
         logging.info('  thresholds: ' + ', '.join('%s=%r' % (n, float(v)) for n, v in zip(tune.NAMES, thresholds)))
+    if pc_cap is not None:
+        logging.info('  pc_cap: %d' % pc_cap)
     logging.info('extract SNP and SV signatures from the haplotagged alignments')
     if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':       # (see sv_phasing.py)
         from duet_amd import launch
@@ -478,7 +490,7 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
     def compute(*args):
         texts = spelled_contigs(home, chroms)
         return device_compute(ctx if ctx is not None else engine.default_context(int(device)), texts if write_sv_calls else None,
-                              row_texts=texts, thresholds=thresholds)(*args)
+                              row_texts=texts, thresholds=thresholds, pc_cap=pc_cap)(*args)
     res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
                           min_sv_size=max(int(svlen_thres), 1), names=bool(write_sv_calls), compute=compute)
     # the data rows come sorted and formatted from the device; without a single mark nothing ran and there are none

@@ -7,7 +7,7 @@
                                            the same for every setting of -s, -r and (svim-gpu mode, from the BAMs) -c
     strata_by_contig(), strata_holdout(texts)   strata (sets of CHROM texts) for sweep_settings(holdout=.., by_contig=..): every
                                            vector scored per stratum in one pass over the candidates (duet_tune_sweep_strata_device)
-    python -m duet_amd.tune WORKDIR TRUTH.vcf --grid GRID.json [-s 30,50 -r 2,3 [--from_bams -c 0.5,0.9]]
+    python -m duet_amd.tune WORKDIR TRUTH.vcf --grid GRID.json [-s 30,50 -r 2,3 [--from_bams -c 0.5,0.9]] [--pc_cap 4000,8100]
                                            [--holdout chr20,chr21 --by_contig FILE.tsv] [...]
     fit(home, truth_vcf, objective, ...)   coordinate descent over exact lines: per axis one vector per distinct value of the feature
                                            the axis is compared with (duet_tune_line_device), scored by the same sweep
@@ -426,6 +426,22 @@ def _strata_rows(rows, contig_rows, vecs, strata_counts, passes, lead):
                     contig_rows.append(row)
 
 
+def _cap_list(pc_cap):
+    """pc_cap of sweep_settings / fit: None -> [None] (the entry without a cap), else a non-empty list of caps in 0 .. 2^30 - 3."""
+    if pc_cap is None:
+        return [None]
+    vals = [pc_cap] if isinstance(pc_cap, (int, np.integer)) else list(pc_cap)
+    if not vals or any(v is None for v in vals):
+        raise ValueError('pc_cap: a non-empty list of integers in 0 .. 2^30 - 3, not %r' % (pc_cap,))
+    return [_lib.check_pc_cap(v) for v in vals]
+
+
+def _lead(c_=None, s_=None, r_=None, p_=None):
+    """The setting columns in front of a row, in LEAD's order."""
+    vals = dict(pc_cap=p_, svlen_thres=s_, suppread_thres=r_, cluster_max_distance=c_)
+    return {n: vals[n] for n in LEAD if vals[n] is not None}
+
+
 def _int_list(name, v):
     vals = [v] if isinstance(v, (int, np.integer)) else list(v)
     if not vals or any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 0 for x in vals):
@@ -435,7 +451,7 @@ def _int_list(name, v):
 
 def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,), cluster_max_distance=None, from_bams=False,
                    refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False, thread=4, ctx=None, on_features=None,
-                   holdout=None, by_contig=None, _each=None):
+                   holdout=None, by_contig=None, _each=None, pc_cap=None):
     """sweep() for every setting of -s (svlen_thres), -r (suppread_thres) and, with from_bams, -c (cluster_max_distance; default
     (0.9,)): -> list of rows, settings outermost in the order c, s, r, each row a dict of svlen_thres, suppread_thres
     [, cluster_max_distance], the 14 thresholds and the ten numbers.  from_bams: the candidates come from <home>/snp_phasing/*.bam
@@ -452,9 +468,14 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     not change.
     _each (fit): called per setting as _each(setting, dt, n_cands, passes) in place of the sweeps, with the features, the plain truth
     arrays and every pass's own truth arrays and strata built and resident in dt (a DeviceTune); dt None: the setting's features
-    report a division by zero.  The rows returned are then nan."""
+    report a division by zero.  The rows returned are then nan.
+    pc_cap: a list of PC caps (a read with a PC tag above the cap does not vote; the reference's is 8100) -- the innermost setting,
+    after c, s, r; every row then gains a leading pc_cap column.  A cap costs the features call (duet_ef_features_cap_device,
+    duet_svim_features_cap_device), the truth build(s) and the sweep(s) on the resident problem: no ingest, no upload and, without
+    from_bams, no host work.  None: the features of the entries without a cap, and rows without the column."""
     vecs = grid if isinstance(grid, np.ndarray) else expand_grid(grid)
     ss, rs = _int_list('svlen_thres', svlen_thres), _int_list('suppread_thres', suppread_thres)
+    ps = _cap_list(pc_cap)
     if cluster_max_distance is not None and not from_bams:
         raise ValueError('cluster_max_distance only acts on candidates clustered from the BAMs: it needs from_bams')
     ctx = ctx or engine.default_context()
@@ -465,7 +486,7 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
         if not cs:
             raise ValueError('cluster_max_distance: an empty list')
         return _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features,
-                           passes, by_contig, _each)
+                           passes, by_contig, _each, ps)
     from duet_amd.devmem import DeviceProblem, DeviceTune
     soa, txt = _candidates(home, ss[0], rs[0], include_all_ctgs, thread)
     cands = dict(pos=soa.cand_pos, svlen=soa.cand_svlen, **txt)
@@ -478,36 +499,35 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     resident = {kind: dt.set_strata(chrom_strata(cands['chrom'], st), b['uid_off'], b['base_uid'], own_truth=_each is not None)
                 for kind, st, b in passes}
     out = []
-    for s_ in ss:
-        for r_ in rs:
-            lead = dict(svlen_thres=s_, suppread_thres=r_)
-            counts, strata_counts = None, {}
-            try:
-                if C:
-                    dp.problem.svlen_thres, dp.problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
-                    ctx.features_device(dp.problem, dt.feat.data_ptr(), dt.stream())
-                dt.build(ctx, C)
+    for s_, r_, p_ in itertools.product(ss, rs, ps):
+        lead = _lead(None, s_, r_, p_)
+        counts, strata_counts = None, {}
+        try:
+            if C:
+                dp.problem.svlen_thres, dp.problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
+                ctx.features_device(dp.problem, dt.feat.data_ptr(), dt.stream(), pc_cap=p_)
+            dt.build(ctx, C)
+            if _each is None:
+                counts = dt.sweep(ctx, C)
+            for kind, p in resident.items():
+                dt.build_strata(ctx, C, strata=p)
                 if _each is None:
-                    counts = dt.sweep(ctx, C)
-                for kind, p in resident.items():
-                    dt.build_strata(ctx, C, strata=p)
-                    if _each is None:
-                        strata_counts[kind] = dt.sweep_strata(ctx, C, p)
-                if _each is not None:
-                    _each(lead, dt, C, resident)
-            except ZeroDivisionError:
-                if _each is not None:
-                    _each(lead, None, 0, resident)
-            if on_features is not None:
-                on_features(lead, dict(cands, feat=dt.features_host(C)))
-            rows = _rows(vecs, counts, base['n_base'], lead)
-            _strata_rows(rows, by_contig, vecs, strata_counts, passes, lead)
-            out.extend(rows)
+                    strata_counts[kind] = dt.sweep_strata(ctx, C, p)
+            if _each is not None:
+                _each(lead, dt, C, resident)
+        except ZeroDivisionError:
+            if _each is not None:
+                _each(lead, None, 0, resident)
+        if on_features is not None:
+            on_features(lead, dict(cands, feat=dt.features_host(C)))
+        rows = _rows(vecs, counts, base['n_base'], lead)
+        _strata_rows(rows, by_contig, vecs, strata_counts, passes, lead)
+        out.extend(rows)
     return out
 
 
 def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features,
-                passes=(), by_contig=None, _each=None):
+                passes=(), by_contig=None, _each=None, ps=(None,)):
     from duet_amd import svim_mode
     from duet_amd.devmem import DeviceSvim, DeviceTune
     from duet_amd.native import NativeIngest
@@ -530,46 +550,45 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
         resident = {kind: dt.set_strata(chrom_strata(texts, st), b['uid_off'], b['base_uid'], own_truth=_each is not None)
                     for kind, st, b in passes}
         ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, s_, rs[0], max_dist=cs[0], device=device) if M else None
-        for c_ in cs:
-            for r_ in rs:
-                if (c_, s_, r_) in done:
-                    continue
-                counts, N, strata_counts = None, 0, {}
-                try:
-                    if M:
-                        ds.sv_problem.marks.max_dist = c_
-                        ds.sv_problem.svlen_thres, ds.sv_problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
-                        N = ds.run_features(ctx, dt.feat.data_ptr())
-                    dt.build(ctx, N, ds.result if M else None)
+        for c_, r_, p_ in itertools.product(cs, rs, ps):
+            if (c_, s_, r_, p_) in done:
+                continue
+            lead = _lead(c_, s_, r_, p_)
+            counts, N, strata_counts = None, 0, {}
+            try:
+                if M:
+                    # (every cap clusters again: the entry keeps no state between calls)
+                    ds.sv_problem.marks.max_dist = c_
+                    ds.sv_problem.svlen_thres, ds.sv_problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
+                    N = ds.run_features(ctx, dt.feat.data_ptr(), pc_cap=p_)
+                dt.build(ctx, N, ds.result if M else None)
+                if _each is None:
+                    counts = dt.sweep(ctx, N)
+                for kind, p in resident.items():
+                    dt.build_strata(ctx, N, ds.result if M else None, p)
                     if _each is None:
-                        counts = dt.sweep(ctx, N)
-                    for kind, p in resident.items():
-                        dt.build_strata(ctx, N, ds.result if M else None, p)
-                        if _each is None:
-                            strata_counts[kind] = dt.sweep_strata(ctx, N, p)
-                    if _each is not None:
-                        _each(dict(cluster_max_distance=c_, svlen_thres=s_, suppread_thres=r_), dt, N, resident)
-                except ZeroDivisionError:
-                    if _each is not None:
-                        _each(dict(cluster_max_distance=c_, svlen_thres=s_, suppread_thres=r_), None, 0, resident)
-                done[(c_, s_, r_)] = counts, strata_counts
-                if on_features is not None:
-                    if M and ds.n_found is None:
-                        ds.n_found = ds.n_cands()           # (a division by zero: the records are written all the same)
-                    res = ds.fetch() if M else dict(cand_contig=[], cand_type=[], cand_pos=[], cand_span=[])
-                    on_features(dict(cluster_max_distance=c_, svlen_thres=s_, suppread_thres=r_), dict(
-                        feat=dt.features_host(len(res['cand_pos'])), chrom=[texts[int(k)] for k in res['cand_contig']],
-                        pos=res['cand_pos'], svlen=res['cand_span'],
-                        svtype=[svim_mode.SV_TYPE_NAMES[int(t) & 3] for t in res['cand_type']]))
+                        strata_counts[kind] = dt.sweep_strata(ctx, N, p)
+                if _each is not None:
+                    _each(lead, dt, N, resident)
+            except ZeroDivisionError:
+                if _each is not None:
+                    _each(lead, None, 0, resident)
+            done[(c_, s_, r_, p_)] = counts, strata_counts
+            if on_features is not None:
+                if M and ds.n_found is None:
+                    ds.n_found = ds.n_cands()           # (a division by zero: the records are written all the same)
+                res = ds.fetch() if M else dict(cand_contig=[], cand_type=[], cand_pos=[], cand_span=[])
+                on_features(lead, dict(
+                    feat=dt.features_host(len(res['cand_pos'])), chrom=[texts[int(k)] for k in res['cand_contig']],
+                    pos=res['cand_pos'], svlen=res['cand_span'],
+                    svtype=[svim_mode.SV_TYPE_NAMES[int(t) & 3] for t in res['cand_type']]))
     out = []
-    for c_ in cs:
-        for s_ in ss:
-            for r_ in rs:
-                lead = dict(cluster_max_distance=c_, svlen_thres=s_, suppread_thres=r_)
-                counts, strata_counts = done[(c_, s_, r_)]
-                rows = _rows(vecs, counts, base['n_base'], lead)
-                _strata_rows(rows, by_contig, vecs, strata_counts, passes, lead)
-                out.extend(rows)
+    for c_, s_, r_, p_ in itertools.product(cs, ss, rs, ps):
+        lead = _lead(c_, s_, r_, p_)
+        counts, strata_counts = done[(c_, s_, r_, p_)]
+        rows = _rows(vecs, counts, base['n_base'], lead)
+        _strata_rows(rows, by_contig, vecs, strata_counts, passes, lead)
+        out.extend(rows)
     return out
 
 
@@ -653,9 +672,9 @@ def _nan_row(holdout):
 
 def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max_values=0, svlen_thres=(50,), suppread_thres=(2,),
         cluster_max_distance=None, from_bams=False, refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False,
-        thread=4, ctx=None, holdout=None):
-    """Fit the vector to the truth set by exact per-threshold line search (see the module text), per setting of -s, -r and -c as
-    sweep_settings takes them.  objective: one of SCORES (with holdout: the `train` stratum's; `test` is reported, never used);
+        thread=4, ctx=None, holdout=None, pc_cap=None):
+    """Fit the vector to the truth set by exact per-threshold line search (see the module text), per setting of -s, -r, -c and
+    pc_cap as sweep_settings takes them (the cap is a setting, fitted per value given: it has no line of its own here).  objective: one of SCORES (with holdout: the `train` stratum's; `test` is reported, never used);
     start: a vector, a partial vector (dict) or None for the defaults; axes: names of the fields to move, in this order (None: all,
     in field order); rounds: at most this many passes over the axes; max_values: 0 for the whole line of every axis, N >= 2 for
     at most N of its values (both ends among them).
@@ -672,6 +691,7 @@ def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max
         raise ValueError('rounds: at least 1')
     if max_values < 0 or max_values == 1:
         raise ValueError('max_values: 0 (all) or at least 2')
+    _cap_list(pc_cap)
     v0 = vector(start) if start is None or isinstance(start, dict) else np.array(start, dtype=np.float64).reshape(len(NAMES))
     ax = _axes(axes)
     score_of = SCORES.index(objective)
@@ -704,8 +724,8 @@ def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max
                          trace=[dict(setting, **r) for r in trace])
 
     rows = sweep_settings(home, truth_vcf, v0[None, :], svlen_thres, suppread_thres, cluster_max_distance, from_bams, refdist, pctsim, bed,
-                          skip_phasing, include_all_ctgs, thread, ctx=ctx, holdout=holdout, _each=each)
-    # (sweep_settings' rows come settings outermost, in c, s, r order)
+                          skip_phasing, include_all_ctgs, thread, ctx=ctx, holdout=holdout, _each=each, pc_cap=pc_cap)
+    # (sweep_settings' rows come settings outermost, in c, s, r, pc_cap order)
     out = [fits[k] for k in dict.fromkeys(tuple(r[n] for n in LEAD if n in r) for r in rows)]
     best = None
     for f in out:
@@ -721,13 +741,22 @@ def apply(cands, thresholds, ctx=None):
     return pred[0], ps
 
 
-def load_vector(path):
-    """--thresholds FILE.json: one partial vector (JSON object)."""
+def load_vector(path, with_cap=False):
+    """--thresholds FILE.json: one partial vector (JSON object) -> float64[14].  The object may carry a 15th key, pc_cap (what
+    `tune --fit --pc_cap` writes): with_cap: -> (float64[14], the cap or None); without, the key is accepted and left out."""
     with open(path) as f:
         obj = json.load(f)
     if not isinstance(obj, dict):
         raise ValueError('%s: a threshold file holds one JSON object of name -> value' % path)
-    return vector(obj)
+    obj = dict(obj)
+    cap = obj.pop('pc_cap', None)
+    if cap is not None:
+        try:
+            cap = _lib.check_pc_cap(cap)
+        except ValueError as e:
+            raise ValueError('%s: %s' % (path, e))
+    vec = vector(obj)
+    return (vec, cap) if with_cap else vec
 
 
 def _write_tsv(path, names, rows):
@@ -747,6 +776,14 @@ def _csv(kind, what):
             raise argparse.ArgumentTypeError('%s: %r holds a negative value' % (what, text))
         return vals
     return parse
+
+
+def _caps(text):
+    """--pc_cap: a comma-separated list of integers in 0 .. 2^30 - 3."""
+    try:
+        return [_lib.check_pc_cap(int(x)) for x in text.split(',')]
+    except ValueError:
+        raise argparse.ArgumentTypeError('--pc_cap: %r is not a comma-separated list of integers in 0 .. 2^30 - 3' % (text,))
 
 
 def parse_args(argv):
@@ -776,6 +813,9 @@ def parse_args(argv):
                     help='take the candidates from snp_phasing/*.bam through the svim-gpu pipeline, not from sv_calling/variants.vcf')
     ap.add_argument('-c', '--cluster_max_distance', type=_csv(float, '-c'), default=None,
                     help='with --from_bams: maximum span-position distance of the clustering; a comma-separated list sweeps it [0.9]')
+    ap.add_argument('--pc_cap', type=_caps, default=None,
+                    help='reads with a PC tag above the cap do not vote; a comma-separated list sweeps it, innermost, and every '
+                         'row gains a leading pc_cap column [8100, without the column]')
     ap.add_argument('-a', '--include_all_ctgs', action='store_true', help='all contigs, not only chr{1..22,X,Y}')
     ap.add_argument('-t', '--thread', type=int, default=4, help='threads of the ingest [%(default)s]')
     ap.add_argument('--refdist', type=int, default=1000, help="the evaluator's --refdist [%(default)s]")
@@ -807,14 +847,14 @@ def parse_args(argv):
     return a
 
 
-LEAD = ('svlen_thres', 'suppread_thres', 'cluster_max_distance')      # the setting columns in front of a row, in this order
+LEAD = ('pc_cap', 'svlen_thres', 'suppread_thres', 'cluster_max_distance')      # the setting columns in front of a row, in this order
 
 
 def features_path(path, setting):
-    """--features with several settings: FILE.ext -> FILE[.c<c>].s<s>.r<r>.ext"""
+    """--features with several settings: FILE.ext -> FILE[.c<c>].s<s>.r<r>[.p<cap>].ext"""
     root, ext = os.path.splitext(path)
-    tag = ''.join('.%s%s' % (t, setting[n]) for t, n in (('c', 'cluster_max_distance'), ('s', 'svlen_thres'), ('r', 'suppread_thres'))
-                  if n in setting)
+    tag = ''.join('.%s%s' % (t, setting[n]) for t, n in (('c', 'cluster_max_distance'), ('s', 'svlen_thres'), ('r', 'suppread_thres'),
+                                                         ('p', 'pc_cap')) if n in setting)
     return root + tag + ext
 
 
@@ -827,7 +867,7 @@ def main_fit(a):
         raise SystemExit('tune: %s' % e)
     got = fit(a.workdir, a.truthset, a.fit, start, a.axes, a.rounds, a.max_values, a.sv_min_size, a.min_support_read,
               a.cluster_max_distance if a.from_bams else None, a.from_bams, a.refdist, a.pctsim, a.bed_file, a.skip_phasing,
-              a.include_all_ctgs, a.thread, ctx=engine.default_context(a.device), holdout=a.holdout)
+              a.include_all_ctgs, a.thread, ctx=engine.default_context(a.device), holdout=a.holdout, pc_cap=a.pc_cap)
     if a.trace:
         lead = tuple(n for n in LEAD if n in got['trace'][0])
         cols = lead + TRACE + SCORES
@@ -839,7 +879,10 @@ def main_fit(a):
         raise SystemExit('tune: no setting has a fit (%s is nan for every vector tried, or the features report a division by zero); '
                          '%s is not written' % (a.fit, a.out_vector))
     with open(a.out_vector, 'w') as f:
-        json.dump(dict(zip(NAMES, (float(x) for x in best['vector']))), f, indent=1)
+        obj = dict(zip(NAMES, (float(x) for x in best['vector'])))
+        if a.pc_cap is not None:
+            obj['pc_cap'] = int(best['setting']['pc_cap'])          # (the 15th key: duet --thresholds applies it)
+        json.dump(obj, f, indent=1)
         f.write('\n')
     print('fit %s=%r at %s; %s -> %s' % (a.fit, best['objective'], ' '.join('%s=%s' % (n, best['setting'][n]) for n in LEAD if n in best['setting']),
                                         ' '.join('%s=%r' % (n, best['scores'][n]) for n in best['scores']), a.out_vector))
@@ -852,7 +895,8 @@ def main(argv):
     vecs = load_grid(a.grid)
     ctx = engine.default_context(a.device)
     cs = a.cluster_max_distance if a.from_bams else None
-    plain = not a.from_bams and len(a.sv_min_size) == 1 and len(a.min_support_read) == 1
+    single = not a.from_bams and len(a.sv_min_size) == 1 and len(a.min_support_read) == 1
+    plain = single and a.pc_cap is None
 
     def write_features(setting, cands):
         f = cands['feat']
@@ -865,8 +909,9 @@ def main(argv):
     rows = sweep_settings(a.workdir, a.truthset, vecs, a.sv_min_size, a.min_support_read, cs, a.from_bams, a.refdist, a.pctsim,
                           a.bed_file, a.skip_phasing, a.include_all_ctgs, a.thread, ctx=ctx,
                           on_features=write_features if a.features else None, holdout=a.holdout,
-                          by_contig=contig_rows if a.by_contig else None)
-    lead = () if plain else tuple(n for n in LEAD if n in rows[0])
+                          by_contig=contig_rows if a.by_contig else None, pc_cap=a.pc_cap)
+    # (one -s and one -r, not from the BAMs: their columns stay away, as without --pc_cap)
+    lead = tuple(n for n in LEAD if n in rows[0] and (n == 'pc_cap' or not single))
     cols = lead + NAMES + SCORES
     if a.holdout is not None:
         cols += tuple('%s_%s' % (part, n) for part in ('train', 'test') for n in SCORES)

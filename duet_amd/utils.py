@@ -3,7 +3,7 @@
 
 Flag names, defaults, help texts and the positional order are upstream's (utils.py:19-44), so an
 existing command line works unchanged.  Two additive options select the device (--device) or shard the contigs
-over several GPUs (--gpus).
+over several GPUs (--gpus); --thresholds and --pc_cap replace the decision's constants on the single-GPU path.
 """
 
 import argparse
@@ -32,6 +32,17 @@ _POSITIONALS = (
 )
 
 
+def pc_cap_arg(text):
+    """--pc_cap: an integer in 0 .. 2^30 - 3 (the read tag word saturates PC at 2^30 - 2, and a saturated value never votes)."""
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('--pc_cap: %r is not an integer' % (text,))
+    if not 0 <= v <= (1 << 30) - 3:
+        raise argparse.ArgumentTypeError('--pc_cap: %d is not in 0 .. 2^30 - 3' % v)
+    return v
+
+
 def build_parser():
     ap = argparse.ArgumentParser(
         description='SNP-Assisted Structural Variant Calling and Phasing Using Oxford Nanopore Sequencing')
@@ -49,6 +60,9 @@ def build_parser():
     ap.add_argument('--thresholds', type=str, default=None,
                     help='JSON object of T1-T5 threshold values (duet_amd/tune.py names; the others keep their defaults) for the '
                          'SV phasing decision; one GPU only (the native path, or -b svim-gpu)')
+    ap.add_argument('--pc_cap', type=pc_cap_arg, default=None,
+                    help='reads with a PC tag above this never vote in the SV phasing decision [8100, or the pc_cap of '
+                         '--thresholds]; one GPU only (the native path, or -b svim-gpu)')
     ap.add_argument('--write_sv_calls', action='store_true',
                     help='with -b svim-gpu, also write the clustered SV calls to OUTPUT/sv_calling/variants.vcf')
     for name, text in _POSITIONALS:

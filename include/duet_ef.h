@@ -411,9 +411,10 @@ DUET_API int duet_eval_run_host(duet_ctx *ctx, const duet_eval_problem *prob, du
  * duet_tune_thresholds: 14 binary64 fields in this fixed order, each named after the reference line it replaces; the
  * defaults (DUET_TUNE_DEFAULTS) are the reference's constants.  Every comparison is the reference's, made in binary64 on
  * the binary64 features Python computes (hapread_ratio = allhap / deg, a1, a2, sv_ratio, totsc_ratio; an integer compared
- * with a double converts exactly), so NaN and +-inf behave as Python's <=, >=, > do.  Fixed, not in the vector: the
- * `sv_ratio == 1` test of :146, the PC cap 8100 and ps_sr (they change classes and seed sets, not the tree) and the dead
- * `sv_num >= 20` test of :157.
+ * with a double converts exactly), so NaN and +-inf behave as Python's <=, >=, > do.  Not in the vector: the `sv_ratio == 1`
+ * test of :146 and ps_sr (fixed), the dead `sv_num >= 20` test of :157, and the PC cap 8100 of :76, :88, :201 -- it changes who
+ * votes and the seed sets, not the tree, so it is a parameter of the feature export (duet_ef_features_cap_*, below), not a
+ * field here.
  * ---------------------------------------------------------------------------------------------------------------------------- */
 typedef struct duet_tune_thresholds {
     double c0_min_sv_num;           /* 4      :146  sv_num >= . (class 0) */
@@ -451,6 +452,21 @@ typedef struct duet_tune_feature {
  * are written all the same).  _host: host arrays as for duet_ef_run_host, out[C] host. */
 DUET_API int duet_ef_features_device(duet_ctx *ctx, const duet_ef_problem *prob, duet_tune_feature *out, void *stream);
 DUET_API int duet_ef_features_host(duet_ctx *ctx, const duet_ef_problem *prob, duet_tune_feature *out);
+
+/* The same records with the PC cap as a run parameter: a mark votes iff its read is tagged and pc <= pc_cap (the reference tests
+ * `read[3] <= 8100`, sv_phasing_fn.py:76, :88, :201).  The PS-class is unchanged (:192-194 has no PC test); the seed set of a contig
+ * is the set of PS values of its kept class-1 candidates that have at least one voter; eligible = kept and that set is not
+ * empty; vote and ps follow get_phase_info with pc_cap in place of 8100.  pc_cap is 0 .. 2^30 - 3 (the tag word saturates pc at
+ * 2^30 - 2, and a saturated value never votes): anything above is DUET_ERR_INVALID and nothing is written.  With
+ * pc_cap == DUET_PC_MAX the records and the status are duet_ef_features_*'s, byte for byte.
+ * These entries build the seed sets themselves (duet_tune_cap.hip) and never run E/F: the kernels of duet_ef_run_* keep the
+ * reference's cap as a compile-time constant.  Their workspace is the context's own and not E/F's -- a call changes nothing of
+ * what a later duet_ef_run_*, duet_ef_get_seed_ps or duet_ef_features_* on the same context returns.  Synchronises `stream`;
+ * DUET_ERR_DIV_ZERO: an eligible candidate has svread + refread == 0 (the records are written all the same) -- eligibility
+ * depends on the cap, so the status of one problem can differ between caps.  _host: host arrays, out[C] host. */
+DUET_API int duet_ef_features_cap_device(duet_ctx *ctx, const duet_ef_problem *prob, uint32_t pc_cap, duet_tune_feature *out,
+                                         void *stream);
+DUET_API int duet_ef_features_cap_host(duet_ctx *ctx, const duet_ef_problem *prob, uint32_t pc_cap, duet_tune_feature *out);
 
 /* A truth set prepared for the candidates (host work, once, independent of the thresholds; duet_amd/tune.py): the call a
  * candidate would be written as, read through the evaluator's own parser, matched once to its nearest truth record
@@ -505,6 +521,13 @@ DUET_API int duet_svim_features_device(duet_ctx *ctx, const duet_svim_problem *p
                                        duet_tune_feature *out_feat, uint32_t *n_cands_host, void *stream);
 DUET_API int duet_svim_features_host(duet_ctx *ctx, const duet_svim_problem *prob, const duet_cluster_result *res,
                                      duet_tune_feature *out_feat);
+
+/* duet_svim_features_* under a PC cap: clusters and adapts in exactly the same way (every call clusters again: the entry keeps
+ * no state between caps), then duet_ef_features_cap_device in place of duet_ef_features_device. */
+DUET_API int duet_svim_features_cap_device(duet_ctx *ctx, const duet_svim_problem *prob, const duet_cluster_result *res, uint32_t pc_cap,
+                                           duet_tune_feature *out_feat, uint32_t *n_cands_host, void *stream);
+DUET_API int duet_svim_features_cap_host(duet_ctx *ctx, const duet_svim_problem *prob, const duet_cluster_result *res, uint32_t pc_cap,
+                                         duet_tune_feature *out_feat);
 
 /* The truth arrays built on the device (duet_tune_truth.hip) -- what duet_amd/tune.py's prepare_truth computes on the host, which
  * stays the normative text.  Per candidate the caller says how the evaluator's parser sees the row the candidate would be
