@@ -36,7 +36,8 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_svim_features_device', 'duet_svim_features_host', 'duet_tune_truth_build_device', 'duet_tune_truth_build_host',
            'duet_tune_strata_build_device', 'duet_tune_strata_build_host', 'duet_tune_sweep_strata_device',
            'duet_tune_sweep_strata_host', 'duet_tune_line_device', 'duet_tune_line_host',
-           'duet_ef_features_cap_device', 'duet_ef_features_cap_host', 'duet_svim_features_cap_device', 'duet_svim_features_cap_host')
+           'duet_ef_features_cap_device', 'duet_ef_features_cap_host', 'duet_svim_features_cap_device', 'duet_svim_features_cap_host',
+           'duet_tune_cap_line_device', 'duet_tune_cap_line_host', 'duet_svim_cap_line_device', 'duet_svim_cap_line_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -289,6 +290,11 @@ def load():
                                                   ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
     lib.duet_svim_features_cap_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult),
                                                 ctypes.c_uint32, ctypes.c_void_p]
+    for fn, prob in ((lib.duet_tune_cap_line_device, EfProblem), (lib.duet_svim_cap_line_device, SvimProblem)):
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(prob), ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+                       ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+    lib.duet_tune_cap_line_host.argtypes = lib.duet_tune_cap_line_device.argtypes[:-1]
+    lib.duet_svim_cap_line_host.argtypes = lib.duet_svim_cap_line_device.argtypes[:-1]
     _lib = lib
     return lib
 
@@ -829,6 +835,47 @@ class Context(object):
             self._raise(rc)
         return n_vec.value, n_distinct.value
 
+    # -- the line of the PC cap (duet_tune_capline.hip) ------------------------------------------------------------------------
+    def _cap_line(self, fn, prob, n_marks, max_values, out_ptr=None, stream=None):
+        """One of the four cap-line entries: out_ptr None -> host form, (caps u32[n_caps], n_distinct); else the device form
+        writing to out_ptr on `stream`, (n_caps, n_distinct)."""
+        n_caps, n_distinct = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        if out_ptr is None:
+            out = np.zeros(cap_line_room(n_marks, max_values), dtype=np.uint32)
+            rc = fn(self.handle, ctypes.byref(prob), clamp_u32(max_values), _ptr(out), ctypes.byref(n_caps), ctypes.byref(n_distinct))
+        else:
+            rc = fn(self.handle, ctypes.byref(prob), clamp_u32(max_values), ctypes.c_void_p(out_ptr), ctypes.byref(n_caps),
+                    ctypes.byref(n_distinct), ctypes.c_void_p(stream or 0))
+        if rc:
+            self._raise(rc)
+        return (out[:n_caps.value].copy() if out_ptr is None else n_caps.value), n_distinct.value
+
+    def cap_line_host(self, soa, svlen_thres, suppread_thres, max_values=0):
+        """duet_tune_cap_line_host: the line of the PC cap of an EfSoA -> (caps u32[n_caps] ascending, n_distinct)."""
+        prob, keep = problem_from_arrays(soa, svlen_thres, suppread_thres)
+        got = self._cap_line(self.lib.duet_tune_cap_line_host, prob, soa.n_marks, max_values)
+        del keep
+        return got
+
+    def cap_line_device(self, prob, max_values, out_ptr, stream=0):
+        """duet_tune_cap_line_device on a resident EfProblem (devmem.DeviceProblem.problem); out_ptr: device room for
+        cap_line_room(prob.n_marks, max_values) words -> (n_caps, n_distinct)."""
+        return self._cap_line(self.lib.duet_tune_cap_line_device, prob, prob.n_marks, max_values, out_ptr, stream)
+
+    def svim_cap_line_host(self, mark_read, read_tag, max_values=0):
+        """duet_svim_cap_line_host: the line of the PC cap over the raw marks (read index per mark, tag word per read)
+        -> (caps u32[n_caps] ascending, n_distinct)."""
+        mr = np.ascontiguousarray(mark_read, dtype=np.uint32)
+        tag = np.ascontiguousarray(read_tag, dtype=np.uint64)
+        p = SvimProblem()
+        p.marks.n_marks, p.n_reads = len(mr), len(tag)
+        p.mark_read, p.read_tag = (a.ctypes.data if a.size else None for a in (mr, tag))
+        return self._cap_line(self.lib.duet_svim_cap_line_host, p, len(mr), max_values)
+
+    def svim_cap_line_device(self, sv_problem, max_values, out_ptr, stream=0):
+        """duet_svim_cap_line_device on a resident SvimProblem (devmem.DeviceSvim.sv_problem) -> (n_caps, n_distinct)."""
+        return self._cap_line(self.lib.duet_svim_cap_line_device, sv_problem, sv_problem.marks.n_marks, max_values, out_ptr, stream)
+
     def apply_device(self, feat_ptr, n_cands, vec_ptr, pred_ptr, ps_ptr, stream=0):
         """duet_tune_sweep_device with one vector and no truth set: pred u8[C] and ps u32[C] on the device, what
         duet_ef_run_device writes with the built-in constants."""
@@ -852,6 +899,12 @@ def check_pc_cap(pc_cap):
     if isinstance(pc_cap, bool) or not isinstance(pc_cap, (int, np.integer)) or not 0 <= int(pc_cap) <= PC_CAP_MAX:
         raise ValueError('pc_cap: an integer in 0 .. 2^30 - 3 (%d), not %r' % (PC_CAP_MAX, pc_cap))
     return int(pc_cap)
+
+
+def cap_line_room(n_marks, max_values=0):
+    """The values a cap-line entry can write at most (include/duet_ef.h): what the caller allocates for out_caps."""
+    room = min(int(n_marks), PC_CAP_MAX + 1) + 1
+    return min(room, int(max_values)) if int(max_values) >= 2 else room
 
 
 def clamp_u32(v):

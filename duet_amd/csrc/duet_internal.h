@@ -86,6 +86,7 @@ struct duet_ctx {
     DuetOwnedBufs tune_strata_ws;          // strata of the sweep: host-run staging of cand_stratum 0 and group_stratum 1; the build's status word 2 and host-run staging 3-8
     DuetOwnedBufs tune_line_ws;            // the line of one axis (duet_tune_line.hip): workspace 0; host-run staging of the features 1 and the vectors 2
     DuetOwnedBufs tune_cap_ws;             // feature export under a PC cap (duet_tune_cap.hip): workspace 0; host-run staging of the features 1
+    DuetOwnedBufs tune_capline_ws;         // the line of the PC cap (duet_tune_capline.hip): workspace 0; host-run staging of the values 1, of a svim problem's mark reads 2 and read tags 3
     DuetOwnedBufs callset_ws;            // svim-gpu callset rows (duet_callset.hip): workspace 0-4, host-run staging 5-14, text 15
     DuetOwnedBufs svim_rows_ws;            // svim-gpu rows of phased_sv.vcf (duet_svim_rows.hip): workspace 0-8, host-run staging 9-14, text 15
 };

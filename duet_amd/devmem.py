@@ -446,6 +446,43 @@ class DeviceTune(object):
                                 s.get('truth', self.truth), s['strata'], s['line_counts'].data_ptr(), self.stream())
         return s['line_counts'][:K * S * rec].cpu().numpy().view(_lib.COUNTS_DTYPE).reshape(K, S).copy()
 
+    # -- the line of the PC cap (tune.fit's pc_cap axis) -------------------------------------------------------------------------
+    def cap_line(self, ctx, prob, max_values=0):
+        """The line of the PC cap of a resident problem -- an EfProblem (duet_tune_cap_line_device) or a SvimProblem
+        (duet_svim_cap_line_device: its raw marks) -- brought to the host: -> (caps u32[n_caps] ascending, D, whether they are
+        the whole line).  max_values as for line()."""
+        torch = self.torch
+        svim = isinstance(prob, _lib.SvimProblem)
+        entry = ctx.svim_cap_line_device if svim else ctx.cap_line_device
+
+        def run(N, fetch=True):
+            room = _lib.cap_line_room(prob.marks.n_marks if svim else prob.n_marks, N)
+            if getattr(self, 'cap_vals', None) is None or self.cap_vals.numel() < room:
+                self.cap_vals = torch.zeros(room, dtype=torch.int32, device=self.device)
+            n, D = entry(prob, N, self.cap_vals.data_ptr(), self.stream())
+            return (self.cap_vals[:n].cpu().numpy().view(np.uint32).copy() if fetch else n), D
+
+        N = int(max_values)
+        caps, D = run(N)
+        if N < 2 or len(caps) < N or D + 1 == N:
+            return caps, D, True
+        if D > N:
+            return caps, D, False
+        # N values came back and D == N: the whole line when it has no 0 in front (L = D), a sample of D + 1 values otherwise --
+        # both start with 0 and end with x_D, and the entry reports D, not L: the one case in which they cannot be told apart asks
+        # once more, for one value more, and reads only how many came (nothing is downloaded)
+        return caps, D, run(N + 1, fetch=False)[0] == N
+
+    def set_line_vector(self, base):
+        """`base` (float64[14], host) as vector 0 of the line block: what sweep_line(ctx, n, 0, 1) then scores."""
+        torch = self.torch
+        if getattr(self, 'line_vec', None) is None:
+            n = self.n_max + 2
+            self.line_vec = torch.zeros(n * self.VEC_BYTES, dtype=torch.uint8, device=self.device)
+            self.line_counts = torch.zeros(n * _lib.COUNTS_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        base = np.ascontiguousarray(base, dtype=np.float64).reshape(len(_lib.TUNE_NAMES))
+        self.line_vec[:self.VEC_BYTES] = torch.from_numpy(base.view(np.uint8).copy()).to(self.device)
+
     def features_host(self, n_cands):
         """(--features) the feature records of the last setting, on the host."""
         return self.feat[:int(n_cands) * _lib.FEATURE_DTYPE.itemsize].cpu().numpy().view(_lib.FEATURE_DTYPE).copy()

@@ -12,7 +12,9 @@
     fit(home, truth_vcf, objective, ...)   coordinate descent over exact lines: per axis one vector per distinct value of the feature
                                            the axis is compared with (duet_tune_line_device), scored by the same sweep
     python -m duet_amd.tune WORKDIR TRUTH.vcf --fit hp_f1 [--start VEC.json --axes a,b --rounds N --max_values N --holdout ..]
-                                           --out_vector best.json [--trace fit.tsv]
+                                           [--fit_cap] --out_vector best.json [--trace fit.tsv]
+                                           --fit_cap, or the name pc_cap in --axes: the PC cap is an axis too, searched along the
+                                           distinct pc values of the marks that can vote (duet_tune_cap_line_device)
 
 The vector's 14 fields, their order and defaults are include/duet_ef.h's duet_tune_thresholds (NAMES, DEFAULTS).  A grid is
 either a list of partial vectors (dicts) or a dict of name -> list of values, expanded as a Cartesian product; names left out
@@ -466,9 +468,10 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     truth record: the setting, vector, contig, the nine counts, n_base and the ten scores.  Each is one stratified pass per
     setting (truth arrays with the pass's id numbering, duet_tune_sweep_strata_device) beside the plain sweep, whose rows do
     not change.
-    _each (fit): called per setting as _each(setting, dt, n_cands, passes) in place of the sweeps, with the features, the plain truth
-    arrays and every pass's own truth arrays and strata built and resident in dt (a DeviceTune); dt None: the setting's features
-    report a division by zero.  The rows returned are then nan.
+    _each (fit): called per setting as _each(setting, dt, n_cands, passes, ops) in place of the sweeps, with the features, the plain
+    truth arrays and every pass's own truth arrays and strata built and resident in dt (a DeviceTune); dt None: the setting's features
+    report a division by zero.  The rows returned are then nan.  ops (a _CapOps): how the fit's pc_cap axis recomputes the resident
+    features and truth arrays of this setting under another cap, and the cap line of its problem.
     pc_cap: a list of PC caps (a read with a PC tag above the cap does not vote; the reference's is 8100) -- the innermost setting,
     after c, s, r; every row then gains a leading pc_cap column.  A cap costs the features call (duet_ef_features_cap_device,
     duet_svim_features_cap_device), the truth build(s) and the sweep(s) on the resident problem: no ingest, no upload and, without
@@ -514,10 +517,13 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
                 if _each is None:
                     strata_counts[kind] = dt.sweep_strata(ctx, C, p)
             if _each is not None:
-                _each(lead, dt, C, resident)
+                _each(lead, dt, C, resident, _CapOps(
+                    features=lambda cap: ctx.features_device(dp.problem, dt.feat.data_ptr(), dt.stream(), pc_cap=cap) if C else None,
+                    n_cands=lambda: C, build=lambda n: dt.build(ctx, n), build_strata=lambda n, p: dt.build_strata(ctx, n, strata=p),
+                    line=lambda max_values: dt.cap_line(ctx, dp.problem, max_values) if C else (np.zeros(1, dtype=np.uint32), 0, True)))
         except ZeroDivisionError:
             if _each is not None:
-                _each(lead, None, 0, resident)
+                _each(lead, None, 0, resident, None)
         if on_features is not None:
             on_features(lead, dict(cands, feat=dt.features_host(C)))
         rows = _rows(vecs, counts, base['n_base'], lead)
@@ -569,10 +575,20 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
                     if _each is None:
                         strata_counts[kind] = dt.sweep_strata(ctx, N, p)
                 if _each is not None:
-                    _each(lead, dt, N, resident)
+                    found = [N]
+
+                    def features(cap):
+                        # (every value clusters again: duet_svim_features_cap_device keeps no state between caps)
+                        if M:
+                            found[0] = ds.run_features(ctx, dt.feat.data_ptr(), pc_cap=cap)
+
+                    _each(lead, dt, N, resident, _CapOps(
+                        features=features, n_cands=lambda: found[0], build=lambda n: dt.build(ctx, n, ds.result if M else None),
+                        build_strata=lambda n, p: dt.build_strata(ctx, n, ds.result if M else None, p),
+                        line=lambda max_values: dt.cap_line(ctx, ds.sv_problem, max_values) if M else (np.zeros(1, dtype=np.uint32), 0, True)))
             except ZeroDivisionError:
                 if _each is not None:
-                    _each(lead, None, 0, resident)
+                    _each(lead, None, 0, resident, None)
             done[(c_, s_, r_, p_)] = counts, strata_counts
             if on_features is not None:
                 if M and ds.n_found is None:
@@ -595,13 +611,30 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
 TRACE = ('round', 'axis', 'n_distinct', 'n_vec', 'exact', 'old', 'new', 'objective_before', 'objective_after')
 
 
-def _axes(axes):
-    """--axes: names (or indices) of the vector's fields -> indices, in the order given; None: all 14 in field order."""
+CAP_AXIS = 'pc_cap'         # the 15th axis of the fit: not a field of the vector -- a step on it changes the features
+
+
+class _CapOps(object):
+    """What the pc_cap axis of the fit needs from the setting it runs in (sweep_settings hands one to _each):
+    features(cap): the features under that cap into the resident array (ZeroDivisionError where they report one); n_cands(): their
+    count; build(n) / build_strata(n, pass): the truth arrays of the resident features; line(max_values) -> (caps, D, whole line?)"""
+
+    def __init__(self, features, n_cands, build, build_strata, line):
+        self.features, self.n_cands, self.build, self.build_strata, self.line = features, n_cands, build, build_strata, line
+        self.cap = None                                      # the current cap, kept by _fit_setting
+
+
+def _axes(axes, fit_cap=False):
+    """--axes: names (or indices) of the vector's fields -> indices, in the order given; None: all 14 in field order.  The name
+    pc_cap (CAP_AXIS) stands for itself, at the place given; fit_cap: appended when it is not named."""
     if axes is None:
-        return list(range(len(NAMES)))
+        return list(range(len(NAMES))) + ([CAP_AXIS] if fit_cap else [])
     out = []
     for a in axes:
-        if isinstance(a, str) and a in NAMES:
+        if a == CAP_AXIS:
+            if a not in out:
+                out.append(a)
+        elif isinstance(a, str) and a in NAMES:
             out.append(NAMES.index(a))
         elif isinstance(a, (int, np.integer)) and not isinstance(a, bool) and 0 <= a < len(NAMES):
             out.append(int(a))
@@ -609,6 +642,8 @@ def _axes(axes):
             raise ValueError('axes: %r is not a threshold name' % (a,))
     if not out:
         raise ValueError('axes: an empty list')
+    if fit_cap and CAP_AXIS not in out:
+        out.append(CAP_AXIS)
     return out
 
 
@@ -617,9 +652,60 @@ def _better(x, best):
     return not math.isnan(x) and (math.isnan(best) or x > best)
 
 
-def _fit_setting(ctx, dt, n_cands, start, axes, rounds, max_values, score_of, n_base, hold=None, n_base_hold=None):
+def _cap_step(ctx, dt, ops, cur, max_values, score_of, n_base, hold, n_base_hold, ten):
+    """One step of the fit on the pc_cap axis: every value of the cap line, ascending, and last the current cap -- the features
+    under it, the truth arrays, the one current vector scored.  Moves ops.cap by the rule of every axis and leaves the features and
+    truth arrays of the cap it ends on resident.  -> (the trace row without its round, moved?)"""
+    caps, n_distinct, whole = ops.line(max_values)
+    dt.set_line_vector(cur)
+
+    def resident(cap):
+        ops.features(cap)
+        n = ops.n_cands()
+        ops.build(n)
+        if hold is not None:
+            ops.build_strata(n, hold)
+        return n
+
+    def evaluate(cap):
+        """-> (objective, plain counts, strata counts or None); a cap whose features divide by zero: nan, nothing built or swept"""
+        try:
+            n = resident(cap)
+        except ZeroDivisionError:
+            return math.nan, None, None
+        plain = dt.sweep_line(ctx, n, 0, 1)[0]
+        if hold is None:
+            return ten(plain, n_base)[score_of], plain, None
+        sc = dt.sweep_line_strata(ctx, n, 0, 1, hold)[0]
+        return ten(sc[0], n_base_hold[0])[score_of], plain, sc
+
+    got = [evaluate(int(c)) for c in caps]
+    here = evaluate(ops.cap)
+    if here[1] is None:
+        raise ZeroDivisionError('division by zero')
+    best, pick = here[0], None
+    for i, g in enumerate(got):
+        if _better(g[0], best):
+            best, pick = g[0], i
+    old = ops.cap
+    if pick is not None:
+        ops.cap = int(caps[pick])
+        resident(ops.cap)                                    # (the threshold axes that follow read these)
+    _, plain, sc = here if pick is None else got[pick]
+    row = dict(axis=CAP_AXIS, n_distinct=n_distinct, n_vec=len(caps), exact=int(whole), old=old, new=ops.cap,
+               objective_before=here[0], objective_after=best)
+    row.update(zip(SCORES, ten(plain, n_base)))
+    if hold is not None:
+        for s_i, part in enumerate(('train', 'test')):
+            row.update(('%s_%s' % (part, n), x) for n, x in zip(SCORES, ten(sc[s_i], n_base_hold[s_i])))
+    return row, pick is not None
+
+
+def _fit_setting(ctx, dt, n_cands, start, axes, rounds, max_values, score_of, n_base, hold=None, n_base_hold=None, ops=None):
     """Coordinate descent for one setting on the resident features and truth arrays of dt -> (vector, trace rows).
-    hold: the holdout pass (its stratum 0 is `train`, whose score is the objective; stratum 1 `test` is only reported)."""
+    hold: the holdout pass (its stratum 0 is `train`, whose score is the objective; stratum 1 `test` is only reported).
+    ops: the setting's _CapOps when CAP_AXIS is among the axes; ops.cap is the cap the resident features were computed under on
+    entry and the fitted cap on return."""
     cur = np.array(start, dtype=np.float64)
     memo = {}
 
@@ -633,6 +719,12 @@ def _fit_setting(ctx, dt, n_cands, start, axes, rounds, max_values, score_of, n_
     for rnd in range(1, rounds + 1):
         moved = False
         for ax in axes:
+            if ax == CAP_AXIS:
+                row, stepped = _cap_step(ctx, dt, ops, cur, max_values, score_of, n_base, hold, n_base_hold, ten)
+                n_cands = ops.n_cands()
+                moved = moved or stepped
+                trace.append(dict(round=rnd, **row))
+                continue
             n_vec, n_distinct = dt.line(ctx, n_cands, cur, ax, max_values)
             K = n_vec + 1                                    # (the line's vectors, then the current vector)
             if hold is not None:
@@ -672,9 +764,15 @@ def _nan_row(holdout):
 
 def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max_values=0, svlen_thres=(50,), suppread_thres=(2,),
         cluster_max_distance=None, from_bams=False, refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False,
-        thread=4, ctx=None, holdout=None, pc_cap=None):
+        thread=4, ctx=None, holdout=None, pc_cap=None, fit_cap=False):
     """Fit the vector to the truth set by exact per-threshold line search (see the module text), per setting of -s, -r, -c and
-    pc_cap as sweep_settings takes them (the cap is a setting, fitted per value given: it has no line of its own here).  objective: one of SCORES (with holdout: the `train` stratum's; `test` is reported, never used);
+    pc_cap as sweep_settings takes them.  The cap is a setting, fitted per value given; with the name pc_cap among the axes (at any
+    place), or fit_cap=True (appended behind the axes in force), it is also an axis: each given value -- else the pc_cap key of a
+    start dict, else 8100 -- is then the START of a fit that moves the cap along its own exact line (the distinct pc values of the
+    marks that can vote, duet_tune_cap_line_device; from_bams: of the raw marks, duet_svim_cap_line_device).  A step on that axis
+    costs, per line value, the features under the value, the truth build(s) and one vector swept (from_bams: every value clusters
+    again); a value whose features divide by zero scores nan and never wins.  The fit dict then carries pc_cap, the fitted cap;
+    setting['pc_cap'], where present, stays the start.  objective: one of SCORES (with holdout: the `train` stratum's; `test` is reported, never used);
     start: a vector, a partial vector (dict) or None for the defaults; axes: names of the fields to move, in this order (None: all,
     in field order); rounds: at most this many passes over the axes; max_values: 0 for the whole line of every axis, N >= 2 for
     at most N of its values (both ends among them).
@@ -692,8 +790,14 @@ def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max
     if max_values < 0 or max_values == 1:
         raise ValueError('max_values: 0 (all) or at least 2')
     _cap_list(pc_cap)
+    cap0 = None
+    if isinstance(start, dict) and CAP_AXIS in start:        # (the 15th key of a fitted file: the cap axis starts there)
+        start = dict(start)
+        cap0 = start.pop(CAP_AXIS)
+        cap0 = None if cap0 is None else _lib.check_pc_cap(cap0)
     v0 = vector(start) if start is None or isinstance(start, dict) else np.array(start, dtype=np.float64).reshape(len(NAMES))
-    ax = _axes(axes)
+    ax = _axes(axes, fit_cap)
+    with_cap = CAP_AXIS in ax
     score_of = SCORES.index(objective)
     ctx = ctx or engine.default_context()
     n_base = truth_side(truth_vcf, bed, skip_phasing)['n_base']
@@ -702,17 +806,27 @@ def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max
         n_base_hold = truth_side(truth_vcf, bed, skip_phasing, strata=strata_holdout(holdout))['n_base_strata']
     fits = {}
 
-    def each(setting, dt, n_cands, resident):
+    def each(setting, dt, n_cands, resident, ops):
         key = tuple(setting[n] for n in LEAD if n in setting)
         if key in fits:
             return
         vec, trace = None, None
+        hold = resident.get('holdout')
         if dt is not None:
             try:
-                vec, trace = _fit_setting(ctx, dt, n_cands, v0, ax, rounds, max_values, score_of, n_base, resident.get('holdout'),
-                                          n_base_hold)
+                if with_cap:
+                    ops.cap = setting.get(CAP_AXIS, cap0 if cap0 is not None else _lib.PC_MAX)
+                    if ops.cap != setting.get(CAP_AXIS, _lib.PC_MAX):
+                        # (the start comes from --start: the resident features are the setting's, those of 8100)
+                        ops.features(ops.cap)
+                        n_cands = ops.n_cands()
+                        ops.build(n_cands)
+                        if hold is not None:
+                            ops.build_strata(n_cands, hold)
+                vec, trace = _fit_setting(ctx, dt, n_cands, v0, ax, rounds, max_values, score_of, n_base, hold, n_base_hold, ops)
             except ZeroDivisionError:
                 pass
+        more = {CAP_AXIS: ops.cap} if with_cap and trace is not None else {}
         if trace is None:
             fits[key] = dict(setting=dict(setting), vector=None, objective=math.nan, scores=dict.fromkeys(SCORES, math.nan),
                              trace=[dict(setting, **_nan_row(holdout is not None))])
@@ -721,7 +835,7 @@ def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max
         obj = last['objective_after']
         fits[key] = dict(setting=dict(setting), vector=None if math.isnan(obj) else vec, objective=obj,
                          scores={n: last[n] for n in last if n in SCORES or n.startswith(('train_', 'test_'))},
-                         trace=[dict(setting, **r) for r in trace])
+                         trace=[dict(setting, **r) for r in trace], **more)
 
     rows = sweep_settings(home, truth_vcf, v0[None, :], svlen_thres, suppread_thres, cluster_max_distance, from_bams, refdist, pctsim, bed,
                           skip_phasing, include_all_ctgs, thread, ctx=ctx, holdout=holdout, _each=each, pc_cap=pc_cap)
@@ -797,7 +911,12 @@ def parse_args(argv):
                          'this score (one of %s); with --holdout the score of the train part' % ', '.join(SCORES))
     ap.add_argument('--start', default=None, help='with --fit: JSON object, the (partial) vector the fit starts from [the defaults]')
     ap.add_argument('--axes', type=lambda t: [x for x in t.split(',')], default=None,
-                    help='with --fit: comma-separated threshold names to move, in this order [all 14, in field order]')
+                    help='with --fit: comma-separated threshold names to move, in this order; pc_cap among them makes the PC cap '
+                         'an axis at that place [all 14, in field order]')
+    ap.add_argument('--fit_cap', action='store_true',
+                    help='with --fit: the PC cap is an axis too, behind the others unless --axes names pc_cap at a place of its own; '
+                         'it starts at --pc_cap (each listed value a start of its own), else at the pc_cap key of --start, else at '
+                         '8100, and moves along the distinct PC values of the marks that can vote')
     ap.add_argument('--rounds', type=int, default=8, help='with --fit: at most this many passes over the axes [%(default)s]')
     ap.add_argument('--max_values', type=int, default=0,
                     help='with --fit: at most this many values of an axis per line, both ends among them; 0 = every distinct value '
@@ -836,6 +955,8 @@ def parse_args(argv):
         ap.error('--fit and --grid exclude each other')
     if a.fit is None and a.grid is None:
         ap.error('the following arguments are required: --grid')
+    if a.fit is None and a.fit_cap:
+        ap.error('--fit_cap belongs to --fit')
     if a.fit is not None and (a.by_contig or a.features):
         ap.error('--fit writes --out_vector and --trace: --by_contig and --features belong to --grid')
     if a.fit is not None and (a.rounds < 1 or a.max_values < 0 or a.max_values == 1):
@@ -861,13 +982,18 @@ def features_path(path, setting):
 def main_fit(a):
     """--fit: the fitted vector -> --out_vector, the trace -> --trace, the best setting and its scores on stdout (one line)."""
     try:
-        start = load_vector(a.start) if a.start else None
-        _axes(a.axes)
+        start = None
+        if a.start:
+            vec, cap = load_vector(a.start, with_cap=True)
+            start = dict(zip(NAMES, (float(x) for x in vec)))
+            if cap is not None:
+                start[CAP_AXIS] = cap
+        _axes(a.axes, a.fit_cap)
     except ValueError as e:
         raise SystemExit('tune: %s' % e)
     got = fit(a.workdir, a.truthset, a.fit, start, a.axes, a.rounds, a.max_values, a.sv_min_size, a.min_support_read,
               a.cluster_max_distance if a.from_bams else None, a.from_bams, a.refdist, a.pctsim, a.bed_file, a.skip_phasing,
-              a.include_all_ctgs, a.thread, ctx=engine.default_context(a.device), holdout=a.holdout, pc_cap=a.pc_cap)
+              a.include_all_ctgs, a.thread, ctx=engine.default_context(a.device), holdout=a.holdout, pc_cap=a.pc_cap, fit_cap=a.fit_cap)
     if a.trace:
         lead = tuple(n for n in LEAD if n in got['trace'][0])
         cols = lead + TRACE + SCORES
@@ -880,12 +1006,17 @@ def main_fit(a):
                          '%s is not written' % (a.fit, a.out_vector))
     with open(a.out_vector, 'w') as f:
         obj = dict(zip(NAMES, (float(x) for x in best['vector'])))
-        if a.pc_cap is not None:
+        if CAP_AXIS in best:
+            obj['pc_cap'] = int(best[CAP_AXIS])                     # (the fitted cap)
+        elif a.pc_cap is not None:
             obj['pc_cap'] = int(best['setting']['pc_cap'])          # (the 15th key: duet --thresholds applies it)
         json.dump(obj, f, indent=1)
         f.write('\n')
-    print('fit %s=%r at %s; %s -> %s' % (a.fit, best['objective'], ' '.join('%s=%s' % (n, best['setting'][n]) for n in LEAD if n in best['setting']),
-                                        ' '.join('%s=%r' % (n, best['scores'][n]) for n in best['scores']), a.out_vector))
+    at = ' '.join('%s=%s' % (n, best['setting'][n]) for n in LEAD if n in best['setting'])
+    if CAP_AXIS in best:
+        at += ', fitted pc_cap=%d' % best[CAP_AXIS]
+    print('fit %s=%r at %s; %s -> %s' % (a.fit, best['objective'], at, ' '.join('%s=%r' % (n, best['scores'][n]) for n in best['scores']),
+                                        a.out_vector))
 
 
 def main(argv):

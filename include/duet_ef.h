@@ -650,6 +650,35 @@ DUET_API int duet_tune_line_host(duet_ctx *ctx, const duet_tune_feature *feat, u
                                  uint32_t axis, uint32_t max_values, duet_tune_thresholds *out_vec, uint32_t *n_vec,
                                  uint32_t *n_distinct);
 
+/* The line of the PC cap (duet_tune_capline.hip).  A mark votes iff its read is tagged and pc <= cap, so the feature records of
+ * duet_ef_features_cap_* are a piecewise-constant function of the cap.  The participants are the marks of kept candidates
+ * (cand_svlen >= svlen_thres, cand_svread >= suppread_thres, cand_gt_ok) whose read is tagged (index not DUET_MARK_ABSENT and
+ * < n_reads, tag word not all-ones) with pc <= 2^30 - 3; the hap field plays no part, and a saturated pc of 2^30 - 2 never votes.
+ * With x_1 < .. < x_D their distinct pc values, a cap in [x_i, x_i+1) gives the records of cap x_i byte for byte, a cap below
+ * x_1 those of cap 0, a cap from x_D up those of x_D.  The line is x_1 .. x_D with 0 in front unless x_1 == 0: L = D or D + 1
+ * values, ascending; no participant: the one value 0.  The best score on it is the exact optimum of the cap over 0 .. 2^30 - 3.
+ * max_values = N >= 2 and L > N: only the line's entries floor(i * (L - 1) / (N - 1)), i = 0 .. N - 1, are written (both ends
+ * among them); 0: all.  *n_distinct = D, *n_caps = the values written; out_caps needs room for max_values values when that is
+ * non-zero, otherwise for min(n_marks, 2^30 - 2) + 1.
+ * duet_svim_cap_line_*: the same for the raw marks of a duet_svim_problem, without clustering -- the participants are EVERY raw
+ * mark whose read is tagged with pc <= 2^30 - 3, a superset of what any -c / -r setting of that extraction keeps, so one line
+ * serves all of them.  The price: a value that no kept mark carries costs one evaluation and scores like its lower neighbour.
+ * Of *prob only marks.n_marks, mark_read, read_tag and n_reads are read.
+ * _device: the arrays of *prob (cand_ctg_off aside) and out_caps are device memory; n_caps and n_distinct host memory.  One host
+ * round trip (D and x_1), then the values are written asynchronously on `stream`.  The workspace is the entry's own (16 bytes per
+ * mark, the sort's histogram and scan partials; grown, never shrunk): a call changes nothing that a later duet_ef_run_*,
+ * duet_ef_features_* or duet_ef_features_cap_* returns.  _host: the same with host arrays, out_caps host; synchronises.
+ * DUET_ERR_INVALID: max_values == 1, a NULL array that is needed, whatever duet_ef_run_* refuses in *prob.  n_cands == 0 or
+ * n_marks == 0: DUET_OK, the line [0]. */
+DUET_API int duet_tune_cap_line_device(duet_ctx *ctx, const duet_ef_problem *prob, uint32_t max_values, uint32_t *out_caps,
+                                       uint32_t *n_caps, uint32_t *n_distinct, void *stream);
+DUET_API int duet_tune_cap_line_host(duet_ctx *ctx, const duet_ef_problem *prob, uint32_t max_values, uint32_t *out_caps,
+                                     uint32_t *n_caps, uint32_t *n_distinct);
+DUET_API int duet_svim_cap_line_device(duet_ctx *ctx, const duet_svim_problem *prob, uint32_t max_values, uint32_t *out_caps,
+                                       uint32_t *n_caps, uint32_t *n_distinct, void *stream);
+DUET_API int duet_svim_cap_line_host(duet_ctx *ctx, const duet_svim_problem *prob, uint32_t max_values, uint32_t *out_caps,
+                                     uint32_t *n_caps, uint32_t *n_distinct);
+
 /* ---------------------------------------------------------------------------------------------
  * The collective of the contig-sharded path: candidates shard by contig over the GPUs of one node,
  * one process and one context per GPU, and ONE all-gather of fixed-size record blocks reassembles the call set
