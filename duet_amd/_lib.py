@@ -37,7 +37,8 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_tune_strata_build_device', 'duet_tune_strata_build_host', 'duet_tune_sweep_strata_device',
            'duet_tune_sweep_strata_host', 'duet_tune_line_device', 'duet_tune_line_host',
            'duet_ef_features_cap_device', 'duet_ef_features_cap_host', 'duet_svim_features_cap_device', 'duet_svim_features_cap_host',
-           'duet_tune_cap_line_device', 'duet_tune_cap_line_host', 'duet_svim_cap_line_device', 'duet_svim_cap_line_host')
+           'duet_tune_cap_line_device', 'duet_tune_cap_line_host', 'duet_svim_cap_line_device', 'duet_svim_cap_line_host',
+           'duet_tune_leaf_census_device', 'duet_tune_leaf_census_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -149,6 +150,14 @@ FEATURE_DTYPE = np.dtype([('t1', '<u8'), ('t2', '<u8'), ('hap1', '<u4'), ('hap2'
 COUNTS_NAMES = ('n_calls', 'n_groups', 'call_tp', 'base_tp', 'call_gt', 'base_gt', 'call_hp', 'base_hp', 'n_raise', 'reserved')
 COUNTS_DTYPE = np.dtype([(n, '<u4') for n in COUNTS_NAMES])
 TUNE_IN_CALLS, TUNE_RAISES, TUNE_MATCHED = 0x1000, 0x2000, 0x4000
+# the leaf census (include/duet_ef.h, "Leaf census"): the 18 exits of the tree, their nominal pred (1: 1 or 2), the record
+LEAF_NAMES = ('c0_call', 'c0_drop', 'c2_low_ratio', 'c2_near_call', 'c2_near_few', 'c2_far_call', 'c2_far_few', 'c1_one_low',
+              'c1_one_het', 'c1_one_het_gated', 'c1_one_hom', 'c1_one_hom_gated', 'c1_two_low', 'c1_two_het_ref', 'c1_two_het',
+              'c1_two_mid_hom', 'c1_two_mid_het', 'c1_two_hom')
+LEAF_PRED = (3, 0, 0, 3, 0, 3, 0, 0, 1, 0, 3, 0, 0, 0, 1, 3, 1, 3)
+N_LEAVES = len(LEAF_NAMES)
+LEAF_COUNTS_NAMES = ('n_cands', 'n_listed', 'n_matched', 'n_calls', 'call_tp', 'call_gt', 'call_hp', 'n_raise')
+LEAF_COUNTS_DTYPE = np.dtype([(n, '<u4') for n in LEAF_COUNTS_NAMES])
 
 
 class TuneTruth(ctypes.Structure):
@@ -280,6 +289,9 @@ def load():
     lib.duet_tune_sweep_strata_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                                   ctypes.POINTER(TuneTruth), ctypes.POINTER(TuneStrata), ctypes.c_void_p, ctypes.c_void_p]
     lib.duet_tune_sweep_strata_host.argtypes = lib.duet_tune_sweep_strata_device.argtypes[:-1]
+    lib.duet_tune_leaf_census_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                                 ctypes.POINTER(TuneTruth), ctypes.POINTER(TuneStrata), ctypes.c_void_p, ctypes.c_void_p]
+    lib.duet_tune_leaf_census_host.argtypes = lib.duet_tune_leaf_census_device.argtypes[:-1]
     lib.duet_tune_line_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
@@ -755,6 +767,46 @@ class Context(object):
         if rc:
             self._raise(rc)
         return counts
+
+    def leaf_census_host(self, feat, vectors, truth=None, strata=None):
+        """duet_tune_leaf_census_host: feat, vectors, truth (or None) as for sweep_host; strata = dict(n_strata, cand_stratum
+        u8[C]) or None (S = 1) -> LEAF_COUNTS_DTYPE[K, S, N_LEAVES]"""
+        feat = np.ascontiguousarray(feat, dtype=FEATURE_DTYPE)
+        vec = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1, len(TUNE_NAMES))
+        C, K = len(feat), len(vec)
+        t, st, keep = None, None, []
+        if truth is not None:
+            t = TuneTruth()
+            t.n_uid, t.n_groups, t.n_pairs = int(truth['n_uid']), int(truth['n_groups']), int(truth['n_pairs'])
+            for name, dt in TRUTH_ARRAYS:
+                a = np.ascontiguousarray(truth[name], dtype=dt)
+                keep.append(a)
+                setattr(t, name, a.ctypes.data if a.size else None)
+        S = 1
+        if strata is not None:
+            S = int(strata['n_strata'])
+            st = TuneStrata()
+            st.n_strata = S if 0 <= S <= 0xFFFFFFFF else 0xFFFFFFFF
+            a = np.ascontiguousarray(strata['cand_stratum'], dtype=np.uint8)
+            assert len(a) == C, 'cand_stratum holds one entry per candidate'
+            keep.append(a)
+            st.cand_stratum = a.ctypes.data if a.size else None
+        out = np.zeros((K, S if 1 <= S <= TUNE_MAX_STRATA else 1, N_LEAVES), dtype=LEAF_COUNTS_DTYPE)
+        rc = self.lib.duet_tune_leaf_census_host(self.handle, _ptr(feat), C, _ptr(vec), K, ctypes.byref(t) if t is not None else None,
+                                                 ctypes.byref(st) if st is not None else None, _ptr(out))
+        del keep
+        if rc:
+            self._raise(rc)
+        return out
+
+    def leaf_census_device(self, feat_ptr, n_cands, vec_ptr, n_vec, truth, strata, out_ptr, stream=0):
+        """duet_tune_leaf_census_device on resident arrays (devmem.DeviceTune.leaf_census); truth / strata: the structures or None."""
+        rc = self.lib.duet_tune_leaf_census_device(self.handle, ctypes.c_void_p(feat_ptr), int(n_cands), ctypes.c_void_p(vec_ptr),
+                                                   int(n_vec), ctypes.byref(truth) if truth is not None else None,
+                                                   ctypes.byref(strata) if strata is not None else None, ctypes.c_void_p(out_ptr),
+                                                   ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
 
     def strata_build_device(self, prob, truth, chrom_stratum_ptr, n_strata, cand_stratum_ptr, group_stratum_ptr, stream=0):
         """duet_tune_strata_build_device on resident arrays (devmem.DeviceTune), after truth_build_device on the same prob / truth."""

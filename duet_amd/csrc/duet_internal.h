@@ -84,7 +84,8 @@ struct duet_ctx {
     DuetOwnedBufs tune_ws;                 // threshold sweep (duet_tune.hip): E/F outputs of the feature export, sweep workspace, host-run staging
     DuetOwnedBufs tune_truth_in, tune_truth_out;   // duet_tune_truth_build_host: staged inputs; base_hp and the six truth arrays (the build's own workspace is tune_ws 15)
     DuetOwnedBufs tune_strata_ws;          // strata of the sweep: host-run staging of cand_stratum 0 and group_stratum 1; the build's status word 2 and host-run staging 3-8
-    DuetOwnedBufs tune_line_ws;            // the line of one axis (duet_tune_line.hip): workspace 0; host-run staging of the features 1 and the vectors 2
+    DuetOwnedBufs tune_leaf_ws;            // leaf census (duet_tune_leaf.hip): the sweep's scratch counts 0, the groups' label bits 1; host-run staging of the features 2, the vectors 3, cand_stratum 4, the records 5, the truth arrays 6-11
+    DuetOwnedBufs tune_line_ws;           // the line of one axis (duet_tune_line.hip): workspace 0; host-run staging of the features 1 and the vectors 2
     DuetOwnedBufs tune_cap_ws;             // feature export under a PC cap (duet_tune_cap.hip): workspace 0; host-run staging of the features 1
     DuetOwnedBufs tune_capline_ws;         // the line of the PC cap (duet_tune_capline.hip): workspace 0; host-run staging of the values 1, of a svim problem's mark reads 2 and read tags 3
     DuetOwnedBufs callset_ws;            // svim-gpu callset rows (duet_callset.hip): workspace 0-4, host-run staging 5-14, text 15

@@ -406,6 +406,24 @@ class DeviceTune(object):
                                 s['counts'].data_ptr(), self.stream())
         return s['counts'][:self.K * S * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).reshape(self.K, S).copy()
 
+    def leaf_census(self, ctx, n_cands, vectors=None, strata=None):
+        """The leaf census (duet_tune_leaf_census_device) over the resident features: `vectors` (float64[K, 14], uploaded; None:
+        the resident grid) over the truth arrays of the last build -- or, with strata (a pass of set_strata), over those of the
+        last build_strata of that pass, one record per stratum -> LEAF_COUNTS_DTYPE[K, S, N_LEAVES] on the host."""
+        torch, rec = self.torch, _lib.LEAF_COUNTS_DTYPE.itemsize * _lib.N_LEAVES
+        if vectors is None:
+            K, vec_ptr = self.K, self.vec_ptr
+        else:
+            vec = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1, len(_lib.TUNE_NAMES))
+            K, vec_ptr = len(vec), self._up('leaf_vectors', vec, np.float64)
+        S = strata['strata'].n_strata if strata is not None else 1
+        if getattr(self, 'leaf_counts', None) is None or self.leaf_counts.numel() < K * S * rec:
+            self.leaf_counts = torch.zeros(max(K * S, 1) * rec, dtype=torch.uint8, device=self.device)
+        truth = strata.get('truth', self.truth) if strata is not None else self.truth
+        ctx.leaf_census_device(self.feat.data_ptr(), int(n_cands), vec_ptr, K, truth, strata['strata'] if strata is not None else None,
+                               self.leaf_counts.data_ptr(), self.stream())
+        return self.leaf_counts[:K * S * rec].cpu().numpy().view(_lib.LEAF_COUNTS_DTYPE).reshape(K, S, _lib.N_LEAVES).copy()
+
     # -- the line of one axis (tune.fit): a block of n_max + 2 vectors next to the grid's, made on the device --------------------
     VEC_BYTES = 8 * len(_lib.TUNE_NAMES)
 

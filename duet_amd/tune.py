@@ -8,7 +8,7 @@
     strata_by_contig(), strata_holdout(texts)   strata (sets of CHROM texts) for sweep_settings(holdout=.., by_contig=..): every
                                            vector scored per stratum in one pass over the candidates (duet_tune_sweep_strata_device)
     python -m duet_amd.tune WORKDIR TRUTH.vcf --grid GRID.json [-s 30,50 -r 2,3 [--from_bams -c 0.5,0.9]] [--pc_cap 4000,8100]
-                                           [--holdout chr20,chr21 --by_contig FILE.tsv] [...]
+                                           [--holdout chr20,chr21 --by_contig FILE.tsv] [--by_leaf FILE.tsv] [...]
     fit(home, truth_vcf, objective, ...)   coordinate descent over exact lines: per axis one vector per distinct value of the feature
                                            the axis is compared with (duet_tune_line_device), scored by the same sweep
     python -m duet_amd.tune WORKDIR TRUTH.vcf --fit hp_f1 [--start VEC.json --axes a,b --rounds N --max_values N --holdout ..]
@@ -29,6 +29,11 @@ matches every call to its nearest truth record by the evaluator's rule and numbe
 binary64 quotients of those counts.  prepare_truth is the same truth match on the host, in the evaluator's own terms: the
 normative text the device build is tested against.  Where upstream would raise (ZeroDivisionError: no calls, or precision +
 recall == 0; IndexError: an emitted call whose (contig, type) has no truth record) the row's ten numbers are nan.
+
+Leaves.  The tree has 18 exits (include/duet_ef.h, "Leaf census"; _lib.LEAF_NAMES).  by_leaf / --by_leaf adds one pass per setting
+over the resident features (duet_tune_leaf_census_device) and one row per setting, vector, stratum and leaf: how many eligible
+candidates the vector sends there, how many of them the evaluator lists and matches, and what the calls among them score -- where
+the calls, the wrong genotypes and the wrong haplotypes come from.  Summed over the leaves, the counts are the plain sweep's.
 
 Fit.  With the other 13 constants fixed, every count of a sweep is a piecewise-constant function of one constant: it changes only
 where the constant crosses a value of the feature it is compared with that some candidate has.  The line of an axis -- those
@@ -428,6 +433,45 @@ def _strata_rows(rows, contig_rows, vecs, strata_counts, passes, lead):
                     contig_rows.append(row)
 
 
+LEAF_PRED_TEXT = {0: '0', 1: '1|0,0|1', 3: '1|1'}
+LEAF_COUNTS = _lib.LEAF_COUNTS_NAMES
+LEAF_RATES = ('call_precision', 'gt_precision', 'hp_precision')         # call_tp, call_gt, call_hp over n_calls
+LEAF_COLS = ('vector', 'stratum', 'leaf', 'pred') + LEAF_COUNTS + LEAF_RATES
+
+
+def leaf_rows(lead, labels, census, strata=('all',)):
+    """The --by_leaf rows of one census: census LEAF_COUNTS_DTYPE[K, S, 18] (None: the setting's features report a division by
+    zero -- every count and quotient nan), labels[k] the vector column, strata[s] the stratum column.  A quotient is nan where
+    the leaf makes no call."""
+    out = []
+    for k, label in enumerate(labels):
+        for s, sname in enumerate(strata):
+            for leaf, lname in enumerate(_lib.LEAF_NAMES):
+                row = dict(lead, vector=label, stratum=sname, leaf=lname, pred=LEAF_PRED_TEXT[_lib.LEAF_PRED[leaf]])
+                if census is None:
+                    row.update(dict.fromkeys(LEAF_COUNTS + LEAF_RATES, math.nan))
+                else:
+                    rec = census[k, s, leaf]
+                    row.update((n, int(rec[n])) for n in LEAF_COUNTS)
+                    n_calls = row['n_calls']
+                    row.update((q, row[n] / n_calls if n_calls else math.nan) for q, n in zip(LEAF_RATES, ('call_tp', 'call_gt', 'call_hp')))
+                out.append(row)
+    return out
+
+
+def _leaf_census(ctx, dt, n_cands, resident, vectors=None):
+    """The censuses --by_leaf owes for the resident features of one setting: `all` over the plain truth arrays and, with a
+    holdout pass, `train` / `test` over the pass's own -> [(census, stratum names)]."""
+    out = [(dt.leaf_census(ctx, n_cands, vectors), ('all',))]
+    if 'holdout' in resident:
+        out.append((dt.leaf_census(ctx, n_cands, vectors, strata=resident['holdout']), ('train', 'test')))
+    return out
+
+
+def _leaf_nan(resident):
+    return [(None, ('all',))] + ([(None, ('train', 'test'))] if 'holdout' in resident else [])
+
+
 def _cap_list(pc_cap):
     """pc_cap of sweep_settings / fit: None -> [None] (the entry without a cap), else a non-empty list of caps in 0 .. 2^30 - 3."""
     if pc_cap is None:
@@ -453,7 +497,7 @@ def _int_list(name, v):
 
 def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,), cluster_max_distance=None, from_bams=False,
                    refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False, thread=4, ctx=None, on_features=None,
-                   holdout=None, by_contig=None, _each=None, pc_cap=None):
+                   holdout=None, by_contig=None, _each=None, pc_cap=None, by_leaf=None):
     """sweep() for every setting of -s (svlen_thres), -r (suppread_thres) and, with from_bams, -c (cluster_max_distance; default
     (0.9,)): -> list of rows, settings outermost in the order c, s, r, each row a dict of svlen_thres, suppread_thres
     [, cluster_max_distance], the 14 thresholds and the ten numbers.  from_bams: the candidates come from <home>/snp_phasing/*.bam
@@ -475,7 +519,10 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     pc_cap: a list of PC caps (a read with a PC tag above the cap does not vote; the reference's is 8100) -- the innermost setting,
     after c, s, r; every row then gains a leading pc_cap column.  A cap costs the features call (duet_ef_features_cap_device,
     duet_svim_features_cap_device), the truth build(s) and the sweep(s) on the resident problem: no ingest, no upload and, without
-    from_bams, no host work.  None: the features of the entries without a cap, and rows without the column."""
+    from_bams, no host work.  None: the features of the entries without a cap, and rows without the column.
+    by_leaf: a list that receives leaf_rows() per setting: one row per vector, stratum (`all`; with holdout also `train`, `test`)
+    and leaf -- one more pass per setting over what is already resident (duet_tune_leaf_census_device), after the plain sweep
+    and after the holdout pass's; every other row and count stays what it is without it."""
     vecs = grid if isinstance(grid, np.ndarray) else expand_grid(grid)
     ss, rs = _int_list('svlen_thres', svlen_thres), _int_list('suppread_thres', suppread_thres)
     ps = _cap_list(pc_cap)
@@ -489,7 +536,7 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
         if not cs:
             raise ValueError('cluster_max_distance: an empty list')
         return _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features,
-                           passes, by_contig, _each, ps)
+                           passes, by_contig, _each, ps, by_leaf)
     from duet_amd.devmem import DeviceProblem, DeviceTune
     soa, txt = _candidates(home, ss[0], rs[0], include_all_ctgs, thread)
     cands = dict(pos=soa.cand_pos, svlen=soa.cand_svlen, **txt)
@@ -504,7 +551,7 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     out = []
     for s_, r_, p_ in itertools.product(ss, rs, ps):
         lead = _lead(None, s_, r_, p_)
-        counts, strata_counts = None, {}
+        counts, strata_counts, leaf = None, {}, None
         try:
             if C:
                 dp.problem.svlen_thres, dp.problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
@@ -512,10 +559,14 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
             dt.build(ctx, C)
             if _each is None:
                 counts = dt.sweep(ctx, C)
+                if by_leaf is not None:
+                    leaf = [(dt.leaf_census(ctx, C), ('all',))]
             for kind, p in resident.items():
                 dt.build_strata(ctx, C, strata=p)
                 if _each is None:
                     strata_counts[kind] = dt.sweep_strata(ctx, C, p)
+                    if by_leaf is not None and kind == 'holdout':
+                        leaf.append((dt.leaf_census(ctx, C, strata=p), ('train', 'test')))
             if _each is not None:
                 _each(lead, dt, C, resident, _CapOps(
                     features=lambda cap: ctx.features_device(dp.problem, dt.feat.data_ptr(), dt.stream(), pc_cap=cap) if C else None,
@@ -529,11 +580,14 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
         rows = _rows(vecs, counts, base['n_base'], lead)
         _strata_rows(rows, by_contig, vecs, strata_counts, passes, lead)
         out.extend(rows)
+        if by_leaf is not None and _each is None:
+            for census, names in leaf if counts is not None else _leaf_nan(resident):
+                by_leaf.extend(leaf_rows(lead, range(len(vecs)), census, names))
     return out
 
 
 def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features,
-                passes=(), by_contig=None, _each=None, ps=(None,)):
+                passes=(), by_contig=None, _each=None, ps=(None,), by_leaf=None):
     from duet_amd import svim_mode
     from duet_amd.devmem import DeviceSvim, DeviceTune
     from duet_amd.native import NativeIngest
@@ -560,7 +614,7 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
             if (c_, s_, r_, p_) in done:
                 continue
             lead = _lead(c_, s_, r_, p_)
-            counts, N, strata_counts = None, 0, {}
+            counts, N, strata_counts, leaf = None, 0, {}, None
             try:
                 if M:
                     # (every cap clusters again: the entry keeps no state between calls)
@@ -570,10 +624,14 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
                 dt.build(ctx, N, ds.result if M else None)
                 if _each is None:
                     counts = dt.sweep(ctx, N)
+                    if by_leaf is not None:
+                        leaf = [(dt.leaf_census(ctx, N), ('all',))]
                 for kind, p in resident.items():
                     dt.build_strata(ctx, N, ds.result if M else None, p)
                     if _each is None:
                         strata_counts[kind] = dt.sweep_strata(ctx, N, p)
+                        if by_leaf is not None and kind == 'holdout':
+                            leaf.append((dt.leaf_census(ctx, N, strata=p), ('train', 'test')))
                 if _each is not None:
                     found = [N]
 
@@ -589,7 +647,7 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
             except ZeroDivisionError:
                 if _each is not None:
                     _each(lead, None, 0, resident, None)
-            done[(c_, s_, r_, p_)] = counts, strata_counts
+            done[(c_, s_, r_, p_)] = counts, strata_counts, leaf if counts is not None else _leaf_nan(resident)
             if on_features is not None:
                 if M and ds.n_found is None:
                     ds.n_found = ds.n_cands()           # (a division by zero: the records are written all the same)
@@ -601,10 +659,13 @@ def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing
     out = []
     for c_, s_, r_, p_ in itertools.product(cs, ss, rs, ps):
         lead = _lead(c_, s_, r_, p_)
-        counts, strata_counts = done[(c_, s_, r_, p_)]
+        counts, strata_counts, leaf = done[(c_, s_, r_, p_)]
         rows = _rows(vecs, counts, base['n_base'], lead)
         _strata_rows(rows, by_contig, vecs, strata_counts, passes, lead)
         out.extend(rows)
+        if by_leaf is not None and _each is None:
+            for census, names in leaf:
+                by_leaf.extend(leaf_rows(lead, range(len(vecs)), census, names))
     return out
 
 
@@ -764,7 +825,7 @@ def _nan_row(holdout):
 
 def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max_values=0, svlen_thres=(50,), suppread_thres=(2,),
         cluster_max_distance=None, from_bams=False, refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False,
-        thread=4, ctx=None, holdout=None, pc_cap=None, fit_cap=False):
+        thread=4, ctx=None, holdout=None, pc_cap=None, fit_cap=False, by_leaf=None):
     """Fit the vector to the truth set by exact per-threshold line search (see the module text), per setting of -s, -r, -c and
     pc_cap as sweep_settings takes them.  The cap is a setting, fitted per value given; with the name pc_cap among the axes (at any
     place), or fit_cap=True (appended behind the axes in force), it is also an axis: each given value -- else the pc_cap key of a
@@ -781,7 +842,10 @@ def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max
             trace = every setting's rows, each the setting's columns, TRACE, the ten SCORES of the new vector and, with holdout,
             its train_ / test_ scores).
     A setting whose features or line report a division by zero, or whose objective never has a number, has no fit: its vector is
-    None and (division by zero) its trace is one row of nan."""
+    None and (division by zero) its trace is one row of nan.
+    by_leaf: a list that receives, per setting, leaf_rows() of the start vector (vector = 'start', on the features the fit starts
+    from) and of the vector the fit ends on (vector = 'fitted', under the fitted cap where the cap moved): where the fit moved the
+    calls.  A setting without a trace has nan rows for both."""
     if objective not in SCORES:
         raise ValueError('objective: %r is not one of %s' % (objective, ', '.join(SCORES)))
     rounds, max_values = int(rounds), int(max_values)
@@ -810,7 +874,7 @@ def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max
         key = tuple(setting[n] for n in LEAD if n in setting)
         if key in fits:
             return
-        vec, trace = None, None
+        vec, trace, leaf = None, None, []
         hold = resident.get('holdout')
         if dt is not None:
             try:
@@ -823,9 +887,17 @@ def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max
                         ops.build(n_cands)
                         if hold is not None:
                             ops.build_strata(n_cands, hold)
+                if by_leaf is not None:
+                    leaf = [_leaf_census(ctx, dt, n_cands, resident, v0[None, :])]
                 vec, trace = _fit_setting(ctx, dt, n_cands, v0, ax, rounds, max_values, score_of, n_base, hold, n_base_hold, ops)
+                if by_leaf is not None:
+                    leaf.append(_leaf_census(ctx, dt, ops.n_cands() if with_cap else n_cands, resident, vec[None, :]))
             except ZeroDivisionError:
                 pass
+        if by_leaf is not None:
+            for i, label in enumerate(('start', 'fitted')):
+                for census, names in leaf[i] if trace is not None else _leaf_nan(resident):
+                    by_leaf.extend(leaf_rows(setting, (label,), census, names))
         more = {CAP_AXIS: ops.cap} if with_cap and trace is not None else {}
         if trace is None:
             fits[key] = dict(setting=dict(setting), vector=None, objective=math.nan, scores=dict.fromkeys(SCORES, math.nan),
@@ -949,6 +1021,10 @@ def parse_args(argv):
                          '(these texts) for the ten scores')
     ap.add_argument('--by_contig', default='', help='also write one row per setting, vector and contig (chr1..chrY, other) that has '
                                                     'a call or a truth record here (TSV): counts, n_base and the ten scores')
+    ap.add_argument('--by_leaf', default='', help='also write one row per setting, vector, stratum (all; with --holdout also train, '
+                                                  'test) and leaf of the tree here (TSV): the candidates the vector sends there, those '
+                                                  'listed and matched, the calls and what they score; with --fit the start vector and '
+                                                  'the fitted one')
     ap.add_argument('--device', type=int, default=0, help='HIP device index [%(default)s]')
     a = ap.parse_args(argv)
     if a.fit is not None and a.grid is not None:
@@ -991,9 +1067,14 @@ def main_fit(a):
         _axes(a.axes, a.fit_cap)
     except ValueError as e:
         raise SystemExit('tune: %s' % e)
+    leaf = []
     got = fit(a.workdir, a.truthset, a.fit, start, a.axes, a.rounds, a.max_values, a.sv_min_size, a.min_support_read,
               a.cluster_max_distance if a.from_bams else None, a.from_bams, a.refdist, a.pctsim, a.bed_file, a.skip_phasing,
-              a.include_all_ctgs, a.thread, ctx=engine.default_context(a.device), holdout=a.holdout, pc_cap=a.pc_cap, fit_cap=a.fit_cap)
+              a.include_all_ctgs, a.thread, ctx=engine.default_context(a.device), holdout=a.holdout, pc_cap=a.pc_cap, fit_cap=a.fit_cap,
+              by_leaf=leaf if a.by_leaf else None)
+    if a.by_leaf:
+        cols = tuple(n for n in LEAD if n in leaf[0]) + LEAF_COLS
+        _write_tsv(a.by_leaf, cols, ([r[n] for n in cols] for r in leaf))
     if a.trace:
         lead = tuple(n for n in LEAD if n in got['trace'][0])
         cols = lead + TRACE + SCORES
@@ -1036,11 +1117,11 @@ def main(argv):
                    ([cands['chrom'][c], int(cands['pos'][c]), cands['svtype'][c], int(cands['svlen'][c])] +
                     [int(f[n][c]) for n in cols[4:]] for c in range(len(f))))
 
-    contig_rows = []
+    contig_rows, leaf = [], []
     rows = sweep_settings(a.workdir, a.truthset, vecs, a.sv_min_size, a.min_support_read, cs, a.from_bams, a.refdist, a.pctsim,
                           a.bed_file, a.skip_phasing, a.include_all_ctgs, a.thread, ctx=ctx,
                           on_features=write_features if a.features else None, holdout=a.holdout,
-                          by_contig=contig_rows if a.by_contig else None, pc_cap=a.pc_cap)
+                          by_contig=contig_rows if a.by_contig else None, pc_cap=a.pc_cap, by_leaf=leaf if a.by_leaf else None)
     # (one -s and one -r, not from the BAMs: their columns stay away, as without --pc_cap)
     lead = tuple(n for n in LEAD if n in rows[0] and (n == 'pc_cap' or not single))
     cols = lead + NAMES + SCORES
@@ -1050,6 +1131,9 @@ def main(argv):
     if a.by_contig:
         cols = lead + ('vector', 'contig') + COUNTS + ('n_base',) + SCORES
         _write_tsv(a.by_contig, cols, ([r[n] for n in cols] for r in contig_rows))
+    if a.by_leaf:
+        cols = lead + LEAF_COLS
+        _write_tsv(a.by_leaf, cols, ([r[n] for n in cols] for r in leaf))
     best = max(range(len(rows)), key=lambda i: -1.0 if math.isnan(rows[i]['hp_f1']) else rows[i]['hp_f1'])
     print('%d vectors scored -> %s; best phasing F1 %r at vector %d' % (len(rows), a.out, rows[best]['hp_f1'], best))
 

@@ -626,6 +626,60 @@ DUET_API int duet_tune_sweep_strata_host(duet_ctx *ctx, const duet_tune_feature 
                                          uint32_t n_vec, const duet_tune_truth *truth, const duet_tune_strata *strata,
                                          duet_tune_counts *counts);
 
+/* Leaf census (duet_tune_leaf.hip): which rule of the tree emits the calls, the wrong genotypes and the wrong haplotypes.  The
+ * tree of predict_hp has 18 exits, numbered by its branch structure (a comparison that is false takes the else branch, for a nan
+ * constant too, so the leaf a candidate ends at is the branch the code takes); a leaf fixes the pred up to the 1-or-2 choice:
+ *    0 c0_call           class 0, sv_ratio == 1 and sv_num >= c0_min_sv_num                                   pred 3
+ *    1 c0_drop           class 0 otherwise                                                                    0
+ *    2 c2_low_ratio      class 2, not sv_ratio >= c2_min_sv_ratio                                             0
+ *    3 c2_near_call      class 2, avgsc_diff <= c2_max_avgsc_diff, sv_num >= c2_min_sv_num                    3
+ *    4 c2_near_few       ... not sv_num >= c2_min_sv_num                                                      0
+ *    5 c2_far_call       class 2, not avgsc_diff <= c2_max_avgsc_diff, hap0 >= c2_min_hap0                    3
+ *    6 c2_far_few        ... not hap0 >= c2_min_hap0                                                          0
+ *    7 c1_one_low        class 1, one voting haplotype, sv_ratio <= c1_onehap_sv_ratio_lo                     0
+ *    8 c1_one_het        ... <= c1_onehap_sv_ratio_hi, the hapread_ratio / avgsc_diff gate of :163 open       1 or 2
+ *    9 c1_one_het_gated  ... the gate closed                                                                  0
+ *   10 c1_one_hom        ... above c1_onehap_sv_ratio_hi, the gate open                                       3
+ *   11 c1_one_hom_gated  ... the gate closed                                                                  0
+ *   12 c1_two_low        class 1 otherwise, sv_ratio <= c1_twohap_sv_ratio_1                                  0
+ *   13 c1_two_het_ref    ... <= c1_twohap_sv_ratio_2, ref_num > c1_max_ref_num                                0
+ *   14 c1_two_het        ... <= c1_twohap_sv_ratio_2 otherwise                                                1 or 2
+ *   15 c1_two_mid_hom    ... <= c1_twohap_sv_ratio_3, totsc_ratio <= c1_max_totsc_ratio                       3
+ *   16 c1_two_mid_het    ... <= c1_twohap_sv_ratio_3 otherwise                                                1 or 2
+ *   17 c1_two_hom        ... above c1_twohap_sv_ratio_3                                                       3
+ * DUET_TUNE_LEAF_PRED gives the nominal pred, 1 standing for "1 or 2".
+ *
+ * One record per (vector v, stratum s, leaf): out[(v * S + s) * 18 + leaf], over the ELIGIBLE candidates of the stratum that end
+ * at the leaf under the vector: n_cands all of them; n_listed those in the evaluator's call list (DUET_TUNE_IN_CALLS); n_matched
+ * listed and DUET_TUNE_MATCHED -- neither depends on the pred: for a pred-0 leaf they say how many matchable candidates the rule
+ * drops; n_calls listed and pred != 0; call_tp, call_gt, n_raise as duet_tune_counts has them, for those calls; call_hp the calls
+ * whose same / flip bit agrees with the labelling their phase-set group takes in the plain sweep of that vector (decided over all
+ * leaves together).  Summed over the leaves, n_calls, call_tp, call_gt, call_hp and n_raise are duet_tune_sweep_device's (S = 1)
+ * and duet_tune_sweep_strata_device's (v, s); summed over the strata they are the S = 1 record.  Base-side set sizes are not
+ * broken down: a truth id hit from two leaves belongs to neither.
+ * truth may be NULL: only n_cands and n_calls (= pred != 0) are filled.  strata may be NULL: S = 1; otherwise only n_strata and
+ * cand_stratum are read, cand_stratum for EVERY candidate (duet_tune_strata_build_* writes it so); a group lies inside one CHROM
+ * id, hence one stratum, so the truth arrays may carry either id numbering.  Batching, workspace and asynchrony are
+ * duet_tune_sweep_device's, which runs per batch for the groups' labellings: a census changes nothing a later sweep returns.
+ * n_vec == 0 or n_cands == 0: DUET_OK, the records zeroed.  DUET_ERR_INVALID: n_strata of 0 or above DUET_TUNE_MAX_STRATA, a NULL
+ * array that is needed and, in the _host form (which can read them), a cand_stratum entry >= n_strata or a call's group index
+ * >= n_groups; the _device form counts a candidate with such a stratum in stratum 0.  _host: host arrays; synchronises. */
+#define DUET_TUNE_N_LEAVES 18
+#define DUET_TUNE_LEAF_NAMES                                                                                                      \
+    {"c0_call", "c0_drop", "c2_low_ratio", "c2_near_call", "c2_near_few", "c2_far_call", "c2_far_few", "c1_one_low", "c1_one_het", \
+     "c1_one_het_gated", "c1_one_hom", "c1_one_hom_gated", "c1_two_low", "c1_two_het_ref", "c1_two_het", "c1_two_mid_hom",        \
+     "c1_two_mid_het", "c1_two_hom"}
+#define DUET_TUNE_LEAF_PRED {3, 0, 0, 3, 0, 3, 0, 0, 1, 0, 3, 0, 0, 0, 1, 3, 1, 3}
+typedef struct duet_tune_leaf_counts {
+    uint32_t n_cands, n_listed, n_matched, n_calls, call_tp, call_gt, call_hp, n_raise;
+} duet_tune_leaf_counts;
+DUET_API int duet_tune_leaf_census_device(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *vec,
+                                          uint32_t n_vec, const duet_tune_truth *truth, const duet_tune_strata *strata,
+                                          duet_tune_leaf_counts *out, void *stream);
+DUET_API int duet_tune_leaf_census_host(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *vec,
+                                        uint32_t n_vec, const duet_tune_truth *truth, const duet_tune_strata *strata,
+                                        duet_tune_leaf_counts *out);
+
 /* The line of one axis (duet_tune_line.hip): with the other 13 constants fixed, every count of a sweep is a piecewise-constant
  * function of one constant and changes only where it crosses a value of the feature it is compared with, so one vector per
  * distinct value plus one sentinel covers every behaviour of the axis.  axis = the field's index in duet_tune_thresholds.  The
