@@ -11,6 +11,12 @@ constexpr int kScanThreads = 256;
 constexpr int kScanItems = 8;
 constexpr int kScanTile = kScanThreads * kScanItems;
 
+// A workspace laid out as one allocation: take() hands out the offset of the next piece, 256-byte aligned; total is its size.
+struct Arena {
+    size_t total = 0;
+    size_t take(size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; }
+};
+
 // The evaluator's nearest truth record (src/scripts/evaluation.py:117-125) among the n >= 1 ascending positions bp[]:
 // np.searchsorted(..., side='left'); the left neighbour when the insertion point is the end or when it is strictly nearer, a
 // tie goes to the right one; among equal positions the first.  Shared by the evaluator (duet_eval.hip) and the sweep's truth

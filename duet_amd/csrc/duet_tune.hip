@@ -19,9 +19,6 @@
 
 namespace {
 
-constexpr int kVecPerBlock = 32;              // tune_decide: vectors applied to one tile of candidates
-constexpr size_t kWsBudget = (size_t)256 << 20;   // sweep workspace per batch of vectors
-
 int fail(duet_ctx *ctx, int code, const char *msg) { return duet_fail(ctx, code, msg); }
 
 #include "duet_tune_feat.hip.h"            // FeatArgs, features_body(): the feature record (shared with duet_tune_cap.hip)
@@ -37,34 +34,7 @@ struct EfSeeds {
 
 __global__ __launch_bounds__(64) void tune_features(const FeatArgs a) { features_body(a, EfSeeds{}); }
 
-#include "duet_tune_derive.hip.h"          // Derived, derive(): what the tree compares (shared with duet_tune_line.hip)
-
-// predict_hp (:142-183) with the constants of vector t
-__device__ __forceinline__ uint32_t decide_vec(const Derived &d, const duet_tune_thresholds &t)
-{
-    uint32_t pred = 0;
-    if (d.cls == 0) {                                                               // :145-147
-        if (d.sv_ratio == 1.0 && d.svread >= t.c0_min_sv_num) pred = 3;
-    } else if (d.cls == 2) {                                                        // :148-155
-        if (d.sv_ratio >= t.c2_min_sv_ratio) {
-            if (d.diff <= t.c2_max_avgsc_diff) { if (d.svread >= t.c2_min_sv_num) pred = 3; }
-            else { if (d.hap0 >= t.c2_min_hap0) pred = 3; }
-        }
-    } else {                                                                        // :156-182
-        const bool gate = (d.hr <= t.c1_hapread_ratio && d.diff <= t.c1_max_avgsc_diff) || d.hr > t.c1_hapread_ratio;
-        if (d.onehap) {
-            if (d.sv_ratio <= t.c1_onehap_sv_ratio_lo) pred = 0;
-            else if (d.sv_ratio <= t.c1_onehap_sv_ratio_hi) { if (gate) pred = d.a1pos ? 1 : 2; }
-            else { if (gate) pred = 3; }
-        } else {
-            if (d.sv_ratio <= t.c1_twohap_sv_ratio_1) pred = 0;
-            else if (d.sv_ratio <= t.c1_twohap_sv_ratio_2) pred = d.refread > t.c1_max_ref_num ? 0 : (d.t1gt ? 1 : 2);
-            else if (d.sv_ratio <= t.c1_twohap_sv_ratio_3) pred = d.totsc <= t.c1_max_totsc_ratio ? 3 : (d.t1gt ? 1 : 2);
-            else pred = 3;
-        }
-    }
-    return pred;
-}
+#include "duet_tune_sweep.hip.h"           // decide_vec, stage_vectors, load_candidate, SweepWs, sweep_batch, stage_truth
 
 struct SweepArgs {
     const duet_tune_feature *feat;
@@ -75,13 +45,9 @@ struct SweepArgs {
     uint32_t *out_ps;                    // [C] or null (written by the first batch)
     // truth (has_truth)
     int has_truth;
-    uint32_t n_groups, n_uid, n_pairs;
     const uint16_t *flags;
     const uint32_t *group, *uid, *pair, *group_pair_off, *pair_uid;
-    // workspace of the batch, per vector: gcnt[3 * n_groups] (present, same calls, flip calls), then bit sets of
-    // uw words (tp ids, gt ids, hp ids) and pw words (same pairs, flip pairs)
-    uint32_t *ws;
-    uint32_t ws_words, uw, pw;
+    SweepWs ws;                          // of the batch
 };
 
 __device__ __forceinline__ void set_bit(uint32_t *w, uint32_t i)
@@ -100,22 +66,13 @@ __device__ __forceinline__ void wave_count(uint32_t *dst, bool pred)
 __global__ __launch_bounds__(256) void tune_decide(const SweepArgs a)
 {
     __shared__ duet_tune_thresholds s_t[kVecPerBlock];
-    const uint32_t vb0 = blockIdx.y * kVecPerBlock;
-    const uint32_t nvb = a.nv - vb0 < (uint32_t)kVecPerBlock ? a.nv - vb0 : (uint32_t)kVecPerBlock;
-    {
-        const double *src = (const double *)(a.vec + a.v0 + vb0);
-        double *dst = (double *)s_t;
-        for (uint32_t i = threadIdx.x; i < nvb * 14u; i += 256u) dst[i] = src[i];
-    }
-    __syncthreads();
+    uint32_t vb0;
+    const uint32_t nvb = stage_vectors(s_t, a.vec + a.v0, a.nv, &vb0);
     const uint32_t c = blockIdx.x * 256u + threadIdx.x;
     const bool live = c < a.C;
     duet_tune_feature f;
-    if (live) f = a.feat[c];
-    else memset(&f, 0, sizeof(f));
-    const bool elig = live && f.eligible;
-    if (!elig) f.deg = 1;                                        // (no division by zero in derive for the lanes that never decide)
-    const Derived d = derive(f);
+    bool elig;
+    const Derived d = load_candidate(a.feat, a.C, c, &f, &elig);
     if (a.out_ps && live && a.v0 == 0 && blockIdx.y == 0) a.out_ps[c] = elig ? f.ps : 0u;
     uint16_t fl = 0;
     uint32_t g = 0, u = 0, pr = 0;
@@ -138,8 +95,7 @@ __global__ __launch_bounds__(256) void tune_decide(const SweepArgs a)
         if (!__any(call)) continue;
         wave_count(&cnt->n_calls, call);
         wave_count(&cnt->n_raise, call && (fl & DUET_TUNE_RAISES));
-        uint32_t *ws = a.ws + (size_t)vb * a.ws_words;
-        uint32_t *gcnt = ws, *tp = ws + 3ull * a.n_groups, *gt = tp + a.uw, *same = gt + 2ull * a.uw, *flip = same + a.pw;
+        uint32_t *gcnt = a.ws.gcnt(vb), *tp = a.ws.tp(vb), *gt = a.ws.gt(vb), *same = a.ws.same(vb), *flip = a.ws.flip(vb);
         if (call) set_bit(gcnt + 3ull * g, 0);
         const bool hit = call && (fl & DUET_TUNE_MATCHED);
         wave_count(&cnt->call_tp, hit);
@@ -158,9 +114,8 @@ __global__ __launch_bounds__(256) void tune_decide(const SweepArgs a)
 __global__ __launch_bounds__(256) void tune_groups(const SweepArgs a)
 {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x, vb = blockIdx.y;
-    const bool live = g < a.n_groups;
-    uint32_t *ws = a.ws + (size_t)vb * a.ws_words;
-    uint32_t *gcnt = ws, *hp = ws + 3ull * a.n_groups + 2ull * a.uw, *same = hp + a.uw, *flip = same + a.pw;
+    const bool live = g < a.ws.n_groups;
+    uint32_t *gcnt = a.ws.gcnt(vb), *hp = a.ws.hp(vb), *same = a.ws.same(vb), *flip = a.ws.flip(vb);
     duet_tune_counts *cnt = a.counts + a.v0 + vb;
     const bool present = live && gcnt[3ull * g] != 0;
     wave_count(&cnt->n_groups, present);
@@ -186,10 +141,10 @@ __global__ __launch_bounds__(256) void tune_groups(const SweepArgs a)
 __global__ __launch_bounds__(256) void tune_popcount(const SweepArgs a)
 {
     const uint32_t w = blockIdx.x * 256u + threadIdx.x, vb = blockIdx.y;
-    const uint32_t *tp = a.ws + (size_t)vb * a.ws_words + 3ull * a.n_groups;
+    const uint32_t *tp = a.ws.tp(vb);                            // (gt and hp follow it, uw words each)
     uint32_t n[3] = {0, 0, 0};
-    if (w < a.uw)
-        for (int s = 0; s < 3; ++s) n[s] = (uint32_t)__popc(tp[(size_t)s * a.uw + w]);
+    if (w < a.ws.uw)
+        for (int s = 0; s < 3; ++s) n[s] = (uint32_t)__popc(tp[(size_t)s * a.ws.uw + w]);
     duet_tune_counts *cnt = a.counts + a.v0 + vb;
     uint32_t *dst[3] = {&cnt->base_tp, &cnt->base_gt, &cnt->base_hp};
     for (int s = 0; s < 3; ++s) {
@@ -220,21 +175,12 @@ __device__ __forceinline__ uint64_t peel(uint64_t rem, bool in, uint32_t st, uin
 __global__ __launch_bounds__(256) void tune_decide_strata(const SweepArgs a, const StrataArgs sa)
 {
     __shared__ duet_tune_thresholds s_t[kVecPerBlock];
-    const uint32_t vb0 = blockIdx.y * kVecPerBlock;
-    const uint32_t nvb = a.nv - vb0 < (uint32_t)kVecPerBlock ? a.nv - vb0 : (uint32_t)kVecPerBlock;
-    {
-        const double *src = (const double *)(a.vec + a.v0 + vb0);
-        double *dst = (double *)s_t;
-        for (uint32_t i = threadIdx.x; i < nvb * 14u; i += 256u) dst[i] = src[i];
-    }
-    __syncthreads();
+    uint32_t vb0;
+    const uint32_t nvb = stage_vectors(s_t, a.vec + a.v0, a.nv, &vb0);
     const uint32_t c = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
     duet_tune_feature f;
-    if (c < a.C) f = a.feat[c];
-    else memset(&f, 0, sizeof(f));
-    const bool elig = c < a.C && f.eligible;
-    if (!elig) f.deg = 1;
-    const Derived d = derive(f);
+    bool elig;
+    const Derived d = load_candidate(a.feat, a.C, c, &f, &elig);
     uint16_t fl = 0;
     uint32_t g = 0, u = 0, pr = 0, st = 0;
     if (elig) {
@@ -265,8 +211,7 @@ __global__ __launch_bounds__(256) void tune_decide_strata(const SweepArgs a, con
             }
             rem &= ~m;
         }
-        uint32_t *ws = a.ws + (size_t)vb * a.ws_words;
-        uint32_t *gcnt = ws, *tp = ws + 3ull * a.n_groups, *gt = tp + a.uw, *same = gt + 2ull * a.uw, *flip = same + a.pw;
+        uint32_t *gcnt = a.ws.gcnt(vb), *tp = a.ws.tp(vb), *gt = a.ws.gt(vb), *same = a.ws.same(vb), *flip = a.ws.flip(vb);
         if (call) set_bit(gcnt + 3ull * g, 0);
         if (hit) {
             set_bit(tp, u);
@@ -280,9 +225,8 @@ __global__ __launch_bounds__(256) void tune_decide_strata(const SweepArgs a, con
 __global__ __launch_bounds__(256) void tune_groups_strata(const SweepArgs a, const StrataArgs sa)
 {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x, vb = blockIdx.y, lane = threadIdx.x & 63u;
-    const bool live = g < a.n_groups;
-    uint32_t *ws = a.ws + (size_t)vb * a.ws_words;
-    uint32_t *gcnt = ws, *hp = ws + 3ull * a.n_groups + 2ull * a.uw, *same = hp + a.uw, *flip = same + a.pw;
+    const bool live = g < a.ws.n_groups;
+    uint32_t *gcnt = a.ws.gcnt(vb), *hp = a.ws.hp(vb), *same = a.ws.same(vb), *flip = a.ws.flip(vb);
     const bool present = live && gcnt[3ull * g] != 0;
     uint32_t take_c = 0, st = 0;
     if (present) {
@@ -321,10 +265,10 @@ __global__ __launch_bounds__(256) void tune_popcount_strata(const SweepArgs a, c
     if (threadIdx.x <= sa.S) s_off[threadIdx.x] = sa.uid_off[threadIdx.x];
     __syncthreads();
     const uint32_t w = blockIdx.x * 256u + threadIdx.x, vb = blockIdx.y, lane = threadIdx.x & 63u;
-    const uint32_t *tp = a.ws + (size_t)vb * a.ws_words + 3ull * a.n_groups;
+    const uint32_t *tp = a.ws.tp(vb);                            // (gt and hp follow it, uw words each)
     uint32_t n[3] = {0, 0, 0}, st = 0;
-    if (w < a.uw) {
-        for (int s = 0; s < 3; ++s) n[s] = (uint32_t)__popc(tp[(size_t)s * a.uw + w]);
+    if (w < a.ws.uw) {
+        for (int s = 0; s < 3; ++s) n[s] = (uint32_t)__popc(tp[(size_t)s * a.ws.uw + w]);
         if (n[0] | n[1] | n[2]) {
             uint32_t lo = 0, hi = sa.S - 1;                      // the first stratum whose range ends behind id 32 w
             while (lo < hi) {
@@ -407,9 +351,16 @@ int check_sweep_args(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_ca
 {
     if (n_cands && !feat) return fail(ctx, DUET_ERR_INVALID, "null feature array");
     if (n_vec && !vec) return fail(ctx, DUET_ERR_INVALID, "null threshold vectors");
-    if (truth && n_cands && (!truth->cand_flags || !truth->cand_group || !truth->cand_uid || !truth->cand_pair ||
-                             !truth->group_pair_off || (truth->n_pairs && !truth->pair_uid)))
-        return fail(ctx, DUET_ERR_INVALID, "null truth array");
+    return check_truth_arrays(ctx, truth, n_cands);
+}
+
+// the truth arrays and the workspace layout of a sweep against `truth`
+int set_truth(duet_ctx *ctx, const duet_tune_truth *truth, SweepArgs *a)
+{
+    a->has_truth = 1;
+    a->flags = truth->cand_flags; a->group = truth->cand_group; a->uid = truth->cand_uid; a->pair = truth->cand_pair;
+    a->group_pair_off = truth->group_pair_off; a->pair_uid = truth->pair_uid;
+    if (!sweep_ws_of(truth, &a->ws)) return fail(ctx, DUET_ERR_INVALID, "truth set too large");
     return DUET_OK;
 }
 
@@ -426,22 +377,10 @@ int check_strata(duet_ctx *ctx, const duet_tune_truth *truth, const duet_tune_st
     return DUET_OK;
 }
 
-// the truth arrays of a host run -> staging buffers 9 .. 14 of tune_ws; *dt = *truth with device pointers
-int stage_truth(duet_ctx *ctx, const duet_tune_truth *truth, size_t C, hipStream_t s, duet_tune_truth *dt)
+// the truth arrays of a host run -> staging buffers 9 .. 14 of tune_ws
+int stage_sweep_truth(duet_ctx *ctx, const duet_tune_truth *truth, size_t C, hipStream_t s, duet_tune_truth *dt)
 {
-    DevBuf *B = ctx->tune_ws.b;
-    const void *src[6] = {truth->cand_flags, truth->cand_group, truth->cand_uid, truth->cand_pair, truth->group_pair_off, truth->pair_uid};
-    const size_t bytes[6] = {C * 2, C * 4, C * 4, C * 4, ((size_t)truth->n_groups + 1) * 4, (size_t)truth->n_pairs * 4};
-    for (int i = 0; i < 6; ++i) {
-        int rc = duet_reserve(ctx, B[9 + i], bytes[i] ? bytes[i] : 16);
-        if (rc) return rc;
-        if (bytes[i] && src[i]) HIP_TRY(ctx, hipMemcpyAsync(B[9 + i].ptr, src[i], bytes[i], hipMemcpyHostToDevice, s));
-    }
-    *dt = *truth;
-    dt->cand_flags = (const uint16_t *)B[9].ptr; dt->cand_group = (const uint32_t *)B[10].ptr;
-    dt->cand_uid = (const uint32_t *)B[11].ptr; dt->cand_pair = (const uint32_t *)B[12].ptr;
-    dt->group_pair_off = (const uint32_t *)B[13].ptr; dt->pair_uid = (const uint32_t *)B[14].ptr;
-    return DUET_OK;
+    return stage_truth(ctx, truth, C, ((size_t)truth->n_groups + 1) * 4, (size_t)truth->n_pairs * 4, ctx->tune_ws.b + 9, s, dt);
 }
 
 }  // namespace
@@ -521,38 +460,20 @@ int duet_tune_sweep_device(duet_ctx *ctx, const duet_tune_feature *feat, uint32_
         return DUET_OK;
     }
     a.feat = feat; a.C = n_cands; a.vec = vec; a.counts = counts; a.out_pred = out_pred; a.out_ps = out_ps;
-    size_t per_vec = 0;
-    if (truth) {
-        a.has_truth = 1;
-        a.n_groups = truth->n_groups; a.n_uid = truth->n_uid; a.n_pairs = truth->n_pairs;
-        a.flags = truth->cand_flags; a.group = truth->cand_group; a.uid = truth->cand_uid; a.pair = truth->cand_pair;
-        a.group_pair_off = truth->group_pair_off; a.pair_uid = truth->pair_uid;
-        a.uw = (truth->n_uid + 31) / 32;
-        a.pw = (truth->n_pairs + 31) / 32;
-        per_vec = 3ull * truth->n_groups + 3ull * a.uw + 2ull * a.pw + 1;
-        if (per_vec > 0xFFFFFFFFull) return fail(ctx, DUET_ERR_INVALID, "truth set too large");
-        a.ws_words = (uint32_t)per_vec;
-    }
-    // vectors per batch: what the workspace budget holds (at least one), and what gridDim.y takes -- tune_decide runs one row of
-    // workgroups per kVecPerBlock vectors, tune_groups and tune_popcount (truth set only) one row per vector
-    uint32_t batch = n_vec;
-    if (per_vec) {
-        const size_t fit = kWsBudget / (per_vec * 4);
-        if (fit < batch) batch = fit ? (uint32_t)fit : 1u;
-    }
-    if (batch > 65535u * kVecPerBlock) batch = 65535u * kVecPerBlock;
-    if (per_vec && batch > 65535u) batch = 65535u;
+    if (truth && (rc = set_truth(ctx, truth, &a))) return rc;
+    const size_t per_vec = a.ws.words;                           // (0 without a truth set: no workspace, no tune_groups, no tune_popcount)
+    const uint32_t batch = sweep_batch(n_vec, a.ws.words);
     if (per_vec && (rc = duet_reserve(ctx, ctx->tune_ws.b[3], (size_t)batch * per_vec * 4))) return rc;
-    a.ws = (uint32_t *)ctx->tune_ws.b[3].ptr;
+    a.ws.base = (uint32_t *)ctx->tune_ws.b[3].ptr;
     const uint32_t tiles = (n_cands + 255) / 256;
     for (uint32_t v0 = 0; v0 < n_vec; v0 += batch) {
         const uint32_t nv = n_vec - v0 < batch ? n_vec - v0 : batch;
         a.v0 = v0; a.nv = nv;
-        if (per_vec) HIP_TRY(ctx, hipMemsetAsync(a.ws, 0, (size_t)nv * per_vec * 4, stream));
+        if (per_vec) HIP_TRY(ctx, hipMemsetAsync(a.ws.base, 0, (size_t)nv * per_vec * 4, stream));
         hipLaunchKernelGGL(tune_decide, dim3(tiles, (nv + kVecPerBlock - 1) / kVecPerBlock), dim3(256), 0, stream, a);
         if (per_vec) {
-            if (a.n_groups) hipLaunchKernelGGL(tune_groups, dim3((a.n_groups + 255) / 256, nv), dim3(256), 0, stream, a);
-            if (a.uw) hipLaunchKernelGGL(tune_popcount, dim3((a.uw + 255) / 256, nv), dim3(256), 0, stream, a);
+            if (a.ws.n_groups) hipLaunchKernelGGL(tune_groups, dim3((a.ws.n_groups + 255) / 256, nv), dim3(256), 0, stream, a);
+            if (a.ws.uw) hipLaunchKernelGGL(tune_popcount, dim3((a.ws.uw + 255) / 256, nv), dim3(256), 0, stream, a);
         }
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -582,7 +503,7 @@ int duet_tune_sweep_host(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t 
     if (out_pred && (rc = up(7, nullptr, K * C))) return rc;
     if (out_ps && (rc = up(8, nullptr, C * 4))) return rc;
     duet_tune_truth dt;
-    if (truth && (rc = stage_truth(ctx, truth, C, s, &dt))) return rc;
+    if (truth && (rc = stage_sweep_truth(ctx, truth, C, s, &dt))) return rc;
     rc = duet_tune_sweep_device(ctx, (const duet_tune_feature *)B[4].ptr, n_cands, (const duet_tune_thresholds *)B[5].ptr, n_vec,
                                 truth ? &dt : nullptr, counts ? (duet_tune_counts *)B[6].ptr : nullptr,
                                 out_pred ? (uint8_t *)B[7].ptr : nullptr, out_ps ? (uint32_t *)B[8].ptr : nullptr, s);
@@ -610,34 +531,23 @@ int duet_tune_sweep_strata_device(duet_ctx *ctx, const duet_tune_feature *feat, 
     SweepArgs a;
     memset(&a, 0, sizeof(a));
     a.feat = feat; a.C = n_cands; a.vec = vec; a.counts = counts;
-    a.has_truth = 1;
-    a.n_groups = truth->n_groups; a.n_uid = truth->n_uid; a.n_pairs = truth->n_pairs;
-    a.flags = truth->cand_flags; a.group = truth->cand_group; a.uid = truth->cand_uid; a.pair = truth->cand_pair;
-    a.group_pair_off = truth->group_pair_off; a.pair_uid = truth->pair_uid;
-    a.uw = truth->n_uid / 32;                    // (uid_off[S] == n_uid is a multiple of 32)
-    a.pw = (truth->n_pairs + 31) / 32;
-    const size_t per_vec = 3ull * truth->n_groups + 3ull * a.uw + 2ull * a.pw + 1;
-    if (per_vec > 0xFFFFFFFFull) return fail(ctx, DUET_ERR_INVALID, "truth set too large");
-    a.ws_words = (uint32_t)per_vec;
+    if ((rc = set_truth(ctx, truth, &a))) return rc;     // (uid_off[S] == n_uid is a multiple of 32: the id sets have n_uid / 32 words)
+    const size_t per_vec = a.ws.words;
     StrataArgs sa;
     memset(&sa, 0, sizeof(sa));
     sa.S = S; sa.cand_stratum = strata->cand_stratum; sa.group_stratum = strata->group_stratum;
     memcpy(sa.uid_off, strata->uid_off, ((size_t)S + 1) * 4);
-    // the batches of duet_tune_sweep_device with a truth set: what the workspace budget holds, at most 65,535 vectors
-    uint32_t batch = n_vec;
-    const size_t fit = kWsBudget / (per_vec * 4);
-    if (fit < batch) batch = fit ? (uint32_t)fit : 1u;
-    if (batch > 65535u) batch = 65535u;
+    const uint32_t batch = sweep_batch(n_vec, a.ws.words);      // (the batches of duet_tune_sweep_device with a truth set)
     if ((rc = duet_reserve(ctx, ctx->tune_ws.b[3], (size_t)batch * per_vec * 4))) return rc;
-    a.ws = (uint32_t *)ctx->tune_ws.b[3].ptr;
+    a.ws.base = (uint32_t *)ctx->tune_ws.b[3].ptr;
     const uint32_t tiles = (n_cands + 255) / 256;
     for (uint32_t v0 = 0; v0 < n_vec; v0 += batch) {
         const uint32_t nv = n_vec - v0 < batch ? n_vec - v0 : batch;
         a.v0 = v0; a.nv = nv;
-        HIP_TRY(ctx, hipMemsetAsync(a.ws, 0, (size_t)nv * per_vec * 4, stream));
+        HIP_TRY(ctx, hipMemsetAsync(a.ws.base, 0, (size_t)nv * per_vec * 4, stream));
         hipLaunchKernelGGL(tune_decide_strata, dim3(tiles, (nv + kVecPerBlock - 1) / kVecPerBlock), dim3(256), 0, stream, a, sa);
-        if (a.n_groups) hipLaunchKernelGGL(tune_groups_strata, dim3((a.n_groups + 255) / 256, nv), dim3(256), 0, stream, a, sa);
-        if (a.uw) hipLaunchKernelGGL(tune_popcount_strata, dim3((a.uw + 255) / 256, nv), dim3(256), 0, stream, a, sa);
+        if (a.ws.n_groups) hipLaunchKernelGGL(tune_groups_strata, dim3((a.ws.n_groups + 255) / 256, nv), dim3(256), 0, stream, a, sa);
+        if (a.ws.uw) hipLaunchKernelGGL(tune_popcount_strata, dim3((a.ws.uw + 255) / 256, nv), dim3(256), 0, stream, a, sa);
         HIP_TRY(ctx, hipGetLastError());
     }
     return DUET_OK;
@@ -664,7 +574,7 @@ int duet_tune_sweep_strata_host(duet_ctx *ctx, const duet_tune_feature *feat, ui
     void *dev[3];
     if ((rc = duet_stage_arrays(ctx, B + 4, src, bytes, 2, s, dev)) || (rc = duet_reserve(ctx, B[6], bytes[2] + 64))) return rc;
     duet_tune_truth dt;
-    if ((rc = stage_truth(ctx, truth, C, s, &dt))) return rc;
+    if ((rc = stage_sweep_truth(ctx, truth, C, s, &dt))) return rc;
     const void *ssrc[2] = {strata->cand_stratum, strata->group_stratum};
     const size_t sbytes[2] = {C, C ? (size_t)truth->n_groups : 0};
     void *sdev[2];

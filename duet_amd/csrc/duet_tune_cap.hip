@@ -93,11 +93,6 @@ __global__ __launch_bounds__(256) void tc_offsets(const uint64_t *seed_key, cons
 
 __global__ __launch_bounds__(64) void tc_features(const FeatArgs a, const CapSeeds sd) { features_body(a, sd); }
 
-struct Arena {
-    size_t total = 0;
-    size_t take(size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; }
-};
-
 int check_cap(duet_ctx *ctx, const duet_ef_problem *pr, uint32_t pc_cap)
 {
     if (!ctx || !pr) return fail(ctx, DUET_ERR_INVALID, "null argument");

@@ -108,11 +108,6 @@ __global__ __launch_bounds__(256) void cl_pick(const PickArgs a)
     a.out[i] = a.zero_front ? (li == 0 ? 0u : a.distinct[li - 1u]) : a.distinct[li];
 }
 
-struct Arena {
-    size_t total = 0;
-    size_t take(size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; }
-};
-
 int check_out(duet_ctx *ctx, const void *prob, uint32_t max_values, const uint32_t *out_caps, const uint32_t *n_caps, const uint32_t *n_distinct)
 {
     if (!ctx) return fail(nullptr, DUET_ERR_INVALID, "null context");

@@ -103,11 +103,6 @@ __global__ __launch_bounds__(256) void tl_vectors(const VecArgs a)
     for (uint32_t k = 0; k < kAxes; ++k) o[k] = k == a.axis ? v : b[k];
 }
 
-struct Arena {
-    size_t total = 0;
-    size_t take(size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; }
-};
-
 int check(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *base, uint32_t axis,
           uint32_t max_values, duet_tune_thresholds *out_vec, uint32_t *n_vec, uint32_t *n_distinct)
 {

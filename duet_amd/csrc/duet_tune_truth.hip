@@ -155,12 +155,6 @@ struct StorePair {
 
 __global__ void tt_close(const uint32_t *tot, uint32_t *group_pair_off) { group_pair_off[tot[0]] = tot[1]; }
 
-// the workspace: one arena in tune_ws.b[15]
-struct Arena {
-    size_t total = 0;
-    size_t take(size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; }
-};
-
 int check(duet_ctx *ctx, const duet_tune_truth_problem *pr, const duet_tune_truth *t, bool *table)
 {
     if (!ctx) return fail(nullptr, DUET_ERR_INVALID, "null context");

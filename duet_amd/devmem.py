@@ -354,10 +354,14 @@ class DeviceTune(object):
             p.cand_contig, p.cand_type, p.cand_pos, p.cand_len = result.cand_contig, result.cand_type, result.cand_pos, result.cand_span
         ctx.truth_build_device(p, truth if truth is not None else self.truth, self.stream())
 
+    def _sweep(self, ctx, n_cands, vec_ptr, K, counts):
+        """K vectors at vec_ptr over the features and truth arrays of the last build, through `counts` -> COUNTS_DTYPE[K] on the host."""
+        ctx.sweep_device(self.feat.data_ptr(), int(n_cands), vec_ptr, K, self.truth, counts.data_ptr(), self.stream())
+        return counts[:K * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).copy()
+
     def sweep(self, ctx, n_cands):
         """The K vectors over the features and truth arrays of the last build -> COUNTS_DTYPE[K] on the host."""
-        ctx.sweep_device(self.feat.data_ptr(), int(n_cands), self.vec_ptr, self.K, self.truth, self.counts.data_ptr(), self.stream())
-        return self.counts[:self.K * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).copy()
+        return self._sweep(ctx, n_cands, self.vec_ptr, self.K, self.counts)
 
     def set_strata(self, chrom_stratum, uid_off, base_uid=None, own_truth=False):
         """One stratified pass (tune.truth_side(strata=...), tune.chrom_strata): chrom_stratum u8[n_chrom], uid_off u32[S + 1] and
@@ -398,13 +402,18 @@ class DeviceTune(object):
         ctx.strata_build_device(p, truth, s['chrom_stratum'], s['strata'].n_strata, s['strata'].cand_stratum,
                                 s['strata'].group_stratum, self.stream())
 
+    def _sweep_strata(self, ctx, n_cands, vec_ptr, K, s, counts):
+        """K vectors at vec_ptr over the features and the truth arrays of the last build_strata of pass s, through `counts`
+        -> COUNTS_DTYPE[K, S] on the host."""
+        S = s['strata'].n_strata
+        ctx.sweep_strata_device(self.feat.data_ptr(), int(n_cands), vec_ptr, K, s.get('truth', self.truth), s['strata'],
+                                counts.data_ptr(), self.stream())
+        return counts[:K * S * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).reshape(K, S).copy()
+
     def sweep_strata(self, ctx, n_cands, strata=None):
         """The K vectors over the features and the truth arrays of the last build_strata -> COUNTS_DTYPE[K, S] on the host."""
         s = strata or self.strata
-        S = s['strata'].n_strata
-        ctx.sweep_strata_device(self.feat.data_ptr(), int(n_cands), self.vec_ptr, self.K, s.get('truth', self.truth), s['strata'],
-                                s['counts'].data_ptr(), self.stream())
-        return s['counts'][:self.K * S * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).reshape(self.K, S).copy()
+        return self._sweep_strata(ctx, n_cands, self.vec_ptr, self.K, s, s['counts'])
 
     def leaf_census(self, ctx, n_cands, vectors=None, strata=None):
         """The leaf census (duet_tune_leaf_census_device) over the resident features: `vectors` (float64[K, 14], uploaded; None:
@@ -427,19 +436,22 @@ class DeviceTune(object):
     # -- the line of one axis (tune.fit): a block of n_max + 2 vectors next to the grid's, made on the device --------------------
     VEC_BYTES = 8 * len(_lib.TUNE_NAMES)
 
+    def _line_block(self):
+        """The line block and its counts, allocated on first use."""
+        if getattr(self, 'line_vec', None) is None:
+            n = self.n_max + 2
+            self.line_vec = self.torch.zeros(n * self.VEC_BYTES, dtype=self.torch.uint8, device=self.device)
+            self.line_counts = self.torch.zeros(n * _lib.COUNTS_DTYPE.itemsize, dtype=self.torch.uint8, device=self.device)
+        return self.line_vec
+
     def line(self, ctx, n_cands, base, axis, max_values=0):
         """The line of `axis` through `base` (float64[14], host) from the resident features (duet_tune_line_device) into the
         line block, and `base` itself behind its n_vec vectors, so that one sweep scores the current vector in the same batch.
         -> (n_vec, n_distinct).  Raises ZeroDivisionError where a compared feature is not finite."""
-        torch = self.torch
-        if getattr(self, 'line_vec', None) is None:
-            n = self.n_max + 2
-            self.line_vec = torch.zeros(n * self.VEC_BYTES, dtype=torch.uint8, device=self.device)
-            self.line_counts = torch.zeros(n * _lib.COUNTS_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
         base = np.ascontiguousarray(base, dtype=np.float64).reshape(len(_lib.TUNE_NAMES))
-        n_vec, n_distinct = ctx.line_device(self.feat.data_ptr(), int(n_cands), base, axis, max_values, self.line_vec.data_ptr(),
+        n_vec, n_distinct = ctx.line_device(self.feat.data_ptr(), int(n_cands), base, axis, max_values, self._line_block().data_ptr(),
                                             self.stream())
-        self.line_vec[n_vec * self.VEC_BYTES:(n_vec + 1) * self.VEC_BYTES] = torch.from_numpy(base.view(np.uint8).copy()).to(self.device)
+        self.set_line_vector(base, n_vec)
         return n_vec, n_distinct
 
     def line_value(self, i, axis):
@@ -450,19 +462,15 @@ class DeviceTune(object):
     def sweep_line(self, ctx, n_cands, first, K):
         """Vectors first .. first + K of the line block over the features and truth arrays of the last build
         -> COUNTS_DTYPE[K] on the host."""
-        ctx.sweep_device(self.feat.data_ptr(), int(n_cands), self.line_vec.data_ptr() + first * self.VEC_BYTES, K, self.truth,
-                         self.line_counts.data_ptr(), self.stream())
-        return self.line_counts[:K * _lib.COUNTS_DTYPE.itemsize].cpu().numpy().view(_lib.COUNTS_DTYPE).copy()
+        return self._sweep(ctx, n_cands, self.line_vec.data_ptr() + first * self.VEC_BYTES, K, self.line_counts)
 
     def sweep_line_strata(self, ctx, n_cands, first, K, strata=None):
         """The same per stratum, over the truth arrays of the last build_strata -> COUNTS_DTYPE[K, S] on the host."""
         s = strata or self.strata
-        S, rec = s['strata'].n_strata, _lib.COUNTS_DTYPE.itemsize
         if s.get('line_counts') is None:
-            s['line_counts'] = self.torch.zeros((self.n_max + 2) * S * rec, dtype=self.torch.uint8, device=self.device)
-        ctx.sweep_strata_device(self.feat.data_ptr(), int(n_cands), self.line_vec.data_ptr() + first * self.VEC_BYTES, K,
-                                s.get('truth', self.truth), s['strata'], s['line_counts'].data_ptr(), self.stream())
-        return s['line_counts'][:K * S * rec].cpu().numpy().view(_lib.COUNTS_DTYPE).reshape(K, S).copy()
+            s['line_counts'] = self.torch.zeros((self.n_max + 2) * s['strata'].n_strata * _lib.COUNTS_DTYPE.itemsize, dtype=self.torch.uint8,
+                                                device=self.device)
+        return self._sweep_strata(ctx, n_cands, self.line_vec.data_ptr() + first * self.VEC_BYTES, K, s, s['line_counts'])
 
     # -- the line of the PC cap (tune.fit's pc_cap axis) -------------------------------------------------------------------------
     def cap_line(self, ctx, prob, max_values=0):
@@ -491,15 +499,10 @@ class DeviceTune(object):
         # once more, for one value more, and reads only how many came (nothing is downloaded)
         return caps, D, run(N + 1, fetch=False)[0] == N
 
-    def set_line_vector(self, base):
-        """`base` (float64[14], host) as vector 0 of the line block: what sweep_line(ctx, n, 0, 1) then scores."""
-        torch = self.torch
-        if getattr(self, 'line_vec', None) is None:
-            n = self.n_max + 2
-            self.line_vec = torch.zeros(n * self.VEC_BYTES, dtype=torch.uint8, device=self.device)
-            self.line_counts = torch.zeros(n * _lib.COUNTS_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+    def set_line_vector(self, base, i=0):
+        """`base` (float64[14], host) as vector i of the line block; i = 0: what sweep_line(ctx, n, 0, 1) then scores."""
         base = np.ascontiguousarray(base, dtype=np.float64).reshape(len(_lib.TUNE_NAMES))
-        self.line_vec[:self.VEC_BYTES] = torch.from_numpy(base.view(np.uint8).copy()).to(self.device)
+        self._line_block()[i * self.VEC_BYTES:(i + 1) * self.VEC_BYTES] = self.torch.from_numpy(base.view(np.uint8).copy()).to(self.device)
 
     def features_host(self, n_cands):
         """(--features) the feature records of the last setting, on the host."""

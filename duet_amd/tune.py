@@ -495,9 +495,160 @@ def _int_list(name, v):
     return [int(x) for x in vals]
 
 
+_NO_CAP_LINE = np.zeros(1, dtype=np.uint32), 0, True        # the cap line of a problem without marks: the one value 0, whole
+
+
+class _Callset(object):
+    """Candidate source: the callset of <home>/sv_calling/variants.vcf.  Ingested, keyed (candidate_keys) and uploaded once; a
+    setting's features are those of the resident DeviceProblem (ctx.features_device).  Every listed setting is computed, in the
+    listed order, a repeated one again.  A source has: settings, the (c, s, r, cap) tuples in row order; ingests(), which makes
+    the candidates resident and yields the settings to compute on them, in that order; and, between two steps of ingests(),
+    n_max (the most candidates a setting can have), texts (the CHROM text per candidate or contig, for chrom_strata), key(dt),
+    features(dt, setting, cap), result, cap_line(dt, max_values) and host(dt)."""
+
+    def __init__(self, ctx, home, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread):
+        self.ctx, self.home, self.bed, self.skip_phasing, self.ingest = ctx, home, bed, skip_phasing, (include_all_ctgs, thread)
+        self.settings = [(None,) + t for t in itertools.product(ss, rs, ps)]
+        self.result = None                                  # (the per-candidate form: build() reads no cluster result)
+
+    def ingests(self):
+        from duet_amd.devmem import DeviceProblem
+        _, s_, r_, _ = self.settings[0]
+        self.soa, txt = _candidates(self.home, s_, r_, *self.ingest)
+        self.cands = dict(pos=self.soa.cand_pos, svlen=self.soa.cand_svlen, **txt)
+        self.n_max, self.texts = self.soa.n_cands, self.cands['chrom']
+        self.dp = DeviceProblem(self.soa, s_, r_, device='cuda:%d' % self.ctx.device_id) if self.n_max else None
+        yield self.settings
+
+    def key(self, dt):
+        dt.set_candidates(self.soa.cand_pos, self.soa.cand_svlen, *candidate_keys(self.cands, self.bed, self.skip_phasing))
+
+    def features(self, dt, setting, cap):
+        """The features of `setting` under `cap` into dt.feat -> how many candidates that makes.  Raises ZeroDivisionError where
+        E/F would (the records are written all the same)."""
+        if self.n_max:
+            p = self.dp.problem
+            p.svlen_thres, p.suppread_thres = _lib.clamp_u32(setting['svlen_thres']), _lib.clamp_u32(setting['suppread_thres'])
+            self.ctx.features_device(p, dt.feat.data_ptr(), dt.stream(), pc_cap=cap)
+        return self.n_max
+
+    def cap_line(self, dt, max_values):
+        return dt.cap_line(self.ctx, self.dp.problem, max_values) if self.n_max else _NO_CAP_LINE
+
+    def host(self, dt):
+        """What on_features is handed: the candidates of the last features() call, on the host."""
+        return dict(self.cands, feat=dt.features_host(self.n_max))
+
+
+class _Bams(object):
+    """Candidate source: <home>/snp_phasing/*.bam through the fused svim-gpu pipeline.  The signatures are extracted and uploaded
+    once per distinct -s, ascending (max(s, 1) is the extraction's minimum size, as in svim_mode.sv_phasing_from_bams), keyed by
+    per-contig tables (contig_tables, bed_tables); a setting's features are DeviceSvim.run_features', which clusters again on
+    every call (the entry keeps no state between calls).  Each distinct setting is computed once, in c, r, cap order per -s."""
+
+    def __init__(self, ctx, home, cs, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread):
+        self.ctx, self.home, self.bed, self.skip_phasing, self.ingest = ctx, home, bed, skip_phasing, (include_all_ctgs, thread)
+        self.settings = list(itertools.product(cs, ss, rs, ps))
+
+    def ingests(self):
+        from duet_amd import svim_mode
+        from duet_amd.devmem import DeviceSvim
+        from duet_amd.native import NativeIngest
+        from duet_amd.read_file import init_chrom_list
+        include_all_ctgs, thread = self.ingest
+        chroms = init_chrom_list(include_all_ctgs, self.home)
+        self.texts = svim_mode.spelled_contigs(self.home, chroms)
+        self.tables = contig_tables(self.texts, self.skip_phasing) + (bed_tables(self.bed, self.texts) if self.bed else None,)
+        depth_bin = 1000                                    # (phase_from_bams's defaults)
+        for s_ in sorted(set(t[1] for t in self.settings)):
+            ing, got = NativeIngest.extract(self.home + '/snp_phasing/', chroms, thread, max(s_, 1), 20, depth_bin)
+            if ing is None:
+                raise RuntimeError('signature extraction declined the input: %s' % got)
+            ing.close()
+            self.n_max = len(got['pos'])
+            todo = list(dict.fromkeys(t for t in self.settings if t[1] == s_))
+            c_, _, r_, _ = todo[0]
+            self.ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, s_, r_, max_dist=c_,
+                                 device='cuda:%d' % self.ctx.device_id) if self.n_max else None
+            yield todo
+
+    @property
+    def result(self):
+        return self.ds.result if self.n_max else None
+
+    def key(self, dt):
+        dt.set_tables(*self.tables)
+
+    def features(self, dt, setting, cap):
+        if not self.n_max:
+            return 0
+        p = self.ds.sv_problem
+        p.marks.max_dist = setting['cluster_max_distance']
+        p.svlen_thres, p.suppread_thres = _lib.clamp_u32(setting['svlen_thres']), _lib.clamp_u32(setting['suppread_thres'])
+        return self.ds.run_features(self.ctx, dt.feat.data_ptr(), pc_cap=cap)
+
+    def cap_line(self, dt, max_values):
+        return dt.cap_line(self.ctx, self.ds.sv_problem, max_values) if self.n_max else _NO_CAP_LINE
+
+    def host(self, dt):
+        from duet_amd.svim_mode import SV_TYPE_NAMES
+        # (after a division by zero the records are written all the same: fetch() then asks the device for their count)
+        res = self.ds.fetch() if self.n_max else dict(cand_contig=[], cand_type=[], cand_pos=[], cand_span=[])
+        return dict(feat=dt.features_host(len(res['cand_pos'])), chrom=[self.texts[int(k)] for k in res['cand_contig']],
+                    pos=res['cand_pos'], svlen=res['cand_span'], svtype=[SV_TYPE_NAMES[int(t) & 3] for t in res['cand_type']])
+
+
+def _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_bams, pc_cap, bed, skip_phasing, include_all_ctgs, thread):
+    """The candidate source of sweep_settings / fit for their -s, -r, -c and pc_cap arguments (nothing is read yet); its ctx is
+    `ctx`, or the default context, opened once the arguments have passed."""
+    ss, rs = _int_list('svlen_thres', svlen_thres), _int_list('suppread_thres', suppread_thres)
+    ps = _cap_list(pc_cap)
+    if cluster_max_distance is not None and not from_bams:
+        raise ValueError('cluster_max_distance only acts on candidates clustered from the BAMs: it needs from_bams')
+    cs = [float(c) for c in (cluster_max_distance if cluster_max_distance is not None else (0.9,))]
+    if from_bams and not cs:
+        raise ValueError('cluster_max_distance: an empty list')
+    ctx = ctx or engine.default_context()
+    if from_bams:
+        return _Bams(ctx, home, cs, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread)
+    return _Callset(ctx, home, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread)
+
+
+def _make_resident(src, dt, setting, cap, passes):
+    """The features of `setting` under `cap`, their plain truth arrays and those of every pass of `passes`, resident in dt
+    -> the candidate count.  Raises ZeroDivisionError where the features report one (nothing is built then)."""
+    n = src.features(dt, setting, cap)
+    dt.build(src.ctx, n, src.result)
+    for p in passes:
+        dt.build_strata(src.ctx, n, src.result, p)
+    return n
+
+
+def _settings(src, vecs, base, passes, refdist, pctsim, on_features=None):
+    """The one loop over settings, for sweep_settings and fit: every setting of `src`, in the source's compute order, as
+    (lead, dt, n_cands, resident, src) -- lead: the setting's leading columns (_lead); dt: the DeviceTune that holds the setting's
+    features, its plain truth arrays and, per pass of `passes`, truth arrays and strata of the pass's own (resident: kind -> the
+    pass of set_strata); n_cands: the candidate count, None where the features report a division by zero (nothing is built
+    then).  on_features(lead, cands) is called when the consumer is done with the setting."""
+    from duet_amd.devmem import DeviceTune
+    for todo in src.ingests():
+        dt = DeviceTune(src.n_max, base, *_match_limits(refdist, pctsim), vectors=vecs, device='cuda:%d' % src.ctx.device_id)
+        src.key(dt)
+        resident = {kind: dt.set_strata(chrom_strata(src.texts, st), b['uid_off'], b['base_uid'], own_truth=True) for kind, st, b in passes}
+        for t in todo:
+            lead = _lead(*t)
+            try:
+                n = _make_resident(src, dt, lead, t[3], resident.values())
+            except ZeroDivisionError:
+                n = None
+            yield lead, dt, n, resident, src
+            if on_features is not None:
+                on_features(lead, src.host(dt))
+
+
 def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,), cluster_max_distance=None, from_bams=False,
                    refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False, thread=4, ctx=None, on_features=None,
-                   holdout=None, by_contig=None, _each=None, pc_cap=None, by_leaf=None):
+                   holdout=None, by_contig=None, pc_cap=None, by_leaf=None):
     """sweep() for every setting of -s (svlen_thres), -r (suppread_thres) and, with from_bams, -c (cluster_max_distance; default
     (0.9,)): -> list of rows, settings outermost in the order c, s, r, each row a dict of svlen_thres, suppread_thres
     [, cluster_max_distance], the 14 thresholds and the ten numbers.  from_bams: the candidates come from <home>/snp_phasing/*.bam
@@ -510,12 +661,11 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     holdout: a list of CHROM texts -- every row gains train_<score> (every other text) and test_<score> (the listed texts) for the
     ten SCORES.  by_contig: a list that receives one row per setting, vector and stratum of strata_by_contig() with a call or a
     truth record: the setting, vector, contig, the nine counts, n_base and the ten scores.  Each is one stratified pass per
-    setting (truth arrays with the pass's id numbering, duet_tune_sweep_strata_device) beside the plain sweep, whose rows do
-    not change.
-    _each (fit): called per setting as _each(setting, dt, n_cands, passes, ops) in place of the sweeps, with the features, the plain
-    truth arrays and every pass's own truth arrays and strata built and resident in dt (a DeviceTune); dt None: the setting's features
-    report a division by zero.  The rows returned are then nan.  ops (a _CapOps): how the fit's pc_cap axis recomputes the resident
-    features and truth arrays of this setting under another cap, and the cap line of its problem.
+    setting (truth arrays of its own with the pass's id numbering, duet_tune_sweep_strata_device) beside the plain sweep, whose
+    rows do not change.
+    The settings come from _settings(), the loop fit() runs too, over one of two candidate sources (_Callset, _Bams): per setting
+    it leaves the features and every truth array resident; here the vectors are swept over them, the census is taken and the rows
+    are made.
     pc_cap: a list of PC caps (a read with a PC tag above the cap does not vote; the reference's is 8100) -- the innermost setting,
     after c, s, r; every row then gains a leading pc_cap column.  A cap costs the features call (duet_ef_features_cap_device,
     duet_svim_features_cap_device), the truth build(s) and the sweep(s) on the resident problem: no ingest, no upload and, without
@@ -524,146 +674,30 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     and leaf -- one more pass per setting over what is already resident (duet_tune_leaf_census_device), after the plain sweep
     and after the holdout pass's; every other row and count stays what it is without it."""
     vecs = grid if isinstance(grid, np.ndarray) else expand_grid(grid)
-    ss, rs = _int_list('svlen_thres', svlen_thres), _int_list('suppread_thres', suppread_thres)
-    ps = _cap_list(pc_cap)
-    if cluster_max_distance is not None and not from_bams:
-        raise ValueError('cluster_max_distance only acts on candidates clustered from the BAMs: it needs from_bams')
-    ctx = ctx or engine.default_context()
+    src = _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_bams, pc_cap, bed, skip_phasing, include_all_ctgs, thread)
+    ctx = src.ctx
     base = truth_side(truth_vcf, bed, skip_phasing)
     passes = _strata_passes(truth_vcf, bed, skip_phasing, holdout, by_contig)
-    if from_bams:
-        cs = [float(c) for c in (cluster_max_distance if cluster_max_distance is not None else (0.9,))]
-        if not cs:
-            raise ValueError('cluster_max_distance: an empty list')
-        return _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features,
-                           passes, by_contig, _each, ps, by_leaf)
-    from duet_amd.devmem import DeviceProblem, DeviceTune
-    soa, txt = _candidates(home, ss[0], rs[0], include_all_ctgs, thread)
-    cands = dict(pos=soa.cand_pos, svlen=soa.cand_svlen, **txt)
-    key, chrom, n_chrom = candidate_keys(cands, bed, skip_phasing)
-    device = 'cuda:%d' % ctx.device_id
-    C = soa.n_cands
-    dt = DeviceTune(C, base, *_match_limits(refdist, pctsim), vectors=vecs, device=device)
-    dt.set_candidates(soa.cand_pos, soa.cand_svlen, key, chrom, n_chrom)
-    dp = DeviceProblem(soa, ss[0], rs[0], device=device) if C else None
-    resident = {kind: dt.set_strata(chrom_strata(cands['chrom'], st), b['uid_off'], b['base_uid'], own_truth=_each is not None)
-                for kind, st, b in passes}
-    out = []
-    for s_, r_, p_ in itertools.product(ss, rs, ps):
-        lead = _lead(None, s_, r_, p_)
-        counts, strata_counts, leaf = None, {}, None
-        try:
-            if C:
-                dp.problem.svlen_thres, dp.problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
-                ctx.features_device(dp.problem, dt.feat.data_ptr(), dt.stream(), pc_cap=p_)
-            dt.build(ctx, C)
-            if _each is None:
-                counts = dt.sweep(ctx, C)
-                if by_leaf is not None:
-                    leaf = [(dt.leaf_census(ctx, C), ('all',))]
-            for kind, p in resident.items():
-                dt.build_strata(ctx, C, strata=p)
-                if _each is None:
-                    strata_counts[kind] = dt.sweep_strata(ctx, C, p)
-                    if by_leaf is not None and kind == 'holdout':
-                        leaf.append((dt.leaf_census(ctx, C, strata=p), ('train', 'test')))
-            if _each is not None:
-                _each(lead, dt, C, resident, _CapOps(
-                    features=lambda cap: ctx.features_device(dp.problem, dt.feat.data_ptr(), dt.stream(), pc_cap=cap) if C else None,
-                    n_cands=lambda: C, build=lambda n: dt.build(ctx, n), build_strata=lambda n, p: dt.build_strata(ctx, n, strata=p),
-                    line=lambda max_values: dt.cap_line(ctx, dp.problem, max_values) if C else (np.zeros(1, dtype=np.uint32), 0, True)))
-        except ZeroDivisionError:
-            if _each is not None:
-                _each(lead, None, 0, resident, None)
-        if on_features is not None:
-            on_features(lead, dict(cands, feat=dt.features_host(C)))
-        rows = _rows(vecs, counts, base['n_base'], lead)
-        _strata_rows(rows, by_contig, vecs, strata_counts, passes, lead)
-        out.extend(rows)
-        if by_leaf is not None and _each is None:
-            for census, names in leaf if counts is not None else _leaf_nan(resident):
-                by_leaf.extend(leaf_rows(lead, range(len(vecs)), census, names))
-    return out
-
-
-def _sweep_bams(home, vecs, base, cs, ss, rs, refdist, pctsim, bed, skip_phasing, include_all_ctgs, thread, ctx, on_features,
-                passes=(), by_contig=None, _each=None, ps=(None,), by_leaf=None):
-    from duet_amd import svim_mode
-    from duet_amd.devmem import DeviceSvim, DeviceTune
-    from duet_amd.native import NativeIngest
-    from duet_amd.read_file import init_chrom_list
-    chroms = init_chrom_list(include_all_ctgs, home)
-    texts = svim_mode.spelled_contigs(home, chroms)
-    key_table, chrom_id, n_chrom = contig_tables(texts, skip_phasing)
-    bed_t = bed_tables(bed, texts) if bed else None
-    device = 'cuda:%d' % ctx.device_id
-    depth_bin = 1000                                        # (phase_from_bams's defaults)
     done = {}
-    for s_ in sorted(set(ss)):
-        ing, got = NativeIngest.extract(home + '/snp_phasing/', chroms, thread, max(s_, 1), 20, depth_bin)
-        if ing is None:
-            raise RuntimeError('signature extraction declined the input: %s' % got)
-        ing.close()
-        M = len(got['pos'])
-        dt = DeviceTune(M, base, *_match_limits(refdist, pctsim), vectors=vecs, device=device)
-        dt.set_tables(key_table, chrom_id, n_chrom, bed_t)
-        resident = {kind: dt.set_strata(chrom_strata(texts, st), b['uid_off'], b['base_uid'], own_truth=_each is not None)
-                    for kind, st, b in passes}
-        ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, s_, rs[0], max_dist=cs[0], device=device) if M else None
-        for c_, r_, p_ in itertools.product(cs, rs, ps):
-            if (c_, s_, r_, p_) in done:
-                continue
-            lead = _lead(c_, s_, r_, p_)
-            counts, N, strata_counts, leaf = None, 0, {}, None
-            try:
-                if M:
-                    # (every cap clusters again: the entry keeps no state between calls)
-                    ds.sv_problem.marks.max_dist = c_
-                    ds.sv_problem.svlen_thres, ds.sv_problem.suppread_thres = _lib.clamp_u32(s_), _lib.clamp_u32(r_)
-                    N = ds.run_features(ctx, dt.feat.data_ptr(), pc_cap=p_)
-                dt.build(ctx, N, ds.result if M else None)
-                if _each is None:
-                    counts = dt.sweep(ctx, N)
-                    if by_leaf is not None:
-                        leaf = [(dt.leaf_census(ctx, N), ('all',))]
-                for kind, p in resident.items():
-                    dt.build_strata(ctx, N, ds.result if M else None, p)
-                    if _each is None:
-                        strata_counts[kind] = dt.sweep_strata(ctx, N, p)
-                        if by_leaf is not None and kind == 'holdout':
-                            leaf.append((dt.leaf_census(ctx, N, strata=p), ('train', 'test')))
-                if _each is not None:
-                    found = [N]
-
-                    def features(cap):
-                        # (every value clusters again: duet_svim_features_cap_device keeps no state between caps)
-                        if M:
-                            found[0] = ds.run_features(ctx, dt.feat.data_ptr(), pc_cap=cap)
-
-                    _each(lead, dt, N, resident, _CapOps(
-                        features=features, n_cands=lambda: found[0], build=lambda n: dt.build(ctx, n, ds.result if M else None),
-                        build_strata=lambda n, p: dt.build_strata(ctx, n, ds.result if M else None, p),
-                        line=lambda max_values: dt.cap_line(ctx, ds.sv_problem, max_values) if M else (np.zeros(1, dtype=np.uint32), 0, True)))
-            except ZeroDivisionError:
-                if _each is not None:
-                    _each(lead, None, 0, resident, None)
-            done[(c_, s_, r_, p_)] = counts, strata_counts, leaf if counts is not None else _leaf_nan(resident)
-            if on_features is not None:
-                if M and ds.n_found is None:
-                    ds.n_found = ds.n_cands()           # (a division by zero: the records are written all the same)
-                res = ds.fetch() if M else dict(cand_contig=[], cand_type=[], cand_pos=[], cand_span=[])
-                on_features(lead, dict(
-                    feat=dt.features_host(len(res['cand_pos'])), chrom=[texts[int(k)] for k in res['cand_contig']],
-                    pos=res['cand_pos'], svlen=res['cand_span'],
-                    svtype=[svim_mode.SV_TYPE_NAMES[int(t) & 3] for t in res['cand_type']]))
+    for lead, dt, n, resident, _ in _settings(src, vecs, base, passes, refdist, pctsim, on_features):
+        counts, strata_counts, leaf = None, {}, _leaf_nan(resident)
+        if n is not None:
+            counts = dt.sweep(ctx, n)
+            if by_leaf is not None:
+                leaf = [(dt.leaf_census(ctx, n), ('all',))]
+            for kind, p in resident.items():
+                strata_counts[kind] = dt.sweep_strata(ctx, n, p)
+                if by_leaf is not None and kind == 'holdout':
+                    leaf.append((dt.leaf_census(ctx, n, strata=p), ('train', 'test')))
+        done[tuple(lead.values())] = counts, strata_counts, leaf
     out = []
-    for c_, s_, r_, p_ in itertools.product(cs, ss, rs, ps):
-        lead = _lead(c_, s_, r_, p_)
-        counts, strata_counts, leaf = done[(c_, s_, r_, p_)]
+    for t in src.settings:
+        lead = _lead(*t)
+        counts, strata_counts, leaf = done[tuple(lead.values())]
         rows = _rows(vecs, counts, base['n_base'], lead)
         _strata_rows(rows, by_contig, vecs, strata_counts, passes, lead)
         out.extend(rows)
-        if by_leaf is not None and _each is None:
+        if by_leaf is not None:
             for census, names in leaf:
                 by_leaf.extend(leaf_rows(lead, range(len(vecs)), census, names))
     return out
@@ -673,16 +707,6 @@ TRACE = ('round', 'axis', 'n_distinct', 'n_vec', 'exact', 'old', 'new', 'objecti
 
 
 CAP_AXIS = 'pc_cap'         # the 15th axis of the fit: not a field of the vector -- a step on it changes the features
-
-
-class _CapOps(object):
-    """What the pc_cap axis of the fit needs from the setting it runs in (sweep_settings hands one to _each):
-    features(cap): the features under that cap into the resident array (ZeroDivisionError where they report one); n_cands(): their
-    count; build(n) / build_strata(n, pass): the truth arrays of the resident features; line(max_values) -> (caps, D, whole line?)"""
-
-    def __init__(self, features, n_cands, build, build_strata, line):
-        self.features, self.n_cands, self.build, self.build_strata, self.line = features, n_cands, build, build_strata, line
-        self.cap = None                                      # the current cap, kept by _fit_setting
 
 
 def _axes(axes, fit_cap=False):
@@ -713,60 +737,57 @@ def _better(x, best):
     return not math.isnan(x) and (math.isnan(best) or x > best)
 
 
-def _cap_step(ctx, dt, ops, cur, max_values, score_of, n_base, hold, n_base_hold, ten):
-    """One step of the fit on the pc_cap axis: every value of the cap line, ascending, and last the current cap -- the features
-    under it, the truth arrays, the one current vector scored.  Moves ops.cap by the rule of every axis and leaves the features and
-    truth arrays of the cap it ends on resident.  -> (the trace row without its round, moved?)"""
-    caps, n_distinct, whole = ops.line(max_values)
+def _cap_step(src, dt, setting, cap, cur, max_values, score_of, n_base, hold, n_base_hold, ten):
+    """One step of the fit on the pc_cap axis of `setting` (its leading columns), from `cap`: every value of the source's cap
+    line, ascending, and last the current cap -- the features under it, the truth arrays, the one current vector scored.  Moves
+    the cap by the rule of every axis and leaves the features and truth arrays of the cap it ends on resident.
+    -> (the trace row without its round, the cap it ends on, the candidate count under that cap)"""
+    ctx, passes = src.ctx, [hold] if hold is not None else []
+    caps, n_distinct, whole = src.cap_line(dt, max_values)
     dt.set_line_vector(cur)
 
-    def resident(cap):
-        ops.features(cap)
-        n = ops.n_cands()
-        ops.build(n)
-        if hold is not None:
-            ops.build_strata(n, hold)
-        return n
-
-    def evaluate(cap):
-        """-> (objective, plain counts, strata counts or None); a cap whose features divide by zero: nan, nothing built or swept"""
+    def evaluate(c):
+        """-> (objective, plain counts, strata counts or None, candidate count); a cap whose features divide by zero: nan, nothing
+        built or swept"""
         try:
-            n = resident(cap)
+            n = _make_resident(src, dt, setting, c, passes)
         except ZeroDivisionError:
-            return math.nan, None, None
+            return math.nan, None, None, 0
         plain = dt.sweep_line(ctx, n, 0, 1)[0]
         if hold is None:
-            return ten(plain, n_base)[score_of], plain, None
+            return ten(plain, n_base)[score_of], plain, None, n
         sc = dt.sweep_line_strata(ctx, n, 0, 1, hold)[0]
-        return ten(sc[0], n_base_hold[0])[score_of], plain, sc
+        return ten(sc[0], n_base_hold[0])[score_of], plain, sc, n
 
     got = [evaluate(int(c)) for c in caps]
-    here = evaluate(ops.cap)
+    here = evaluate(cap)
     if here[1] is None:
         raise ZeroDivisionError('division by zero')
     best, pick = here[0], None
     for i, g in enumerate(got):
         if _better(g[0], best):
             best, pick = g[0], i
-    old = ops.cap
+    old = cap
     if pick is not None:
-        ops.cap = int(caps[pick])
-        resident(ops.cap)                                    # (the threshold axes that follow read these)
-    _, plain, sc = here if pick is None else got[pick]
-    row = dict(axis=CAP_AXIS, n_distinct=n_distinct, n_vec=len(caps), exact=int(whole), old=old, new=ops.cap,
+        cap = int(caps[pick])
+        _make_resident(src, dt, setting, cap, passes)       # (the threshold axes that follow read these)
+    _, plain, sc, n_cands = here if pick is None else got[pick]
+    row = dict(axis=CAP_AXIS, n_distinct=n_distinct, n_vec=len(caps), exact=int(whole), old=old, new=cap,
                objective_before=here[0], objective_after=best)
     row.update(zip(SCORES, ten(plain, n_base)))
     if hold is not None:
         for s_i, part in enumerate(('train', 'test')):
             row.update(('%s_%s' % (part, n), x) for n, x in zip(SCORES, ten(sc[s_i], n_base_hold[s_i])))
-    return row, pick is not None
+    return row, cap, n_cands
 
 
-def _fit_setting(ctx, dt, n_cands, start, axes, rounds, max_values, score_of, n_base, hold=None, n_base_hold=None, ops=None):
-    """Coordinate descent for one setting on the resident features and truth arrays of dt -> (vector, trace rows).
+def _fit_setting(ctx, dt, n_cands, start, axes, rounds, max_values, score_of, n_base, hold=None, n_base_hold=None, src=None,
+                 setting=None, cap=None):
+    """Coordinate descent for one setting on the resident features and truth arrays of dt
+    -> (vector, trace rows, the fitted cap, the candidate count of the features it leaves resident).
     hold: the holdout pass (its stratum 0 is `train`, whose score is the objective; stratum 1 `test` is only reported).
-    ops: the setting's _CapOps when CAP_AXIS is among the axes; ops.cap is the cap the resident features were computed under on
-    entry and the fitted cap on return."""
+    src, setting, cap -- for CAP_AXIS among the axes: the candidate source, the setting's leading columns and the cap the resident
+    features were computed under."""
     cur = np.array(start, dtype=np.float64)
     memo = {}
 
@@ -781,9 +802,8 @@ def _fit_setting(ctx, dt, n_cands, start, axes, rounds, max_values, score_of, n_
         moved = False
         for ax in axes:
             if ax == CAP_AXIS:
-                row, stepped = _cap_step(ctx, dt, ops, cur, max_values, score_of, n_base, hold, n_base_hold, ten)
-                n_cands = ops.n_cands()
-                moved = moved or stepped
+                row, cap, n_cands = _cap_step(src, dt, setting, cap, cur, max_values, score_of, n_base, hold, n_base_hold, ten)
+                moved = moved or row['new'] != row['old']
                 trace.append(dict(round=rnd, **row))
                 continue
             n_vec, n_distinct = dt.line(ctx, n_cands, cur, ax, max_values)
@@ -812,7 +832,7 @@ def _fit_setting(ctx, dt, n_cands, start, axes, rounds, max_values, score_of, n_
             trace.append(row)
         if not moved:
             break
-    return cur, trace
+    return cur, trace, cap, n_cands
 
 
 def _nan_row(holdout):
@@ -864,55 +884,48 @@ def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max
     with_cap = CAP_AXIS in ax
     score_of = SCORES.index(objective)
     ctx = ctx or engine.default_context()
-    n_base = truth_side(truth_vcf, bed, skip_phasing)['n_base']
-    n_base_hold = None
-    if holdout is not None:
-        n_base_hold = truth_side(truth_vcf, bed, skip_phasing, strata=strata_holdout(holdout))['n_base_strata']
-    fits = {}
+    base = truth_side(truth_vcf, bed, skip_phasing)
+    passes = _strata_passes(truth_vcf, bed, skip_phasing, holdout, None)
+    n_base, n_base_hold = base['n_base'], passes[0][2]['n_base_strata'] if passes else None
+    src = _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_bams, pc_cap, bed, skip_phasing, include_all_ctgs, thread)
 
-    def each(setting, dt, n_cands, resident, ops):
-        key = tuple(setting[n] for n in LEAD if n in setting)
-        if key in fits:
-            return
-        vec, trace, leaf = None, None, []
+    def one(setting, dt, n_cands, resident):
+        """The fit of one setting (n_cands None: its features report a division by zero) -> its dict of `fits`"""
+        vec, trace, cap, leaf = None, None, None, []
         hold = resident.get('holdout')
-        if dt is not None:
+        if n_cands is not None:
             try:
                 if with_cap:
-                    ops.cap = setting.get(CAP_AXIS, cap0 if cap0 is not None else _lib.PC_MAX)
-                    if ops.cap != setting.get(CAP_AXIS, _lib.PC_MAX):
+                    cap = setting.get(CAP_AXIS, cap0 if cap0 is not None else _lib.PC_MAX)
+                    if cap != setting.get(CAP_AXIS, _lib.PC_MAX):
                         # (the start comes from --start: the resident features are the setting's, those of 8100)
-                        ops.features(ops.cap)
-                        n_cands = ops.n_cands()
-                        ops.build(n_cands)
-                        if hold is not None:
-                            ops.build_strata(n_cands, hold)
+                        n_cands = _make_resident(src, dt, setting, cap, resident.values())
                 if by_leaf is not None:
                     leaf = [_leaf_census(ctx, dt, n_cands, resident, v0[None, :])]
-                vec, trace = _fit_setting(ctx, dt, n_cands, v0, ax, rounds, max_values, score_of, n_base, hold, n_base_hold, ops)
+                vec, trace, cap, n_cands = _fit_setting(ctx, dt, n_cands, v0, ax, rounds, max_values, score_of, n_base, hold, n_base_hold,
+                                                        src, setting, cap)
                 if by_leaf is not None:
-                    leaf.append(_leaf_census(ctx, dt, ops.n_cands() if with_cap else n_cands, resident, vec[None, :]))
+                    leaf.append(_leaf_census(ctx, dt, n_cands, resident, vec[None, :]))
             except ZeroDivisionError:
-                pass
+                trace = None
         if by_leaf is not None:
             for i, label in enumerate(('start', 'fitted')):
                 for census, names in leaf[i] if trace is not None else _leaf_nan(resident):
                     by_leaf.extend(leaf_rows(setting, (label,), census, names))
-        more = {CAP_AXIS: ops.cap} if with_cap and trace is not None else {}
         if trace is None:
-            fits[key] = dict(setting=dict(setting), vector=None, objective=math.nan, scores=dict.fromkeys(SCORES, math.nan),
-                             trace=[dict(setting, **_nan_row(holdout is not None))])
-            return
+            return dict(setting=dict(setting), vector=None, objective=math.nan, scores=dict.fromkeys(SCORES, math.nan),
+                        trace=[dict(setting, **_nan_row(holdout is not None))])
         last = trace[-1]
         obj = last['objective_after']
-        fits[key] = dict(setting=dict(setting), vector=None if math.isnan(obj) else vec, objective=obj,
-                         scores={n: last[n] for n in last if n in SCORES or n.startswith(('train_', 'test_'))},
-                         trace=[dict(setting, **r) for r in trace], **more)
+        return dict(setting=dict(setting), vector=None if math.isnan(obj) else vec, objective=obj,
+                    scores={n: last[n] for n in last if n in SCORES or n.startswith(('train_', 'test_'))},
+                    trace=[dict(setting, **r) for r in trace], **({CAP_AXIS: cap} if with_cap else {}))
 
-    rows = sweep_settings(home, truth_vcf, v0[None, :], svlen_thres, suppread_thres, cluster_max_distance, from_bams, refdist, pctsim, bed,
-                          skip_phasing, include_all_ctgs, thread, ctx=ctx, holdout=holdout, _each=each, pc_cap=pc_cap)
-    # (sweep_settings' rows come settings outermost, in c, s, r, pc_cap order)
-    out = [fits[k] for k in dict.fromkeys(tuple(r[n] for n in LEAD if n in r) for r in rows)]
+    fits = {}
+    for lead, dt, n, resident, _ in _settings(src, v0[None, :], base, passes, refdist, pctsim):
+        if tuple(lead.values()) not in fits:                # (the callset source computes a repeated setting again: it is fitted once)
+            fits[tuple(lead.values())] = one(lead, dt, n, resident)
+    out = [fits[k] for k in dict.fromkeys(tuple(_lead(*t).values()) for t in src.settings)]
     best = None
     for f in out:
         if f['vector'] is not None and (best is None or f['objective'] > best['objective']):

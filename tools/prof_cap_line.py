@@ -25,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from duet_amd import _lib, engine, synth, tune
-from duet_amd.devmem import DeviceProblem, DeviceTune
+from duet_amd.devmem import DeviceTune
 
 ROUNDS = 7
 CAP_MAX = _lib.PC_CAP_MAX
@@ -49,7 +49,12 @@ base = dict(base_off=np.searchsorted(base_key, np.arange(n_keys + 1)).astype(np.
 n_base = int(has.sum())
 
 dev = torch.device('cuda', 0)
-dp = DeviceProblem(soa, S_THRES, R_THRES, device='cuda:0')
+# the resident problem: the fit's own candidate source over the synthetic candidates in place of a work directory's
+tune._candidates = lambda *a: (soa, dict(chrom=[], ref=[], alt=[], svtype=[]))
+src = tune._Callset(ctx, 'unused', [S_THRES], [R_THRES], [None], '', False, False, 1)
+next(src.ingests())
+dp = src.dp
+SETTING = dict(svlen_thres=S_THRES, suppread_thres=R_THRES)
 dt = DeviceTune(C, base, 1000, 0.0, tune.vector()[None, :], device='cuda:0')
 dt.set_candidates(soa.cand_pos, np.maximum(soa.cand_svlen, 50), cand_key, ctg, K)
 sp = _lib.SvimProblem()
@@ -136,19 +141,16 @@ med = {k: round(statistics.median(v), 4) for k, v in pieces.items()}
 emit(dict(what='value', C=C, M=M, rounds=ROUNDS, dominant=max(med, key=med.get), total_ms=round(sum(med.values()), 4), **{k + '_ms': v for k, v in med.items()}))
 
 # (d): one whole step on the cap axis
-ops = tune._CapOps(features=lambda cap: ctx.features_device(dp.problem, dt.feat.data_ptr(), dt.stream(), pc_cap=cap), n_cands=lambda: C,
-                   build=lambda n: dt.build(ctx, n), build_strata=None, line=lambda max_values: dt.cap_line(ctx, dp.problem, max_values))
 for max_values in (256, 4096, 0):
     ts, row = [], None
     for rnd in range(ROUNDS + (1 if max_values else 0)):    # (the smaller steps have warmed everything up for the whole line)
         memo = {}
-        ops.cap = _lib.PC_MAX
-        ops.features(ops.cap)
+        src.features(dt, SETTING, _lib.PC_MAX)
         dt.build(ctx, C)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        row, moved = tune._cap_step(ctx, dt, ops, vec, max_values, score_of, n_base, None, None,
-                                    lambda rec, nb: memo.setdefault((rec.tobytes(), nb), tune.scores(rec, nb)))
+        row, _, _ = tune._cap_step(src, dt, SETTING, _lib.PC_MAX, vec, max_values, score_of, n_base, None, None,
+                                   lambda rec, nb: memo.setdefault((rec.tobytes(), nb), tune.scores(rec, nb)))
         torch.cuda.synchronize()
         if rnd or not max_values:
             ts.append((time.perf_counter() - t0) * 1e3)

@@ -126,7 +126,7 @@ for max_values in (0, 4096):
     for rnd in range(ROUNDS + 1):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        _, trace = tune._fit_setting(ctx, dt, C, base, list(range(14)), 1, max_values, tune.SCORES.index('hp_f1'), n_base)
+        _, trace, _, _ = tune._fit_setting(ctx, dt, C, base, list(range(14)), 1, max_values, tune.SCORES.index('hp_f1'), n_base)
         torch.cuda.synchronize()
         if rnd:
             ts.append((time.perf_counter() - t0) * 1e3)
