@@ -38,7 +38,8 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_tune_sweep_strata_host', 'duet_tune_line_device', 'duet_tune_line_host',
            'duet_ef_features_cap_device', 'duet_ef_features_cap_host', 'duet_svim_features_cap_device', 'duet_svim_features_cap_host',
            'duet_tune_cap_line_device', 'duet_tune_cap_line_host', 'duet_svim_cap_line_device', 'duet_svim_cap_line_host',
-           'duet_tune_leaf_census_device', 'duet_tune_leaf_census_host')
+           'duet_tune_leaf_census_device', 'duet_tune_leaf_census_host', 'duet_tune_leaves_device', 'duet_tune_leaves_host',
+           'duet_evidence_rows_device', 'duet_evidence_rows_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -156,8 +157,31 @@ LEAF_NAMES = ('c0_call', 'c0_drop', 'c2_low_ratio', 'c2_near_call', 'c2_near_few
               'c1_two_mid_hom', 'c1_two_mid_het', 'c1_two_hom')
 LEAF_PRED = (3, 0, 0, 3, 0, 3, 0, 0, 1, 0, 3, 0, 0, 0, 1, 3, 1, 3)
 N_LEAVES = len(LEAF_NAMES)
+# the evidence table (include/duet_ef.h, "Evidence table"): the two states beside the 18 leaves, the columns of a row
+LEAF_NO_SEED, LEAF_FILTERED = 0xFD, 0xFE
+EVIDENCE_COLUMNS = ('CHROM', 'POS', 'SVTYPE', 'SVLEN', 'SVREAD', 'REFREAD', 'MARKS', 'RULE', 'CLASS', 'HAP1', 'HAP2', 'HAP0', 'VOTERS',
+                    'PCSUM1', 'PCSUM2', 'PS', 'HP')
+EVIDENCE_ROW_MAX = 180          # a row's bytes at most, without its CHROM and SVTYPE pieces
 LEAF_COUNTS_NAMES = ('n_cands', 'n_listed', 'n_matched', 'n_calls', 'call_tp', 'call_gt', 'call_hp', 'n_raise')
 LEAF_COUNTS_DTYPE = np.dtype([(n, '<u4') for n in LEAF_COUNTS_NAMES])
+
+
+class EvidenceProblem(ctypes.Structure):
+    """duet_evidence_problem; chrom is host memory in both forms."""
+    _fields_ = [('n_cands', ctypes.c_uint32), ('n_contigs', ctypes.c_uint32)] + \
+               [(n, ctypes.c_void_p) for n in ('feat', 'leaf', 'pred', 'cand_pos', 'cand_svlen', 'pool')] + \
+               [('pool_bytes', ctypes.c_uint64)] + [(n, ctypes.c_void_p) for n in ('str_off', 'cand_contig', 'cand_type')] + \
+               [('chrom', ctypes.POINTER(ctypes.c_char_p))]
+
+
+def evidence_bound(n_cands, longest_chrom, longest_svtype=3):
+    """The size duet_evidence_rows_* can need at most (include/duet_ef.h): what the caller allocates for one call."""
+    return int(n_cands) * (int(longest_chrom) + int(longest_svtype) + EVIDENCE_ROW_MAX)
+
+
+def evidence_header():
+    """The header line of phased_sv.evidence.tsv."""
+    return ('\t'.join(EVIDENCE_COLUMNS) + '\n').encode()
 
 
 class TuneTruth(ctypes.Structure):
@@ -292,6 +316,12 @@ def load():
     lib.duet_tune_leaf_census_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                                  ctypes.POINTER(TuneTruth), ctypes.POINTER(TuneStrata), ctypes.c_void_p, ctypes.c_void_p]
     lib.duet_tune_leaf_census_host.argtypes = lib.duet_tune_leaf_census_device.argtypes[:-1]
+    lib.duet_tune_leaves_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p]
+    lib.duet_tune_leaves_host.argtypes = lib.duet_tune_leaves_device.argtypes[:-1]
+    lib.duet_evidence_rows_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(EvidenceProblem), ctypes.c_void_p, ctypes.c_uint64,
+                                              ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+    lib.duet_evidence_rows_host.argtypes = lib.duet_evidence_rows_device.argtypes[:-1]
     lib.duet_tune_line_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
@@ -807,6 +837,81 @@ class Context(object):
                                                    ctypes.c_void_p(stream))
         if rc:
             self._raise(rc)
+
+    # -- the evidence table (duet_evidence.hip) ---------------------------------------------------------------------------------
+    def leaves_host(self, feat, vector):
+        """duet_tune_leaves_host: feat FEATURE_DTYPE[C], one vector float64[14] -> (leaf u8[C], pred u8[C]): 0 .. 17, LEAF_NO_SEED,
+        LEAF_FILTERED, and the pred sweep_host returns for that vector."""
+        feat = np.ascontiguousarray(feat, dtype=FEATURE_DTYPE)
+        vec = np.ascontiguousarray(vector, dtype=np.float64).reshape(len(TUNE_NAMES))
+        leaf, pred = np.zeros(len(feat), dtype=np.uint8), np.zeros(len(feat), dtype=np.uint8)
+        rc = self.lib.duet_tune_leaves_host(self.handle, _ptr(feat), len(feat), _ptr(vec), _ptr(leaf), _ptr(pred))
+        if rc:
+            self._raise(rc)
+        return leaf, pred
+
+    def leaves_device(self, feat_ptr, n_cands, vector, leaf_ptr, pred_ptr, stream=0):
+        """duet_tune_leaves_device on resident arrays; the vector (float64[14]) is host memory."""
+        vec = np.ascontiguousarray(vector, dtype=np.float64).reshape(len(TUNE_NAMES))
+        rc = self.lib.duet_tune_leaves_device(self.handle, ctypes.c_void_p(feat_ptr), int(n_cands), _ptr(vec), ctypes.c_void_p(leaf_ptr),
+                                              ctypes.c_void_p(pred_ptr), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+
+    def evidence_rows_host(self, feat, leaf, pred, cand_pos, cand_svlen, rows=None, cand_contig=None, cand_type=None, chrom_texts=None):
+        """duet_evidence_rows_host: the data rows of the evidence table (EVIDENCE_COLUMNS) for host arrays -> bytes.
+        Text form: rows = dict(pool, str_off, pool_bytes) as NativeIngest.rows() gives it.  Table form: cand_contig u16[C],
+        cand_type u8[C] (0 .. 3 = DEL, INS, INV, DUP) and chrom_texts, the CHROM text per contig."""
+        feat = np.ascontiguousarray(feat, dtype=FEATURE_DTYPE)
+        C = len(feat)
+        arr = [np.ascontiguousarray(a, dtype=dt) for a, dt in ((leaf, np.uint8), (pred, np.uint8), (cand_pos, np.uint32),
+                                                               (cand_svlen, np.uint32))]
+        for a in arr:
+            assert len(a) == C, 'one entry per candidate'
+        p = EvidenceProblem()
+        p.n_cands = C
+        p.feat = feat.ctypes.data if C else None
+        p.leaf, p.pred, p.cand_pos, p.cand_svlen = [a.ctypes.data if C else None for a in arr]
+        keep = [feat, arr]
+        if rows is not None:
+            pool = np.ascontiguousarray(rows['pool'], dtype=np.uint8)
+            str_off = np.ascontiguousarray(rows['str_off'], dtype=np.uint32)
+            assert len(str_off) >= 4 * C + 1, 'str_off holds 4 C + 1 offsets'
+            p.pool_bytes = int(rows.get('pool_bytes', len(pool)))
+            if len(pool) == 0:
+                pool = np.zeros(1, dtype=np.uint8)          # (an empty pool is still the text form: a readable address)
+            p.pool, p.str_off = pool.ctypes.data, str_off.ctypes.data
+            keep += [pool, str_off]
+            d = np.diff(str_off[:4 * C + 1].astype(np.int64)) if C else np.zeros(0, dtype=np.int64)
+            cap = evidence_bound(C, max(int(d[0::4].max()), 0) if C else 0, max(int(d[3::4].max()), 0) if C else 0)
+        else:
+            contig = np.ascontiguousarray(cand_contig, dtype=np.uint16)
+            ctype = np.ascontiguousarray(cand_type, dtype=np.uint8)
+            assert len(contig) == C and len(ctype) == C, 'one entry per candidate'
+            texts = [None if c is None else (c if isinstance(c, bytes) else c.encode()) for c in chrom_texts]
+            chrom = (ctypes.c_char_p * max(len(texts), 1))(*texts)
+            p.n_contigs = len(texts)
+            p.cand_contig, p.cand_type = (a.ctypes.data if C else None for a in (contig, ctype))
+            p.chrom = chrom
+            keep += [contig, ctype, chrom]
+            cap = evidence_bound(C, max([len(c) for c in texts if c is not None] + [0]))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        n = ctypes.c_uint64(0)
+        rc = self.lib.duet_evidence_rows_host(self.handle, ctypes.byref(p), out.ctypes.data, ctypes.c_uint64(cap), ctypes.byref(n))
+        del keep
+        if rc:
+            self._raise(rc)
+        return out[:n.value].tobytes()
+
+    def evidence_rows_device(self, prob, out_ptr, cap, stream=0):
+        """duet_evidence_rows_device on resident arrays (an EvidenceProblem of device pointers) -> the text's exact size; raises
+        when cap is smaller (nothing is written then)."""
+        n = ctypes.c_uint64(0)
+        rc = self.lib.duet_evidence_rows_device(self.handle, ctypes.byref(prob), ctypes.c_void_p(out_ptr), ctypes.c_uint64(cap),
+                                                ctypes.byref(n), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return n.value
 
     def strata_build_device(self, prob, truth, chrom_stratum_ptr, n_strata, cand_stratum_ptr, group_stratum_ptr, stream=0):
         """duet_tune_strata_build_device on resident arrays (devmem.DeviceTune), after truth_build_device on the same prob / truth."""

@@ -25,7 +25,8 @@ def pipeline(a):
             (stages.snp_phasing, (a.OUTPUT, a.REFERENCE, a.BAM, a.thread)),
             (sv_phasing_from_bams, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs,
                                     a.cluster_max_distance, a.device, a.gpus, a.write_sv_calls,
-                                    getattr(a, 'threshold_vector', None), getattr(a, 'pc_cap_value', None))),
+                                    getattr(a, 'threshold_vector', None), getattr(a, 'pc_cap_value', None),
+                                    bool(getattr(a, 'write_evidence', False)))),
         )
     return (
         (stages.snp_calling, (a.OUTPUT, a.REFERENCE, a.BAM, a.min_allele_frequency, a.thread, a.include_all_ctgs)),
@@ -33,7 +34,7 @@ def pipeline(a):
                              a.min_support_read)),
         (stages.snp_phasing, (a.OUTPUT, a.REFERENCE, a.BAM, a.thread)),
         (sv_phasing, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs, a.device, a.gpus,
-                      a.threshold_vector, a.pc_cap_value)),
+                      a.threshold_vector, a.pc_cap_value, bool(getattr(a, 'write_evidence', False)))),
     )
 
 
@@ -57,6 +58,14 @@ def main(argv):
         if a.gpus > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
             raise SystemExit('duet: --pc_cap works on the single-GPU path only (not with --gpus > 1)')
         a.pc_cap_value = a.pc_cap
+    if a.write_evidence:
+        # (additive: the evidence table, OUTPUT/phased_sv.evidence.tsv -- it takes the route of --thresholds, with the default
+        # vector where none is given, so it is refused where that route is)
+        if a.gpus > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise SystemExit('duet: --write_evidence works on the single-GPU path only (not with --gpus > 1)')
+        if a.threshold_vector is None:
+            from duet_amd import tune
+            a.threshold_vector = tune.vector()
     check_envs(a.REFERENCE, a.BAM)
     os.makedirs(a.OUTPUT, exist_ok=True)
     set_logging(a.OUTPUT)

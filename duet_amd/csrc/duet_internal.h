@@ -89,6 +89,7 @@ struct duet_ctx {
     DuetOwnedBufs tune_cap_ws;             // feature export under a PC cap (duet_tune_cap.hip): workspace 0; host-run staging of the features 1
     DuetOwnedBufs tune_capline_ws;         // the line of the PC cap (duet_tune_capline.hip): workspace 0; host-run staging of the values 1, of a svim problem's mark reads 2 and read tags 3
     DuetOwnedBufs callset_ws;            // svim-gpu callset rows (duet_callset.hip): workspace 0-4, host-run staging 5-14, text 15
+    DuetOwnedBufs evidence_ws;             // evidence table (duet_evidence.hip): row lengths 0, row offsets 1, tile sums 2, status words and CHROM texts 3; host-run staging 4-12, text 13
     DuetOwnedBufs svim_rows_ws;            // svim-gpu rows of phased_sv.vcf (duet_svim_rows.hip): workspace 0-8, host-run staging 9-14, text 15
 };
 

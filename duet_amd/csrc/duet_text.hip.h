@@ -1,6 +1,7 @@
-// duet_text.hip.h -- device parts shared by the units that write VCF rows as text (duet_rows.hip, duet_callset.hip,
-// duet_svim_rows.hip): decimal digits, 64-bit shuffles, wave scans and sums, the 64-bit spine scan, the kept-candidate functors
-// of the compaction scan, and the two steps of a row that one wavefront writes piece by piece.  Included inside each unit's
+// duet_text.hip.h -- device parts shared by the units that write rows as text (duet_rows.hip, duet_callset.hip,
+// duet_svim_rows.hip, duet_evidence.hip): decimal digits, 64-bit shuffles, wave scans and sums, the 64-bit spine scan and the
+// tile scans around it, the kept-candidate functors of the compaction scan, and the two steps of a row that one wavefront writes
+// piece by piece.  Included inside each unit's
 // anonymous namespace (after duet_prims.hip.h where the unit uses that too); nothing here needs it.
 
 // decimal digits of v.  The compare chain is on rows_write's and sr_write's path, the loop on cs_write's: both stay.
@@ -101,6 +102,56 @@ __global__ __launch_bounds__(1024) void scan_spine_u64(uint64_t *part, uint32_t 
         const uint64_t v = part[i];
         part[i] = run;
         run += v;
+    }
+}
+
+// 64-bit exclusive scan of 32-bit row lengths, around scan_spine_u64 (row lengths are 32-bit, their sums are not): tiles of
+// kThreads * kItems rows, one workgroup of kThreads (a multiple of 64, at most 1024) each.  Templates: only a unit that launches
+// them compiles them.  (duet_callset.hip keeps the pair it had before these: cs_scan_reduce, cs_scan_apply.)
+//   rows_scan_reduce    part[tile] <- the tile's sum
+//   scan_spine_u64      part[] <- exclusive sums, *total
+//   rows_scan_apply     row_off[i] <- part[tile] + the sum of the tile's rows before i
+template <uint32_t kThreads, uint32_t kItems>
+__global__ __launch_bounds__(kThreads) void rows_scan_reduce(const uint32_t *len, uint32_t n, uint64_t *part)
+{
+    __shared__ uint64_t s_w[kThreads / 64];
+    const uint32_t tid = threadIdx.x, base = blockIdx.x * (kThreads * kItems) + tid * kItems;
+    uint64_t acc = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kItems; ++j)
+        if (base + j < n) acc += len[base + j];
+    acc = wave_sum(acc);
+    if ((tid & 63u) == 0) s_w[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        uint64_t sum = 0;
+        for (uint32_t w = 0; w < kThreads / 64; ++w) sum += s_w[w];
+        part[blockIdx.x] = sum;
+    }
+}
+
+template <uint32_t kThreads, uint32_t kItems>
+__global__ __launch_bounds__(kThreads) void rows_scan_apply(const uint32_t *len, uint32_t n, const uint64_t *part, uint64_t *row_off)
+{
+    __shared__ uint64_t s_w[kThreads / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t base = blockIdx.x * (kThreads * kItems) + tid * kItems;
+    uint32_t v[kItems];
+    uint64_t acc = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kItems; ++j) {
+        v[j] = base + j < n ? len[base + j] : 0u;
+        acc += v[j];
+    }
+    const uint64_t x = wave_scan(acc, lane);
+    if (lane == 63) s_w[wave] = x;
+    __syncthreads();
+    uint64_t run = part[blockIdx.x] + x - acc;
+    for (uint32_t w = 0; w < wave; ++w) run += s_w[w];
+#pragma unroll
+    for (uint32_t j = 0; j < kItems; ++j) {
+        if (base + j < n) row_off[base + j] = run;
+        run += v[j];
     }
 }
 

@@ -184,6 +184,7 @@ class DeviceSvim(DeviceCluster):
         self.out_pred = torch.zeros(self.M + 64, dtype=torch.uint8, device=self.device)
         self.out_ps = torch.zeros(self.M + 16, dtype=torch.int32, device=self.device)
         self.n_found = 0
+        self.feat, self.vector = None, None          # run_thresholds(keep_features=True): the candidates' features and its vector
 
     def run_fused(self, ctx, stream=None, wait=True):
         """wait=True: the call learns the candidate count (one host round trip inside).  wait=False: fully
@@ -192,6 +193,7 @@ class DeviceSvim(DeviceCluster):
             stream = self.torch.cuda.current_stream(self.device).cuda_stream
         ct = self._ct
         n = ct.c_uint32(0)
+        self.feat, self.vector = None, None          # (features of an earlier run_thresholds are not this run's)
         rc = ctx.lib.duet_svim_phase_device(ctx.handle, ct.byref(self.sv_problem), ct.byref(self.result),
                                             ct.c_void_p(self.out_pred.data_ptr()), ct.c_void_p(self.out_ps.data_ptr()),
                                             ct.byref(n) if wait else None, ct.c_void_p(stream))
@@ -207,13 +209,15 @@ class DeviceSvim(DeviceCluster):
         if stream is None:
             stream = self.torch.cuda.current_stream(self.device).cuda_stream
         self.n_found = None
+        self.feat, self.vector = None, None
         self.n_found = ctx.svim_features_device(self.sv_problem, self.result, feat_ptr, stream, pc_cap=pc_cap)
         return self.n_found
 
-    def run_thresholds(self, ctx, thresholds, stream=None, pc_cap=None):
+    def run_thresholds(self, ctx, thresholds, stream=None, pc_cap=None, keep_features=False):
         """run_fused with the decision's 14 constants taken from `thresholds` (float64[14]): the candidates' features
         (duet_svim_features_device; pc_cap: under that PC cap), then the one vector applied to them (duet_tune_sweep_device) into
-        out_pred / out_ps.  Raises ZeroDivisionError where the fused run would."""
+        out_pred / out_ps.  Raises ZeroDivisionError where the fused run would.  keep_features: the feature records stay resident
+        for evidence_rows (56 bytes a candidate, until the next run of any kind on this object)."""
         torch = self.torch
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -222,8 +226,41 @@ class DeviceSvim(DeviceCluster):
         d_vec = torch.from_numpy(vec.copy()).to(self.device)
         N = self.run_features(ctx, feat.data_ptr(), stream, pc_cap=pc_cap)
         ctx.apply_device(feat.data_ptr(), N, d_vec.data_ptr(), self.out_pred.data_ptr(), self.out_ps.data_ptr(), stream)
-        torch.cuda.current_stream(self.device).synchronize()       # (feat and d_vec are released when this returns)
+        torch.cuda.current_stream(self.device).synchronize()       # (d_vec, and feat unless kept, are released when this returns)
+        if keep_features:
+            self.feat, self.vector = feat, vec                     # (what evidence_rows reads)
         return stream
+
+    def evidence_rows(self, ctx, chrom_texts, stream=None):
+        """The data rows of the evidence table (_lib.EVIDENCE_COLUMNS) for the last run_thresholds' candidates: their leaves under
+        its vector (duet_tune_leaves_device) and one row each in candidate order, formatted on the device from the resident
+        features, cluster result and pred (duet_evidence_rows_device, the table form).  chrom_texts: CHROM text per contig.
+        -> uint8 numpy array of the text."""
+        torch = self.torch
+        if self.feat is None:
+            raise RuntimeError('evidence_rows needs run_thresholds(keep_features=True) as the last run on this object')
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.n_found is None:
+            self.n_found = self.n_cands()
+        N = self.n_found
+        if N == 0:
+            return np.zeros(0, dtype=np.uint8)
+        leaf = torch.zeros(N + 64, dtype=torch.uint8, device=self.device)
+        pred = torch.zeros(N + 64, dtype=torch.uint8, device=self.device)
+        ctx.leaves_device(self.feat.data_ptr(), N, self.vector, leaf.data_ptr(), pred.data_ptr(), stream)
+        texts = _lib.chrom_bytes(chrom_texts)
+        chrom = (self._ct.c_char_p * max(len(texts), 1))(*texts)
+        p = _lib.EvidenceProblem()
+        p.n_cands, p.n_contigs = N, len(texts)
+        p.feat, p.leaf, p.pred = self.feat.data_ptr(), leaf.data_ptr(), pred.data_ptr()
+        p.cand_pos, p.cand_svlen = self.result.cand_pos, self.result.cand_span
+        p.cand_contig, p.cand_type = self.result.cand_contig, self.result.cand_type
+        p.chrom = chrom
+        cap = _lib.evidence_bound(N, max([len(c) for c in texts] + [0]))
+        out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        n = ctx.evidence_rows_device(p, out.data_ptr(), cap, stream)
+        return out[:n].cpu().numpy()
 
     def vcf_rows(self, ctx, names, chrom_texts, stream=None):
         """Rows of sv_calling/variants.vcf for the last run_fused's candidates, formatted on the device from the resident

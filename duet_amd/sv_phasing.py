@@ -10,7 +10,9 @@ fields ...) and the Python path then takes over, so the observable behaviour is 
 Set DUET_NATIVE_INGEST=0 to force the Python path; DUET_DEVICE_ROWS=0 keeps the native path but formats the rows on
 the host instead of on the device.
 
-Four additive keyword arguments (upstream's five positionals are unchanged): `thresholds` = a vector of the decision's
+Five additive keyword arguments (upstream's five positionals are unchanged): `evidence` = also write
+<home>/phased_sv.evidence.tsv, one row per candidate with its vote, the rule of the tree it ended at and the call (the route of
+`thresholds`, with the default vector where none is given), `thresholds` = a vector of the decision's
 T1-T5 constants (duet_amd/tune.py; native single-GPU path only), `pc_cap` = the PC cap of the vote in place of 8100 (the same
 path; without `thresholds` the vector is the defaults), `device` = HIP device index of a
 single-GPU run, `gpus` = N > 1 shards the contigs over N GPUs of the node, one process per GPU
@@ -92,14 +94,28 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
     return True
 
 
-def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, vec, pc_cap=None):
+def evidence_path(home):
+    return home + '/phased_sv.evidence.tsv'
+
+
+def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, vec, pc_cap=None,
+                       evidence=False):
     """The native path with the decision's constants taken from `vec` (duet_amd/tune.py): ingest, the feature export (pc_cap:
-    under that PC cap, duet_ef_features_cap_host), a sweep of one vector that keeps its (pred, ps), the rows."""
-    from duet_amd import tune
+    under that PC cap, duet_ef_features_cap_host), a sweep of one vector that keeps its (pred, ps), the rows.
+    evidence: also <home>/phased_sv.evidence.tsv, one row per candidate formatted on the device (duet_evidence_rows_host, the text
+    form over the ingest's string pool)."""
+    from duet_amd import _lib, tune
     ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf)
     if ing is None:
-        raise RuntimeError('--thresholds / --pc_cap need the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
+        raise RuntimeError('--thresholds / --pc_cap / --write_evidence need the native ingest, which declined this input '
+                           '(or DUET_NATIVE_INGEST=0)')
+    table = None
     try:
+        rows = None
+        if evidence and ing.soa.n_cands:
+            rows = ing.rows()                       # (before the output file is created: a refusal leaves nothing behind)
+            if rows is None:
+                raise RuntimeError('--write_evidence: the native ingest has no string pool for this input')
         write_header(ing, include_all_ctgs, out_vcf)
         log_ingest(ing, chrom_list)
         logging.info('integrate read weight information')
@@ -113,14 +129,32 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
             feat = ctx.features_host(ing.soa, svlen_thres, suppread_thres, pc_cap=pc_cap)
             pred, ps = tune.apply(dict(feat=feat), vec, ctx=ctx)
             body = ing.emit_rows(pred, ps)
+        if evidence:
+            table = b''
+            if ing.soa.n_cands:
+                leaf, _ = tune.explain(dict(feat=feat), vec, ctx=ctx)
+                table = ctx.evidence_rows_host(feat, leaf, pred, ing.soa.cand_pos, ing.soa.cand_svlen, rows=rows)
         logging.info('write phased callset into .vcf file')
     finally:
         ing.close()
     with open(out_vcf, 'ab') as out:
         out.write(body)
+    if table is not None:
+        logging.info('write the evidence table into phased_sv.evidence.tsv')
+        with open(evidence_path(home), 'wb') as out:
+            out.write(_lib.evidence_header())
+            out.write(table)
 
 
-def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, device=0, gpus=1, thresholds=None, pc_cap=None):
+def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, device=0, gpus=1, thresholds=None, pc_cap=None,
+               evidence=False):
+    if evidence:
+        # (additive: the evidence table -- the route is that of `thresholds`, with the default vector where none is given)
+        from duet_amd import tune
+        if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise ValueError('evidence: single-GPU path only')
+        if thresholds is None:
+            thresholds = tune.vector()
     if pc_cap is not None:
         # (additive: the PC cap of the vote -- refused before anything is opened; the route is that of `thresholds`)
         from duet_amd import _lib, tune
@@ -140,7 +174,7 @@ def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, devi
         if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
             raise ValueError('thresholds: single-GPU path only')
         _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf,
-                           engine.default_context(int(device)), thresholds, pc_cap)
+                           engine.default_context(int(device)), thresholds, pc_cap, evidence=bool(evidence))
         done = True
     # (DUET_FORCE_RANKS=1: the one-process-per-GPU path even with one GPU -- rank 0 of 1 over RCCL; tests use it to take the
     # collective through the real backend on a one-GPU box)

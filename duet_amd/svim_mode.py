@@ -17,7 +17,7 @@ from duet_amd.native import NativeIngest
 from duet_amd.read_file import init_chrom_list
 
 
-def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_cap=None):
+def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_cap=None, evidence_texts=None):
     """-> compute(extracted arrays, svlen_thres, suppread_thres, max_dist, depth_bin) -> dict of result arrays, on ctx's GPU:
     stage A0 -> adapter -> step E/F in one device pipeline (duet_svim_phase_device).  chrom_texts (CHROM text per contig): the
     extracted arrays carry the marks' read names, and the result also holds `calls`, the rows of sv_calling/variants.vcf formatted
@@ -25,13 +25,17 @@ def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_ca
     `n_rows`, the data rows of phased_sv.vcf sorted and formatted on the resident arrays (duet_svim_phased_rows_device).
     thresholds (float64[14], --thresholds): the decision is made with this vector -- the candidates' features
     (duet_svim_features_device; pc_cap: under that PC cap, duet_svim_features_cap_device) and one vector applied to them
-    (duet_tune_sweep_device) in place of the fused run's E/F."""
+    (duet_tune_sweep_device) in place of the fused run's E/F.  evidence_texts (CHROM text per contig; needs thresholds): the result
+    also holds `evidence`, the data rows of the evidence table, one per candidate (duet_evidence_rows_device)."""
+    if evidence_texts is not None and thresholds is None:
+        raise ValueError('the evidence table needs a threshold vector')
+
     def compute(got, svlen_thres, suppread_thres, max_dist, depth_bin):
         from duet_amd.devmem import DeviceSvim
         ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, svlen_thres, suppread_thres,
                         max_dist=max_dist, device='cuda:%d' % ctx.device_id)
         if thresholds is not None:
-            ds.run_thresholds(ctx, thresholds, pc_cap=pc_cap)
+            ds.run_thresholds(ctx, thresholds, pc_cap=pc_cap, keep_features=evidence_texts is not None)
         else:
             ds.run_fused(ctx)
             ctx.check(ds.torch.cuda.current_stream(ds.device).cuda_stream)
@@ -42,6 +46,8 @@ def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_ca
             res['rows'], res['n_rows'] = ds.phased_rows(ctx, row_texts)
         if chrom_texts is not None:
             res['calls'] = ds.vcf_rows(ctx, got, chrom_texts)
+        if evidence_texts is not None:
+            res['evidence'] = ds.evidence_rows(ctx, evidence_texts)
         return res
     return compute
 
@@ -427,7 +433,7 @@ def rank_main(argv):
 
 
 def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, cluster_max_distance=0.9, device=0,
-                         gpus=1, write_sv_calls=False, thresholds=None, pc_cap=None):
+                         gpus=1, write_sv_calls=False, thresholds=None, pc_cap=None, evidence=False):
     """`duet ... -b svim-gpu -c <max distance>`: SV calling (signatures + clustering, what `-b svim` delegates to the
     external `svim alignment ... --cluster_max_distance c`, sv_calling.py:13-15) AND SV phasing on the GPU, from the
     haplotagged BAMs of <home>/snp_phasing -> <home>/phased_sv.vcf.  The clustering half is this repository's own rule
@@ -437,7 +443,15 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
     thresholds (--thresholds): a vector of the decision's 14 constants (duet_amd/tune.py: vector) in place of the built-in ones;
     single-GPU path only.
     pc_cap (--pc_cap): the PC cap of the vote in place of 8100, on the same route (without thresholds the vector is the defaults);
-    the clustered calls of --write_sv_calls do not depend on it."""
+    the clustered calls of --write_sv_calls do not depend on it.
+    evidence (--write_evidence): also <home>/phased_sv.evidence.tsv, one row per clustered candidate with its vote, the rule of the
+    tree it ended at and the call, formatted on the device; the route of thresholds (without one the vector is the defaults)."""
+    if evidence:
+        from duet_amd import tune
+        if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise ValueError('evidence: single-GPU path only')
+        if thresholds is None:
+            thresholds = tune.vector()
     if pc_cap is not None:
         from duet_amd import _lib, tune
         pc_cap = _lib.check_pc_cap(pc_cap)
@@ -490,7 +504,7 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
     def compute(*args):
         texts = spelled_contigs(home, chroms)
         return device_compute(ctx if ctx is not None else engine.default_context(int(device)), texts if write_sv_calls else None,
-                              row_texts=texts, thresholds=thresholds, pc_cap=pc_cap)(*args)
+                              row_texts=texts, thresholds=thresholds, pc_cap=pc_cap, evidence_texts=texts if evidence else None)(*args)
     res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
                           min_sv_size=max(int(svlen_thres), 1), names=bool(write_sv_calls), compute=compute)
     # the data rows come sorted and formatted from the device; without a single mark nothing ran and there are none
@@ -500,6 +514,12 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
     logging.info('  %d SV marks clustered into %d candidates, %d phased (clustering rule: parity unpinned)' % (
         res['n_marks'], len(res['pred']), n_rows))
     logging.info('write phased callset into .vcf file')
+    if evidence:
+        from duet_amd import _lib
+        from duet_amd.sv_phasing import evidence_path
+        with open(evidence_path(home), 'wb') as out:       # (without a single mark nothing ran: the header line alone)
+            out.write(_lib.evidence_header())
+            out.write(bytes(memoryview(np.ascontiguousarray(res.get('evidence', np.zeros(0, dtype=np.uint8))))))
     if write_sv_calls:
         with open(out_vcf, 'wb') as out:
             out.write(header_text(home, chroms).encode())

@@ -940,6 +940,14 @@ def apply(cands, thresholds, ctx=None):
     return pred[0], ps
 
 
+def explain(cands, thresholds, ctx=None):
+    """Why each candidate is called as it is under one vector: -> (leaf u8[C], pred u8[C]).  leaf is the exit of predict_hp's tree
+    the candidate takes (an index into _lib.LEAF_NAMES: what the leaf census counts), _lib.LEAF_NO_SEED where its contig has no
+    seed phase set, _lib.LEAF_FILTERED where the -s / -r / genotype filter drops it; pred is apply()'s."""
+    ctx = ctx or engine.default_context()
+    return ctx.leaves_host(cands['feat'], np.asarray(thresholds, dtype=np.float64).reshape(-1))
+
+
 def load_vector(path, with_cap=False):
     """--thresholds FILE.json: one partial vector (JSON object) -> float64[14].  The object may carry a 15th key, pc_cap (what
     `tune --fit --pc_cap` writes): with_cap: -> (float64[14], the cap or None); without, the key is accepted and left out."""

@@ -3,7 +3,8 @@
 
 Flag names, defaults, help texts and the positional order are upstream's (utils.py:19-44), so an
 existing command line works unchanged.  Two additive options select the device (--device) or shard the contigs
-over several GPUs (--gpus); --thresholds and --pc_cap replace the decision's constants on the single-GPU path.
+over several GPUs (--gpus); --thresholds and --pc_cap replace the decision's constants on the single-GPU path,
+--write_evidence adds the per-candidate evidence table there.
 """
 
 import argparse
@@ -63,6 +64,9 @@ def build_parser():
     ap.add_argument('--pc_cap', type=pc_cap_arg, default=None,
                     help='reads with a PC tag above this never vote in the SV phasing decision [8100, or the pc_cap of '
                          '--thresholds]; one GPU only (the native path, or -b svim-gpu)')
+    ap.add_argument('--write_evidence', action='store_true',
+                    help='also write OUTPUT/phased_sv.evidence.tsv: one row per SV candidate, phased or not, with its vote, the rule '
+                         'of the decision tree it ended at and the call; one GPU only (the native path, or -b svim-gpu)')
     ap.add_argument('--write_sv_calls', action='store_true',
                     help='with -b svim-gpu, also write the clustered SV calls to OUTPUT/sv_calling/variants.vcf')
     for name, text in _POSITIONALS:

@@ -680,6 +680,64 @@ DUET_API int duet_tune_leaf_census_host(duet_ctx *ctx, const duet_tune_feature *
                                         uint32_t n_vec, const duet_tune_truth *truth, const duet_tune_strata *strata,
                                         duet_tune_leaf_counts *out);
 
+/* Evidence table (duet_evidence.hip): per candidate the exit of the tree it takes under ONE vector, and
+ * one text row per candidate -- its evidence, the rule that decided it and the call.
+ *
+ * duet_tune_leaves_*: out_leaf[c] = the leaf (0 .. 17, the numbering above: what duet_tune_leaf_census_* counts) of an eligible
+ * candidate, DUET_TUNE_LEAF_NO_SEED for one that is kept but not eligible (its contig has no seed phase set),
+ * DUET_TUNE_LEAF_FILTERED for one that is not kept; out_pred[c] = what duet_tune_sweep_device writes to out_pred for that vector
+ * (0 for a candidate that is not eligible).  *vec is HOST memory in both forms.  _device: feat, out_leaf, out_pred device memory;
+ * asynchronous on `stream`.  _host: host arrays; uploads, runs the same kernel, downloads, synchronises.  n_cands == 0: DUET_OK.
+ * DUET_ERR_INVALID: a NULL array (or vector) with n_cands > 0. */
+#define DUET_TUNE_LEAF_NO_SEED 0xFDu
+#define DUET_TUNE_LEAF_FILTERED 0xFEu
+DUET_API int duet_tune_leaves_device(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *vec,
+                                     uint8_t *out_leaf, uint8_t *out_pred, void *stream);
+DUET_API int duet_tune_leaves_host(duet_ctx *ctx, const duet_tune_feature *feat, uint32_t n_cands, const duet_tune_thresholds *vec,
+                                   uint8_t *out_leaf, uint8_t *out_pred);
+
+/* The rows: one per candidate, in candidate order (no sort, no compaction), tab-separated, one '\n' behind each row:
+ *     CHROM POS SVTYPE SVLEN SVREAD REFREAD MARKS RULE CLASS HAP1 HAP2 HAP0 VOTERS PCSUM1 PCSUM2 PS HP
+ * (DUET_EVIDENCE_COLUMNS; the header line stays with the host).  POS = cand_pos; SVLEN = cand_svlen, unsigned; SVREAD, REFREAD,
+ * MARKS = the record's svread, refread, deg; RULE = `filtered`, `no_seed` or the leaf's name (DUET_TUNE_LEAF_NAMES) for leaf[c];
+ * CLASS = cls where the record is kept, else `.`; HAP1 HAP2 HAP0 VOTERS PCSUM1 PCSUM2 PS = hap1, hap2, hap0, allhap, t1, t2, ps
+ * where the record is eligible, else `.` each (t1, t2: full unsigned 64-bit decimals); HP = 1|0, 0|1, 1|1 for pred 1, 2, 3 and
+ * `.` for pred 0.  Integers only: every binary64 feature the tree compares is a quotient of these columns.
+ * Text form (pool != NULL; a caller's VCF): CHROM = pool[str_off[4c] .. str_off[4c+1]), SVTYPE = pool[str_off[4c+3] ..
+ * str_off[4c+4]) -- the layout of duet_rows_problem; either piece may be empty.  Table form (pool == NULL; a cluster result):
+ * CHROM = chrom[cand_contig[c]], SVTYPE = DEL, INS, INV, DUP for cand_type[c] = 0 .. 3, cand_svlen = the result's cand_span.
+ * _device: every array device memory except chrom (HOST), out_text device; asynchronous on `stream` apart from ONE host round
+ * trip that learns the text's size and the status word.  _host: everything HOST; uploads, runs the same kernels, copies the text
+ * back, synchronises.
+ * Both: *out_len = the text's exact size, always; when out_cap is smaller nothing is written and the call returns
+ * DUET_ERR_INVALID.  A row is at most its CHROM and SVTYPE pieces + 180 bytes, so
+ *     n_cands * (longest CHROM piece + longest SVTYPE piece + 180)           (table form: SVTYPE is 3 bytes)
+ * always suffices.  Row offsets are 64-bit: a text of 4 GiB or more is legal.  out_text may sit at any byte address.
+ * DUET_ERR_INVALID, nothing written, duet_last_error names the case: a NULL array that is needed; a leaf code other than 0 .. 17,
+ * DUET_TUNE_LEAF_NO_SEED, DUET_TUNE_LEAF_FILTERED; pred > 3; string offsets that descend or leave the pool (text form); a type
+ * code > 3, cand_contig >= n_contigs, n_contigs of 0 or more than 65535, a NULL chrom[k] (table form).  n_cands == 0: DUET_OK, zero
+ * bytes.  The workspace is the context's own (grown, never shrunk) and not E/F's: a call changes nothing a later duet_ef_run_* or
+ * duet_ef_features_* on the same context returns. */
+#define DUET_EVIDENCE_COLUMNS                                                                                                     \
+    {"CHROM", "POS", "SVTYPE", "SVLEN", "SVREAD", "REFREAD", "MARKS", "RULE", "CLASS", "HAP1", "HAP2", "HAP0", "VOTERS", "PCSUM1", \
+     "PCSUM2", "PS", "HP"}
+typedef struct duet_evidence_problem {
+    uint32_t n_cands, n_contigs;            /* n_contigs: table form only */
+    const duet_tune_feature *feat;          /* [C] */
+    const uint8_t *leaf, *pred;             /* [C] from duet_tune_leaves_* */
+    const uint32_t *cand_pos, *cand_svlen;  /* [C] */
+    const char *pool;                       /* text form */
+    uint64_t pool_bytes;
+    const uint32_t *str_off;                /* [4C+1] */
+    const uint16_t *cand_contig;            /* [C] table form */
+    const uint8_t *cand_type;               /* [C] */
+    const char *const *chrom;               /* HOST [n_contigs], NUL-terminated */
+} duet_evidence_problem;
+DUET_API int duet_evidence_rows_device(duet_ctx *ctx, const duet_evidence_problem *prob, char *out_text, uint64_t out_cap,
+                                       uint64_t *out_len, void *stream);
+DUET_API int duet_evidence_rows_host(duet_ctx *ctx, const duet_evidence_problem *prob, char *out_text, uint64_t out_cap,
+                                     uint64_t *out_len);
+
 /* The line of one axis (duet_tune_line.hip): with the other 13 constants fixed, every count of a sweep is a piecewise-constant
  * function of one constant and changes only where it crosses a value of the feature it is compared with, so one vector per
  * distinct value plus one sentinel covers every behaviour of the axis.  axis = the field's index in duet_tune_thresholds.  The
