@@ -345,6 +345,31 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None and a.size else ctypes.c_void_p(0)
 
 
+def fill_cluster_problem(p, contig, mtype, pos, span, max_dist, part_gap, part_max, normalizer, hints=True):
+    """The scalar fields of ClusterProblem p and, with hints, the four sizes the sort key is packed by, from the mark arrays
+    (the array pointers are the caller's: host or device)."""
+    M = len(pos)
+    p.n_marks, p.part_gap, p.part_max = M, int(part_gap), int(part_max)
+    p.max_dist, p.normalizer = float(max_dist), float(normalizer)
+    if hints and M:
+        p.n_contigs_hint = int(np.max(contig)) + 1
+        p.n_types_hint = int(np.max(mtype)) + 1
+        p.max_pos_hint = int(np.max(pos))
+        p.max_span_hint = max(int(np.max(span)), 1)
+    return M
+
+
+def bind_cluster_result(arrays, n_cands=None):
+    """-> a ClusterResult over the host arrays of dict `arrays` (a field without an array, or with an empty one, stays null);
+    n_cands: the c_uint32 the entry writes the count to."""
+    res = ClusterResult()
+    for k, a in arrays.items():
+        setattr(res, k, a.ctypes.data if a is not None and a.size else None)
+    if n_cands is not None:
+        res.n_cands = ctypes.addressof(n_cands)
+    return res
+
+
 CONTEXTS_CREATED = 0            # > 0: this process has initialised HIP (duet_amd/launch.py refuses to start ranks from it)
 
 
@@ -469,25 +494,15 @@ class Context(object):
         mtype = np.ascontiguousarray(mtype, dtype=np.uint8)
         pos = np.ascontiguousarray(pos, dtype=np.uint32)
         span = np.ascontiguousarray(span, dtype=np.uint32)
-        M = len(pos)
         prob = ClusterProblem()
-        prob.n_marks, prob.part_gap, prob.part_max = M, int(part_gap), int(part_max)
-        if hints and M:
-            prob.n_contigs_hint = int(contig.max()) + 1
-            prob.n_types_hint = int(mtype.max()) + 1
-            prob.max_pos_hint = int(pos.max())
-            prob.max_span_hint = max(int(span.max()), 1)
-        prob.max_dist, prob.normalizer = float(max_dist), float(normalizer)
+        M = fill_cluster_problem(prob, contig, mtype, pos, span, max_dist, part_gap, part_max, normalizer, hints)
         prob.mark_contig, prob.mark_type, prob.mark_pos, prob.mark_span = [
             a.ctypes.data if a.size else None for a in (contig, mtype, pos, span)]
         out = dict(order=np.zeros(max(M, 1), dtype=np.uint32), cand_off=np.zeros(M + 1, dtype=np.uint32),
                    cand_contig=np.zeros(max(M, 1), dtype=np.uint16), cand_type=np.zeros(max(M, 1), dtype=np.uint8),
                    cand_pos=np.zeros(max(M, 1), dtype=np.uint32), cand_span=np.zeros(max(M, 1), dtype=np.uint32))
         n = ctypes.c_uint32(0)
-        res = ClusterResult()
-        for k in ('order', 'cand_off', 'cand_contig', 'cand_type', 'cand_pos', 'cand_span'):
-            setattr(res, k, out[k].ctypes.data)
-        res.n_cands = ctypes.addressof(n)
+        res = bind_cluster_result(out, n)
         rc = self.lib.duet_cluster_run_host(self.handle, ctypes.byref(prob), ctypes.byref(res))
         if rc:
             self._raise(rc)
@@ -503,15 +518,8 @@ class Context(object):
         read_tag = np.ascontiguousarray(read_tag, dtype=np.uint64)
         depth = np.ascontiguousarray(depth, dtype=np.uint32)
         depth_off = np.ascontiguousarray(depth_off, dtype=np.uint32)
-        M = len(arr['pos'])
         p = SvimProblem()
-        p.marks.n_marks, p.marks.part_gap, p.marks.part_max = M, int(part_gap), int(part_max)
-        p.marks.max_dist, p.marks.normalizer = float(max_dist), float(normalizer)
-        if M:
-            p.marks.n_contigs_hint = int(arr['contig'].max()) + 1
-            p.marks.n_types_hint = int(arr['type'].max()) + 1
-            p.marks.max_pos_hint = int(arr['pos'].max())
-            p.marks.max_span_hint = max(int(arr['span'].max()), 1)
+        M = fill_cluster_problem(p.marks, arr['contig'], arr['type'], arr['pos'], arr['span'], max_dist, part_gap, part_max, normalizer)
         p.marks.mark_contig, p.marks.mark_type = arr['contig'].ctypes.data, arr['type'].ctypes.data
         p.marks.mark_pos, p.marks.mark_span = arr['pos'].ctypes.data, arr['span'].ctypes.data
         p.mark_read = arr['read'].ctypes.data
@@ -524,12 +532,8 @@ class Context(object):
                    cand_type=np.zeros(max(M, 1), dtype=np.uint8), cand_pos=np.zeros(max(M, 1), dtype=np.uint32),
                    cand_span=np.zeros(max(M, 1), dtype=np.uint32))
         n = ctypes.c_uint32(0)
-        res = ClusterResult()
-        for k in out:
-            setattr(res, k, out[k].ctypes.data)
         order = np.zeros(max(M, 1), dtype=np.uint32) if want_order else None
-        res.order = order.ctypes.data if want_order else None
-        res.n_cands = ctypes.addressof(n)
+        res = bind_cluster_result(dict(out, order=order), n)
         return p, res, out, order, n, (arr, read_tag, depth, depth_off)
 
     @staticmethod
@@ -592,9 +596,7 @@ class Context(object):
         arr = {k: np.ascontiguousarray(res[k], dtype=dt) for k, dt in (
             ('order', np.uint32), ('cand_off', np.uint32), ('cand_contig', np.uint16), ('cand_type', np.uint8),
             ('cand_pos', np.uint32), ('cand_span', np.uint32))}
-        r = ClusterResult()
-        for k in arr:
-            setattr(r, k, arr[k].ctypes.data)
+        r = bind_cluster_result(arr)
         depth = np.ascontiguousarray(depth, dtype=np.uint32)
         depth_off = np.ascontiguousarray(depth_off, dtype=np.uint32)
         p = SvimProblem()
@@ -636,9 +638,7 @@ class Context(object):
             ('cand_contig', np.uint16), ('cand_type', np.uint8), ('cand_pos', np.uint32), ('cand_span', np.uint32),
             ('pred', np.uint8), ('ps', np.uint32))}
         N = len(arr['pred'])
-        r = ClusterResult()
-        for k in ('cand_contig', 'cand_type', 'cand_pos', 'cand_span'):
-            setattr(r, k, arr[k].ctypes.data if N else None)
+        r = bind_cluster_result({k: arr[k] for k in ('cand_contig', 'cand_type', 'cand_pos', 'cand_span')})
         texts = chrom_bytes(chrom_texts)
         chrom = (ctypes.c_char_p * max(len(texts), 1))(*texts)
         cap = phased_rows_bound(int(np.count_nonzero(arr['pred'])), texts)

@@ -2976,55 +2976,19 @@ __global__ __launch_bounds__(256) void cl_emit(const ClParams p)
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// fused SVIM-mode pipeline: clusters -> the arrays ef_classify reads
-// ---------------------------------------------------------------------------------------------
-
-// ctg_off[k] = first candidate whose contig is >= k (candidates are sorted by contig); ctg_off[K] = N
-__global__ void sv_contig_offsets(const uint16_t *cand_contig, const uint32_t *n_cands, uint32_t K, uint32_t *ctg_off)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k > K) return;
-    const uint32_t N = *n_cands;
-    uint32_t lo = 0, hi = N;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (cand_contig[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    ctg_off[k] = k == K ? N : lo;
-}
-
-
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
-struct SvExtra {
-    const uint32_t *mark_in, *depth, *depth_off;
-    uint32_t depth_bin;
-    uint32_t *mark_out, *svread, *refread;
-    uint8_t *gt;
-    uint32_t *ef_ctg_off, *ef_zero;       // step E/F's plan, written by cl_emit (null: E/F plans for itself)
-    uint32_t n_contigs;
-};
-int cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_cluster_result *res, void *stream_, const SvExtra *sv);
 }  // namespace
 
 extern "C" {
 
 int duet_cluster_run_device(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_cluster_result *res, void *stream_)
 {
-    return cluster_run(ctx, pr, res, stream_, nullptr);
+    return duet_cluster_run(ctx, pr, res, stream_, nullptr);
 }
 
 }  // extern "C"
 
-namespace {
-
-int cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_cluster_result *res, void *stream_, const SvExtra *sv)
+// (declared in duet_internal.h: the fused pipeline of duet_svim.hip passes sv)
+int duet_cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_cluster_result *res, void *stream_, const SvExtra *sv)
 {
     if (!ctx) return duet_fail(nullptr, DUET_ERR_INVALID, "null context");
     if (!pr || !res) return duet_fail(ctx, DUET_ERR_INVALID, "null argument");
@@ -3422,8 +3386,6 @@ int cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_cluste
     return DUET_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 int duet_cluster_run_host(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_cluster_result *res)
@@ -3438,340 +3400,16 @@ int duet_cluster_run_host(duet_ctx *ctx, const duet_cluster_problem *pr, const d
     }
     hipStream_t s = ctx->own_stream;
     int rc;
-    const void *src[4] = {pr->mark_contig, pr->mark_type, pr->mark_pos, pr->mark_span};
-    const size_t ib[4] = {(size_t)M * 2, (size_t)M, (size_t)M * 4, (size_t)M * 4};
-    for (int i = 0; i < 4; ++i) {
-        if (!src[i]) return duet_fail(ctx, DUET_ERR_INVALID, "null array");
-        if ((rc = duet_reserve(ctx, ctx->cl_in[i], ib[i]))) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->cl_in[i].ptr, src[i], ib[i], hipMemcpyHostToDevice, s));
-    }
-    const size_t ob[6] = {(size_t)M * 4, ((size_t)M + 1) * 4 + 16, (size_t)M * 2, (size_t)M, (size_t)M * 4, (size_t)M * 4};
-    for (int i = 0; i < 6; ++i)
-        if ((rc = duet_reserve(ctx, ctx->cl_out[i], ob[i]))) return rc;
-    duet_cluster_problem d = *pr;
-    d.mark_contig = (const uint16_t *)ctx->cl_in[0].ptr;
-    d.mark_type = (const uint8_t *)ctx->cl_in[1].ptr;
-    d.mark_pos = (const uint32_t *)ctx->cl_in[2].ptr;
-    d.mark_span = (const uint32_t *)ctx->cl_in[3].ptr;
+    duet_cluster_problem d;
     duet_cluster_result r;
-    r.order = (uint32_t *)ctx->cl_out[0].ptr;
-    r.cand_off = (uint32_t *)ctx->cl_out[1].ptr;
-    r.cand_contig = (uint16_t *)ctx->cl_out[2].ptr;
-    r.cand_type = (uint8_t *)ctx->cl_out[3].ptr;
-    r.cand_pos = (uint32_t *)ctx->cl_out[4].ptr;
-    r.cand_span = (uint32_t *)ctx->cl_out[5].ptr;
-    r.n_cands = (uint32_t *)((char *)ctx->cl_out[1].ptr + ((size_t)M + 1) * 4);        // spare word after cand_off
+    if ((rc = duet_stage_marks(ctx, pr, &d, s))) return rc;
+    if ((rc = duet_bind_cluster_result(ctx, M, &r))) return rc;
     if ((rc = duet_cluster_run_device(ctx, &d, &r, s))) return rc;
     uint32_t n = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&n, r.n_cands, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     *res->n_cands = n;
-    HIP_TRY(ctx, hipMemcpy(res->order, r.order, (size_t)M * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_off, r.cand_off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_contig, r.cand_contig, (size_t)n * 2, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_type, r.cand_type, (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_pos, r.cand_pos, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_span, r.cand_span, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return DUET_OK;
-}
-
-int duet_svim_phase_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, uint8_t *out_pred,
-                           uint32_t *out_ps, uint32_t *n_cands_host, void *stream_)
-{
-    if (!ctx) return duet_fail(nullptr, DUET_ERR_INVALID, "null context");
-    if (!pr || !res || !out_pred || !out_ps) return duet_fail(ctx, DUET_ERR_INVALID, "null argument");
-    if (!pr->depth_off || pr->depth_bin == 0 || pr->n_contigs == 0 || pr->n_contigs > 65535)
-        return duet_fail(ctx, DUET_ERR_INVALID, "bad depth / contig description");
-    hipStream_t st = (hipStream_t)stream_;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint32_t M = pr->marks.n_marks, K = pr->n_contigs;
-    if (n_cands_host) *n_cands_host = 0;
-    if (M == 0) {
-        if (res->n_cands) HIP_TRY(ctx, hipMemsetAsync(res->n_cands, 0, 4, st));
-        return DUET_OK;
-    }
-    if (!pr->mark_read || !pr->depth) return duet_fail(ctx, DUET_ERR_INVALID, "null array");
-    // workspace: ctg_off + depth_off on the device, the adapted candidate columns, the gathered marks
-    int rc;
-    const size_t sz[5] = {((size_t)K + 1) * 4 * 2, (size_t)M * 4, (size_t)M * 4, (size_t)M, (size_t)M * 4};
-    for (int i = 0; i < 5; ++i)
-        if ((rc = duet_reserve(ctx, ctx->sv_ws[i], sz[i]))) return rc;
-    uint32_t *d_ctg_off = (uint32_t *)ctx->sv_ws[0].ptr, *d_depth_off = d_ctg_off + (K + 1);
-    // (uploaded only when they change: a pageable host-to-device copy in front of every run keeps the host from queueing the
-    // run's thirty launches ahead of the device -- 45 us of gaps per 0.37 ms run at 1 M marks)
-    // (the copy is ordered on the stream it was issued on: a run on ANOTHER stream uploads again -- after waiting for that
-    // stream, whose pageable copy may still be reading the host vector)
-    if (ctx->sv_depth_off_at != (void *)d_depth_off || ctx->sv_depth_off.size() != (size_t)K + 1 || ctx->sv_depth_off_stream != st ||
-        memcmp(ctx->sv_depth_off.data(), pr->depth_off, ((size_t)K + 1) * 4) != 0) {
-        // (the previous copy's source is about to change: wait for THAT COPY -- an event recorded behind it, not the stream it
-        // was issued on, which the caller may have destroyed in the meantime)
-        if (!ctx->sv_depth_off_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->sv_depth_off_ev, hipEventDisableTiming));
-        if (ctx->sv_depth_off_at) HIP_TRY(ctx, hipEventSynchronize(ctx->sv_depth_off_ev));
-        ctx->sv_depth_off.assign(pr->depth_off, pr->depth_off + K + 1);
-        HIP_TRY(ctx, hipMemcpyAsync(d_depth_off, ctx->sv_depth_off.data(), ((size_t)K + 1) * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipEventRecord(ctx->sv_depth_off_ev, st));
-        ctx->sv_depth_off_at = (void *)d_depth_off;
-        ctx->sv_depth_off_stream = st;
-    }
-    // clustering; its emit kernel also writes what a caller VCF would have carried (support, reference reads, GT)
-    // and the marks' read indices in output order
-    SvExtra sv;
-    sv.mark_in = pr->mark_read; sv.depth = pr->depth; sv.depth_off = d_depth_off; sv.depth_bin = pr->depth_bin;
-    sv.mark_out = (uint32_t *)ctx->sv_ws[4].ptr; sv.svread = (uint32_t *)ctx->sv_ws[1].ptr;
-    sv.refread = (uint32_t *)ctx->sv_ws[2].ptr; sv.gt = (uint8_t *)ctx->sv_ws[3].ptr;
-    sv.ef_ctg_off = nullptr; sv.ef_zero = nullptr; sv.n_contigs = K;
-    // (fully asynchronous runs: cl_emit writes step E/F's plan into E/F's workspace, sized for the bound of M candidates)
-    if (!n_cands_host && (rc = duet_ef_plan_on_device_prepare(ctx, K, M, st, &sv.ef_ctg_off, &sv.ef_zero))) return rc;
-    if ((rc = cluster_run(ctx, &pr->marks, res, st, &sv))) return rc;
-    if (!n_cands_host) {
-        // fully asynchronous: E/F is planned on the device from the candidates' contig column; buffers and grids are
-        // sized for the upper bound (a candidate has at least one mark) and the kernels read the real count
-        duet_ef_problem ef;
-        memset(&ef, 0, sizeof(ef));
-        ef.n_contigs = K; ef.n_cands = M; ef.n_marks = M; ef.n_reads = pr->n_reads;
-        ef.read_tag = pr->read_tag;
-        ef.cand_pos = res->cand_pos; ef.cand_svlen = res->cand_span; ef.cand_svread = sv.svread; ef.cand_refread = sv.refread;
-        ef.cand_gt_ok = sv.gt; ef.cand_off = res->cand_off; ef.mark_read = sv.mark_out;
-        ef.svlen_thres = pr->svlen_thres; ef.suppread_thres = pr->suppread_thres;
-        return duet_ef_run_planned_on_device(ctx, &ef, M, (const uint32_t *)res->n_cands, nullptr, (const uint16_t *)res->cand_contig,
-                                             out_pred, out_ps, st, true);
-    }
-    hipLaunchKernelGGL(sv_contig_offsets, dim3((K + 1 + 255) / 256), dim3(256), 0, st, (const uint16_t *)res->cand_contig,
-                       (const uint32_t *)res->n_cands, K, d_ctg_off);
-    std::vector<uint32_t> ctg_off(K + 1);
-    HIP_TRY(ctx, hipMemcpyAsync(ctg_off.data(), d_ctg_off, ((size_t)K + 1) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));             // the one host round trip: candidates per contig
-    const uint32_t N = ctg_off[K];
-    *n_cands_host = N;
-    if (N == 0) return DUET_OK;
-    duet_ef_problem ef;
-    memset(&ef, 0, sizeof(ef));
-    ef.n_contigs = K; ef.n_cands = N; ef.n_marks = M; ef.n_reads = pr->n_reads;
-    ef.cand_ctg_off = ctg_off.data();
-    ef.read_tag = pr->read_tag;
-    ef.cand_pos = res->cand_pos; ef.cand_svlen = res->cand_span; ef.cand_svread = sv.svread; ef.cand_refread = sv.refread;
-    ef.cand_gt_ok = sv.gt; ef.cand_off = res->cand_off; ef.mark_read = sv.mark_out;
-    ef.svlen_thres = pr->svlen_thres; ef.suppread_thres = pr->suppread_thres;
-    return duet_ef_run_device(ctx, &ef, out_pred, out_ps, st);
-}
-
-int duet_svim_phase_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, uint8_t *out_pred, uint32_t *out_ps)
-{
-    if (!ctx) return duet_fail(nullptr, DUET_ERR_INVALID, "null context");
-    if (!pr || !res || !res->n_cands || !out_pred || !out_ps) return duet_fail(ctx, DUET_ERR_INVALID, "null argument");
-    if (!pr->depth_off || pr->n_contigs == 0) return duet_fail(ctx, DUET_ERR_INVALID, "bad depth / contig description");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint32_t M = pr->marks.n_marks;
-    *res->n_cands = 0;
-    if (M == 0) return DUET_OK;
-    // every array is on the host here: what the device entry has to trust is checked -- a contig id beyond the depth description
-    // would index sv_depth_off / the E/F plan outside their K + 1 entries
-    if (!res->cand_off || !res->cand_contig || !res->cand_type || !res->cand_pos || !res->cand_span)
-        return duet_fail(ctx, DUET_ERR_INVALID, "null result array");
-    for (uint32_t k = 0; k < pr->n_contigs; ++k)
-        if (pr->depth_off[k] > pr->depth_off[k + 1]) return duet_fail(ctx, DUET_ERR_INVALID, "depth_off must be non-decreasing");
-    if (!pr->marks.mark_contig) return duet_fail(ctx, DUET_ERR_INVALID, "null array");
-    for (uint32_t i = 0; i < M; ++i)
-        if (pr->marks.mark_contig[i] >= pr->n_contigs)
-            return duet_fail(ctx, DUET_ERR_INVALID, "a mark's contig id is not below n_contigs (the depth description's contig count)");
-    hipStream_t s = ctx->own_stream;
-    int rc;
-    const size_t n_depth = pr->depth_off[pr->n_contigs];
-    const void *src[7] = {pr->marks.mark_contig, pr->marks.mark_type, pr->marks.mark_pos, pr->marks.mark_span, pr->mark_read, pr->read_tag, pr->depth};
-    const size_t ib[7] = {(size_t)M * 2, (size_t)M, (size_t)M * 4, (size_t)M * 4, (size_t)M * 4, (size_t)pr->n_reads * 8, n_depth * 4};
-    DevBuf *in[7] = {&ctx->cl_in[0], &ctx->cl_in[1], &ctx->cl_in[2], &ctx->cl_in[3], &ctx->sv_in[0], &ctx->sv_in[1], &ctx->sv_in[2]};
-    for (int i = 0; i < 7; ++i) {
-        if (!src[i] && ib[i]) return duet_fail(ctx, DUET_ERR_INVALID, "null array");
-        if ((rc = duet_reserve(ctx, *in[i], ib[i] + 16))) return rc;           // (+16: a readable word even for an empty table)
-        if (ib[i]) HIP_TRY(ctx, hipMemcpyAsync(in[i]->ptr, src[i], ib[i], hipMemcpyHostToDevice, s));
-    }
-    const size_t ob[6] = {(size_t)M * 4, ((size_t)M + 1) * 4 + 16, (size_t)M * 2, (size_t)M, (size_t)M * 4, (size_t)M * 4};
-    for (int i = 0; i < 6; ++i)
-        if ((rc = duet_reserve(ctx, ctx->cl_out[i], ob[i]))) return rc;
-    if ((rc = duet_reserve(ctx, ctx->sv_out[0], (size_t)M + 16))) return rc;
-    if ((rc = duet_reserve(ctx, ctx->sv_out[1], (size_t)M * 4 + 16))) return rc;
-    duet_svim_problem d = *pr;
-    d.marks.mark_contig = (const uint16_t *)ctx->cl_in[0].ptr;
-    d.marks.mark_type = (const uint8_t *)ctx->cl_in[1].ptr;
-    d.marks.mark_pos = (const uint32_t *)ctx->cl_in[2].ptr;
-    d.marks.mark_span = (const uint32_t *)ctx->cl_in[3].ptr;
-    d.mark_read = (const uint32_t *)ctx->sv_in[0].ptr;
-    d.read_tag = (const uint64_t *)ctx->sv_in[1].ptr;
-    d.depth = (const uint32_t *)ctx->sv_in[2].ptr;
-    duet_cluster_result r;
-    r.order = (uint32_t *)ctx->cl_out[0].ptr;
-    r.cand_off = (uint32_t *)ctx->cl_out[1].ptr;
-    r.cand_contig = (uint16_t *)ctx->cl_out[2].ptr;
-    r.cand_type = (uint8_t *)ctx->cl_out[3].ptr;
-    r.cand_pos = (uint32_t *)ctx->cl_out[4].ptr;
-    r.cand_span = (uint32_t *)ctx->cl_out[5].ptr;
-    r.n_cands = (uint32_t *)((char *)ctx->cl_out[1].ptr + ((size_t)M + 1) * 4);        // spare word after cand_off
-    uint32_t n = 0;
-    if ((rc = duet_svim_phase_device(ctx, &d, &r, (uint8_t *)ctx->sv_out[0].ptr, (uint32_t *)ctx->sv_out[1].ptr, &n, s))) return rc;
-    if ((rc = duet_ef_check(ctx, s))) return rc;                                        // (synchronises; DUET_ERR_DIV_ZERO comes out here)
-    *res->n_cands = n;
-    if (res->order) HIP_TRY(ctx, hipMemcpy(res->order, r.order, (size_t)M * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_off, r.cand_off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_contig, r.cand_contig, (size_t)n * 2, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_type, r.cand_type, (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_pos, r.cand_pos, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_span, r.cand_span, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out_pred, ctx->sv_out[0].ptr, (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out_ps, ctx->sv_out[1].ptr, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return DUET_OK;
-}
-
-// The fused pipeline up to the adapted E/F problem, then the features of that problem (duet_tune.hip) instead of its decisions: the
-// host-planned branch of duet_svim_phase_device with duet_ef_features_device in place of duet_ef_run_device.  (That entry stays
-// as it is -- its asynchronous branch has no counterpart here -- so the set-up in front of the clustering is restated.)
-// (pc_cap == nullptr: the reference's cap through duet_ef_features_device; else duet_ef_features_cap_device with *pc_cap)
-static int svim_features_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat,
-                                uint32_t *n_cands_host, void *stream_, const uint32_t *pc_cap)
-{
-    if (!ctx) return duet_fail(nullptr, DUET_ERR_INVALID, "null context");
-    if (pc_cap && *pc_cap > (1u << 30) - 3u) return duet_fail(ctx, DUET_ERR_INVALID, "pc_cap is above 2^30 - 3 (the tag word saturates pc at 2^30 - 2)");
-    if (!pr || !res || !out_feat || !n_cands_host) return duet_fail(ctx, DUET_ERR_INVALID, "null argument");
-    if (!pr->depth_off || pr->depth_bin == 0 || pr->n_contigs == 0 || pr->n_contigs > 65535)
-        return duet_fail(ctx, DUET_ERR_INVALID, "bad depth / contig description");
-    hipStream_t st = (hipStream_t)stream_;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint32_t M = pr->marks.n_marks, K = pr->n_contigs;
-    *n_cands_host = 0;
-    if (M == 0) {
-        if (res->n_cands) HIP_TRY(ctx, hipMemsetAsync(res->n_cands, 0, 4, st));
-        return DUET_OK;
-    }
-    if (!pr->mark_read || !pr->depth) return duet_fail(ctx, DUET_ERR_INVALID, "null array");
-    int rc;
-    const size_t sz[5] = {((size_t)K + 1) * 4 * 2, (size_t)M * 4, (size_t)M * 4, (size_t)M, (size_t)M * 4};
-    for (int i = 0; i < 5; ++i)
-        if ((rc = duet_reserve(ctx, ctx->sv_ws[i], sz[i]))) return rc;
-    uint32_t *d_ctg_off = (uint32_t *)ctx->sv_ws[0].ptr, *d_depth_off = d_ctg_off + (K + 1);
-    // (the depth offsets are uploaded only when they change, ordered as duet_svim_phase_device orders them)
-    if (ctx->sv_depth_off_at != (void *)d_depth_off || ctx->sv_depth_off.size() != (size_t)K + 1 || ctx->sv_depth_off_stream != st ||
-        memcmp(ctx->sv_depth_off.data(), pr->depth_off, ((size_t)K + 1) * 4) != 0) {
-        if (!ctx->sv_depth_off_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->sv_depth_off_ev, hipEventDisableTiming));
-        if (ctx->sv_depth_off_at) HIP_TRY(ctx, hipEventSynchronize(ctx->sv_depth_off_ev));
-        ctx->sv_depth_off.assign(pr->depth_off, pr->depth_off + K + 1);
-        HIP_TRY(ctx, hipMemcpyAsync(d_depth_off, ctx->sv_depth_off.data(), ((size_t)K + 1) * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipEventRecord(ctx->sv_depth_off_ev, st));
-        ctx->sv_depth_off_at = (void *)d_depth_off;
-        ctx->sv_depth_off_stream = st;
-    }
-    SvExtra sv;
-    sv.mark_in = pr->mark_read; sv.depth = pr->depth; sv.depth_off = d_depth_off; sv.depth_bin = pr->depth_bin;
-    sv.mark_out = (uint32_t *)ctx->sv_ws[4].ptr; sv.svread = (uint32_t *)ctx->sv_ws[1].ptr;
-    sv.refread = (uint32_t *)ctx->sv_ws[2].ptr; sv.gt = (uint8_t *)ctx->sv_ws[3].ptr;
-    sv.ef_ctg_off = nullptr; sv.ef_zero = nullptr; sv.n_contigs = K;
-    if ((rc = cluster_run(ctx, &pr->marks, res, st, &sv))) return rc;
-    hipLaunchKernelGGL(sv_contig_offsets, dim3((K + 1 + 255) / 256), dim3(256), 0, st, (const uint16_t *)res->cand_contig,
-                       (const uint32_t *)res->n_cands, K, d_ctg_off);
-    std::vector<uint32_t> ctg_off(K + 1);
-    HIP_TRY(ctx, hipMemcpyAsync(ctg_off.data(), d_ctg_off, ((size_t)K + 1) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));             // candidates per contig
-    const uint32_t N = ctg_off[K];
-    *n_cands_host = N;
-    if (N == 0) return DUET_OK;
-    duet_ef_problem ef;
-    memset(&ef, 0, sizeof(ef));
-    ef.n_contigs = K; ef.n_cands = N; ef.n_marks = M; ef.n_reads = pr->n_reads;
-    ef.cand_ctg_off = ctg_off.data();
-    ef.read_tag = pr->read_tag;
-    ef.cand_pos = res->cand_pos; ef.cand_svlen = res->cand_span; ef.cand_svread = sv.svread; ef.cand_refread = sv.refread;
-    ef.cand_gt_ok = sv.gt; ef.cand_off = res->cand_off; ef.mark_read = sv.mark_out;
-    ef.svlen_thres = pr->svlen_thres; ef.suppread_thres = pr->suppread_thres;
-    return pc_cap ? duet_ef_features_cap_device(ctx, &ef, *pc_cap, out_feat, st) : duet_ef_features_device(ctx, &ef, out_feat, st);
-}
-
-int duet_svim_features_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat,
-                              uint32_t *n_cands_host, void *stream_)
-{
-    return svim_features_device(ctx, pr, res, out_feat, n_cands_host, stream_, nullptr);
-}
-
-int duet_svim_features_cap_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, uint32_t pc_cap,
-                                  duet_tune_feature *out_feat, uint32_t *n_cands_host, void *stream_)
-{
-    return svim_features_device(ctx, pr, res, out_feat, n_cands_host, stream_, &pc_cap);
-}
-
-static int svim_features_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat,
-                              const uint32_t *pc_cap)
-{
-    if (!ctx) return duet_fail(nullptr, DUET_ERR_INVALID, "null context");
-    if (pc_cap && *pc_cap > (1u << 30) - 3u) return duet_fail(ctx, DUET_ERR_INVALID, "pc_cap is above 2^30 - 3 (the tag word saturates pc at 2^30 - 2)");
-    if (!pr || !res || !res->n_cands || !out_feat) return duet_fail(ctx, DUET_ERR_INVALID, "null argument");
-    if (!pr->depth_off || pr->n_contigs == 0) return duet_fail(ctx, DUET_ERR_INVALID, "bad depth / contig description");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint32_t M = pr->marks.n_marks;
-    *res->n_cands = 0;
-    if (M == 0) return DUET_OK;
-    // (host arrays: what the device entry has to trust is checked, as in duet_svim_phase_host)
-    if (!res->cand_off || !res->cand_contig || !res->cand_type || !res->cand_pos || !res->cand_span)
-        return duet_fail(ctx, DUET_ERR_INVALID, "null result array");
-    for (uint32_t k = 0; k < pr->n_contigs; ++k)
-        if (pr->depth_off[k] > pr->depth_off[k + 1]) return duet_fail(ctx, DUET_ERR_INVALID, "depth_off must be non-decreasing");
-    if (!pr->marks.mark_contig) return duet_fail(ctx, DUET_ERR_INVALID, "null array");
-    for (uint32_t i = 0; i < M; ++i)
-        if (pr->marks.mark_contig[i] >= pr->n_contigs)
-            return duet_fail(ctx, DUET_ERR_INVALID, "a mark's contig id is not below n_contigs (the depth description's contig count)");
-    hipStream_t s = ctx->own_stream;
-    int rc;
-    const size_t n_depth = pr->depth_off[pr->n_contigs];
-    const void *src[7] = {pr->marks.mark_contig, pr->marks.mark_type, pr->marks.mark_pos, pr->marks.mark_span, pr->mark_read, pr->read_tag, pr->depth};
-    const size_t ib[7] = {(size_t)M * 2, (size_t)M, (size_t)M * 4, (size_t)M * 4, (size_t)M * 4, (size_t)pr->n_reads * 8, n_depth * 4};
-    DevBuf *in[7] = {&ctx->cl_in[0], &ctx->cl_in[1], &ctx->cl_in[2], &ctx->cl_in[3], &ctx->sv_in[0], &ctx->sv_in[1], &ctx->sv_in[2]};
-    for (int i = 0; i < 7; ++i) {
-        if (!src[i] && ib[i]) return duet_fail(ctx, DUET_ERR_INVALID, "null array");
-        if ((rc = duet_reserve(ctx, *in[i], ib[i] + 16))) return rc;
-        if (ib[i]) HIP_TRY(ctx, hipMemcpyAsync(in[i]->ptr, src[i], ib[i], hipMemcpyHostToDevice, s));
-    }
-    const size_t ob[6] = {(size_t)M * 4, ((size_t)M + 1) * 4 + 16, (size_t)M * 2, (size_t)M, (size_t)M * 4, (size_t)M * 4};
-    for (int i = 0; i < 6; ++i)
-        if ((rc = duet_reserve(ctx, ctx->cl_out[i], ob[i]))) return rc;
-    DevBuf &bf = ctx->tune_ws.b[2];                     // (the feature staging of duet_ef_features_host)
-    if ((rc = duet_reserve(ctx, bf, (size_t)M * sizeof(duet_tune_feature)))) return rc;
-    duet_svim_problem d = *pr;
-    d.marks.mark_contig = (const uint16_t *)ctx->cl_in[0].ptr;
-    d.marks.mark_type = (const uint8_t *)ctx->cl_in[1].ptr;
-    d.marks.mark_pos = (const uint32_t *)ctx->cl_in[2].ptr;
-    d.marks.mark_span = (const uint32_t *)ctx->cl_in[3].ptr;
-    d.mark_read = (const uint32_t *)ctx->sv_in[0].ptr;
-    d.read_tag = (const uint64_t *)ctx->sv_in[1].ptr;
-    d.depth = (const uint32_t *)ctx->sv_in[2].ptr;
-    duet_cluster_result r;
-    r.order = (uint32_t *)ctx->cl_out[0].ptr;
-    r.cand_off = (uint32_t *)ctx->cl_out[1].ptr;
-    r.cand_contig = (uint16_t *)ctx->cl_out[2].ptr;
-    r.cand_type = (uint8_t *)ctx->cl_out[3].ptr;
-    r.cand_pos = (uint32_t *)ctx->cl_out[4].ptr;
-    r.cand_span = (uint32_t *)ctx->cl_out[5].ptr;
-    r.n_cands = (uint32_t *)((char *)ctx->cl_out[1].ptr + ((size_t)M + 1) * 4);        // spare word after cand_off
-    uint32_t n = 0;
-    rc = svim_features_device(ctx, &d, &r, (duet_tune_feature *)bf.ptr, &n, s, pc_cap);
-    if (rc && rc != DUET_ERR_DIV_ZERO) return rc;
-    const std::string msg = ctx->err;
-    *res->n_cands = n;
-    if (res->order) HIP_TRY(ctx, hipMemcpy(res->order, r.order, (size_t)M * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_off, r.cand_off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_contig, r.cand_contig, (size_t)n * 2, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_type, r.cand_type, (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_pos, r.cand_pos, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(res->cand_span, r.cand_span, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out_feat, bf.ptr, (size_t)n * sizeof(duet_tune_feature), hipMemcpyDeviceToHost));
-    if (rc) ctx->err = msg;
-    return rc;
-}
-
-int duet_svim_features_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, duet_tune_feature *out_feat)
-{
-    return svim_features_host(ctx, pr, res, out_feat, nullptr);
-}
-
-int duet_svim_features_cap_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, uint32_t pc_cap,
-                                duet_tune_feature *out_feat)
-{
-    return svim_features_host(ctx, pr, res, out_feat, &pc_cap);
+    return duet_fetch_cluster_result(ctx, M, n, &r, res);
 }
 
 }  // extern "C"

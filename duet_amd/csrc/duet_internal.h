@@ -110,7 +110,7 @@ inline int duet_fail(duet_ctx *ctx, int code, const std::string &msg)
                              std::string(#expr) + ": " + hipGetErrorString(e_));                \
     } while (0)
 
-// device-planned E/F run (duet_ef.hip), for the fused pipeline in duet_cluster.hip.  _prepare sizes the workspace for the bound
+// device-planned E/F run (duet_ef.hip), for the fused pipeline in duet_svim.hip.  _prepare sizes the workspace for the bound
 // and names the plan's place in it: ctg_off[K + 1], and K + 8 words to zero (seeds per contig, status words) -- a producer that
 // writes both itself passes planned = true and no plan kernel is launched
 int duet_ef_plan_on_device_prepare(duet_ctx *ctx, uint32_t K, uint32_t c_max, hipStream_t stream, uint32_t **ctg_off_out,
@@ -149,6 +149,68 @@ inline int duet_stage_arrays(duet_ctx *ctx, DevBuf *bufs, const void *const *src
         if (bytes[i]) HIP_TRY(ctx, hipMemcpyAsync(bufs[i].ptr, src[i], bytes[i], hipMemcpyHostToDevice, s));
         dev[i] = bufs[i].ptr;
     }
+    return DUET_OK;
+}
+
+// Stage A0 (duet_cluster.hip) as the fused pipeline (duet_svim.hip) runs it: with sv, cl_emit also writes what a caller VCF
+// would have carried and the marks' read indices in output order.  sv == nullptr: duet_cluster_run_device.
+struct SvExtra {
+    const uint32_t *mark_in, *depth, *depth_off;
+    uint32_t depth_bin;
+    uint32_t *mark_out, *svread, *refread;
+    uint8_t *gt;
+    uint32_t *ef_ctg_off, *ef_zero;       // step E/F's plan, written by cl_emit (null: E/F plans for itself)
+    uint32_t n_contigs;
+};
+int duet_cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_cluster_result *res, void *stream_, const SvExtra *sv);
+
+// Host staging of the clustering's host entries (duet_cluster_run_host, and the SVIM host entries of duet_svim.hip).
+// The four mark arrays of a host problem -> cl_in; *d = the problem over them
+inline int duet_stage_marks(duet_ctx *ctx, const duet_cluster_problem *pr, duet_cluster_problem *d, hipStream_t s)
+{
+    const size_t M = pr->n_marks;
+    const void *src[4] = {pr->mark_contig, pr->mark_type, pr->mark_pos, pr->mark_span};
+    const size_t bytes[4] = {M * 2, M, M * 4, M * 4};
+    void *dev[4];
+    for (int i = 0; i < 4; ++i)
+        if (!src[i] && bytes[i]) return duet_fail(ctx, DUET_ERR_INVALID, "null array");
+    int rc = duet_stage_arrays(ctx, ctx->cl_in, src, bytes, 4, s, dev);
+    if (rc) return rc;
+    *d = *pr;
+    d->mark_contig = (const uint16_t *)dev[0];
+    d->mark_type = (const uint8_t *)dev[1];
+    d->mark_pos = (const uint32_t *)dev[2];
+    d->mark_span = (const uint32_t *)dev[3];
+    return DUET_OK;
+}
+
+// cl_out reserved for M marks; *r = the device result in it
+inline int duet_bind_cluster_result(duet_ctx *ctx, size_t M, duet_cluster_result *r)
+{
+    const size_t ob[6] = {M * 4, (M + 1) * 4 + 16, M * 2, M, M * 4, M * 4};
+    for (int i = 0; i < 6; ++i) {
+        int rc = duet_reserve(ctx, ctx->cl_out[i], ob[i]);
+        if (rc) return rc;
+    }
+    r->order = (uint32_t *)ctx->cl_out[0].ptr;
+    r->cand_off = (uint32_t *)ctx->cl_out[1].ptr;
+    r->cand_contig = (uint16_t *)ctx->cl_out[2].ptr;
+    r->cand_type = (uint8_t *)ctx->cl_out[3].ptr;
+    r->cand_pos = (uint32_t *)ctx->cl_out[4].ptr;
+    r->cand_span = (uint32_t *)ctx->cl_out[5].ptr;
+    r->n_cands = (uint32_t *)((char *)ctx->cl_out[1].ptr + (M + 1) * 4);        // spare word after cand_off
+    return DUET_OK;
+}
+
+// n candidates of the device result r -> the host arrays of res (order[M] only where the caller wants it); the device is idle
+inline int duet_fetch_cluster_result(duet_ctx *ctx, size_t M, size_t n, const duet_cluster_result *r, const duet_cluster_result *res)
+{
+    if (res->order) HIP_TRY(ctx, hipMemcpy(res->order, r->order, M * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(res->cand_off, r->cand_off, (n + 1) * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(res->cand_contig, r->cand_contig, n * 2, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(res->cand_type, r->cand_type, n, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(res->cand_pos, r->cand_pos, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(res->cand_span, r->cand_span, n * 4, hipMemcpyDeviceToHost));
     return DUET_OK;
 }
 

@@ -10,6 +10,16 @@ DEVICE_FIELDS = ('read_tag', 'cand_pos', 'cand_svlen', 'cand_svread', 'cand_refr
                  'cand_off', 'mark_read')
 
 
+def upload(torch, device, a, dt=None):
+    """Host array a (as dtype dt) -> a uint8 tensor of its bytes on the device, with 64 zero bytes behind them: kernels read
+    past empty tables, so even an empty array has a readable address."""
+    a = np.ascontiguousarray(a, dtype=dt)
+    t = torch.zeros(a.nbytes + 64, dtype=torch.uint8, device=device)
+    if a.nbytes:
+        t[:a.nbytes] = torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(device)
+    return t
+
+
 class DeviceProblem(object):
     """An EfSoA uploaded once to HBM, plus output buffers, ready for repeated duet_ef_run_device."""
 
@@ -70,15 +80,7 @@ def device_rows(ctx, dp, rows, slot=0, stream=None):
     if stream is None:
         stream = torch.cuda.current_stream(dp.device).cuda_stream
     soa = dp.soa
-
-    def up(a):
-        a = np.ascontiguousarray(a)
-        t = torch.zeros(a.nbytes + 64, dtype=torch.uint8, device=dp.device)
-        if a.nbytes:
-            t[:a.nbytes] = torch.from_numpy(a.view(np.uint8).reshape(-1)).to(dp.device)
-        return t
-
-    keep = [up(rows['pool']), up(rows['str_off']), up(rows['chrom_rank']), up(rows['plus'])]
+    keep = [upload(torch, dp.device, rows[k]) for k in ('pool', 'str_off', 'chrom_rank', 'plus')]
     ctg_off = np.ascontiguousarray(soa.cand_ctg_off, dtype=np.uint32)
     blk = dp.out_blocks[slot]
     p = _lib.RowsProblem()
@@ -109,24 +111,11 @@ class DeviceCluster(object):
         self.M = M
         self.keep = {}
 
-        def up(a, dt):
-            a = np.ascontiguousarray(a, dtype=dt)
-            t = torch.zeros(a.nbytes + 64, dtype=torch.uint8, device=self.device)
-            if a.nbytes:
-                t[:a.nbytes] = torch.from_numpy(np.frombuffer(a.tobytes(), dtype=np.uint8).copy()).to(self.device)
-            return t
-
         p = _lib.ClusterProblem()
-        p.n_marks, p.part_gap, p.part_max = M, int(part_gap), int(part_max)
-        p.max_dist, p.normalizer = float(max_dist), float(normalizer)
-        if M:
-            p.n_contigs_hint = int(np.max(marks['contig'])) + 1
-            p.n_types_hint = int(np.max(marks['type'])) + 1
-            p.max_pos_hint = int(np.max(marks['pos']))
-            p.max_span_hint = max(int(np.max(marks['span'])), 1)
+        _lib.fill_cluster_problem(p, marks['contig'], marks['type'], marks['pos'], marks['span'], max_dist, part_gap, part_max, normalizer)
         for field, key, dt in (('mark_contig', 'contig', np.uint16), ('mark_type', 'type', np.uint8),
                                ('mark_pos', 'pos', np.uint32), ('mark_span', 'span', np.uint32)):
-            self.keep[field] = up(marks[key], dt)
+            self.keep[field] = upload(torch, self.device, marks[key], dt)
             setattr(p, field, self.keep[field].data_ptr())
         self.problem = p
         r = _lib.ClusterResult()
@@ -160,16 +149,9 @@ class DeviceSvim(DeviceCluster):
                                device=device)
         torch = self.torch
 
-        def up(a, dt):
-            a = np.ascontiguousarray(a, dtype=dt)
-            t = torch.zeros(a.nbytes + 64, dtype=torch.uint8, device=self.device)
-            if a.nbytes:
-                t[:a.nbytes] = torch.from_numpy(np.frombuffer(a.tobytes(), dtype=np.uint8).copy()).to(self.device)
-            return t
-
-        self.keep['sv_read'] = up(marks['read'], np.uint32)
-        self.keep['sv_tag'] = up(read_tag, np.uint64)
-        self.keep['sv_depth'] = up(depth, np.uint32)
+        self.keep['sv_read'] = upload(torch, self.device, marks['read'], np.uint32)
+        self.keep['sv_tag'] = upload(torch, self.device, read_tag, np.uint64)
+        self.keep['sv_depth'] = upload(torch, self.device, depth, np.uint32)
         self.depth_off = np.ascontiguousarray(depth_off, dtype=np.uint32)
         p = _lib.SvimProblem()
         p.marks = self.problem
@@ -274,15 +256,7 @@ class DeviceSvim(DeviceCluster):
         N = self.n_found
         if N == 0:
             return np.zeros(0, dtype=np.uint8)
-
-        def up(a, dt):
-            a = np.ascontiguousarray(a, dtype=dt)
-            t = torch.zeros(a.nbytes + 64, dtype=torch.uint8, device=self.device)
-            if a.nbytes:
-                t[:a.nbytes] = torch.from_numpy(a.view(np.uint8).reshape(-1)).to(self.device)
-            return t
-
-        keep = [up(names['mark_name'], np.uint32), up(names['name_off'], np.uint64), up(names['name_pool'], np.uint8)]
+        keep = [upload(torch, self.device, names[k], dt) for k, dt in (('mark_name', np.uint32), ('name_off', np.uint64), ('name_pool', np.uint8))]
         hold = []
         nm = _lib.callset_names(keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), chrom_texts, hold)
         nm.n_names = len(names['name_off']) - 1
@@ -348,12 +322,8 @@ class DeviceTune(object):
         self.counts = torch.zeros(max(self.K, 1) * _lib.COUNTS_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
 
     def _up(self, name, a, dt):
-        a = np.ascontiguousarray(a, dtype=dt)
-        t = self.torch.zeros(a.nbytes + 64, dtype=self.torch.uint8, device=self.device)
-        if a.nbytes:
-            t[:a.nbytes] = self.torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(self.device)
-        self.keep[name] = t
-        return t.data_ptr()
+        self.keep[name] = upload(self.torch, self.device, a, dt)
+        return self.keep[name].data_ptr()
 
     def _truth_arrays(self, tag):
         """A TuneTruth over six resident arrays of their own, sized for n_max candidates."""

@@ -3,7 +3,8 @@
 entries (duet_svim_phase_device with and without the host round trip, duet_svim_phase_host), field for field against
 tests/svim_ref.py, under the launch structures the debug bits select, with reruns on one context and the output words
 behind the candidate count watched.  tests/test_svim_fuzz_cases.py shows on the CPU that the cases have the structure they
-are named for."""
+are named for.  The feature entries (duet_svim_features[_cap]_device / _host) run at the same edge shapes, and the cached depth_off
+upload is driven across streams by both of its callers."""
 import ctypes
 
 import numpy as np
@@ -11,7 +12,9 @@ import pytest
 
 from duet_amd import _lib
 from duet_amd.devmem import DeviceSvim
-from tests import svim_fuzz, svim_ref
+from oracle import c_oracle
+from tests import pc_cap_ref, svim_fuzz, svim_ref
+from tests.test_gpu_pc_cap import assert_fields
 
 pytestmark = pytest.mark.gpu
 
@@ -148,3 +151,117 @@ def test_edge_case_matches_the_reference(ctx, name, entry):
     run(ctx, name, entry, 0, 'again', ds)
     for dbg in COMBOS[1:] + ((OWN_ALL,) if entry != 'device_nowait' and svim_fuzz.case(name).K <= 64 else ()):
         run(ctx, name, entry, dbg, 'combination', ds)
+
+
+# ---- the feature entries at the edge shapes ----------------------------------------------------------------------------------------
+
+FEATURE_CASES = ('marks_0', 'marks_1', 'marks_2', 'marks_64', 'marks_65', 'contigs_2', 'contigs_65', 'empty_contigs_around',
+                 'contigs_without_bins', 'all_marks_absent', 'no_reads')
+# the cases whose read tags the Python feature reference takes (the others carry haplotype values only the C oracle does)
+PY_REFERENCE = ('marks_0', 'marks_1', 'marks_2', 'marks_64', 'marks_65', 'all_marks_absent', 'no_reads')
+CAPS = (None, 8100, 300)
+NAMED = tuple(n for n in _lib.FEATURE_DTYPE.names if not n.startswith('reserved'))
+COLUMNS = FIELDS[1:6]
+REC = _lib.FEATURE_DTYPE.itemsize
+_soa, _want_feat = {}, {}
+
+
+def adapted(name):
+    """the E/F problem the fused pipeline adapts from the case: svim_ref.adapt on the C cluster oracle's output"""
+    if name not in _soa:
+        c = svim_fuzz.case(name)
+        cl = c_oracle.cluster(c.marks['contig'], c.marks['type'], c.marks['pos'], c.marks['span'], **c.kw)
+        _soa[name] = svim_ref.adapt(cl, c.marks, c.read_tag, c.depth, c.depth_off, c.depth_bin)[0]
+    return _soa[name]
+
+
+def feature_reference(ctx, name, cap):
+    """the records of duet_ef_features[_cap]_host on the adapted problem"""
+    if (name, cap) not in _want_feat:
+        c = svim_fuzz.case(name)
+        _want_feat[name, cap] = ctx.features_host(adapted(name), c.svlen_thres, c.suppread_thres, pc_cap=cap)
+    return _want_feat[name, cap]
+
+
+def check_columns(tag, want, n, got):
+    N = len(want['pred'])
+    assert n == N, (tag, 'n_cands', n, N)
+    for f in COLUMNS:
+        ref = want[f][:N + (f == 'cand_off')]
+        assert np.array_equal(got[f], ref), (tag, f, got[f][:5], ref[:5])
+
+
+def check_records(tag, got, want):
+    assert len(got) == len(want), (tag, len(got), len(want))
+    for f in NAMED:
+        bad = np.nonzero(got[f] != want[f])[0]
+        assert bad.size == 0, (tag, f, bad[:5], got[f][bad[:5]], want[f][bad[:5]])
+
+
+@pytest.mark.parametrize('name', FEATURE_CASES)
+def test_feature_entries_at_the_edge_shapes(ctx, name):
+    c, want = svim_fuzz.case(name), reference(name)
+    ds = resident(name)
+    torch = ds.torch
+    buf = torch.zeros(max(c.M, 1) * REC + 64, dtype=torch.uint8, device=ds.device)
+    seen = {}
+    for cap in CAPS:
+        tag = (name, 'pc_cap', cap)
+        ref = feature_reference(ctx, name, cap)
+        buf.fill_(FILL)
+        n = ds.run_features(ctx, buf.data_ptr(), pc_cap=cap)
+        torch.cuda.synchronize()
+        raw = buf.cpu().numpy()
+        dev = raw[:n * REC].view(_lib.FEATURE_DTYPE)
+        check_columns(tag + ('device',), want, n, ds.fetch())
+        check_records(tag + ('device',), dev, ref)
+        tail = np.nonzero(raw[n * REC:] != FILL)[0]
+        assert tail.size == 0, (tag, 'written behind record %d' % n, tail[:5])
+        host = ctx.svim_features_host(c.marks, c.read_tag, c.depth, c.depth_off, c.depth_bin, c.svlen_thres, c.suppread_thres,
+                                      pc_cap=cap, **c.kw)
+        check_columns(tag + ('host',), want, len(host['feat']), host)
+        check_records(tag + ('host',), host['feat'], ref)
+        assert host['feat'].tobytes() == dev.tobytes(), tag
+        if name in PY_REFERENCE:
+            assert_fields(host['feat'], pc_cap_ref.features(adapted(name), c.svlen_thres, c.suppread_thres, 8100 if cap is None else cap),
+                          '%s, cap %s' % (name, cap))
+        seen[cap] = dev.tobytes()
+    assert seen[None] == seen[8100]
+    # the decisions of the default vector over those features are the C oracle's
+    ds.run_thresholds(ctx, _lib.TUNE_DEFAULTS)
+    got = ds.fetch()
+    check_columns((name, 'thresholds'), want, ds.n_found, got)
+    assert np.array_equal(got['pred'], want['pred']), (name, 'pred')
+    live = got['pred'] != 0
+    assert np.array_equal(got['ps'][live], want['ps'][live]), (name, 'ps')
+
+
+# ---- the cached depth_off upload across streams -----------------------------------------------------------------------------------
+
+def test_depth_off_cache_across_streams(ctx):
+    """Two problems with another K and another depth_off on one context and two streams: the same contents on another stream
+    (uploaded again), other contents, the first ones again, and a hit -- first through duet_svim_phase_device alone, then with
+    duet_svim_features_device as every second caller of the same cache."""
+    A, B = 'contigs_2', 'contigs_65'
+    ds = {n: resident(n, keep=True) for n in (A, B)}
+    torch = ds[A].torch
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    feat = torch.zeros(max(svim_fuzz.case(A).M, 1) * REC + 64, dtype=torch.uint8, device=ds[A].device)
+    torch.cuda.synchronize()
+    order = ((A, s1), (A, s2), (B, s2), (A, s1), (A, s1))
+    for features in (False, True):
+        for i, (name, stream) in enumerate(order):
+            d, want, tag = ds[name], reference(name), (name, 'run %d' % i, 'features' if features else 'fused')
+            if features and i % 2:
+                n = d.run_features(ctx, feat.data_ptr(), stream=stream.cuda_stream)
+                stream.synchronize()
+                check_columns(tag, want, n, d.fetch())
+                got = feat[:n * REC].cpu().numpy().view(_lib.FEATURE_DTYPE)
+                check_records(tag, got, feature_reference(ctx, name, None))
+                continue
+            d.run_fused(ctx, stream=stream.cuda_stream, wait=False)
+            stream.synchronize()
+            got = d.fetch()
+            check_columns(tag, want, d.n_found, got)
+            for f in ('order', 'pred', 'ps'):
+                assert np.array_equal(got[f], want[f]), (tag, f)
