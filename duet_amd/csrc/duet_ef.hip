@@ -46,8 +46,8 @@ namespace {
 #define STAMP(k, i) do { } while (0)
 #endif
 
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;          // "no seed" / "no PS yet"
-constexpr uint64_t kUntagged = ~0ull;             // LDS tag word of an absent mark
+#include "duet_seeds.hip.h"
+
 constexpr uint32_t kPcMax = DUET_PC_MAX;
 
 // provisional code written by ef_classify into out_pred; values < 4 are already final
@@ -81,10 +81,6 @@ struct Vote {
     uint32_t hap1, hap2, hap0, allhap;
     uint64_t t1, t2;
 };
-
-__device__ __forceinline__ uint32_t tag_ps(uint64_t t) { return (uint32_t)t; }
-__device__ __forceinline__ uint32_t tag_pc(uint64_t t) { return (uint32_t)(t >> 32) & 0x3FFFFFFFu; }
-__device__ __forceinline__ uint32_t tag_hap(uint64_t t) { return (uint32_t)(t >> 62); }
 
 // predict_hp, sv_phasing_fn.py:142-183, on the features of :112-139.  cls in {0,1,2}.
 __device__ int decide(int cls, const Vote &v, uint32_t deg, uint32_t svread, uint32_t refread)
@@ -840,16 +836,6 @@ __device__ uint32_t unique_copy(const uint32_t *src, uint32_t n, uint32_t *dst, 
     return total;
 }
 
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *a, uint32_t n, uint32_t key)
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(kSortThreads) void ef_seed_sort(const Params p)
 {
     __shared__ __align__(16) uint32_t s_key[kSortLds];
@@ -1220,79 +1206,147 @@ __global__ __launch_bounds__(kSortThreads) void ef_seed_sort(const Params p)
 // kernel 3: contig drop, nearest PS, multi-PS vote + decision
 // ---------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ bool is_member(const uint32_t *a, uint32_t n, uint32_t key)
-{
-    const uint32_t at = lower_bound_u32(a, n, key);
-    return at < n && a[at] == key;
-}
+// ef_finalize's per-candidate rule (finalize_rule) puts two questions to the contig's seed set -- member(ps): is this PS a seed
+// (:91); nearest(pos): which seed is nearest to this position (:106-111, ties to the larger seed); none(): the contig has no seed at
+// all (:209-210) -- and is written against a seed view that answers them.  ArraySeeds is the view of the ascending array ef_seed_sort
+// made, in LDS or in global memory.  (ef_finalize_own below still states the rule itself, against its hash set and against a walk over
+// the contig's entries: put on this rule through two more views, its kernel measured 0.3 us slower at configs[1] for no reason found
+// in its text, so that step is left for when the reason is.)
 
-// sv_phasing_fn.py:107-111 -- ties go to the larger seed
-__device__ __forceinline__ uint32_t nearest_ps(const uint32_t *a, uint32_t n, uint32_t pos)
-{
-    const uint32_t i = lower_bound_u32(a, n, pos);
-    const uint32_t lo = i > 0 ? i - 1 : 0;
-    const uint32_t hi = i < n - 1 ? i : n - 1;
-    const int64_t dl = llabs((int64_t)pos - (int64_t)a[lo]);
-    const int64_t dh = llabs((int64_t)pos - (int64_t)a[hi]);
-    return dl < dh ? a[lo] : a[hi];
-}
+struct ArraySeeds {
+    const uint32_t *one;
+    uint32_t n;
+    __device__ __forceinline__ bool none() const { return n == 0; }
+    __device__ __forceinline__ bool member(uint32_t ps) const
+    {
+        const uint32_t at = lower_bound_u32(one, n, ps);
+        return at < n && one[at] == ps;
+    }
+    __device__ __forceinline__ uint32_t nearest(uint32_t pos) const { return nearest_seed(one, n, pos); }
+};
 
 // f(tag) for every mark of [b, e) in list order, the marks' two dependent loads (read index, then tag) eight marks at a time:
 // one pair of round trips per eight marks instead of one per mark
 template <class F>
-__device__ __forceinline__ void for_each_tag(const Params &p, uint32_t b, uint32_t e, F f)
+__device__ __forceinline__ void for_each_tag(const uint32_t *mark_read, const uint64_t *read_tag, uint32_t b, uint32_t e, F f)
 {
     for (uint32_t m0 = b; m0 < e; m0 += 8) {
         uint32_t r[8];
         uint64_t t[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = p.mark_read[m0 + j < e ? m0 + j : b];
+        for (int j = 0; j < 8; ++j) r[j] = mark_read[m0 + j < e ? m0 + j : b];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = p.read_tag[r[j] == kEmpty ? 0u : r[j]];       // (read_tag always has >= 1 readable word)
+        for (int j = 0; j < 8; ++j) t[j] = read_tag[r[j] == kEmpty ? 0u : r[j]];         // (read_tag always has >= 1 readable word)
 #pragma unroll
         for (int j = 0; j < 8; ++j)
             if (m0 + j < e) f(r[j] == kEmpty ? kUntagged : t[j]);
     }
 }
 
-// multi-PS vote straight from the marks (:85-105): only for candidates without a group summary.  mem(ps): is this PS a seed of
-// the contig (:91)
-template <class Mem>
-__device__ __forceinline__ void class2_from_marks_m(const Params &p, uint32_t c, Mem mem, Vote &v, uint32_t &ps)
+// multi-PS vote straight from the marks [b, e) (:85-105): only for candidates without a group summary
+template <class Seeds>
+__device__ __forceinline__ void vote_from_marks(const Seeds &sd, const uint32_t *mark_read, const uint64_t *read_tag, uint32_t b,
+                                                uint32_t e, Vote &v, uint32_t &ps)
 {
-    const uint32_t b = p.cand_off[c], e = p.cand_off[c + 1];
     uint32_t best = 0;
-    for_each_tag(p, b, e, [&](uint64_t t) {
+    for_each_tag(mark_read, read_tag, b, e, [&](uint64_t t) {
         if (t != kUntagged && tag_pc(t) <= kPcMax) ++v.allhap;
     });
     uint32_t done_ps = kEmpty;                                 // last group evaluated (cheap duplicate skip)
-    for_each_tag(p, b, e, [&](uint64_t t) {
+    for_each_tag(mark_read, read_tag, b, e, [&](uint64_t t) {
         if (t == kUntagged || tag_pc(t) > kPcMax) return;
         const uint32_t g = tag_ps(t);
         if (g == done_ps || (g == ps && best)) return;
-        if (!mem(g)) return;                                   // :91
+        if (!sd.member(g)) return;                             // :91
         // size and sums of g's group over the whole list; a later occurrence of an already
         // evaluated group reproduces the same n and cannot beat it (strict '>', :101)
         uint32_t n = 0, n1 = 0, n2 = 0;
         uint64_t s1 = 0, s2 = 0;
-        for_each_tag(p, b, e, [&](uint64_t u) {
+        for_each_tag(mark_read, read_tag, b, e, [&](uint64_t u) {
             if (u == kUntagged || tag_pc(u) > kPcMax || tag_ps(u) != g) return;
             ++n;
-            const uint32_t hap = tag_hap(u);
-            if (hap == 1) { ++n1; s1 += tag_pc(u); }
-            else if (hap == 2) { ++n2; s2 += tag_pc(u); }
+            const uint32_t hap = tag_hap(u), pc = tag_pc(u);
+            // (selects, not a branch: the compiler turned the branch into a select of the counters' addresses -- a stack)
+            n1 += hap == 1 ? 1u : 0u; s1 += hap == 1 ? pc : 0u;
+            n2 += hap == 2 ? 1u : 0u; s2 += hap == 2 ? pc : 0u;
         });
         done_ps = g;
-        if (n > best) {
+        if (n > best) {                                        // strict: the first-seen group wins ties (:101)
             best = n; ps = g;
             v.hap1 = n1; v.hap2 = n2; v.t1 = s1; v.t2 = s2;
             v.hap0 = v.allhap - n1 - n2;                       // only with a winner (:105)
         }
     });
 }
-__device__ void class2_from_marks(const Params &p, uint32_t c, const uint32_t *one, uint32_t n_one, Vote &v, uint32_t &ps)
+
+// the same vote from a group summary w (ef_classify: store_summary); slots beyond ng hold stale words, never used
+template <class Seeds>
+__device__ __forceinline__ void vote_from_summary(const Seeds &sd, const uint32_t (&w)[kC2Words], Vote &v, uint32_t &ps)
 {
-    class2_from_marks_m(p, c, [&](uint32_t g) { return is_member(one, n_one, g); }, v, ps);
+    v.allhap = w[0];
+    const uint32_t ng = w[1];
+    uint32_t best = 0;
+#pragma unroll
+    for (int k = 0; k < kC2Groups; ++k) {
+        if ((uint32_t)k < ng && w[2 + 6 * k + 1] > best && sd.member(w[2 + 6 * k])) {
+            best = w[2 + 6 * k + 1];
+            ps = w[2 + 6 * k];
+            v.hap1 = w[2 + 6 * k + 2]; v.hap2 = w[2 + 6 * k + 3];
+            v.t1 = w[2 + 6 * k + 4]; v.t2 = w[2 + 6 * k + 5];
+            v.hap0 = v.allhap - v.hap1 - v.hap2;               // (:105, as in vote_from_marks)
+        }
+    }
+}
+
+// What finalize_rule is given besides the seeds: the candidate -- ef_classify's provisional code and PS word, and its own columns as
+// VALUES (both kernels have them in flight long before) -- and the arrays it reads its marks from and writes to.
+struct CandCols {
+    uint32_t c, code, ps_in, pos, o0, o1, svread, refread;     // o0, o1: the candidate's marks are [o0, o1)
+};
+struct FinalizeIo {
+    const uint32_t *mark_read;
+    const uint64_t *read_tag;
+    uint32_t *status;
+    uint8_t *out_pred;
+    uint32_t *out_ps;
+};
+
+// What is left to do for a candidate once its contig's seeds can be asked (sd).  load_summary(w) fetches the group summary that
+// ps_in names, from wherever the kernel keeps it.
+template <class Seeds, class LoadSummary>
+__device__ __forceinline__ void finalize_rule(const Seeds &sd, const CandCols &cd, LoadSummary load_summary, const FinalizeIo &io)
+{
+    const uint32_t c = cd.c, code = cd.code;
+    if (sd.none()) {                                           // :209-210
+        if (code != 0) io.out_pred[c] = 0;
+        if (cd.ps_in != 0) io.out_ps[c] = 0;
+        return;
+    }
+    if (code < 4) return;                                      // already final
+    if (code & kDivZero) {                                     // :123 would raise
+        atomicOr(&io.status[0], 1u);
+        io.out_pred[c] = 0;
+        io.out_ps[c] = 0;
+        return;
+    }
+    if (code & (kClass2 | kClass2Slow)) {                      // :85-105, :148-155
+        Vote v = {0, 0, 0, 0, 0, 0};
+        uint32_t ps = 0;
+        if (code & kClass2) {
+            uint32_t w[kC2Words];
+            load_summary(w);
+            vote_from_summary(sd, w, v, ps);
+        } else {
+            vote_from_marks(sd, io.mark_read, io.read_tag, cd.o0, cd.o1, v, ps);
+        }
+        if (v.hap1 == 0 && v.hap2 == 0) ps = sd.nearest(cd.pos);                         // :106
+        io.out_pred[c] = (uint8_t)decide(2, v, cd.o1 - cd.o0, cd.svread, cd.refread);
+        io.out_ps[c] = ps;
+        return;
+    }
+    // kNeedNearest
+    io.out_pred[c] = (uint8_t)(code & 3u);
+    io.out_ps[c] = sd.nearest(cd.pos);
 }
 
 // one candidate's part of ef_finalize (everything after the tile's seed array is staged)
@@ -1304,65 +1358,21 @@ __device__ __forceinline__ void finalize_candidate(const Params &p, uint32_t c, 
     // round trip behind them)
     const bool two = (code & (kClass2 | kClass2Slow)) != 0 && !(code & kDivZero);
     const bool work = code >= 4 && !(code & kDivZero);
-    uint32_t c_pos = 0, c_o0 = 0, c_o1 = 0, c_svread = 0, c_refread = 0;
-    if (work) c_pos = p.cand_pos[c];
-    if (two) { c_o0 = p.cand_off[c]; c_o1 = p.cand_off[c + 1]; c_svread = p.cand_svread[c]; c_refread = p.cand_refread[c]; }
-    const uint32_t *one;
-    uint32_t n_one;
-    if (lds_mode) {
-        one = s_one;
-        n_one = n_lds;
-    } else {
+    CandCols cd = {c, code, ps_in, 0, 0, 0, 0, 0};
+    if (work) cd.pos = p.cand_pos[c];
+    if (two) { cd.o0 = p.cand_off[c]; cd.o1 = p.cand_off[c + 1]; cd.svread = p.cand_svread[c]; cd.refread = p.cand_refread[c]; }
+    ArraySeeds sd = {s_one, n_lds};
+    if (!lds_mode) {
         uint32_t k = k0;
         while (c >= p.ctg_off[k + 1]) ++k;
-        n_one = p.n_one[k];
-        one = p.onebuf + p.ctg_off[k] + k + 1;
+        sd.n = p.n_one[k];
+        sd.one = p.onebuf + p.ctg_off[k] + k + 1;
     }
-    if (n_one == 0) {                                          // :209-210
-        if (code != 0) p.out_pred[c] = 0;
-        if (ps_in != 0) p.out_ps[c] = 0;
-        return;
-    }
-    if (code < 4) return;
-    if (code & kDivZero) {                                     // :123 would raise
-        atomicOr(&p.status[0], 1u);
-        p.out_pred[c] = 0;
-        p.out_ps[c] = 0;
-        return;
-    }
-    if (code & (kClass2 | kClass2Slow)) {                      // :85-105, :148-155
-        Vote v = {0, 0, 0, 0, 0, 0};
-        uint32_t ps = 0;
-        if (code & kClass2) {
-            const uint32_t *rec = p.c2rec + (size_t)ps_in * kC2Words;
-            uint32_t w[kC2Words];
+    finalize_rule(sd, cd, [&](uint32_t (&w)[kC2Words]) {
+        const uint32_t *rec = p.c2rec + (size_t)ps_in * kC2Words;
 #pragma unroll
-            for (int i = 0; i < kC2Words; ++i) w[i] = rec[i];  // slots beyond ng hold stale words, never used
-            v.allhap = w[0];
-            const uint32_t ng = w[1];
-            uint32_t best = 0;
-#pragma unroll
-            for (int k = 0; k < kC2Groups; ++k) {
-                if ((uint32_t)k < ng && w[2 + 6 * k + 1] > best && is_member(one, n_one, w[2 + 6 * k])) {
-                    best = w[2 + 6 * k + 1];
-                    ps = w[2 + 6 * k];
-                    v.hap1 = w[2 + 6 * k + 2]; v.hap2 = w[2 + 6 * k + 3];
-                    v.t1 = w[2 + 6 * k + 4]; v.t2 = w[2 + 6 * k + 5];
-                    v.hap0 = v.allhap - v.hap1 - v.hap2;       // only with a winner (:105)
-                }
-            }
-        } else {
-            class2_from_marks(p, c, one, n_one, v, ps);
-        }
-        if (v.hap1 == 0 && v.hap2 == 0) ps = nearest_ps(one, n_one, c_pos);              // :106
-        const uint32_t deg = c_o1 - c_o0;
-        p.out_pred[c] = (uint8_t)decide(2, v, deg, c_svread, c_refread);
-        p.out_ps[c] = ps;
-        return;
-    }
-    // kNeedNearest
-    p.out_pred[c] = code & 3;
-    p.out_ps[c] = nearest_ps(one, n_one, c_pos);
+        for (int i = 0; i < kC2Words; ++i) w[i] = rec[i];
+    }, FinalizeIo{p.mark_read, p.read_tag, p.status, p.out_pred, p.out_ps});
 }
 
 // TPB: tiles of 256 candidates per workgroup (host-planned runs with the contig offsets in the kernel arguments only)
@@ -1546,7 +1556,7 @@ __device__ __forceinline__ uint32_t own_nearest_walk(const OwnArgs &a, uint32_t 
     int64_t bd = -1;
     own_each_entry(a.recs, a.seed_ent, a.c_lo, a.c_hi, 0u, 1u, [&](uint32_t ps) {
         const int64_t d = llabs((int64_t)pos - (int64_t)ps);
-        // nearest_ps: the left neighbour only when strictly nearer -- among equally near seeds the larger one
+        // nearest_seed: the left neighbour only when strictly nearer -- among equally near seeds the larger one
         if (bd < 0 || d < bd || (d == bd && ps > best)) { bd = d; best = ps; }
     });
     return best;
@@ -1567,7 +1577,7 @@ __device__ __forceinline__ void own_each_tag(const OwnArgs &a, uint32_t b, uint3
     }
 }
 
-// one candidate of a contig whose seeds did not fit the LDS set (finalize_candidate's logic, array-free; the contig has seeds)
+// one candidate of a contig whose seeds did not fit the LDS set (finalize_rule's logic, array-free; the contig has seeds)
 __device__ __forceinline__ void finalize_candidate_walk(const OwnArgs &a, uint32_t c, uint32_t code, uint32_t ps_in)
 {
     if (code & kDivZero) {
@@ -1596,7 +1606,7 @@ __device__ __forceinline__ void finalize_candidate_walk(const OwnArgs &a, uint32
                     v.hap0 = v.allhap - v.hap1 - v.hap2;       // only with a winner (:105)
                 }
             }
-        } else {                                               // (class2_from_marks, membership by walking)
+        } else {                                               // (vote_from_marks, membership by walking)
             uint32_t best = 0;
             own_each_tag(a, mb, me, [&](uint64_t t) {
                 if (t != kUntagged && tag_pc(t) <= kPcMax) ++v.allhap;
@@ -1709,7 +1719,7 @@ __device__ __forceinline__ void own_sort_set(const uint32_t *s_tab, uint32_t *s_
 }
 
 // (rare path of ef_finalize_own) the multi-PS vote of a candidate without a group summary, straight from its marks (:85-105,
-// class2_from_marks); "is this PS a seed" (:91) from the hash set in LDS
+// vote_from_marks); "is this PS a seed" (:91) from the hash set in LDS
 __device__ __forceinline__ void own_vote_from_marks(const uint32_t *mark_read, const uint64_t *read_tag, uint32_t mb, uint32_t me_,
                                                  const uint32_t *s_tab, Vote *vo, uint32_t *pso)
 {
@@ -2025,7 +2035,7 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
         // ---- this tile's candidates of contig k ------------------------------------------------------
         // :107-111 -- ties go to the larger seed
         auto nearest = [&](uint32_t pos) -> uint32_t {
-            if (sorted) return nearest_ps(s_one, u, pos);
+            if (sorted) return nearest_seed(s_one, u, pos);
             uint32_t best = 0;
             int64_t bd = -1;
             auto look = [&](uint32_t v) {

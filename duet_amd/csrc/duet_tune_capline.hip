@@ -22,23 +22,22 @@
 namespace {
 
 #include "duet_prims.hip.h"
+#include "duet_seeds.hip.h"                // kEmpty, kUntagged, tag_pc
 
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-constexpr uint64_t kUntagged = ~0ull;
 constexpr uint64_t kNoKey = ~0ull;
 constexpr uint32_t kCapMax = (1u << 30) - 3u;         // the tag word saturates pc at 2^30 - 2: a saturated value never votes
 constexpr uint32_t kKeyBits = 30;
 
 int fail(duet_ctx *ctx, int code, const char *msg) { return duet_fail(ctx, code, msg); }
 
-// the key of one mark: the tagged test is mark_tag's (duet_tune_feat.hip.h), the pc field tg_pc's
+// the key of one mark: the tagged test is mark_tag's (duet_tune_feat.hip.h), the pc field tag_pc's
 __device__ __forceinline__ uint64_t mark_key(const uint32_t *mark_read, const uint64_t *read_tag, uint32_t n_reads, uint32_t m)
 {
     const uint32_t r = mark_read[m];
     if (r == kEmpty || r >= n_reads) return kNoKey;
     const uint64_t t = read_tag[r];
     if (t == kUntagged) return kNoKey;
-    const uint32_t pc = (uint32_t)(t >> 32) & 0x3FFFFFFFu;
+    const uint32_t pc = tag_pc(t);
     return pc <= kCapMax ? (uint64_t)pc : kNoKey;
 }
 

@@ -11,35 +11,9 @@
 #ifndef DUET_TUNE_FEAT_HIP_H
 #define DUET_TUNE_FEAT_HIP_H
 
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-constexpr uint64_t kUntagged = ~0ull;
+#include "duet_seeds.hip.h"                // kEmpty, kUntagged, tag_ps / tag_pc / tag_hap, lower_bound_u32, nearest_seed
+
 constexpr int kStage = 1024;                  // features_body: voter words staged in LDS per pass over a candidate's marks (8 KiB)
-
-// the tag word's fields (include/duet_ef.h: DUET_TAG)
-__device__ __forceinline__ uint32_t tg_ps(uint64_t t) { return (uint32_t)t; }
-__device__ __forceinline__ uint32_t tg_pc(uint64_t t) { return (uint32_t)(t >> 32) & 0x3FFFFFFFu; }
-__device__ __forceinline__ uint32_t tg_hap(uint64_t t) { return (uint32_t)(t >> 62); }
-
-__device__ __forceinline__ uint32_t lower_bound(const uint32_t *a, uint32_t n, uint32_t key)
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// sv_phasing_fn.py:107-111 -- the nearest seed, ties to the larger one (n >= 1)
-__device__ __forceinline__ uint32_t nearest_seed(const uint32_t *a, uint32_t n, uint32_t pos)
-{
-    const uint32_t i = lower_bound(a, n, pos);
-    const uint32_t lo = i > 0 ? i - 1 : 0;
-    const uint32_t hi = i < n - 1 ? i : n - 1;
-    const int64_t dl = llabs((int64_t)pos - (int64_t)a[lo]);
-    const int64_t dh = llabs((int64_t)pos - (int64_t)a[hi]);
-    return dl < dh ? a[lo] : a[hi];
-}
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 {
@@ -75,7 +49,7 @@ __device__ __forceinline__ uint64_t mark_tag(const FeatArgs &a, uint32_t m)
     const uint32_t r = a.mark_read[m];
     return (r == kEmpty || r >= a.n_reads) ? kUntagged : a.read_tag[r];
 }
-__device__ __forceinline__ bool is_voter(uint64_t t, uint32_t cap) { return t != kUntagged && tg_pc(t) <= cap; }
+__device__ __forceinline__ bool is_voter(uint64_t t, uint32_t cap) { return t != kUntagged && tag_pc(t) <= cap; }
 
 // One candidate per workgroup of one wavefront: every walk over the marks goes 64 at a time, so a candidate of any degree and any
 // number of phase sets takes the same code.  The multi-PS winner (:85-105): among voters whose PS is a seed, the PS with the most
@@ -106,10 +80,10 @@ __device__ __forceinline__ void features_body(const FeatArgs &a, const S &sd)
                 const bool tagged = t != kUntagged;
                 const uint64_t bal = __ballot(tagged);
                 if (!have && bal) {
-                    p0 = __shfl(tg_ps(t), __ffsll((unsigned long long)bal) - 1);
+                    p0 = __shfl(tag_ps(t), __ffsll((unsigned long long)bal) - 1);
                     have = true;
                 }
-                if (have) multi = __any(tagged && tg_ps(t) != p0);
+                if (have) multi = __any(tagged && tag_ps(t) != p0);
             }
             f.cls = multi ? 2 : (have ? 1 : 0);
             // the contig and its seed set
@@ -141,8 +115,8 @@ __device__ __forceinline__ void features_body(const FeatArgs &a, const S &sd)
                         const uint32_t m = m0 + lane;
                         const uint64_t t = m < e ? mark_tag(a, m) : kUntagged;
                         if (is_voter(t, cap)) {
-                            if (tg_hap(t) == 1) { ++hap1; t1 += tg_pc(t); }
-                            else if (tg_hap(t) == 2) { ++hap2; t2 += tg_pc(t); }
+                            if (tag_hap(t) == 1) { ++hap1; t1 += tag_pc(t); }
+                            else if (tag_hap(t) == 2) { ++hap2; t2 += tag_pc(t); }
                         }
                     }
                     hap1 = wave_sum(hap1); hap2 = wave_sum(hap2);
@@ -156,12 +130,12 @@ __device__ __forceinline__ void features_body(const FeatArgs &a, const S &sd)
                         const uint64_t t = i < e ? mark_tag(a, i) : kUntagged;
                         const bool voter = is_voter(t, cap);
                         allhap += voter ? 1u : 0u;
-                        const uint64_t my = voter ? ((1ull << 32) | tg_ps(t)) : 0ull;
+                        const uint64_t my = voter ? ((1ull << 32) | tag_ps(t)) : 0ull;
                         const uint32_t ni = n_seed;
                         bool cand = false;
                         if (voter) {
-                            const uint32_t at = lower_bound(seeds, ni, tg_ps(t));
-                            cand = at < ni && seeds[at] == tg_ps(t);     // :91
+                            const uint32_t at = lower_bound_u32(seeds, ni, tag_ps(t));
+                            cand = at < ni && seeds[at] == tag_ps(t);     // :91
                         }
                         if (!__any(cand)) continue;
                         uint32_t n = 0;
@@ -171,7 +145,7 @@ __device__ __forceinline__ void features_body(const FeatArgs &a, const S &sd)
                             __syncthreads();
                             for (uint32_t jj = lane; jj < cnt; jj += 64) {
                                 const uint64_t u = mark_tag(a, j0 + jj);
-                                s_w[jj] = is_voter(u, cap) ? ((1ull << 32) | tg_ps(u)) : 0ull;
+                                s_w[jj] = is_voter(u, cap) ? ((1ull << 32) | tag_ps(u)) : 0ull;
                             }
                             __syncthreads();
                             if (cand)
@@ -188,13 +162,13 @@ __device__ __forceinline__ void features_body(const FeatArgs &a, const S &sd)
                     allhap = wave_sum(allhap);
                     if (best) {
                         const uint32_t at = b + ~(uint32_t)best;
-                        const uint32_t win = tg_ps(mark_tag(a, at));
+                        const uint32_t win = tag_ps(mark_tag(a, at));
                         for (uint32_t m0 = b; m0 < e; m0 += 64) {
                             const uint32_t m = m0 + lane;
                             const uint64_t t = m < e ? mark_tag(a, m) : kUntagged;
-                            if (is_voter(t, cap) && tg_ps(t) == win) {
-                                if (tg_hap(t) == 1) { ++hap1; t1 += tg_pc(t); }
-                                else if (tg_hap(t) == 2) { ++hap2; t2 += tg_pc(t); }
+                            if (is_voter(t, cap) && tag_ps(t) == win) {
+                                if (tag_hap(t) == 1) { ++hap1; t1 += tag_pc(t); }
+                                else if (tag_hap(t) == 2) { ++hap2; t2 += tag_pc(t); }
                             }
                         }
                         hap1 = wave_sum(hap1); hap2 = wave_sum(hap2);

@@ -476,3 +476,84 @@ def test_two_launches_three_launches_and_the_array_free_walk_agree(ctx):
                     check_against_c_oracle(ctx, soa, 0, 0)
             finally:
                 ctx.set_debug(0)
+
+
+def finalize_census(soa, svlen_thres=50, suppread_thres=2):
+    """Per contig: the number of distinct seeds (sv_phasing_fn.py:195-203: the PS of every kept candidate that sees one phase set and has
+    a voter) and how many kept candidates take each branch of the finalize rule -- 'nearest' (no tagged mark, or no voter: :106-111
+    outright), 'summary' (several PS, at most the two voter groups a group summary holds), 'marks' (several PS, three or more voter
+    groups: the vote straight from the marks)."""
+    tagged = soa.mark_read != engine.MARK_ABSENT
+    tag = soa.read_tag[np.where(tagged, soa.mark_read, 0)]
+    tagged &= tag != np.uint64(0xFFFFFFFFFFFFFFFF)
+    ps = (tag & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    voter = tagged & (((tag >> np.uint64(32)) & np.uint64(0x3FFFFFFF)) <= 8100)
+    kept = (soa.cand_svlen >= svlen_thres) & (soa.cand_svread >= suppread_thres) & (soa.cand_gt_ok != 0)
+    out = []
+    for k in range(soa.n_contigs):
+        seeds, kinds = set(), dict(nearest=0, summary=0, marks=0)
+        for c in range(int(soa.cand_ctg_off[k]), int(soa.cand_ctg_off[k + 1])):
+            if not kept[c]:
+                continue
+            m = slice(int(soa.cand_off[c]), int(soa.cand_off[c + 1]))
+            n_ps = len(set(ps[m][tagged[m]].tolist()))
+            groups = set(ps[m][voter[m]].tolist())
+            if n_ps == 1 and groups:
+                seeds |= groups
+            if n_ps == 0 or not groups:
+                kinds['nearest'] += 1
+            elif n_ps >= 2:
+                kinds['summary' if len(groups) <= 2 else 'marks'] += 1
+        out.append((len(seeds), kinds))
+    return out
+
+
+def test_finalize_rule_every_seed_view_by_every_candidate_kind(ctx):
+    """The finalize rule is one piece of code over three views of a contig's seed set: the ascending array (three launches: OWN_OFF,
+    also with two tiles per workgroup), the hash set in LDS (two launches: the default here, 0x80, and -- OWN_SMALLTAB, a set of 8 --
+    contigs of up to 8 seeds), and the walk over the contig's seed entries (OWN_SMALLTAB, contigs of more than 8 seeds).  Every view
+    has to meet every kind of candidate: nearest seed outright, the vote from a group summary, the vote from the marks; a contig
+    without seeds (:209-210); the division by zero (:123).
+    What keeps this honest: the census below, taken from the input alone before anything runs on the device, asserts that `few` has
+    a contig of 1 .. 8 seeds and `many` one of more than 8 seeds with candidates of all three kinds, and that `none` has no seed."""
+    shape = dict(cands_per_contig=(300, 600), reads_per_contig=(60, 90), deg=(1, 30), absent_rate=2, empty_contig_rate=0)
+    inputs = dict(few=dict(n_contigs=3, n_ps=(3, 6), no_seed_contig_rate=0), many=dict(n_contigs=3, n_ps=(10, 14), no_seed_contig_rate=0),
+                  none=dict(n_contigs=2, n_ps=(3, 6), no_seed_contig_rate=1))
+    modes = (0, OWN_OFF, OWN_OFF | 0x20, 0x80, OWN_ALL | OWN_SMALLTAB)
+
+    def in_every_mode(run):
+        for dbg in modes:
+            ctx.set_debug(dbg)
+            try:
+                run(dbg)
+            finally:
+                ctx.set_debug(0)
+
+    for name, kw in sorted(inputs.items()):
+        for seed in (7000, 7001):
+            for sorted_pos in (True, False):
+                soa = soa_fuzz.random_soa(seed, sorted_pos=sorted_pos, **dict(shape, **kw))
+                census = finalize_census(soa)
+                full = [n for n, kinds in census if min(kinds.values()) > 0]
+                if name == 'few':
+                    assert any(1 <= n <= 8 for n in full), census
+                elif name == 'many':
+                    assert any(n > 8 for n in full), census
+                else:
+                    assert all(n == 0 for n, _ in census), census
+                seeds = []
+
+                def run(dbg):
+                    check_against_c_oracle(ctx, soa, 50, 2)
+                    seeds.append([ctx.seed_ps(k).copy() for k in range(soa.n_contigs)])
+                    assert [len(s) for s in seeds[-1]] == [n for n, _ in census], (name, seed, sorted_pos, dbg)
+                    assert all(np.array_equal(a, b) for a, b in zip(seeds[-1], seeds[0])), (name, seed, sorted_pos, dbg)
+                in_every_mode(run)
+    for sorted_pos in (True, False):
+        soa = soa_fuzz.random_soa(7000, sorted_pos=sorted_pos, allow_divzero=True, **dict(shape, **inputs['few']))
+        assert c_oracle.ef(soa, 50, 0)[0] != 0
+
+        def run(dbg):
+            with pytest.raises(ZeroDivisionError):
+                ctx.run_host(soa, 50, 0)
+        in_every_mode(run)
