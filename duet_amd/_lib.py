@@ -39,7 +39,8 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_ef_features_cap_device', 'duet_ef_features_cap_host', 'duet_svim_features_cap_device', 'duet_svim_features_cap_host',
            'duet_tune_cap_line_device', 'duet_tune_cap_line_host', 'duet_svim_cap_line_device', 'duet_svim_cap_line_host',
            'duet_tune_leaf_census_device', 'duet_tune_leaf_census_host', 'duet_tune_leaves_device', 'duet_tune_leaves_host',
-           'duet_evidence_rows_device', 'duet_evidence_rows_host')
+           'duet_evidence_rows_device', 'duet_evidence_rows_host',
+           'duet_ps_links_device', 'duet_ps_links_host', 'duet_svim_ps_links_device', 'duet_svim_ps_links_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -184,6 +185,24 @@ def evidence_header():
     return ('\t'.join(EVIDENCE_COLUMNS) + '\n').encode()
 
 
+# phase-set links (include/duet_ef.h, "Phase-set links"; duet_amd/ps_links.py): one record per (contig, ps_a, ps_b)
+class PsLink(ctypes.Structure):
+    """duet_ps_link (56 bytes)."""
+    _fields_ = [('w_same', ctypes.c_uint64), ('w_flip', ctypes.c_uint64)] + \
+               [(n, ctypes.c_uint32) for n in ('contig', 'ps_a', 'ps_b', 'n_sv', 'n_same', 'n_flip', 'n_open', 'pos_min', 'pos_max',
+                                               'reserved')]
+
+
+PS_LINK_DTYPE = np.dtype([('w_same', '<u8'), ('w_flip', '<u8')] +
+                         [(n, '<u4') for n in ('contig', 'ps_a', 'ps_b', 'n_sv', 'n_same', 'n_flip', 'n_open', 'pos_min', 'pos_max',
+                                               'reserved')])
+
+
+def ps_links_room(n_marks):
+    """The records duet_ps_links_* can write at most (include/duet_ef.h): what the caller allocates for one call."""
+    return max(int(n_marks), 1) - 1
+
+
 class TuneTruth(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ('n_uid', 'n_groups', 'n_pairs', 'reserved')] + \
                [(n, ctypes.c_void_p) for n in ('cand_flags', 'cand_group', 'cand_uid', 'cand_pair', 'group_pair_off', 'pair_uid')]
@@ -322,6 +341,14 @@ def load():
     lib.duet_evidence_rows_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(EvidenceProblem), ctypes.c_void_p, ctypes.c_uint64,
                                               ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
     lib.duet_evidence_rows_host.argtypes = lib.duet_evidence_rows_device.argtypes[:-1]
+    lib.duet_ps_links_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(EfProblem), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                         ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+    lib.duet_ps_links_host.argtypes = lib.duet_ps_links_device.argtypes[:-1]
+    lib.duet_svim_ps_links_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult), ctypes.c_uint32,
+                                              ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                              ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+    lib.duet_svim_ps_links_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult), ctypes.c_uint32,
+                                            ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     lib.duet_tune_line_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
@@ -912,6 +939,63 @@ class Context(object):
         if rc:
             self._raise(rc)
         return n.value
+
+    # -- phase-set links (duet_pslinks.hip) -------------------------------------------------------------------------------------
+    def ps_links_host(self, soa, svlen_thres, suppread_thres, pc_cap=None):
+        """duet_ps_links_host: the links of an EfSoA -> structured array of PS_LINK_DTYPE, ascending by (contig, ps_a, ps_b).
+        pc_cap: the PC cap of the voters (None: the reference's 8100)."""
+        cap = check_pc_cap(pc_cap)
+        prob, keep = problem_from_arrays(soa, svlen_thres, suppread_thres)
+        room = ps_links_room(soa.n_marks)
+        out = np.zeros(room, dtype=PS_LINK_DTYPE)
+        n = ctypes.c_uint32(0)
+        rc = self.lib.duet_ps_links_host(self.handle, ctypes.byref(prob), PC_MAX if cap is None else cap, _ptr(out), room, ctypes.byref(n))
+        del keep
+        if rc:
+            self._raise(rc)
+        return out[:n.value].copy()
+
+    def ps_links_device(self, prob, out_ptr, out_cap, stream=0, pc_cap=None):
+        """duet_ps_links_device on a resident EfProblem (devmem.DeviceProblem.problem); out_ptr: device room for out_cap records
+        -> the record count."""
+        cap = check_pc_cap(pc_cap)
+        n = ctypes.c_uint32(0)
+        rc = self.lib.duet_ps_links_device(self.handle, ctypes.byref(prob), PC_MAX if cap is None else cap, ctypes.c_void_p(out_ptr),
+                                           int(out_cap), ctypes.byref(n), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return n.value
+
+    def svim_ps_links_device(self, sv_problem, result, out_ptr, out_cap, stream=0, pc_cap=None):
+        """duet_svim_ps_links_device on a resident SvimProblem (devmem.DeviceSvim) -> (record count, candidate count)."""
+        cap = check_pc_cap(pc_cap)
+        n, n_cands = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        rc = self.lib.duet_svim_ps_links_device(self.handle, ctypes.byref(sv_problem), ctypes.byref(result), PC_MAX if cap is None else cap,
+                                                ctypes.c_void_p(out_ptr), int(out_cap), ctypes.byref(n), ctypes.byref(n_cands),
+                                                ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return n.value, n_cands.value
+
+    def svim_ps_links_host(self, marks, read_tag, depth, depth_off, depth_bin, svlen_thres, suppread_thres, max_dist=0.9, part_gap=1000,
+                           part_max=100, normalizer=900.0, pc_cap=None, want_order=False):
+        """duet_svim_ps_links_host: like svim_host, with the links (PS_LINK_DTYPE) of the clustered candidates in place of pred / ps
+        -> dict(cluster arrays trimmed to the candidate count, links)."""
+        cap = check_pc_cap(pc_cap)
+        p, res, out, order, n, keep = self._svim_host_problem(marks, read_tag, depth, depth_off, depth_bin, svlen_thres, suppread_thres,
+                                                              max_dist, part_gap, part_max, normalizer, want_order)
+        room = ps_links_room(p.marks.n_marks)
+        links = np.zeros(room, dtype=PS_LINK_DTYPE)
+        n_links = ctypes.c_uint32(0)
+        rc = self.lib.duet_svim_ps_links_host(self.handle, ctypes.byref(p), ctypes.byref(res), PC_MAX if cap is None else cap, _ptr(links),
+                                              room, ctypes.byref(n_links))
+        del keep
+        if rc:
+            self._raise(rc)
+        got = dict(self._svim_trim(out, n.value), links=links[:n_links.value].copy())
+        if want_order:
+            got['order'] = order[:p.marks.n_marks]
+        return got
 
     def strata_build_device(self, prob, truth, chrom_stratum_ptr, n_strata, cand_stratum_ptr, group_stratum_ptr, stream=0):
         """duet_tune_strata_build_device on resident arrays (devmem.DeviceTune), after truth_build_device on the same prob / truth."""

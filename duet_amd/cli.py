@@ -18,23 +18,27 @@ def pipeline(a):
     """(callable, arguments) per stage, in upstream's fixed order: SNP call, SV call, SNP phase, SV phase.
     `-b svim-gpu` (additive): no external SV caller -- signatures, `--cluster_max_distance` clustering and phasing all run on
     the GPU from the haplotagged BAMs (duet_amd/svim_mode.py)."""
+    # (--write_ps_links travels as a keyword: the positional arguments of the last stage stay what they were)
+    extra = {'ps_links': True} if getattr(a, 'write_ps_links', False) else {}
     if a.sv_caller == 'svim-gpu':
         from duet_amd.svim_mode import sv_phasing_from_bams
+        last = (lambda *args: sv_phasing_from_bams(*args, **extra)) if extra else sv_phasing_from_bams
         return (
             (stages.snp_calling, (a.OUTPUT, a.REFERENCE, a.BAM, a.min_allele_frequency, a.thread, a.include_all_ctgs)),
             (stages.snp_phasing, (a.OUTPUT, a.REFERENCE, a.BAM, a.thread)),
-            (sv_phasing_from_bams, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs,
-                                    a.cluster_max_distance, a.device, a.gpus, a.write_sv_calls,
-                                    getattr(a, 'threshold_vector', None), getattr(a, 'pc_cap_value', None),
-                                    bool(getattr(a, 'write_evidence', False)))),
+            (last, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs,
+                    a.cluster_max_distance, a.device, a.gpus, a.write_sv_calls,
+                    getattr(a, 'threshold_vector', None), getattr(a, 'pc_cap_value', None),
+                    bool(getattr(a, 'write_evidence', False)))),
         )
+    last = (lambda *args: sv_phasing(*args, **extra)) if extra else sv_phasing
     return (
         (stages.snp_calling, (a.OUTPUT, a.REFERENCE, a.BAM, a.min_allele_frequency, a.thread, a.include_all_ctgs)),
         (stages.sv_calling, (a.OUTPUT, a.REFERENCE, a.BAM, a.cluster_max_distance, a.sv_min_size, a.thread, a.sv_caller,
                              a.min_support_read)),
         (stages.snp_phasing, (a.OUTPUT, a.REFERENCE, a.BAM, a.thread)),
-        (sv_phasing, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs, a.device, a.gpus,
-                      a.threshold_vector, a.pc_cap_value, bool(getattr(a, 'write_evidence', False)))),
+        (last, (a.OUTPUT, a.sv_min_size, a.min_support_read, a.thread, a.include_all_ctgs, a.device, a.gpus,
+                a.threshold_vector, a.pc_cap_value, bool(getattr(a, 'write_evidence', False)))),
     )
 
 
@@ -66,6 +70,11 @@ def main(argv):
         if a.threshold_vector is None:
             from duet_amd import tune
             a.threshold_vector = tune.vector()
+    if a.write_ps_links:
+        # (additive: the phase-set link tables, OUTPUT/phased_sv.ps_links.tsv and OUTPUT/phased_sv.ps_blocks.tsv -- built from the
+        # problem one GPU holds; the decision keeps whatever route the other flags give it)
+        if a.gpus > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise SystemExit('duet: --write_ps_links works on the single-GPU path only (not with --gpus > 1)')
     check_envs(a.REFERENCE, a.BAM)
     os.makedirs(a.OUTPUT, exist_ok=True)
     set_logging(a.OUTPUT)

@@ -91,6 +91,7 @@ struct duet_ctx {
     DuetOwnedBufs callset_ws;            // svim-gpu callset rows (duet_callset.hip): workspace 0-4, host-run staging 5-14, text 15
     DuetOwnedBufs evidence_ws;             // evidence table (duet_evidence.hip): row lengths 0, row offsets 1, tile sums 2, status words and CHROM texts 3; host-run staging 4-12, text 13
     DuetOwnedBufs svim_rows_ws;            // svim-gpu rows of phased_sv.vcf (duet_svim_rows.hip): workspace 0-8, host-run staging 9-14, text 15
+    DuetOwnedBufs pslinks_ws;              // phase-set links (duet_pslinks.hip): per-candidate workspace 0, per-voter workspace 1; host-run staging of the records 2
 };
 
 extern thread_local std::string duet_g_last_error;
@@ -126,6 +127,11 @@ int duet_ef_validate(duet_ctx *ctx, const duet_ef_problem *pr);
 
 // host arrays of an E/F problem -> the context's staging buffers (duet_ef.hip)
 int duet_ef_upload(duet_ctx *ctx, const duet_ef_problem *pr, duet_ef_problem *d, hipStream_t s);
+
+// phase-set links (duet_pslinks.hip) of a device-resident problem, checked by the caller; out is device memory, or with
+// out_on_host host memory (the records are staged and copied, the stream synchronised).  For the SVIM drivers in duet_svim.hip.
+int duet_ps_links_run(duet_ctx *ctx, const duet_ef_problem *pr, uint32_t pc_cap, duet_ps_link *out, uint32_t out_cap, uint32_t *n_links,
+                      hipStream_t st, bool out_on_host);
 
 inline int duet_reserve(duet_ctx *ctx, DevBuf &b, size_t bytes)
 {

@@ -202,9 +202,65 @@ int svim_features_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cl
     return rc;
 }
 
+// The phase-set links of the fused pipeline's candidates (duet_pslinks.hip): the front, the host plan, then the links of the
+// adapted problem -- as svim_features_device reaches the feature export.  out_on_host: the records go to host memory.
+int svim_ps_links_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, uint32_t pc_cap, duet_ps_link *out,
+                         uint32_t out_cap, uint32_t *n_links, uint32_t *n_cands_host, hipStream_t st, bool out_on_host)
+{
+    if (n_links) *n_links = 0;
+    int rc = svim_cap_check(ctx, &pc_cap);
+    if (rc) return rc;
+    duet_ef_problem ef;
+    std::vector<uint32_t> ctg_off;
+    rc = svim_front(ctx, pr, res, n_links && n_cands_host && (out || !out_cap), n_cands_host, st, ef);
+    if (rc || ef.n_marks == 0) return rc;
+    if ((rc = svim_host_plan(ctx, res, st, ctg_off, ef))) return rc;
+    *n_cands_host = ef.n_cands;
+    if (ef.n_cands == 0) return DUET_OK;
+    return duet_ps_links_run(ctx, &ef, pc_cap, out, out_cap, n_links, st, out_on_host);
+}
+
+int svim_ps_links_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, uint32_t pc_cap, duet_ps_link *out,
+                       uint32_t out_cap, uint32_t *n_links)
+{
+    if (n_links) *n_links = 0;
+    int rc = svim_cap_check(ctx, &pc_cap);
+    if (rc) return rc;
+    rc = svim_host_check(ctx, pr, res, n_links && (out || !out_cap));
+    if (rc || pr->marks.n_marks == 0) return rc;
+    hipStream_t s = ctx->own_stream;
+    const uint32_t M = pr->marks.n_marks;
+    duet_svim_problem d;
+    duet_cluster_result r;
+    if ((rc = svim_stage(ctx, pr, &d, &r, s))) return rc;
+    uint32_t n = 0;
+    rc = svim_ps_links_device(ctx, &d, &r, pc_cap, out, out_cap, n_links, &n, s, true);
+    // (a record buffer that is too small: the cluster result comes back all the same, and the message with the exact count)
+    if (rc && !(rc == DUET_ERR_INVALID && *n_links > out_cap)) return rc;
+    const std::string msg = ctx->err;
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    *res->n_cands = n;
+    int rc2 = duet_fetch_cluster_result(ctx, M, n, &r, res);
+    if (rc2) return rc2;
+    if (rc) ctx->err = msg;
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+int duet_svim_ps_links_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, uint32_t pc_cap, duet_ps_link *out,
+                              uint32_t out_cap, uint32_t *n_links, uint32_t *n_cands_host, void *stream_)
+{
+    return svim_ps_links_device(ctx, pr, res, pc_cap, out, out_cap, n_links, n_cands_host, (hipStream_t)stream_, false);
+}
+
+int duet_svim_ps_links_host(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, uint32_t pc_cap, duet_ps_link *out,
+                            uint32_t out_cap, uint32_t *n_links)
+{
+    return svim_ps_links_host(ctx, pr, res, pc_cap, out, out_cap, n_links);
+}
 
 int duet_svim_phase_device(duet_ctx *ctx, const duet_svim_problem *pr, const duet_cluster_result *res, uint8_t *out_pred,
                            uint32_t *out_ps, uint32_t *n_cands_host, void *stream_)

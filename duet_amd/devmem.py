@@ -244,6 +244,18 @@ class DeviceSvim(DeviceCluster):
         n = ctx.evidence_rows_device(p, out.data_ptr(), cap, stream)
         return out[:n].cpu().numpy()
 
+    def ps_links(self, ctx, pc_cap=None, stream=None):
+        """The phase-set links (_lib.PS_LINK_DTYPE, ascending by (contig, ps_a, ps_b)) of the candidates the resident marks cluster
+        into (duet_svim_ps_links_device: it clusters again and leaves the same cluster result in self.result; out_pred / out_ps
+        of an earlier run stay as they are).  pc_cap: the PC cap of the voters (None: 8100).  -> structured numpy array."""
+        torch = self.torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        room = _lib.ps_links_room(self.M)
+        out = torch.zeros(max(room, 1) * _lib.PS_LINK_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        n, self.n_found = ctx.svim_ps_links_device(self.sv_problem, self.result, out.data_ptr(), room, stream, pc_cap=pc_cap)
+        return out[:n * _lib.PS_LINK_DTYPE.itemsize].cpu().numpy().view(_lib.PS_LINK_DTYPE).copy()
+
     def vcf_rows(self, ctx, names, chrom_texts, stream=None):
         """Rows of sv_calling/variants.vcf for the last run_fused's candidates, formatted on the device from the resident
         cluster result and depth (duet_svim_vcf_rows_device).  names: dict(mark_name, name_off, name_pool) of

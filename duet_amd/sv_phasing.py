@@ -10,7 +10,10 @@ fields ...) and the Python path then takes over, so the observable behaviour is 
 Set DUET_NATIVE_INGEST=0 to force the Python path; DUET_DEVICE_ROWS=0 keeps the native path but formats the rows on
 the host instead of on the device.
 
-Five additive keyword arguments (upstream's five positionals are unchanged): `evidence` = also write
+Six additive keyword arguments (upstream's five positionals are unchanged): `ps_links` = also write
+<home>/phased_sv.ps_links.tsv and <home>/phased_sv.ps_blocks.tsv, how the SV candidates tie neighbouring phase sets together
+(duet_amd/ps_links.py; single-GPU native path, with or without `thresholds`; under `pc_cap` the voters are that cap's),
+`evidence` = also write
 <home>/phased_sv.evidence.tsv, one row per candidate with its vote, the rule of the tree it ended at and the call (the route of
 `thresholds`, with the default vector where none is given), `thresholds` = a vector of the decision's
 T1-T5 constants (duet_amd/tune.py; native single-GPU path only), `pc_cap` = the PC cap of the vote in place of 8100 (the same
@@ -67,11 +70,47 @@ def write_header(ing, include_all_ctgs, out_vcf):
         out.write(ing.header(include_all_ctgs))
 
 
-def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx):
+def contig_texts(ing, chrom_list):
+    """The CHROM text the rows of phased_sv.vcf carry for every contig: that of the contig's first candidate in the ingest's
+    string pool (a contig without candidates: its name in the chrom list -- no row carries it)."""
+    texts = list(chrom_list)
+    if ing.soa.n_cands:
+        rows = ing.rows()
+        if rows is None:
+            raise RuntimeError('--write_ps_links: the native ingest has no string pool for this input')
+        pool, off, ctg = rows['pool'], rows['str_off'], ing.soa.cand_ctg_off
+        for k in range(ing.soa.n_contigs):
+            if ctg[k + 1] > ctg[k]:
+                c = int(ctg[k])
+                texts[k] = pool[int(off[4 * c]):int(off[4 * c + 1])].tobytes().decode('utf-8', 'replace')
+    return texts
+
+
+def native_ps_links(ing, chrom_list, svlen_thres, suppread_thres, ctx, pc_cap=None):
+    """(records, CHROM text per contig) of the ingest's problem (duet_ps_links_host), while the ingest is still open."""
+    from duet_amd import ps_links
+    texts = contig_texts(ing, chrom_list)
+    records = ctx.ps_links_host(ing.soa, svlen_thres, suppread_thres, pc_cap=pc_cap) if ing.soa.n_cands else ps_links.empty()
+    return records, texts
+
+
+def write_ps_links(home, links):
+    from duet_amd import ps_links
+    logging.info('write the phase-set links into phased_sv.ps_links.tsv and phased_sv.ps_blocks.tsv')
+    n, n_ps, n_conflicts = ps_links.write(home, *links)
+    logging.info('  %d links over %d phase sets, %d contradicted' % (n, n_ps, n_conflicts))
+
+
+def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, ps_links=False):
     ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf)
     if ing is None:
+        if ps_links:
+            raise RuntimeError('--write_ps_links needs the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
         return False
+    links = None
     try:
+        if ps_links:
+            contig_texts(ing, chrom_list)           # (before the output file is created: a refusal leaves nothing behind)
         write_header(ing, include_all_ctgs, out_vcf)
         log_ingest(ing, chrom_list)
         logging.info('integrate read weight information')
@@ -84,6 +123,8 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
         else:
             pred, ps = engine.run_ef(ing.soa, svlen_thres, suppread_thres, ctx=ctx)
             body = ing.emit_rows(pred, ps)
+        if ps_links:
+            links = native_ps_links(ing, chrom_list, svlen_thres, suppread_thres, ctx)
         logging.info('write phased callset into .vcf file')
     except BaseException:
         ing.close()
@@ -91,6 +132,8 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
     ing.close_in_background()                       # (the rows are out: freeing the ingest's memory needs nobody's attention)
     with open(out_vcf, 'ab') as out:
         out.write(body)
+    if links is not None:
+        write_ps_links(home, links)
     return True
 
 
@@ -99,19 +142,21 @@ def evidence_path(home):
 
 
 def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, vec, pc_cap=None,
-                       evidence=False):
+                       evidence=False, ps_links=False):
     """The native path with the decision's constants taken from `vec` (duet_amd/tune.py): ingest, the feature export (pc_cap:
     under that PC cap, duet_ef_features_cap_host), a sweep of one vector that keeps its (pred, ps), the rows.
     evidence: also <home>/phased_sv.evidence.tsv, one row per candidate formatted on the device (duet_evidence_rows_host, the text
-    form over the ingest's string pool)."""
+    form over the ingest's string pool).  ps_links: also the two phase-set link tables, the voters under the same PC cap."""
     from duet_amd import _lib, tune
     ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf)
     if ing is None:
-        raise RuntimeError('--thresholds / --pc_cap / --write_evidence need the native ingest, which declined this input '
-                           '(or DUET_NATIVE_INGEST=0)')
-    table = None
+        raise RuntimeError('--thresholds / --pc_cap / --write_evidence%s need the native ingest, which declined this input '
+                           '(or DUET_NATIVE_INGEST=0)' % (' / --write_ps_links' if ps_links else ''))
+    table, links = None, None
     try:
         rows = None
+        if ps_links:
+            contig_texts(ing, chrom_list)           # (before the output file is created: a refusal leaves nothing behind)
         if evidence and ing.soa.n_cands:
             rows = ing.rows()                       # (before the output file is created: a refusal leaves nothing behind)
             if rows is None:
@@ -134,6 +179,8 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
             if ing.soa.n_cands:
                 leaf, _ = tune.explain(dict(feat=feat), vec, ctx=ctx)
                 table = ctx.evidence_rows_host(feat, leaf, pred, ing.soa.cand_pos, ing.soa.cand_svlen, rows=rows)
+        if ps_links:
+            links = native_ps_links(ing, chrom_list, svlen_thres, suppread_thres, ctx, pc_cap=pc_cap)
         logging.info('write phased callset into .vcf file')
     finally:
         ing.close()
@@ -144,10 +191,15 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
         with open(evidence_path(home), 'wb') as out:
             out.write(_lib.evidence_header())
             out.write(table)
+    if links is not None:
+        write_ps_links(home, links)
 
 
 def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, device=0, gpus=1, thresholds=None, pc_cap=None,
-               evidence=False):
+               evidence=False, ps_links=False):
+    if ps_links and (int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1'):
+        # (additive: the phase-set links -- the native single-GPU path, whichever route the decision takes)
+        raise ValueError('ps_links: single-GPU path only')
     if evidence:
         # (additive: the evidence table -- the route is that of `thresholds`, with the default vector where none is given)
         from duet_amd import tune
@@ -174,7 +226,7 @@ def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, devi
         if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
             raise ValueError('thresholds: single-GPU path only')
         _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf,
-                           engine.default_context(int(device)), thresholds, pc_cap, evidence=bool(evidence))
+                           engine.default_context(int(device)), thresholds, pc_cap, evidence=bool(evidence), ps_links=bool(ps_links))
         done = True
     # (DUET_FORCE_RANKS=1: the one-process-per-GPU path even with one GPU -- rank 0 of 1 over RCCL; tests use it to take the
     # collective through the real backend on a one-GPU box)
@@ -183,7 +235,7 @@ def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, devi
         done = multi.sv_phasing_sharded(home, svlen_thres, suppread_thres, thread, include_all_ctgs, int(gpus))
     if not done:
         ctx = engine.default_context(int(device))
-        if not _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx):
+        if not _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, ps_links=bool(ps_links)):
             print_sv_header(caller_vcf, out_vcf, include_all_ctgs)
             rows = generate_phased_callset(caller_vcf, home + '/snp_phasing/', svlen_thres, suppread_thres, thread,
                                            include_all_ctgs, ctx=ctx)

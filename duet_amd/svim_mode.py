@@ -17,7 +17,7 @@ from duet_amd.native import NativeIngest
 from duet_amd.read_file import init_chrom_list
 
 
-def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_cap=None, evidence_texts=None):
+def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_cap=None, evidence_texts=None, ps_links=False):
     """-> compute(extracted arrays, svlen_thres, suppread_thres, max_dist, depth_bin) -> dict of result arrays, on ctx's GPU:
     stage A0 -> adapter -> step E/F in one device pipeline (duet_svim_phase_device).  chrom_texts (CHROM text per contig): the
     extracted arrays carry the marks' read names, and the result also holds `calls`, the rows of sv_calling/variants.vcf formatted
@@ -26,7 +26,8 @@ def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_ca
     thresholds (float64[14], --thresholds): the decision is made with this vector -- the candidates' features
     (duet_svim_features_device; pc_cap: under that PC cap, duet_svim_features_cap_device) and one vector applied to them
     (duet_tune_sweep_device) in place of the fused run's E/F.  evidence_texts (CHROM text per contig; needs thresholds): the result
-    also holds `evidence`, the data rows of the evidence table, one per candidate (duet_evidence_rows_device)."""
+    also holds `evidence`, the data rows of the evidence table, one per candidate (duet_evidence_rows_device).  ps_links: the result
+    also holds `ps_links`, the phase-set link records of the candidates (duet_svim_ps_links_device; the voters under pc_cap)."""
     if evidence_texts is not None and thresholds is None:
         raise ValueError('the evidence table needs a threshold vector')
 
@@ -48,6 +49,8 @@ def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_ca
             res['calls'] = ds.vcf_rows(ctx, got, chrom_texts)
         if evidence_texts is not None:
             res['evidence'] = ds.evidence_rows(ctx, evidence_texts)
+        if ps_links:
+            res['ps_links'] = ds.ps_links(ctx, pc_cap=pc_cap)       # (last: it clusters again, into the same result arrays)
         return res
     return compute
 
@@ -433,7 +436,7 @@ def rank_main(argv):
 
 
 def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, cluster_max_distance=0.9, device=0,
-                         gpus=1, write_sv_calls=False, thresholds=None, pc_cap=None, evidence=False):
+                         gpus=1, write_sv_calls=False, thresholds=None, pc_cap=None, evidence=False, ps_links=False):
     """`duet ... -b svim-gpu -c <max distance>`: SV calling (signatures + clustering, what `-b svim` delegates to the
     external `svim alignment ... --cluster_max_distance c`, sv_calling.py:13-15) AND SV phasing on the GPU, from the
     haplotagged BAMs of <home>/snp_phasing -> <home>/phased_sv.vcf.  The clustering half is this repository's own rule
@@ -445,7 +448,11 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
     pc_cap (--pc_cap): the PC cap of the vote in place of 8100, on the same route (without thresholds the vector is the defaults);
     the clustered calls of --write_sv_calls do not depend on it.
     evidence (--write_evidence): also <home>/phased_sv.evidence.tsv, one row per clustered candidate with its vote, the rule of the
-    tree it ended at and the call, formatted on the device; the route of thresholds (without one the vector is the defaults)."""
+    tree it ended at and the call, formatted on the device; the route of thresholds (without one the vector is the defaults).
+    ps_links (--write_ps_links): also <home>/phased_sv.ps_links.tsv and <home>/phased_sv.ps_blocks.tsv, how the clustered candidates
+    tie neighbouring phase sets together (duet_amd/ps_links.py); single-GPU path only, whichever route the decision takes."""
+    if ps_links and (int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1'):
+        raise ValueError('ps_links: single-GPU path only')
     if evidence:
         from duet_amd import tune
         if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
@@ -504,7 +511,8 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
     def compute(*args):
         texts = spelled_contigs(home, chroms)
         return device_compute(ctx if ctx is not None else engine.default_context(int(device)), texts if write_sv_calls else None,
-                              row_texts=texts, thresholds=thresholds, pc_cap=pc_cap, evidence_texts=texts if evidence else None)(*args)
+                              row_texts=texts, thresholds=thresholds, pc_cap=pc_cap, evidence_texts=texts if evidence else None,
+                              ps_links=bool(ps_links))(*args)
     res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
                           min_sv_size=max(int(svlen_thres), 1), names=bool(write_sv_calls), compute=compute)
     # the data rows come sorted and formatted from the device; without a single mark nothing ran and there are none
@@ -520,6 +528,10 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
         with open(evidence_path(home), 'wb') as out:       # (without a single mark nothing ran: the header line alone)
             out.write(_lib.evidence_header())
             out.write(bytes(memoryview(np.ascontiguousarray(res.get('evidence', np.zeros(0, dtype=np.uint8))))))
+    if ps_links:
+        from duet_amd import ps_links as links_mod
+        from duet_amd.sv_phasing import write_ps_links       # (without a single mark nothing ran: the header lines alone)
+        write_ps_links(home, (res.get('ps_links', links_mod.empty()), spelled_contigs(home, chroms)))
     if write_sv_calls:
         with open(out_vcf, 'wb') as out:
             out.write(header_text(home, chroms).encode())

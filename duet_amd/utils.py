@@ -4,7 +4,7 @@
 Flag names, defaults, help texts and the positional order are upstream's (utils.py:19-44), so an
 existing command line works unchanged.  Two additive options select the device (--device) or shard the contigs
 over several GPUs (--gpus); --thresholds and --pc_cap replace the decision's constants on the single-GPU path,
---write_evidence adds the per-candidate evidence table there.
+--write_evidence adds the per-candidate evidence table there, --write_ps_links the phase-set link tables.
 """
 
 import argparse
@@ -67,6 +67,10 @@ def build_parser():
     ap.add_argument('--write_evidence', action='store_true',
                     help='also write OUTPUT/phased_sv.evidence.tsv: one row per SV candidate, phased or not, with its vote, the rule '
                          'of the decision tree it ended at and the call; one GPU only (the native path, or -b svim-gpu)')
+    ap.add_argument('--write_ps_links', action='store_true',
+                    help='also write OUTPUT/phased_sv.ps_links.tsv and OUTPUT/phased_sv.ps_blocks.tsv: which WhatsHap phase sets the SV '
+                         'candidates tie together, in which sense and how strongly, and the blocks they join into; one GPU only (the '
+                         'native path, or -b svim-gpu)')
     ap.add_argument('--write_sv_calls', action='store_true',
                     help='with -b svim-gpu, also write the clustered SV calls to OUTPUT/sv_calling/variants.vcf')
     for name, text in _POSITIONALS:

@@ -792,6 +792,62 @@ DUET_API int duet_svim_cap_line_host(duet_ctx *ctx, const duet_svim_problem *pro
                                      uint32_t *n_caps, uint32_t *n_distinct);
 
 /* ---------------------------------------------------------------------------------------------
+ * Phase-set links (duet_pslinks.hip): how the SV candidates tie neighbouring phase sets together.  A
+ * candidate whose supporting reads fall into two phase sets says which haplotype of the one is which haplotype of the other:
+ * reads of haplotype 1 in phase set A and of haplotype 2 in phase set B mean that A's haplotype 1 and B's haplotype 2 are one
+ * chromosome copy.  One record per pair of phase sets collects that over all candidates of a contig.  tests/ps_links_ref.py
+ * states the rule in plain Python.
+ *
+ *   Candidates  the kept ones: cand_svlen >= svlen_thres, cand_svread >= suppread_thres, cand_gt_ok != 0.  Neither the seed sets
+ *               nor the call play a part.
+ *   Voters      a mark votes iff its read index is not DUET_MARK_ABSENT and < n_reads, its tag word is not all-ones,
+ *               pc <= pc_cap and hap is 1 or 2 (a tagged read with hap 3 takes no part: unlike `allhap`).  A read marked twice
+ *               counts twice, as in the vote.
+ *   Groups      a candidate's voters grouped by PS: h1, h2 = the voters of haplotype 1, 2; d = h1 - h2.
+ *   Pairs       the candidate's distinct PS values ascending (unsigned); each two neighbours (a, b), a < b, are one observation
+ *               on the link (contig, a, b): a candidate with G groups gives G - 1 observations, none between non-neighbours.
+ *   Kind        open when d_a == 0 or d_b == 0; same when both have the same sign; flip otherwise.  Weight w = min(|d_a|, |d_b|)
+ *               (0 for an open observation).
+ *   Record      one per distinct (contig, ps_a, ps_b): n_same, n_flip, n_open = the observations of each kind, n_sv their sum;
+ *               w_same, w_flip = the weights summed over the same / flip observations; pos_min, pos_max over the cand_pos of
+ *               the contributing candidates; contig = the contig index; reserved = 0.  Records ascend by (contig, ps_a, ps_b),
+ *               the PS values compared as full unsigned 32-bit numbers.
+ * Every sum is an integer sum and no kernel of the unit uses an atomic (the shared sort's histogram counts with integer atomics up
+ * to 1024 tiles: sums), so nothing depends on the order in which anything arrives: two runs give identical bytes.
+ *
+ * pc_cap: 0 .. 2^30 - 3 (DUET_PC_MAX for the reference's cap); above: DUET_ERR_INVALID.
+ * *n_links = the exact record count, always (0 on a refusal of the arguments).  n_links > out_cap: nothing is written to out and
+ * the call returns DUET_ERR_INVALID.  max(n_marks, 1) - 1 records always suffice.  out may be NULL when out_cap is 0.
+ * Whatever duet_ef_run_* refuses in *prob is refused here.  n_cands == 0 or n_marks == 0: DUET_OK, 0 links, no array is read.
+ * _device: the arrays of *prob (cand_ctg_off aside: HOST, as always) and out are device memory, n_links host memory.  The call makes
+ * up to THREE host round trips, each a few words: the number of voting marks of the candidates with two or more phase sets (sizes
+ * the first sort; 0 ends the call), the number of observations (sizes the second and third sort), the number of records (checked
+ * against out_cap before anything is written).  The records are written asynchronously on `stream`.
+ * _host: host arrays, out host; uploads, runs the same kernels, copies the records back, synchronises.
+ * The workspace is the entry's own (about 60 bytes per voting mark of a multi-phase-set candidate, 8 per candidate; grown, never
+ * shrunk): a call changes nothing that a later duet_ef_run_*, duet_ef_features_* or duet_tune_* returns.
+ *
+ * duet_svim_ps_links_*: the same for the candidates of the fused pipeline -- clusters and adapts as duet_svim_features_device does
+ * (every call clusters again: the entry keeps no state; one more host round trip for the candidates per contig), then the links
+ * of the adapted problem.  The cluster result stays in *res; _device: *n_cands_host = the candidate count (mandatory); _host: arrays
+ * as for duet_svim_phase_host, the count in *res->n_cands. */
+typedef struct duet_ps_link {            /* 56 bytes */
+    uint64_t w_same, w_flip;
+    uint32_t contig, ps_a, ps_b;
+    uint32_t n_sv, n_same, n_flip, n_open;
+    uint32_t pos_min, pos_max;
+    uint32_t reserved;                   /* 0 */
+} duet_ps_link;
+DUET_API int duet_ps_links_device(duet_ctx *ctx, const duet_ef_problem *prob, uint32_t pc_cap, duet_ps_link *out, uint32_t out_cap,
+                                  uint32_t *n_links, void *stream);
+DUET_API int duet_ps_links_host(duet_ctx *ctx, const duet_ef_problem *prob, uint32_t pc_cap, duet_ps_link *out, uint32_t out_cap,
+                                uint32_t *n_links);
+DUET_API int duet_svim_ps_links_device(duet_ctx *ctx, const duet_svim_problem *prob, const duet_cluster_result *res, uint32_t pc_cap,
+                                       duet_ps_link *out, uint32_t out_cap, uint32_t *n_links, uint32_t *n_cands_host, void *stream);
+DUET_API int duet_svim_ps_links_host(duet_ctx *ctx, const duet_svim_problem *prob, const duet_cluster_result *res, uint32_t pc_cap,
+                                     duet_ps_link *out, uint32_t out_cap, uint32_t *n_links);
+
+/* ---------------------------------------------------------------------------------------------
  * The collective of the contig-sharded path: candidates shard by contig over the GPUs of one node,
  * one process and one context per GPU, and ONE all-gather of fixed-size record blocks reassembles the call set
  * (src/duet/sv_phasing_fn.py:15-18, 195-210: nothing crosses contigs before the final sort at :229).  RCCL over xGMI,
