@@ -191,38 +191,41 @@ __device__ __forceinline__ uint32_t find_contig(const uint32_t *__restrict__ ctg
 }
 
 struct Params {
+    // ---- what ef_classify reads, side by side at the front: the kernel takes them all at entry, behind one wait (round 8; a field
+    // first touched later is a scalar round trip of its own wherever that is) ----
     uint32_t K, C, M;
     uint32_t n_reads;                 // entries of read_tag (an index at or beyond it: the mark has no tag)
-    const uint64_t *untagged;         // the context's all-ones word (what such a mark gathers instead)
-    const uint64_t *read_tag;
-    const uint32_t *cand_pos, *cand_svlen, *cand_svread, *cand_refread;
-    const uint8_t *cand_gt_ok;
     const uint32_t *cand_off, *mark_read;
+    const uint64_t *read_tag;
+    const uint64_t *untagged;         // the context's all-ones word (what such a mark gathers instead)
+    const uint32_t *cand_svlen, *cand_svread, *cand_refread;
+    const uint8_t *cand_gt_ok;
+    const uint8_t *ctg_start;         // [C]   1 where a candidate is the first of its contig (workspace, plan-time constant)
     uint32_t svlen_thres, suppread_thres;
-    // workspace (plan-time constants)
-    const uint32_t *ctg_off;          // [K+1] device copy of cand_ctg_off
-    const uint8_t *ctg_start;         // [C]   1 where a candidate is the first of its contig
-    const uint32_t *blk_ctg;          // [B]   contig of candidate 256*b
+    uint32_t heavy_t;                 // ef_classify: candidates with more marks than this leave the lanes' serial walk for the wave-cooperative one
+    uint32_t dbg;                     // diagnostic DUET_DBG_* bits (0 in production)
+    uint8_t *out_pred;
+    uint32_t *out_ps;
     // workspace (per run)
     uint64_t *blk_rec;                // [B][8] per classify block, one 64-byte line: {entry count, entries 0 .. 6} (entries 3 .. also in seed_ent:
                                       //        ef_seed_sort reads the first half, ef_finalize_own the line -- no dependent trip for a tile of up to seven)
     uint64_t *seed_ent;               // [B*256] entries 3.. of a block: (candidate << 32 | seed PS)
+    uint32_t *c2rec;                  // [c2_cap][kC2Words] group summaries of multi-PS candidates: kC2Quota slots per tile, then a shared pool
+    uint32_t *status;                 // [0] = div-zero flag, [1] = pool slots handed out in this run (ef_finalize zeroes it again)
+    uint32_t c2_fixed, c2_cap;        // B * kC2Quota; that + the pool's slots
+    unsigned long long *stamps;       // diagnostic build only: [kernel][block][8] wall-clock stamps
+    const uint32_t *dyn_c;            // device-planned runs (DYN kernels): the candidate count lives on the device, C is an upper bound
+    const uint16_t *cand_contig;      // ... and, when the plan came from the candidates' contig column, that column (else null)
+    const uint32_t *blk_ctg;          // [B]   contig of candidate 256*b (workspace, plan-time constant)
+    const uint32_t *ctg_off;          // [K+1] device copy of cand_ctg_off (workspace, plan-time constant)
+    // ---- what only the other kernels read ----
+    const uint32_t *cand_pos;
     uint32_t *onebuf;                 // [C+K] per contig at ctg_off[k]+k: {n, ascending distinct seed PS...}
     uint32_t one_cap;                 // C + K
     uint32_t *tmpbuf;                 // [C]   scratch of the out-of-LDS seed sort
     uint32_t *n_one;                  // [K]   length of contig k's seed array
-    uint32_t *c2rec;                  // [c2_cap][kC2Words] group summaries of multi-PS candidates: kC2Quota slots per tile, then a shared pool
-    uint32_t c2_fixed, c2_cap;        // B * kC2Quota; that + the pool's slots
-    uint32_t *status;                 // [0] = div-zero flag, [1] = pool slots handed out in this run (ef_finalize zeroes it again)
-    uint8_t *out_pred;
-    uint32_t *out_ps;
     uint32_t n_small;                 // K when K <= kSmallK: the contig offsets then also ride in the kernel arguments
     uint32_t ctg_small[kSmallK + 1];  //   (scalar loads instead of a dependent HBM round trip)
-    const uint32_t *dyn_c;            // device-planned runs (DYN kernels): the candidate count lives on the device, C is an upper bound
-    const uint16_t *cand_contig;      // ... and, when the plan came from the candidates' contig column, that column (else null)
-    uint32_t dbg;                     // diagnostic DUET_DBG_* bits (0 in production)
-    uint32_t heavy_t;                 // ef_classify: candidates with more marks than this leave the lanes' serial walk for the wave-cooperative one
-    unsigned long long *stamps;       // diagnostic build only: [kernel][block][8] wall-clock stamps
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -430,6 +433,11 @@ __device__ __forceinline__ void consume_heavy(CandState &st, const uint64_t *s_t
     }
 }
 
+// A workgroup barrier that waits for the wavefront's LDS traffic only.  __syncthreads() is a fence as well: it drains the global
+// loads in flight (s_waitcnt vmcnt(0)) in front of s_barrier -- in ef_finalize_own that would put the summaries' round trip, issued
+// early so that it runs beside the seed set's phases, in front of the first of them.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // a tile's 64-byte record: [b] = its first half {count, entries 0 .. 2}, second(b) = entries 3 .. 6
 struct TileRecs {
     const ulonglong4 *p;
@@ -567,21 +575,33 @@ __device__ __forceinline__ void seeds_tile(const Params &p, TileShared &sh, uint
     if (tid == 0) p.blk_rec[(size_t)tile * 8] = total;
 }
 
-// ---- staging pieces: 4 * kStageIt marks per thread and pass, kStageIt x (16-byte index load -> 4 tag gathers) ----
+// ---- staging pieces: 4 * kStageIt marks per thread and pass, kStageIt 16-byte index loads, then 4 * kStageIt tag gathers ----
 // Index loads are branch-free and their values are not touched here: a conditional load, or any use of the
-// loaded registers, makes the compiler wait on the spot, which would serialise the four loads and break the
+// loaded registers, makes the compiler wait on the spot, which would serialise the loads and break the
 // software pipeline.  The mark array is 16-byte aligned on this path, so an aligned 16-byte load that starts
 // inside it stays inside its last 16-byte granule even when M is not a multiple of 4; lanes past m_end read
-// a harmless in-range address.  stage_gather masks both cases when it finally consumes the indices.
-// (What the compiler makes of it is not that yet: in the gfx950 ISA the first pass's it = 0 load sits in a branch of its own and the
-// gather's `idx < n_reads` compare waits between the first and second index loads -- more than the one trip this intends.)
-__device__ __forceinline__ void stage_load_marks(const Params &p, uint4 (&r)[kStageIt], uint32_t cs, uint32_t m_end, uint32_t tid)
+// a harmless in-range address (cs itself: cs < m_end <= M).  stage_gather masks both cases when it finally consumes the indices.
+// (Round 8: in the gfx950 ISA the kStageIt loads now leave back to back -- the scheduling barrier behind them keeps the gathers'
+// compares from moving up between them -- and the gathers of load `it` wait with vmcnt(kStageIt - 1 - it + 4 * it), for that load
+// alone, loads returning in order; the first wait for everything is stage_store's, behind the last gather.
+// tests/test_isa_classify_trips.py reads exactly that off the assembly.)
+// Nothing moves across this point, neither in the compiler's instruction selection (the empty asm "may write memory": every load
+// in front of it stays in front, every load behind it behind) nor in its schedulers.  It emits no instruction and waits for nothing.
+__device__ __forceinline__ void issue_fence()
+{
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+__device__ __forceinline__ void stage_load_marks(const uint32_t *__restrict__ mark_read, uint4 (&r)[kStageIt], uint32_t cs, uint32_t m_end,
+                                                 uint32_t tid)
 {
 #pragma unroll
     for (int it = 0; it < kStageIt; ++it) {
         const uint32_t m = cs + 4u * (tid + it * kCandPerBlock);
-        r[it] = *reinterpret_cast<const uint4 *>(p.mark_read + (m < m_end ? m : cs));
+        r[it] = *reinterpret_cast<const uint4 *>(mark_read + (m < m_end ? m : cs));
     }
+    issue_fence();
 }
 
 // Tag gathers, branch-free for the same reason -- and with nothing left to do once the tags arrive: a mark without a tag (an absent
@@ -590,28 +610,34 @@ __device__ __forceinline__ void stage_load_marks(const Params &p, uint4 (&r)[kSt
 // marks, kept twelve validity bits packed in a word and unpacked them again for a select per tag half: 8.5 vector instructions per
 // mark where this takes 4 -- the counters put this kernel at 80 % vector issue.)  The compare also covers the indices a 16-byte load
 // picks up behind the last mark of the array (anything below the table's size is a harmless gather into an LDS slot nobody reads).
-__device__ __forceinline__ void stage_gather(const Params &p, uint64_t (&t)[4 * kStageIt], const uint4 (&r)[kStageIt])
+// (a scheduling barrier behind every group of four: the groups leave in the order of the index loads they wait for)
+__device__ __forceinline__ void stage_gather(const uint64_t *__restrict__ read_tag, const uint64_t *__restrict__ untagged, uint32_t n_reads,
+                                             uint64_t (&t)[4 * kStageIt], const uint4 (&r)[kStageIt])
 {
 #pragma unroll
     for (int it = 0; it < kStageIt; ++it) {
-        const uint32_t idx[4] = {r[it].x, r[it].y, r[it].z, r[it].w};
+        // the wait for index load `it` stands here and nowhere earlier (the asm takes the four indices and hands them back: whatever
+        // is computed from them comes behind it, and it comes behind the previous group's gathers)
+        uint32_t idx[4] = {r[it].x, r[it].y, r[it].z, r[it].w};
+        asm volatile("" : "+v"(idx[0]), "+v"(idx[1]), "+v"(idx[2]), "+v"(idx[3])::"memory");
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint64_t *a = idx[j] < p.n_reads ? p.read_tag + idx[j] : p.untagged;
+            const uint64_t *a = idx[j] < n_reads ? read_tag + idx[j] : untagged;      // idx < n_reads: inside the table; else the one word
             t[4 * it + j] = *a;
         }
+        issue_fence();
     }
 }
 
-__device__ __forceinline__ void stage_store(uint64_t *s_tag, const uint64_t (&t)[4 * kStageIt], uint32_t cs, uint32_t m_end, uint32_t tid)
+__device__ __forceinline__ void stage_store(uint64_t *s_tag, const uint64_t (&t)[4 * kStageIt], uint32_t tid)
 {
 #pragma unroll
     for (int it = 0; it < kStageIt; ++it) {
+        // unconditional, like the loads: a thread's slots i .. i + 3 lie inside s_tag whatever m_end is (i + 3 <= 4 * 767 + 3 = kChunk - 1),
+        // and the walk reads s_tag[m - cs] for cs <= m < m_end only -- what lands behind the tile's last mark is never looked at
         const uint32_t i = 4u * (tid + it * kCandPerBlock);
-        if (cs + i < m_end) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) s_tag[i + j] = t[4 * it + j];
-        }
+        for (int j = 0; j < 4; ++j) s_tag[i + j] = t[4 * it + j];
     }
 }
 
@@ -619,54 +645,109 @@ __device__ __forceinline__ void stage_store(uint64_t *s_tag, const uint64_t (&t)
 // round trips of tile i+1 / i+2 under the LDS walk of tile i was measured at 2e7 marks and was NOT faster --
 // 80 us vs 72 us: with four workgroups per CU in different phases the staging latency is already hidden and
 // the kernel is bound by the sum of VALU issue (consume + fp64 decision) and memory time; see DESIGN.md.)
-// (six waves per SIMD: what the 26.7 KB of LDS allow -- the device-planned variant came out at 83 registers, five waves, without the bound)
+// (six waves per SIMD: what the 25.6 KB of LDS allow -- the device-planned variant came out at 83 registers, five waves, without the bound)
+//
+// Round 8: a tile's dependent memory trips before its walk are the three the data flow needs -- offsets and candidate scalars, mark
+// indices, tags.
+//   * The kernel arguments it reads are taken at entry (one scalar wait; Params has them side by side at its front).
+//   * The prologue's loads are all unconditional, at clamped addresses, and leave before the first wait: the candidate's two offsets
+//     (kept in registers: no s_off array, no barrier in front of the staging), its four columns and start flag, and -- host-planned
+//     runs -- the tile's first and last offset at their uniform addresses.  Lanes at or past the tile's candidate count compute from
+//     the clamped values and are masked (`live`, `kept`).  Bounds, with C = p.C (the count, or the device-planned runs' bound c_max,
+//     for which every array is sized): cand_off has C + 1 entries and is read at min(., C); the columns, ctg_start and cand_contig
+//     have C and are read at min(., C - 1); C >= 1 (the host entries return before the launch otherwise).
+//   * Device-planned runs read the real count beside those loads and mask with it once it is there; the tile's last offset is then a
+//     lane's second offset, handed over through LDS (its address depends on the count).
 template <bool VEC, bool DYN = false>
 __global__ __launch_bounds__(kCandPerBlock, 6) void ef_classify(const Params p)
 {
     __shared__ uint64_t s_tag[kChunk];
-    __shared__ uint32_t s_off[kCandPerBlock + 1];
+    __shared__ uint32_t s_span[2];                             // (device-planned runs) the tile's first and last mark offset
     __shared__ TileShared sh;
 
     const uint32_t tid = threadIdx.x;
     STAMP(0, 0);
-    const uint32_t n_cands = DYN ? *p.dyn_c : p.C;
+    // the arguments, all at once (the asm takes the values: none of these loads is sunk to its first use)
+    const uint32_t C = p.C, n_reads = p.n_reads, svlen_thres = p.svlen_thres, suppread_thres = p.suppread_thres;
+    const uint32_t heavy_t = min(p.heavy_t, 255u);             // (the lane walk packs counts into bytes)
+    const uint32_t *__restrict__ const cand_off = p.cand_off, *__restrict__ const mark_read = p.mark_read;
+    const uint64_t *__restrict__ const read_tag = p.read_tag, *__restrict__ const untagged = p.untagged;
+    const uint32_t *__restrict__ const cand_svlen = p.cand_svlen, *__restrict__ const cand_svread = p.cand_svread;
+    const uint32_t *__restrict__ const cand_refread = p.cand_refread;
+    const uint8_t *__restrict__ const cand_gt_ok = p.cand_gt_ok, *__restrict__ const ctg_start = p.ctg_start;
+    asm volatile("" ::"s"(C), "s"(n_reads), "s"(svlen_thres), "s"(suppread_thres), "s"(heavy_t), "s"(cand_off), "s"(mark_read),
+                 "s"(read_tag), "s"(untagged), "s"(cand_svlen), "s"(cand_svread), "s"(cand_refread), "s"(cand_gt_ok), "s"(ctg_start));
+    asm volatile("" ::"s"(p.dbg), "s"(p.out_pred), "s"(p.out_ps), "s"(p.blk_rec), "s"(p.seed_ent), "s"(p.c2rec), "s"(p.status),
+                 "s"(p.c2_fixed), "s"(p.c2_cap));
     // device-planned runs know only an upper bound of the candidate count on the host: their grid is a fraction of that
     // bound and strides over the real tiles (a grid of the full bound is ~10x too many workgroups on SV-like data, and
-    // starting the empty ones cost the fused pipeline 9 of 18 us at 1 M marks)
-    for (uint32_t tile = blockIdx.x; !DYN || tile * (uint32_t)kCandPerBlock < n_cands; tile += gridDim.x) {
-        const uint32_t c0 = tile * kCandPerBlock;
-        const uint32_t nc = min((uint32_t)kCandPerBlock, n_cands - c0);
-        for (uint32_t i = tid; i <= nc; i += kCandPerBlock) s_off[i] = p.cand_off[c0 + i];
-        if (tid == 0) sh.c2n = 0;
-
-        // candidate scalars, coalesced (candidate c0 + tid)
-        uint32_t svlen = 0, svread = 0, refread = 0, gt_ok = 0, is_start = 0;
-        if (tid < nc) {
-            svlen = p.cand_svlen[c0 + tid];
-            svread = p.cand_svread[c0 + tid];
-            refread = p.cand_refread[c0 + tid];
-            gt_ok = p.cand_gt_ok[c0 + tid];
-            if (DYN) {
-                // device-planned runs have no start flags.  With the candidates' contig column at hand a start is where the column
-                // changes (two coalesced loads beside the other scalars, no dependent chain); else the contig of this candidate is
-                // walked from the contig of the tile's first one
-                const uint32_t c = c0 + tid;
-                if (p.cand_contig) {
-                    is_start = (c == 0 || p.cand_contig[c] != p.cand_contig[c - 1]) ? 1u : 0u;
-                } else {
-                    uint32_t k = p.blk_ctg[tile];
-                    while (c >= p.ctg_off[k + 1]) ++k;
-                    is_start = c == p.ctg_off[k] ? 1u : 0u;
-                }
-            } else {
-                is_start = p.ctg_start[c0 + tid];
+    // starting the empty ones cost the fused pipeline 9 of 18 us at 1 M marks).  The count is read beside every tile's vector loads
+    // and looked at only after they have left (the asm hands the index 0 back: a load hoisted out of the loop stands in front of
+    // the first tile's trip, a trip of its own).
+    uint32_t n_cands = C;
+    for (uint32_t tile = blockIdx.x;; tile += gridDim.x) {
+        const uint32_t c0 = tile * kCandPerBlock, c = c0 + tid;
+        // ---- ONE round trip: offsets and candidate scalars (candidate c0 + tid), coalesced, unconditional ----
+        const uint32_t ic = min(c, C - 1u);                                // a column's last entry is C - 1
+        const uint32_t o0_ld = cand_off[min(c, C)], o1_ld = cand_off[min(c + 1u, C)];       // cand_off's last entry is C
+        const uint32_t svlen_ld = cand_svlen[ic], svread_ld = cand_svread[ic], refread_ld = cand_refread[ic], gt_ld = cand_gt_ok[ic];
+        uint32_t start_ld = 0, cc0_ld = 0, cc1_ld = 0, mb_ld = 0, me_ld = 0;
+        if constexpr (DYN) {
+            // device-planned runs have no start flags.  With the candidates' contig column at hand a start is where the column
+            // changes (two coalesced loads beside the other scalars, no dependent chain); else the contig of this candidate is
+            // walked from the contig of the tile's first one (below)
+            if (p.cand_contig) {
+                cc0_ld = p.cand_contig[ic];
+                cc1_ld = p.cand_contig[max(ic, 1u) - 1u];                  // (candidate 0 is a start whatever stands here)
             }
+        } else {
+            start_ld = ctg_start[ic];
+            // the tile's first and last offset, at uniform addresses (c0 < C in a host-planned grid; min(c0 + 256, C) <= C)
+            mb_ld = cand_off[c0];
+            me_ld = cand_off[min(c0 + (uint32_t)kCandPerBlock, C)];
         }
-        const bool kept = tid < nc && svlen >= p.svlen_thres && svread >= p.suppread_thres && gt_ok != 0;     // :189-190
+        if constexpr (DYN) {
+            uint32_t zero = 0;
+            asm volatile("" : "+s"(zero));
+            n_cands = p.dyn_c[zero];
+            if (c0 >= n_cands) break;                                      // (uniform: the whole workgroup leaves)
+        }
+        const uint32_t nc = min((uint32_t)kCandPerBlock, n_cands - c0);
+        // one wait for all of them
+        asm volatile("" ::"v"(o0_ld), "v"(o1_ld), "v"(svlen_ld), "v"(svread_ld), "v"(refread_ld), "v"(gt_ld), "v"(start_ld), "v"(cc0_ld),
+                     "v"(cc1_ld));
+        // (no barrier orders this store against decide_store's atomicAdd on the host-planned path unless the tile has a staging
+        // pass -- and only a candidate with marks, two phase sets among them, ever gets there: a tile without a pass has none)
+        if (tid == 0) sh.c2n = 0;
+        const bool live = tid < nc;
+        const uint32_t svlen = svlen_ld, svread = svread_ld, refread = refread_ld, gt_ok = gt_ld;
+        uint32_t is_start = 0;
+        if constexpr (DYN) {
+            if (p.cand_contig) {
+                is_start = (live && (c == 0 || cc0_ld != cc1_ld)) ? 1u : 0u;
+            } else if (live) {
+                uint32_t k = p.blk_ctg[tile];
+                while (c >= p.ctg_off[k + 1]) ++k;
+                is_start = c == p.ctg_off[k] ? 1u : 0u;
+            }
+        } else {
+            is_start = live ? start_ld : 0u;
+        }
+        const bool kept = live && svlen >= svlen_thres && svread >= suppread_thres && gt_ok != 0;     // :189-190
         const bool divzero = kept && ((uint64_t)svread + (uint64_t)refread == 0);
-        __syncthreads();
+        uint32_t m_begin, m_end;
+        if constexpr (DYN) {
+            // (the closing barrier of the previous tile stands between its reads of s_span and these stores)
+            if (tid == 0) s_span[0] = o0_ld;
+            if (tid == nc - 1u) s_span[1] = o1_ld;                         // cand_off[c0 + nc]: c0 + nc <= n_cands <= C, not clamped
+            lds_barrier();
+            m_begin = s_span[0]; m_end = s_span[1];
+        } else {
+            m_begin = mb_ld; m_end = me_ld;
+        }
+        m_begin = (uint32_t)__builtin_amdgcn_readfirstlane((int)m_begin);
+        m_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)m_end);
         STAMP(0, 1);
-        const uint32_t m_begin = s_off[0], m_end = s_off[nc];
 
         // thread t walks candidate c0 + t.  (Dealing a tile's candidates to the lanes in descending order of their mark count -- so
         // that the four waves loop 18/14/10/6 times instead of 4 x 18 -- was measured in rounds 1 and 4, and in round 5 with the wave
@@ -674,9 +755,8 @@ __global__ __launch_bounds__(kCandPerBlock, 6) void ef_classify(const Params p)
         // profiles/history/r05_ef_classify_dealt_by_size_with_rotation_REJECTED.txt.  The kernel is bound by the latency of a tile --
         // three dependent round trips before its walk can start -- at five tiles per CU, not by the walk's issue slots.)
         const uint32_t j = tid;
-        const bool live = j < nc;
         const bool active = kept && !divzero;
-        const uint32_t my_b = live ? s_off[j] : 0, my_e = live ? s_off[j + 1] : 0;
+        const uint32_t my_b = live ? o0_ld : 0, my_e = live ? o1_ld : 0;
         CandState st;
 
         const uint32_t base = VEC ? (m_begin & ~3u) : m_begin;
@@ -685,13 +765,13 @@ __global__ __launch_bounds__(kCandPerBlock, 6) void ef_classify(const Params p)
             if (VEC) {
                 uint4 r[kStageIt];
                 uint64_t t[4 * kStageIt];
-                stage_load_marks(p, r, cs, m_end, tid);
-                stage_gather(p, t, r);
-                stage_store(s_tag, t, cs, m_end, tid);
+                stage_load_marks(mark_read, r, cs, m_end, tid);
+                stage_gather(read_tag, untagged, n_reads, t, r);
+                stage_store(s_tag, t, tid);
             } else {
                 for (uint32_t i = tid; i < kChunk && cs + i < m_end; i += kCandPerBlock) {
-                    const uint32_t r = p.mark_read[cs + i];
-                    s_tag[i] = r < p.n_reads ? p.read_tag[r] : kUntagged;        // (as stage_gather: an index beyond the table has no tag)
+                    const uint32_t r = mark_read[cs + i];
+                    s_tag[i] = r < n_reads ? read_tag[r] : kUntagged;        // (as stage_gather: an index beyond the table has no tag)
                 }
             }
             __syncthreads();
@@ -702,7 +782,7 @@ __global__ __launch_bounds__(kCandPerBlock, 6) void ef_classify(const Params p)
             if (!kept) lo = hi;
             // candidates with more marks than heavy_t: the wavefront walks them together, 64 marks per step, after the lanes
             // have walked the others side by side
-            const bool heavy = lo < hi && my_e - my_b > min(p.heavy_t, 255u);      // (the lane walk packs counts into bytes)
+            const bool heavy = lo < hi && my_e - my_b > heavy_t;
             unsigned long long hm = __ballot(heavy);
             consume_range(st, s_tag, heavy ? hi : lo, hi, cs);
             while (hm) {
@@ -718,6 +798,9 @@ __global__ __launch_bounds__(kCandPerBlock, 6) void ef_classify(const Params p)
         uint32_t c2_rank;
         const uint32_t seed = decide_store(p, sh, tile, live, c0 + j, active, divzero, st, my_e - my_b, svread, refread, c2_rank);
         sh.seed[j] = seed;
+        // (This barrier and seeds_tile's two order LDS only -- sh.seed, sh.c2n, sh.wlast, sh.wclean, sh.wcnt: within a launch no thread
+        // reads another thread's global stores -- yet LDS-only barriers in their place, which do not wait for decide_store's stores,
+        // measured no gain in round 8: profiles/history/r08_ef_classify_tail_lds_barriers_REJECTED.txt.)
         __syncthreads();
         if (sh.c2n > kC2Quota) {
             // more multi-PS candidates than the tile has slots (fragmented phasing: short phase sets against long reads): the
@@ -1643,11 +1726,6 @@ __device__ __forceinline__ void finalize_candidate_walk(const OwnArgs &a, uint32
     a.out_pred[c] = (uint8_t)(code & 3u);
     a.out_ps[c] = own_nearest_walk(a, c_pos);
 }
-
-// A workgroup barrier that waits for the wavefront's LDS traffic only.  __syncthreads() is a fence as well: it drains the global
-// loads in flight (s_waitcnt vmcnt(0)) in front of s_barrier -- here that would put the summaries' round trip, issued early so that it
-// runs beside the seed set's phases, in front of the first of them.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // maximum of one value per lane over the wavefront (row rotations, then the two row broadcasts: wave_sum's pattern)
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
