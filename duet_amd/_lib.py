@@ -40,7 +40,8 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_tune_cap_line_device', 'duet_tune_cap_line_host', 'duet_svim_cap_line_device', 'duet_svim_cap_line_host',
            'duet_tune_leaf_census_device', 'duet_tune_leaf_census_host', 'duet_tune_leaves_device', 'duet_tune_leaves_host',
            'duet_evidence_rows_device', 'duet_evidence_rows_host',
-           'duet_ps_links_device', 'duet_ps_links_host', 'duet_svim_ps_links_device', 'duet_svim_ps_links_host')
+           'duet_ps_links_device', 'duet_ps_links_host', 'duet_svim_ps_links_device', 'duet_svim_ps_links_host',
+           'duet_read_tags_device', 'duet_read_tags_host', 'duet_read_tags_rows_device', 'duet_read_tags_rows_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -203,6 +204,28 @@ def ps_links_room(n_marks):
     return max(int(n_marks), 1) - 1
 
 
+# read tags from phased SVs (include/duet_ef.h, "Read tags from phased SVs"; duet_amd/read_tags.py): one record per (name, ps)
+READ_TAG_FIELDS = ('name', 'contig', 'ps', 'read', 'n_h1', 'n_h2', 'pos_min', 'pos_max', 'status', 'reserved')
+READ_TAG_DTYPE = np.dtype([(n, '<u4') for n in READ_TAG_FIELDS])                     # duet_read_tag_rec (40 bytes)
+READ_TAG_STATUS_NAMES = ('agree', 'disagree', 'tie', 'new', 'other_ps')            # DUET_READ_TAG_AGREE .. DUET_READ_TAG_OTHER_PS
+READ_TAG_COLUMNS = ('CHROM', 'READ', 'PS', 'N_SV', 'N_H1', 'N_H2', 'HP_SV', 'TAG_HP', 'TAG_PS', 'TAG_PC', 'STATUS', 'POS_MIN', 'POS_MAX')
+READ_TAG_ROW_MAX = 104          # a row's bytes at most, without its CHROM and READ pieces
+
+
+class ReadTagsProblem(ctypes.Structure):
+    """duet_read_tags_problem; cand_ctg_off is host memory in both forms."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ('n_cands', 'n_marks', 'n_reads', 'n_names', 'n_contigs', 'reserved')] + \
+               [(n, ctypes.c_void_p) for n in ('cand_off', 'mark_order', 'mark_read', 'mark_name', 'pred', 'ps', 'cand_pos',
+                                               'cand_ctg_off', 'cand_contig', 'read_tag')]
+
+
+def read_tags_bound(n_recs, name_off, chrom_texts):
+    """The size duet_read_tags_rows_* can need at most (include/duet_ef.h): what the caller allocates for one call."""
+    longest = int(np.max(np.diff(np.asarray(name_off, dtype=np.int64)))) if len(name_off) > 1 else 0
+    chrom = max([len(c) for c in chrom_bytes(chrom_texts)] + [0])
+    return int(n_recs) * (chrom + longest + READ_TAG_ROW_MAX)
+
+
 class TuneTruth(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ('n_uid', 'n_groups', 'n_pairs', 'reserved')] + \
                [(n, ctypes.c_void_p) for n in ('cand_flags', 'cand_group', 'cand_uid', 'cand_pair', 'group_pair_off', 'pair_uid')]
@@ -349,6 +372,13 @@ def load():
                                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
     lib.duet_svim_ps_links_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult), ctypes.c_uint32,
                                             ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+    lib.duet_read_tags_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(ReadTagsProblem), ctypes.c_uint32, ctypes.c_void_p,
+                                          ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+    lib.duet_read_tags_host.argtypes = lib.duet_read_tags_device.argtypes[:-1]
+    lib.duet_read_tags_rows_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(CallsetNames),
+                                               ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+    lib.duet_read_tags_rows_host.argtypes = lib.duet_read_tags_rows_device.argtypes[:-1]
     lib.duet_tune_line_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
@@ -996,6 +1026,90 @@ class Context(object):
         if want_order:
             got['order'] = order[:p.marks.n_marks]
         return got
+
+    # -- read tags from phased SVs (duet_readtags.hip) ---------------------------------------------------------------------------
+    def read_tags_host(self, cand_off, mark_read, mark_name, n_names, pred, ps, cand_pos, read_tag, cand_ctg_off=None, cand_contig=None,
+                       mark_order=None, pc_cap=None, out_cap=None):
+        """duet_read_tags_host over host arrays -> structured array of READ_TAG_DTYPE, ascending by (name, ps).  Exactly one of
+        cand_ctg_off / cand_contig names the candidates' contigs; mark_order: the CSR slots' raw marks (None: identity); pc_cap: the
+        PC cap of a usable tag (None: the reference's 8100); out_cap: the room offered (None: n_marks, which always suffices) --
+        when it is too small the DuetLibraryError carries the exact count as `n_recs`."""
+        conv = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)
+        arrays = dict(cand_off=conv(cand_off, np.uint32), mark_order=conv(mark_order, np.uint32), mark_read=conv(mark_read, np.uint32),
+                      mark_name=conv(mark_name, np.uint32), pred=conv(pred, np.uint8), ps=conv(ps, np.uint32),
+                      cand_pos=conv(cand_pos, np.uint32), cand_ctg_off=conv(cand_ctg_off, np.uint32),
+                      cand_contig=conv(cand_contig, np.uint16), read_tag=conv(read_tag, np.uint64))
+        prob = ReadTagsProblem()
+        prob.n_cands, prob.n_marks = len(arrays['pred']), len(arrays['mark_read'])
+        prob.n_reads, prob.n_names = len(arrays['read_tag']), int(n_names)
+        prob.n_contigs = len(arrays['cand_ctg_off']) - 1 if cand_ctg_off is not None else 0
+        spare = np.zeros(1, dtype=np.uint64)
+        for k, a in arrays.items():
+            # (an empty array still has an address: which contig form is meant must not depend on the candidate count)
+            setattr(prob, k, None if a is None else a.ctypes.data if a.size else spare.ctypes.data)
+        room = prob.n_marks if out_cap is None else int(out_cap)
+        out = np.zeros(max(room, 1), dtype=READ_TAG_DTYPE)
+        n = ctypes.c_uint32(0)
+        cap = PC_MAX if pc_cap is None else int(pc_cap)
+        if not 0 <= cap <= 0xFFFFFFFF:
+            raise ValueError('pc_cap: %r' % (pc_cap,))
+        rc = self.lib.duet_read_tags_host(self.handle, ctypes.byref(prob), cap, _ptr(out), room, ctypes.byref(n))
+        del arrays
+        if rc:
+            try:
+                self._raise(rc)
+            except DuetLibraryError as e:
+                e.n_recs, e.out = n.value, out
+                raise
+        return out[:n.value].copy()
+
+    def read_tags_device(self, prob, out_ptr, out_cap, stream=0, pc_cap=None):
+        """duet_read_tags_device on a resident ReadTagsProblem (cand_ctg_off host memory); out_ptr: device room for out_cap records
+        -> the record count."""
+        n = ctypes.c_uint32(0)
+        rc = self.lib.duet_read_tags_device(self.handle, ctypes.byref(prob), PC_MAX if pc_cap is None else int(pc_cap),
+                                            ctypes.c_void_p(out_ptr), int(out_cap), ctypes.byref(n), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return n.value
+
+    def read_tags_rows_host(self, records, name_off, name_pool, chrom_texts, read_tag, cap=None):
+        """duet_read_tags_rows_host: the data rows of phased_sv.read_tags.tsv for `records` (READ_TAG_DTYPE) -> bytes.  name_off
+        (uint64, n_names + 1) and name_pool (bytes or uint8 array): the read names; cap: the room offered (None: read_tags_bound) --
+        when it is too small the DuetLibraryError carries the exact size as `out_len`."""
+        records = np.ascontiguousarray(records, dtype=READ_TAG_DTYPE)
+        name_off = np.ascontiguousarray(name_off, dtype=np.uint64)
+        pool = np.frombuffer(bytes(name_pool), dtype=np.uint8) if isinstance(name_pool, (bytes, bytearray)) else \
+            np.ascontiguousarray(name_pool, dtype=np.uint8)
+        pool = pool if pool.size else np.zeros(1, dtype=np.uint8)
+        read_tag = np.ascontiguousarray(read_tag, dtype=np.uint64)
+        keep = []
+        names = callset_names(np.zeros(0, dtype=np.uint32), name_off, pool, chrom_texts, keep)
+        names.n_names = max(len(name_off), 1) - 1
+        room = read_tags_bound(len(records), name_off, chrom_texts) if cap is None else int(cap)
+        out = np.zeros(max(room, 1), dtype=np.uint8)
+        n = ctypes.c_uint64(0)
+        rc = self.lib.duet_read_tags_rows_host(self.handle, _ptr(records), len(records), ctypes.byref(names), _ptr(read_tag), len(read_tag),
+                                               _ptr(out), ctypes.c_uint64(room), ctypes.byref(n))
+        del keep
+        if rc:
+            try:
+                self._raise(rc)
+            except DuetLibraryError as e:
+                e.out_len, e.out = n.value, out
+                raise
+        return out[:n.value].tobytes()
+
+    def read_tags_rows_device(self, recs_ptr, n_recs, names, read_tag_ptr, n_reads, out_ptr, cap, stream=0):
+        """duet_read_tags_rows_device on resident arrays (names: a CallsetNames of device pointers, chrom host) -> the text's exact
+        size; raises when cap is smaller (nothing is written then)."""
+        n = ctypes.c_uint64(0)
+        rc = self.lib.duet_read_tags_rows_device(self.handle, ctypes.c_void_p(recs_ptr), int(n_recs), ctypes.byref(names),
+                                                 ctypes.c_void_p(read_tag_ptr), int(n_reads), ctypes.c_void_p(out_ptr), ctypes.c_uint64(cap),
+                                                 ctypes.byref(n), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return n.value
 
     def strata_build_device(self, prob, truth, chrom_stratum_ptr, n_strata, cand_stratum_ptr, group_stratum_ptr, stream=0):
         """duet_tune_strata_build_device on resident arrays (devmem.DeviceTune), after truth_build_device on the same prob / truth."""

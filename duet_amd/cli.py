@@ -20,6 +20,8 @@ def pipeline(a):
     the GPU from the haplotagged BAMs (duet_amd/svim_mode.py)."""
     # (--write_ps_links travels as a keyword: the positional arguments of the last stage stay what they were)
     extra = {'ps_links': True} if getattr(a, 'write_ps_links', False) else {}
+    if getattr(a, 'write_read_tags', False):
+        extra['read_tags'] = True                           # (--write_read_tags: a keyword too)
     if a.sv_caller == 'svim-gpu':
         from duet_amd.svim_mode import sv_phasing_from_bams
         last = (lambda *args: sv_phasing_from_bams(*args, **extra)) if extra else sv_phasing_from_bams
@@ -75,6 +77,11 @@ def main(argv):
         # problem one GPU holds; the decision keeps whatever route the other flags give it)
         if a.gpus > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
             raise SystemExit('duet: --write_ps_links works on the single-GPU path only (not with --gpus > 1)')
+    if a.write_read_tags:
+        # (additive: the per-read table, OUTPUT/phased_sv.read_tags.tsv -- built from the calls and the marks one GPU holds; the
+        # decision keeps whatever route the other flags give it)
+        if a.gpus > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise SystemExit('duet: --write_read_tags works on the single-GPU path only (not with --gpus > 1)')
     check_envs(a.REFERENCE, a.BAM)
     os.makedirs(a.OUTPUT, exist_ok=True)
     set_logging(a.OUTPUT)

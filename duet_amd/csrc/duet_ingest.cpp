@@ -286,6 +286,10 @@ struct duet_ingest {
     std::vector<uint32_t> m_name;
     std::vector<uint64_t> name_off{0};
     std::string name_pool;
+    // ... and per mark of the VCF path (the order of mark_read), filled by the join when keep_names is set before the parse
+    std::vector<uint32_t> v_name;
+    std::vector<uint64_t> v_name_off{0};
+    std::string v_name_pool;
 };
 
 namespace {
@@ -1161,7 +1165,8 @@ int vcf_finish(duet_ingest *g, VcfStage &st)
     g->c_chrom.assign(C, Span{nullptr, 0}); g->c_ref.assign(C, Span{nullptr, 0}); g->c_alt.assign(C, Span{nullptr, 0});
     g->c_type.assign(C, Span{nullptr, 0});
     std::vector<uint32_t> deg(C, 0);
-    struct PartB { std::vector<uint32_t> marks; std::string why; };
+    struct PartB { std::vector<uint32_t> marks; std::vector<Span> names; std::string why; };
+    const bool keep_names = g->keep_names;
     int TB = C < 4096 ? 1 : T;
     std::vector<PartB> pb(TB);
     auto work_b = [&](int t) {
@@ -1172,6 +1177,9 @@ int vcf_finish(duet_ingest *g, VcfStage &st)
         std::vector<uint32_t> marks;
         marks.reserve((hi - lo) * 12);
         struct HandOver { std::vector<uint32_t> &from, &to; ~HandOver() { to.swap(from); } } hand_over{marks, o.marks};
+        std::vector<Span> names;                  // (keep_names: every mark's name as it stands in the file, the marks' order)
+        if (keep_names) names.reserve((hi - lo) * 12);
+        struct HandOverNames { std::vector<Span> &from, &to; ~HandOverNames() { to.swap(from); } } hand_over_names{names, o.names};
         int k = 0;
         for (size_t c = lo; c < hi; ++c) {
             while (c >= g->cand_ctg_off[k + 1]) ++k;
@@ -1228,6 +1236,7 @@ int vcf_finish(duet_ingest *g, VcfStage &st)
                         const int idx = tab.find_hashed(nm[q].p, nm[q].n, hh[q]);
                         marks.push_back(idx < 0 ? kAbsent : rbase + (uint32_t)idx);
                     }
+                    if (keep_names) names.insert(names.end(), nm, nm + nb);
                     cnt += (uint32_t)nb;
                 }
                 deg[c] = cnt;
@@ -1293,6 +1302,28 @@ int vcf_finish(duet_ingest *g, VcfStage &st)
             if (!pb[t].marks.empty()) memcpy(g->mark_read.data() + at, pb[t].marks.data(), pb[t].marks.size() * 4);
             at += pb[t].marks.size();
         }
+    }
+    g->v_name.clear();
+    g->v_name_off.assign(1, 0);
+    g->v_name_pool.clear();
+    if (keep_names) {
+        // one entry per distinct name of a contig, tagged or not, in order of first mark (the spans point into the file, alive here)
+        g->v_name.reserve(total);
+        std::unordered_map<std::string_view, uint32_t> interned;
+        size_t c = 0, left = C ? deg[0] : 0;
+        int k = 0;
+        for (int t = 0; t < TB; ++t)
+            for (const Span &nm : pb[t].names) {
+                while (left == 0) left = deg[++c];
+                --left;
+                while (c >= g->cand_ctg_off[k + 1]) { ++k; interned.clear(); }
+                auto it = interned.emplace(std::string_view(nm.p, nm.n), (uint32_t)(g->v_name_off.size() - 1));
+                if (it.second) {
+                    g->v_name_pool.append(nm.p, nm.n);
+                    g->v_name_off.push_back((uint64_t)g->v_name_pool.size());
+                }
+                g->v_name.push_back(it.first->second);
+            }
     }
     lap("finish");
     g->parsed = true;
@@ -1721,20 +1752,25 @@ int duet_ingest_keep_mark_names(duet_ingest *g, int enable)
 {
     if (!g) return DUET_INGEST_INVALID;
     if (!g->m_pos.empty()) { g->err = "duet_ingest_keep_mark_names after marks were extracted"; return DUET_INGEST_INVALID; }
+    if (g->parsed || g->stage) { g->err = "duet_ingest_keep_mark_names after the caller VCF was parsed"; return DUET_INGEST_INVALID; }
     g->keep_names = enable != 0;
     return DUET_INGEST_OK;
 }
 
 int duet_ingest_get_mark_names(duet_ingest *g, duet_ingest_mark_names *o)
 {
-    if (!g || !o || !g->extract || !g->keep_names) return DUET_INGEST_INVALID;
-    if (g->name_off.size() - 1 > 0xFFFFFFFEull) return unsupported(g, "more than 2^32 - 2 distinct read names");
-    o->n_marks = (uint32_t)g->m_name.size();
-    o->n_names = (uint32_t)(g->name_off.size() - 1);
-    o->mark_name = g->m_name.data();
-    o->name_off = g->name_off.data();
-    o->name_pool = g->name_pool.data();
-    o->pool_bytes = (uint64_t)g->name_pool.size();
+    if (!g || !o || !(g->extract || g->parsed) || !g->keep_names) return DUET_INGEST_INVALID;
+    // the extraction's names where it ran, else the names of the caller VCF's marks
+    const std::vector<uint32_t> &name = g->extract ? g->m_name : g->v_name;
+    const std::vector<uint64_t> &off = g->extract ? g->name_off : g->v_name_off;
+    const std::string &pool = g->extract ? g->name_pool : g->v_name_pool;
+    if (off.size() - 1 > 0xFFFFFFFEull) return unsupported(g, "more than 2^32 - 2 distinct read names");
+    o->n_marks = (uint32_t)name.size();
+    o->n_names = (uint32_t)(off.size() - 1);
+    o->mark_name = name.data();
+    o->name_off = off.data();
+    o->name_pool = pool.data();
+    o->pool_bytes = (uint64_t)pool.size();
     return DUET_INGEST_OK;
 }
 

@@ -256,6 +256,37 @@ class DeviceSvim(DeviceCluster):
         n, self.n_found = ctx.svim_ps_links_device(self.sv_problem, self.result, out.data_ptr(), room, stream, pc_cap=pc_cap)
         return out[:n * _lib.PS_LINK_DTYPE.itemsize].cpu().numpy().view(_lib.PS_LINK_DTYPE).copy()
 
+    def read_tags(self, ctx, names, chrom_texts, pc_cap=None, stream=None):
+        """The read tags of the last run's candidates and calls (duet_read_tags_device, duet_read_tags_rows_device), built on the
+        resident arrays: the cluster result's cand_off / cand_contig / cand_pos, its `order` as the slots' raw marks, out_pred /
+        out_ps, the marks' read indices and the read tags.  names: dict(mark_name, name_off, name_pool) of
+        NativeIngest.extract(..., names=True); chrom_texts: CHROM text per contig; pc_cap: the cap of a usable tag (None: 8100).
+        -> (records as a structured numpy array of _lib.READ_TAG_DTYPE, uint8 numpy array of the rows' text)."""
+        torch = self.torch
+        DT = _lib.READ_TAG_DTYPE
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.n_found is None:
+            self.n_found = self.n_cands()
+        N = self.n_found
+        if N == 0:
+            return np.zeros(0, dtype=DT), np.zeros(0, dtype=np.uint8)
+        keep = [upload(torch, self.device, names[k], dt) for k, dt in (('mark_name', np.uint32), ('name_off', np.uint64), ('name_pool', np.uint8))]
+        p = _lib.ReadTagsProblem()
+        p.n_cands, p.n_marks, p.n_reads, p.n_names = N, self.M, self.sv_problem.n_reads, len(names['name_off']) - 1
+        p.cand_off, p.mark_order, p.cand_pos, p.cand_contig = self.result.cand_off, self.result.order, self.result.cand_pos, self.result.cand_contig
+        p.mark_read, p.mark_name, p.read_tag = self.keep['sv_read'].data_ptr(), keep[0].data_ptr(), self.keep['sv_tag'].data_ptr()
+        p.pred, p.ps = self.out_pred.data_ptr(), self.out_ps.data_ptr()
+        recs = torch.zeros(max(self.M, 1) * DT.itemsize, dtype=torch.uint8, device=self.device)
+        n = ctx.read_tags_device(p, recs.data_ptr(), self.M, stream, pc_cap=pc_cap)
+        hold = []
+        nm = _lib.callset_names(0, keep[1].data_ptr(), keep[2].data_ptr(), chrom_texts, hold)
+        nm.n_names = p.n_names
+        cap = _lib.read_tags_bound(n, names['name_off'], chrom_texts)
+        text = torch.empty(max(cap, 1), dtype=torch.uint8, device=self.device)
+        size = ctx.read_tags_rows_device(recs.data_ptr(), n, nm, p.read_tag, p.n_reads, text.data_ptr(), cap, stream)
+        return recs[:n * DT.itemsize].cpu().numpy().view(DT).copy(), text[:size].cpu().numpy()
+
     def vcf_rows(self, ctx, names, chrom_texts, stream=None):
         """Rows of sv_calling/variants.vcf for the last run_fused's candidates, formatted on the device from the resident
         cluster result and depth (duet_svim_vcf_rows_device).  names: dict(mark_name, name_off, name_pool) of

@@ -138,19 +138,20 @@ class NativeIngest(object):
             lib.duet_ingest_destroy(h)
 
     @classmethod
-    def load(cls, vcf_path, sam_home, chrom_list, thread=4, owned=None, plan=None):
+    def load(cls, vcf_path, sam_home, chrom_list, thread=4, owned=None, plan=None, names=False):
         """-> NativeIngest, or None when the native library is missing / declines the input (reason logged by
         the caller through .why of the returned tuple).  owned (sharded runs): the contig indices this rank reads --
         the other listed contigs' BAMs are not opened and their records are dropped at their first token (their rank
         vouches for them); header lines and the contig list stay complete.
         plan (sharded runs, instead of owned): a callable (records per contig, line bytes per contig) -> owned, called with the
         pre-count taken on THIS handle -- the file the pre-count read stays loaded for the parse that follows (a rank that
-        pre-counted through NativeIngest.precount read the caller VCF twice)."""
+        pre-counted through NativeIngest.precount read the caller VCF twice).
+        names=True: the join also keeps every mark's read name (duet_ingest_keep_mark_names; .mark_names() returns them)."""
         lib = load()
         if lib is None:
             return None
-        names = (ctypes.c_char_p * len(chrom_list))(*[c.encode('utf-8') for c in chrom_list])
-        h = lib.duet_ingest_create(len(chrom_list), names)
+        labels = (ctypes.c_char_p * len(chrom_list))(*[c.encode('utf-8') for c in chrom_list])
+        h = lib.duet_ingest_create(len(chrom_list), labels)
         if not h:
             return None
 
@@ -176,6 +177,8 @@ class NativeIngest(object):
         # Both halves get `thread` workers: the first half is over after a few milliseconds, and splitting the budget between
         # them cost 10 ms of a 37 ms run at -t 4 (while both run, up to 2 x thread workers exist; DUET_INGEST_STRICT_THREADS=1
         # splits the budget instead and keeps `thread` a strict upper bound).
+        if names and lib.duet_ingest_keep_mark_names(h, 1) != OK:
+            return decline()
         import threading
         t_vcf = t_bam = max(1, int(thread))
         if os.environ.get('DUET_INGEST_STRICT_THREADS') == '1':
@@ -267,6 +270,15 @@ class NativeIngest(object):
             out['name_off'] = _view(nm.name_off, nm.n_names + 1, np.uint64).copy()
             out['name_pool'] = _view(nm.name_pool, nm.pool_bytes, np.uint8).copy()
         return cls(h, lib, None), out
+
+    def mark_names(self):
+        """The read names of the marks, in the order of soa.mark_read (load(..., names=True)): dict(mark_name u32[M] into name_off
+        u64[n_names + 1], name_pool u8[]) -- views owned by the native object; names interned per contig, tagged or not."""
+        nm = IngestMarkNames()
+        if self.lib.duet_ingest_get_mark_names(self.handle, ctypes.byref(nm)) != OK:
+            raise RuntimeError('duet_ingest_get_mark_names: no names were kept (NativeIngest.load(..., names=True))')
+        return dict(mark_name=_view(nm.mark_name, nm.n_marks, np.uint32), name_off=_view(nm.name_off, nm.n_names + 1, np.uint64),
+                    name_pool=_view(nm.name_pool, nm.pool_bytes, np.uint8))
 
     def emit(self, pred, ps, include_all_ctgs):
         """Full text of phased_sv.vcf (header + rows) as bytes."""

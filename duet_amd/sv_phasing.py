@@ -10,7 +10,10 @@ fields ...) and the Python path then takes over, so the observable behaviour is 
 Set DUET_NATIVE_INGEST=0 to force the Python path; DUET_DEVICE_ROWS=0 keeps the native path but formats the rows on
 the host instead of on the device.
 
-Six additive keyword arguments (upstream's five positionals are unchanged): `ps_links` = also write
+Seven additive keyword arguments (upstream's five positionals are unchanged): `read_tags` = also write
+<home>/phased_sv.read_tags.tsv, the haplotype the heterozygous calls place each of their supporting reads on, per read and phase
+set (duet_amd/read_tags.py; single-GPU native path, with or without `thresholds`; under `pc_cap` a read's own tag is usable under
+that cap), `ps_links` = also write
 <home>/phased_sv.ps_links.tsv and <home>/phased_sv.ps_blocks.tsv, how the SV candidates tie neighbouring phase sets together
 (duet_amd/ps_links.py; single-GPU native path, with or without `thresholds`; under `pc_cap` the voters are that cap's),
 `evidence` = also write
@@ -35,14 +38,14 @@ from duet_amd.write_file import print_sv, print_sv_header
 _BAR = '*' * 25
 
 
-def load_native(home, thread, include_all_ctgs, caller_vcf, log=True):
+def load_native(home, thread, include_all_ctgs, caller_vcf, log=True, names=False):
     """Native ingest of <home> -> (NativeIngest, chrom_list) or (None, chrom_list) when the Python path has to take
-    over (library missing, input declined, or switched off)."""
+    over (library missing, input declined, or switched off).  names: the join keeps every mark's read name (--write_read_tags)."""
     chrom_list = init_chrom_list(include_all_ctgs, home)
     if os.environ.get('DUET_NATIVE_INGEST') == '0' or os.environ.get('DUET_USE_SAMTOOLS') == '1':
         return None, chrom_list
     from duet_amd.native import NativeIngest
-    ing = NativeIngest.load(caller_vcf, home + '/snp_phasing/', chrom_list, thread)
+    ing = NativeIngest.load(caller_vcf, home + '/snp_phasing/', chrom_list, thread, names=names)
     if ing is None:
         return None, chrom_list
     if ing.handle is None:
@@ -70,14 +73,14 @@ def write_header(ing, include_all_ctgs, out_vcf):
         out.write(ing.header(include_all_ctgs))
 
 
-def contig_texts(ing, chrom_list):
+def contig_texts(ing, chrom_list, flag='--write_ps_links'):
     """The CHROM text the rows of phased_sv.vcf carry for every contig: that of the contig's first candidate in the ingest's
     string pool (a contig without candidates: its name in the chrom list -- no row carries it)."""
     texts = list(chrom_list)
     if ing.soa.n_cands:
         rows = ing.rows()
         if rows is None:
-            raise RuntimeError('--write_ps_links: the native ingest has no string pool for this input')
+            raise RuntimeError('%s: the native ingest has no string pool for this input' % flag)
         pool, off, ctg = rows['pool'], rows['str_off'], ing.soa.cand_ctg_off
         for k in range(ing.soa.n_contigs):
             if ctg[k + 1] > ctg[k]:
@@ -101,16 +104,40 @@ def write_ps_links(home, links):
     logging.info('  %d links over %d phase sets, %d contradicted' % (n, n_ps, n_conflicts))
 
 
-def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, ps_links=False):
-    ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf)
+def native_read_tags(ing, chrom_list, pred, ps, ctx, pc_cap=None):
+    """(records, data rows as bytes) of phased_sv.read_tags.tsv for the ingest's problem and its calls (duet_read_tags_host,
+    duet_read_tags_rows_host), while the ingest is still open."""
+    from duet_amd import read_tags
+    soa = ing.soa
+    if not soa.n_cands or not soa.n_marks:
+        return read_tags.empty(), b''
+    nm, texts = ing.mark_names(), contig_texts(ing, chrom_list, '--write_read_tags')
+    records = ctx.read_tags_host(soa.cand_off, soa.mark_read, nm['mark_name'], len(nm['name_off']) - 1, pred, ps, soa.cand_pos,
+                                 soa.read_tag, cand_ctg_off=soa.cand_ctg_off, pc_cap=pc_cap)
+    return records, ctx.read_tags_rows_host(records, nm['name_off'], nm['name_pool'], texts, soa.read_tag)
+
+
+def write_read_tags(home, tags):
+    from duet_amd import read_tags
+    logging.info('write the read tags into phased_sv.read_tags.tsv')
+    read_tags.write(home, tags[1])
+    logging.info('  ' + read_tags.summary_text(tags[0]))
+
+
+def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, ps_links=False, read_tags=False):
+    ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf, names=read_tags)
     if ing is None:
+        if read_tags:
+            raise RuntimeError('--write_read_tags needs the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
         if ps_links:
             raise RuntimeError('--write_ps_links needs the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
         return False
-    links = None
+    links, tags = None, None
     try:
         if ps_links:
             contig_texts(ing, chrom_list)           # (before the output file is created: a refusal leaves nothing behind)
+        if read_tags:
+            contig_texts(ing, chrom_list, '--write_read_tags')
         write_header(ing, include_all_ctgs, out_vcf)
         log_ingest(ing, chrom_list)
         logging.info('integrate read weight information')
@@ -125,6 +152,11 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
             body = ing.emit_rows(pred, ps)
         if ps_links:
             links = native_ps_links(ing, chrom_list, svlen_thres, suppread_thres, ctx)
+        if read_tags:
+            # (the rows above keep their route, so phased_sv.vcf is what it is without the flag; the calls themselves come from
+            # one more E/F run on the same problem)
+            pred, ps = engine.run_ef(ing.soa, svlen_thres, suppread_thres, ctx=ctx) if ing.soa.n_cands else ((), ())
+            tags = native_read_tags(ing, chrom_list, pred, ps, ctx)
         logging.info('write phased callset into .vcf file')
     except BaseException:
         ing.close()
@@ -134,6 +166,8 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
         out.write(body)
     if links is not None:
         write_ps_links(home, links)
+    if tags is not None:
+        write_read_tags(home, tags)
     return True
 
 
@@ -142,21 +176,25 @@ def evidence_path(home):
 
 
 def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, vec, pc_cap=None,
-                       evidence=False, ps_links=False):
+                       evidence=False, ps_links=False, read_tags=False):
     """The native path with the decision's constants taken from `vec` (duet_amd/tune.py): ingest, the feature export (pc_cap:
     under that PC cap, duet_ef_features_cap_host), a sweep of one vector that keeps its (pred, ps), the rows.
     evidence: also <home>/phased_sv.evidence.tsv, one row per candidate formatted on the device (duet_evidence_rows_host, the text
-    form over the ingest's string pool).  ps_links: also the two phase-set link tables, the voters under the same PC cap."""
+    form over the ingest's string pool).  ps_links: also the two phase-set link tables, the voters under the same PC cap.
+    read_tags: also <home>/phased_sv.read_tags.tsv from this route's (pred, ps), a read's own tag usable under the same PC cap."""
     from duet_amd import _lib, tune
-    ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf)
+    ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf, names=read_tags)
     if ing is None:
         raise RuntimeError('--thresholds / --pc_cap / --write_evidence%s need the native ingest, which declined this input '
-                           '(or DUET_NATIVE_INGEST=0)' % (' / --write_ps_links' if ps_links else ''))
-    table, links = None, None
+                           '(or DUET_NATIVE_INGEST=0)' % ((' / --write_ps_links' if ps_links else '') +
+                                                          (' / --write_read_tags' if read_tags else '')))
+    table, links, tags = None, None, None
     try:
         rows = None
         if ps_links:
             contig_texts(ing, chrom_list)           # (before the output file is created: a refusal leaves nothing behind)
+        if read_tags:
+            contig_texts(ing, chrom_list, '--write_read_tags')
         if evidence and ing.soa.n_cands:
             rows = ing.rows()                       # (before the output file is created: a refusal leaves nothing behind)
             if rows is None:
@@ -181,6 +219,9 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
                 table = ctx.evidence_rows_host(feat, leaf, pred, ing.soa.cand_pos, ing.soa.cand_svlen, rows=rows)
         if ps_links:
             links = native_ps_links(ing, chrom_list, svlen_thres, suppread_thres, ctx, pc_cap=pc_cap)
+        if read_tags:
+            tags = native_read_tags(ing, chrom_list, pred, ps, ctx, pc_cap=pc_cap) if ing.soa.n_cands else \
+                native_read_tags(ing, chrom_list, (), (), ctx)
         logging.info('write phased callset into .vcf file')
     finally:
         ing.close()
@@ -193,10 +234,15 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
             out.write(table)
     if links is not None:
         write_ps_links(home, links)
+    if tags is not None:
+        write_read_tags(home, tags)
 
 
 def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, device=0, gpus=1, thresholds=None, pc_cap=None,
-               evidence=False, ps_links=False):
+               evidence=False, ps_links=False, read_tags=False):
+    if read_tags and (int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1'):
+        # (additive: the read tags -- the native single-GPU path, whichever route the decision takes)
+        raise ValueError('read_tags: single-GPU path only')
     if ps_links and (int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1'):
         # (additive: the phase-set links -- the native single-GPU path, whichever route the decision takes)
         raise ValueError('ps_links: single-GPU path only')
@@ -226,7 +272,8 @@ def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, devi
         if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
             raise ValueError('thresholds: single-GPU path only')
         _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf,
-                           engine.default_context(int(device)), thresholds, pc_cap, evidence=bool(evidence), ps_links=bool(ps_links))
+                           engine.default_context(int(device)), thresholds, pc_cap, evidence=bool(evidence), ps_links=bool(ps_links),
+                           read_tags=bool(read_tags))
         done = True
     # (DUET_FORCE_RANKS=1: the one-process-per-GPU path even with one GPU -- rank 0 of 1 over RCCL; tests use it to take the
     # collective through the real backend on a one-GPU box)
@@ -235,7 +282,8 @@ def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, devi
         done = multi.sv_phasing_sharded(home, svlen_thres, suppread_thres, thread, include_all_ctgs, int(gpus))
     if not done:
         ctx = engine.default_context(int(device))
-        if not _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, ps_links=bool(ps_links)):
+        if not _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, ps_links=bool(ps_links),
+                       read_tags=bool(read_tags)):
             print_sv_header(caller_vcf, out_vcf, include_all_ctgs)
             rows = generate_phased_callset(caller_vcf, home + '/snp_phasing/', svlen_thres, suppread_thres, thread,
                                            include_all_ctgs, ctx=ctx)

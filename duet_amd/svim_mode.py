@@ -17,7 +17,8 @@ from duet_amd.native import NativeIngest
 from duet_amd.read_file import init_chrom_list
 
 
-def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_cap=None, evidence_texts=None, ps_links=False):
+def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_cap=None, evidence_texts=None, ps_links=False,
+                   read_tag_texts=None):
     """-> compute(extracted arrays, svlen_thres, suppread_thres, max_dist, depth_bin) -> dict of result arrays, on ctx's GPU:
     stage A0 -> adapter -> step E/F in one device pipeline (duet_svim_phase_device).  chrom_texts (CHROM text per contig): the
     extracted arrays carry the marks' read names, and the result also holds `calls`, the rows of sv_calling/variants.vcf formatted
@@ -27,7 +28,9 @@ def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_ca
     (duet_svim_features_device; pc_cap: under that PC cap, duet_svim_features_cap_device) and one vector applied to them
     (duet_tune_sweep_device) in place of the fused run's E/F.  evidence_texts (CHROM text per contig; needs thresholds): the result
     also holds `evidence`, the data rows of the evidence table, one per candidate (duet_evidence_rows_device).  ps_links: the result
-    also holds `ps_links`, the phase-set link records of the candidates (duet_svim_ps_links_device; the voters under pc_cap)."""
+    also holds `ps_links`, the phase-set link records of the candidates (duet_svim_ps_links_device; the voters under pc_cap).
+    read_tag_texts (CHROM text per contig; the extracted arrays carry the marks' read names): the result also holds `read_tags`,
+    (records, rows) of the read tags of the calls just made (duet_read_tags_device and its rows; a tag usable under pc_cap)."""
     if evidence_texts is not None and thresholds is None:
         raise ValueError('the evidence table needs a threshold vector')
 
@@ -49,6 +52,8 @@ def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_ca
             res['calls'] = ds.vcf_rows(ctx, got, chrom_texts)
         if evidence_texts is not None:
             res['evidence'] = ds.evidence_rows(ctx, evidence_texts)
+        if read_tag_texts is not None:
+            res['read_tags'] = ds.read_tags(ctx, got, read_tag_texts, pc_cap=pc_cap)
         if ps_links:
             res['ps_links'] = ds.ps_links(ctx, pc_cap=pc_cap)       # (last: it clusters again, into the same result arrays)
         return res
@@ -86,16 +91,17 @@ def check_read_names(got):
 
 
 def phase_from_bams(home, svlen_thres=50, suppread_thres=2, thread=4, include_all_ctgs=False, max_dist=0.9,
-                    min_sv_size=40, min_mapq=20, depth_bin=1000, ctx=None, only=None, compute=None, names=False):
+                    min_sv_size=40, min_mapq=20, depth_bin=1000, ctx=None, only=None, compute=None, names=False, keep_names=False):
     """-> dict(chroms, cand_contig u16[N], cand_type u8[N] (1 INS / 0 DEL), cand_pos, cand_span, support, pred, ps).
     only: the contig indices to read (a rank of a sharded run; the contig numbering stays the whole list's);
     compute: what turns the extracted arrays into results (default: the GPU pipeline on ctx);
     names (--write_sv_calls): the marks' read names are extracted and checked before anything runs on the device, and the
     result also holds `calls`, the rows of sv_calling/variants.vcf (a compute made with chrom_texts).  A compute made with
-    row_texts adds `rows` / `n_rows`: the data rows of phased_sv.vcf, sorted and formatted on the device."""
+    row_texts adds `rows` / `n_rows`: the data rows of phased_sv.vcf, sorted and formatted on the device.
+    keep_names (--write_read_tags): the marks' read names are extracted for the compute, unchecked: no READS= lists them."""
     chroms = init_chrom_list(include_all_ctgs, home)
     ing, got = NativeIngest.extract(home + '/snp_phasing/', chroms, thread, min_sv_size, min_mapq, depth_bin, only=only,
-                                    names=names)
+                                    names=names or keep_names)
     if ing is None:
         raise RuntimeError('signature extraction declined the input: %s' % got)
     ing.close()
@@ -436,7 +442,7 @@ def rank_main(argv):
 
 
 def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, cluster_max_distance=0.9, device=0,
-                         gpus=1, write_sv_calls=False, thresholds=None, pc_cap=None, evidence=False, ps_links=False):
+                         gpus=1, write_sv_calls=False, thresholds=None, pc_cap=None, evidence=False, ps_links=False, read_tags=False):
     """`duet ... -b svim-gpu -c <max distance>`: SV calling (signatures + clustering, what `-b svim` delegates to the
     external `svim alignment ... --cluster_max_distance c`, sv_calling.py:13-15) AND SV phasing on the GPU, from the
     haplotagged BAMs of <home>/snp_phasing -> <home>/phased_sv.vcf.  The clustering half is this repository's own rule
@@ -450,7 +456,11 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
     evidence (--write_evidence): also <home>/phased_sv.evidence.tsv, one row per clustered candidate with its vote, the rule of the
     tree it ended at and the call, formatted on the device; the route of thresholds (without one the vector is the defaults).
     ps_links (--write_ps_links): also <home>/phased_sv.ps_links.tsv and <home>/phased_sv.ps_blocks.tsv, how the clustered candidates
-    tie neighbouring phase sets together (duet_amd/ps_links.py); single-GPU path only, whichever route the decision takes."""
+    tie neighbouring phase sets together (duet_amd/ps_links.py); single-GPU path only, whichever route the decision takes.
+    read_tags (--write_read_tags): also <home>/phased_sv.read_tags.tsv, the haplotype the heterozygous calls place each supporting
+    read on (duet_amd/read_tags.py), from the resident cluster result and calls; single-GPU path only."""
+    if read_tags and (int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1'):
+        raise ValueError('read_tags: single-GPU path only')
     if ps_links and (int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1'):
         raise ValueError('ps_links: single-GPU path only')
     if evidence:
@@ -512,9 +522,10 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
         texts = spelled_contigs(home, chroms)
         return device_compute(ctx if ctx is not None else engine.default_context(int(device)), texts if write_sv_calls else None,
                               row_texts=texts, thresholds=thresholds, pc_cap=pc_cap, evidence_texts=texts if evidence else None,
-                              ps_links=bool(ps_links))(*args)
+                              ps_links=bool(ps_links), read_tag_texts=texts if read_tags else None)(*args)
     res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
-                          min_sv_size=max(int(svlen_thres), 1), names=bool(write_sv_calls), compute=compute)
+                          min_sv_size=max(int(svlen_thres), 1), names=bool(write_sv_calls), compute=compute,
+                          keep_names=bool(read_tags))
     # the data rows come sorted and formatted from the device; without a single mark nothing ran and there are none
     if 'rows' not in res and len(res['pred']):
         raise RuntimeError('svim-gpu: the device pipeline returned candidates without the rows of phased_sv.vcf')
@@ -532,6 +543,11 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
         from duet_amd import ps_links as links_mod
         from duet_amd.sv_phasing import write_ps_links       # (without a single mark nothing ran: the header lines alone)
         write_ps_links(home, (res.get('ps_links', links_mod.empty()), spelled_contigs(home, chroms)))
+    if read_tags:
+        from duet_amd import read_tags as tags_mod
+        from duet_amd.sv_phasing import write_read_tags      # (without a single mark nothing ran: the header line alone)
+        recs, text = res.get('read_tags', (tags_mod.empty(), np.zeros(0, dtype=np.uint8)))
+        write_read_tags(home, (recs, bytes(memoryview(np.ascontiguousarray(text)))))
     if write_sv_calls:
         with open(out_vcf, 'wb') as out:
             out.write(header_text(home, chroms).encode())

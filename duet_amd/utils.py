@@ -4,7 +4,8 @@
 Flag names, defaults, help texts and the positional order are upstream's (utils.py:19-44), so an
 existing command line works unchanged.  Two additive options select the device (--device) or shard the contigs
 over several GPUs (--gpus); --thresholds and --pc_cap replace the decision's constants on the single-GPU path,
---write_evidence adds the per-candidate evidence table there, --write_ps_links the phase-set link tables.
+--write_evidence adds the per-candidate evidence table there, --write_ps_links the phase-set link tables, --write_read_tags the
+per-read table of the haplotypes the phased SVs place their supporting reads on.
 """
 
 import argparse
@@ -71,6 +72,10 @@ def build_parser():
                     help='also write OUTPUT/phased_sv.ps_links.tsv and OUTPUT/phased_sv.ps_blocks.tsv: which WhatsHap phase sets the SV '
                          'candidates tie together, in which sense and how strongly, and the blocks they join into; one GPU only (the '
                          'native path, or -b svim-gpu)')
+    ap.add_argument('--write_read_tags', action='store_true',
+                    help='also write OUTPUT/phased_sv.read_tags.tsv: one row per supporting read and phase set of the heterozygous '
+                         'calls, with the haplotype the calls place the read on, its own tag, and whether they agree; one GPU only '
+                         '(the native path, or -b svim-gpu)')
     ap.add_argument('--write_sv_calls', action='store_true',
                     help='with -b svim-gpu, also write the clustered SV calls to OUTPUT/sv_calling/variants.vcf')
     for name, text in _POSITIONALS:

@@ -848,6 +848,95 @@ DUET_API int duet_svim_ps_links_host(duet_ctx *ctx, const duet_svim_problem *pro
                                      duet_ps_link *out, uint32_t out_cap, uint32_t *n_links);
 
 /* ---------------------------------------------------------------------------------------------
+ * Read tags from phased SVs (duet_readtags.hip): which haplotype each supporting read lies on.  A
+ * heterozygous call 1|0 in phase set P says that each of its supporting reads lies on haplotype 1 of P -- the reads without a
+ * usable tag of their own included.  The mark CSR goes candidate -> reads; this is its transpose, read -> candidates, summed per
+ * (read name, phase set).  tests/read_tags_ref.py states the rule in plain Python.
+ *
+ *   Slots       CSR slot i (cand_off[c] <= i < cand_off[c + 1]) is raw mark mark_order[i], or raw mark i when mark_order is NULL;
+ *               mark_read and mark_name are indexed by raw mark.  mark_name is the read's identity: equal for all marks of one
+ *               read and < n_names (names are interned per contig: one name, one contig, one read index).
+ *   Marks       every mark of a candidate with pred 1 (1|0) or 2 (0|1) contributes; pred 0 and 3 say nothing about a read's
+ *               haplotype.  A read listed twice in one candidate counts twice, as in the vote.
+ *   Record      one per distinct (name, ps[c]) over the contributing marks: n_h1, n_h2 = its marks from 1|0 / 0|1 calls; pos_min,
+ *               pos_max over cand_pos; contig = the candidates' contig (cand_contig[c], or the k with cand_ctg_off[k] <= c <
+ *               cand_ctg_off[k + 1]); read = the mark_read of its marks; reserved = 0.  Records ascend by (name, ps), PS compared
+ *               as a full unsigned 32-bit number.
+ *   Status      sv = 1 if n_h1 > n_h2, 2 if n_h2 > n_h1, else 0.  The read's tag is usable when `read` is not DUET_MARK_ABSENT
+ *               and < n_reads, the word is not all-ones, hap is 1 or 2 and pc <= pc_cap.  In this order:
+ *                 DUET_READ_TAG_OTHER_PS   a usable tag whose PS is not the record's
+ *                 DUET_READ_TAG_TIE        sv == 0, whatever the tag
+ *                 DUET_READ_TAG_AGREE      a usable tag and sv == hap;  DUET_READ_TAG_DISAGREE  sv is the other haplotype
+ *                 DUET_READ_TAG_NEW        no usable tag: the SVs place a read WhatsHap could not
+ *   Refused     contributing marks of one name on two contigs, or with two different mark_read values: DUET_ERR_INVALID, nothing
+ *               written, *n_recs = 0.  Found from the minimum and maximum inside the reduction, not by a pass of its own.
+ * Integer sums, minima and maxima only, and no kernel of the unit uses an atomic (the shared sort's histogram counts with integer
+ * atomics up to 1024 tiles: sums): two runs give identical bytes.
+ *
+ * pc_cap: 0 .. 2^30 - 3; above: DUET_ERR_INVALID.  Also refused, nothing written: both or neither of cand_ctg_off and cand_contig;
+ * pred > 3; mark_name >= n_names; mark_order >= n_marks; a cand_ctg_off that does not ascend from 0 to n_cands; a NULL array that is
+ * needed.  *n_recs = the exact record count, also when out_cap is smaller: then nothing is written and the call returns
+ * DUET_ERR_INVALID.  n_marks records always suffice.  out may be NULL when out_cap is 0.  n_cands == 0, n_marks == 0 or no
+ * candidate with pred 1 or 2: DUET_OK, 0 records.
+ * _device: the arrays of *prob (cand_ctg_off aside: HOST) and out are device memory, n_recs host memory.  Up to THREE host round
+ * trips, each a few words: the number of contributing marks V (sizes the sort; 0 ends the call), the record count (checked against
+ * out_cap), the refusals of the reduction -- the records wait in the workspace until that word is read, then are copied to out
+ * asynchronously on `stream`.  _host: host arrays, out host; uploads, runs the same kernels, copies the records back, synchronises.
+ * The workspace is the entry's own (32 bytes per contributing mark + the sort's histogram, 8 per candidate, 40 per record; grown,
+ * never shrunk): a call changes nothing that a later duet_ef_run_*, duet_ef_features_*, duet_tune_* or duet_ps_links_* returns.
+ *
+ * The rows (duet_read_tags_rows_*): one per record, in record order, tab-separated, one '\n' behind each row:
+ *     CHROM READ PS N_SV N_H1 N_H2 HP_SV TAG_HP TAG_PS TAG_PC STATUS POS_MIN POS_MAX
+ * (DUET_READ_TAG_COLUMNS; the header line stays with the host).  CHROM = names->chrom[contig]; READ = name_pool[name_off[name] ..
+ * name_off[name + 1]); N_SV = n_h1 + n_h2; HP_SV = 1, 2 or `.` for sv; TAG_HP TAG_PS TAG_PC = the read's own tag word, whatever
+ * the cap: all three `.` when `read` is DUET_MARK_ABSENT or >= n_reads or the word is all-ones, TAG_HP `.` for hap 0 and 3;
+ * STATUS = DUET_READ_TAG_STATUS_NAMES[status].  Of *names only name_off, name_pool, n_names, n_contigs and chrom are read.
+ * _device: recs, name_off, name_pool, read_tag and out_text device memory, chrom HOST; asynchronous on `stream` apart from ONE host
+ * round trip that learns the text's size and the status words.  _host: everything HOST.
+ * Both: *out_len = the text's exact size, always; when out_cap is smaller nothing is written and the call returns
+ * DUET_ERR_INVALID.  A row is at most its CHROM and READ pieces + 103 bytes, so
+ *     n_recs * (longest CHROM text + longest name + 104)
+ * always suffices.  Row offsets are 64-bit.  DUET_ERR_INVALID, nothing written: a record's name >= n_names, contig >= n_contigs
+ * or status > 4; name offsets that descend; n_contigs of 0 or more than 65535; a NULL array or text that is needed.  n_recs == 0:
+ * DUET_OK, zero bytes.  The workspace is the entry's own. */
+#define DUET_READ_TAG_AGREE 0u
+#define DUET_READ_TAG_DISAGREE 1u
+#define DUET_READ_TAG_TIE 2u
+#define DUET_READ_TAG_NEW 3u
+#define DUET_READ_TAG_OTHER_PS 4u
+#define DUET_READ_TAG_STATUS_NAMES {"agree", "disagree", "tie", "new", "other_ps"}
+#define DUET_READ_TAG_COLUMNS \
+    {"CHROM", "READ", "PS", "N_SV", "N_H1", "N_H2", "HP_SV", "TAG_HP", "TAG_PS", "TAG_PC", "STATUS", "POS_MIN", "POS_MAX"}
+typedef struct duet_read_tag_rec {       /* 40 bytes */
+    uint32_t name, contig, ps, read;
+    uint32_t n_h1, n_h2, pos_min, pos_max;
+    uint32_t status;
+    uint32_t reserved;                   /* 0 */
+} duet_read_tag_rec;
+typedef struct duet_read_tags_problem {
+    uint32_t n_cands, n_marks, n_reads, n_names;
+    uint32_t n_contigs, reserved;        /* n_contigs: with cand_ctg_off */
+    const uint32_t *cand_off;            /* [C+1] */
+    const uint32_t *mark_order;          /* [M] or NULL (identity) */
+    const uint32_t *mark_read;           /* [M] per raw mark: index into read_tag, or DUET_MARK_ABSENT */
+    const uint32_t *mark_name;           /* [M] per raw mark */
+    const uint8_t *pred;                 /* [C] 0 .. 3 */
+    const uint32_t *ps, *cand_pos;       /* [C] */
+    const uint32_t *cand_ctg_off;        /* HOST [K+1], or NULL ... */
+    const uint16_t *cand_contig;         /* ... then [C], non-descending */
+    const uint64_t *read_tag;            /* [R] */
+} duet_read_tags_problem;
+DUET_API int duet_read_tags_device(duet_ctx *ctx, const duet_read_tags_problem *prob, uint32_t pc_cap, duet_read_tag_rec *out,
+                                   uint32_t out_cap, uint32_t *n_recs, void *stream);
+DUET_API int duet_read_tags_host(duet_ctx *ctx, const duet_read_tags_problem *prob, uint32_t pc_cap, duet_read_tag_rec *out,
+                                 uint32_t out_cap, uint32_t *n_recs);
+DUET_API int duet_read_tags_rows_device(duet_ctx *ctx, const duet_read_tag_rec *recs, uint32_t n_recs, const duet_callset_names *names,
+                                        const uint64_t *read_tag, uint32_t n_reads, char *out_text, uint64_t out_cap, uint64_t *out_len,
+                                        void *stream);
+DUET_API int duet_read_tags_rows_host(duet_ctx *ctx, const duet_read_tag_rec *recs, uint32_t n_recs, const duet_callset_names *names,
+                                      const uint64_t *read_tag, uint32_t n_reads, char *out_text, uint64_t out_cap, uint64_t *out_len);
+
+/* ---------------------------------------------------------------------------------------------
  * The collective of the contig-sharded path: candidates shard by contig over the GPUs of one node,
  * one process and one context per GPU, and ONE all-gather of fixed-size record blocks reassembles the call set
  * (src/duet/sv_phasing_fn.py:15-18, 195-210: nothing crosses contigs before the final sort at :229).  RCCL over xGMI,

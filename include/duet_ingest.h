@@ -134,7 +134,11 @@ int duet_ingest_get_marks(duet_ingest *ing, duet_ingest_marks *out);
  * duet_ingest_keep_mark_names(ing, 1) BEFORE the BAMs are added (DUET_INGEST_INVALID once marks exist); without it the extraction
  * keeps no names and duet_ingest_get_mark_names returns DUET_INGEST_INVALID.  Names are interned per contig: mark_name[i] is the
  * name of mark i of duet_ingest_get_marks (same order), an index into name_off; name n is name_pool[name_off[n] .. name_off[n + 1]).
- * A read that supplies marks on two contigs has one entry per contig. */
+ * A read that supplies marks on two contigs has one entry per contig.
+ * The VCF path takes the same opt-in: enabled BEFORE duet_ingest_parse_vcf* (DUET_INGEST_INVALID afterwards), the join also interns
+ * the name of every mark of the caller VCF per contig, tagged or not, and on an ingest without extraction
+ * duet_ingest_get_mark_names returns them: mark_name[i] is the name of mark i of duet_ingest_arrays.mark_read (same order), the
+ * pool laid out as above, in order of first mark.  Without the call nothing is kept and the parse does what it did. */
 typedef struct duet_ingest_mark_names {  /* views into memory owned by the duet_ingest object */
     uint32_t n_marks, n_names;
     const uint32_t *mark_name;          /* [M] */
