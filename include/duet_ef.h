@@ -147,10 +147,10 @@ DUET_API int duet_ef_profile_collect(duet_ctx *ctx, duet_ef_stats *stats);
 #define DUET_DBG_EF_HEAVY_OFF 0x100000u  /* ... only those of more than 255 marks (the lane walk keeps its counts in bytes): every other candidate by its own lane, mark after mark */
 #define DUET_DBG_EF_FP_DECIDE 0x400000u  /* E/F: ef_classify takes every class-0 / class-1 decision through the binary64 expressions (rounds 1-4) instead of the
                                             integer form with the binary64 fallback */
-#define DUET_DBG_EF_OWN_OFF 0x800000u     /* E/F: three launches (ef_classify, ef_seed_sort, ef_finalize) at every size; default up to 1024 tiles of 256 candidates
+#define DUET_DBG_EF_OWN_OFF 0x800000u     /* E/F: three launches (ef_classify, ef_seed_sort, ef_finalize) at every size; default up to 2048 tiles of 256 candidates
                                           * and 64 contigs: two -- every finalize tile builds its contig's seed set itself (ef_finalize_own) */
 #define DUET_DBG_EF_OWN_ALL 0x1000000u    /* ... the two launches at every size (up to 64 contigs; host-planned runs only) */
-#define DUET_DBG_EF_OWN_SMALLTAB 0x2000000u /* ... and their seed set in LDS holds 8 distinct seeds (default 2048): contigs with more take the array-free walk */
+#define DUET_DBG_EF_OWN_SMALLTAB 0x2000000u /* ... and their seed set in LDS holds 8 distinct seeds (default 1024): contigs with more take the array-free walk */
 #define DUET_DBG_CLUSTER_EVENT_FORKS 0x4000000u /* A0: the side streams fork off behind hipEventRecord / hipStreamWaitEvent (rounds 1-5) instead of a signal kernel on the
                                           * main stream and a gate kernel on the side stream (round 6) */
 #define DUET_DBG_CLUSTER_WIDE_OFF 0x8000000u /* A0: small inputs keep ONE wavefront per partition of more than 64 marks (rounds 1-5: cl_tight_big + cl_link_one) instead

@@ -12,6 +12,7 @@ from duet_amd.sv_phasing import sv_phasing
 from oracle import c_oracle
 from tests import helpers as H
 from tests import soa_fuzz
+from tests.seed_edges import seed_list_soa
 from tests.test_c_oracle import materialise_bams
 
 pytestmark = pytest.mark.gpu
@@ -143,31 +144,6 @@ def test_unsorted_candidates_seed_set_paths(ctx, n_ps):
             assert np.array_equal(ctx.seed_ps(k), seeds[k]) and np.all(seeds[k][1:] > seeds[k][:-1])
     finally:
         ctx.set_debug(0)
-
-
-def seed_list_soa(seqs):
-    """One contig per sequence; candidate i of a contig is a class-1 candidate whose two marks are one read of phase set seq[i]:
-    ef_seed_sort's list for the contig is seq with consecutive repeats dropped."""
-    tags, mark_read, cand_off, ctg_off, read_off = [], [], [0], [0], [0]
-    cols = dict(pos=[], svlen=[], svread=[], refread=[], gt=[])
-    for seq in seqs:
-        base = len(tags)
-        for i, ps in enumerate(seq):
-            tags.append((1 + i % 2, 10 + i % 50, ps))
-            mark_read += [i, i]                                # (contig-local read ids)
-            cand_off.append(len(mark_read))
-            cols['pos'].append(1000 + 7 * i); cols['svlen'].append(100); cols['svread'].append(5); cols['refread'].append(5); cols['gt'].append(1)
-        ctg_off.append(len(cols['pos'])); read_off.append(len(tags))
-    hap = np.array([t[0] for t in tags]); pc = np.array([t[1] for t in tags]); ps = np.array([t[2] for t in tags])
-    # mark_read: global read index = contig's read offset + local id
-    mr = np.array(mark_read, dtype=np.uint64)
-    co = np.array(cand_off)
-    for k in range(len(seqs)):
-        lo, hi = co[ctg_off[k]], co[ctg_off[k + 1]]
-        mr[lo:hi] += read_off[k]
-    return engine.EfSoA(cand_ctg_off=ctg_off, read_off=read_off, read_tag=engine.pack_tags(hap, pc, ps), cand_pos=cols['pos'],
-                        cand_svlen=cols['svlen'], cand_svread=cols['svread'], cand_refread=cols['refread'], cand_gt_ok=cols['gt'],
-                        cand_off=cand_off, mark_read=mr)
 
 
 def test_seed_lists_with_local_disorder(ctx):
@@ -435,7 +411,7 @@ OWN_OFF, OWN_ALL, OWN_SMALLTAB = 0x800000, 0x1000000, 0x2000000     # include/du
 
 
 def test_two_launches_three_launches_and_the_array_free_walk_agree(ctx):
-    """Round 6: up to 1024 tiles and 64 contigs step E/F is TWO launches -- every finalize tile builds its contig's seed set itself
+    """Round 6: up to 2048 tiles and 64 contigs step E/F is TWO launches -- every finalize tile builds its contig's seed set itself
     (ef_finalize_own: hash set + ordered blocks in LDS) -- beyond that the three of rounds 1-5.  Every case through: the default,
     the three launches forced, the two launches forced (also on the large case), and the two launches with a seed set of 8 entries
     (contigs with more distinct seeds answer "is this PS a seed" / "which seed is nearest" by walking the contig's seed entries);
