@@ -10,7 +10,8 @@
 //                 candidates leave a 14-word summary of their first two voter groups.  Seeds leave the
 //                 tile as compacted (candidate, PS) entries in candidate order -- repeats of the previous
 //                 seed-bearing candidate dropped with ballots -- in the tile's own slots: no atomics, no
-//                 hash set.
+//                 hash set.  (ef_classify_split, round 9: the same tile by 512 threads, two lanes per candidate whose states are
+//                 folded -- small host-planned problems, in front of ef_finalize_own.)
 //   ef_seed_sort  one workgroup per contig: gathers the contig's entries in candidate order (an
 //                 exclusive scan of per-thread counts), finishes local disorder with a few odd-even
 //                 rounds, merges a few long ascending runs by rank or falls back to a bitonic network
@@ -523,17 +524,19 @@ __device__ __forceinline__ uint32_t decide_store(const Params &p, TileShared &sh
 // Seed entries of one tile, in candidate order (thread t speaks for candidate c0 + t; sh.seed[] must hold every
 // candidate's seed or kEmpty and be visible).  A seed equal to the seed of the previous seed-bearing candidate is
 // dropped, unless a contig starts in between (seed sets are per contig).  Only the set matters downstream, so
-// dropping duplicates early just shortens ef_seed_sort's input.  All 256 threads call it (it synchronises).
+// dropping duplicates early just shortens ef_seed_sort's input.  Every thread of the workgroup calls it (it synchronises): the 256
+// that speak for a candidate, and in ef_classify_split the helper wavefronts too, with `owner` false -- they meet the barriers and
+// touch nothing.
 __device__ __forceinline__ void seeds_tile(const Params &p, TileShared &sh, uint32_t tile, uint32_t tid, uint32_t c,
-                                           uint32_t is_start)
+                                           uint32_t is_start, bool owner = true)
 {
-    const uint32_t seed = sh.seed[tid];
+    const uint32_t seed = owner ? sh.seed[tid] : kEmpty;
     const bool want_seed = seed != kEmpty;
     const uint32_t lane = tid & 63u, wave = tid >> 6;
     const unsigned long long wmask = __ballot(want_seed);
     const unsigned long long smask = __ballot(is_start != 0);
     const unsigned long long upto = lane == 63 ? ~0ull : ((1ull << (lane + 1)) - 1ull);    // lanes 0..lane
-    if (lane == 0) {
+    if (lane == 0 && owner) {
         if (wmask) {
             const uint32_t li = 63u - (uint32_t)__clzll(wmask);
             sh.wlast[wave] = sh.seed[wave * 64 + li];
@@ -556,7 +559,7 @@ __device__ __forceinline__ void seeds_tile(const Params &p, TileShared &sh, uint
         }
     }
     const unsigned long long mask = __ballot(keep);
-    if (lane == 0) sh.wcnt[wave] = (uint32_t)__popcll(mask);
+    if (lane == 0 && owner) sh.wcnt[wave] = (uint32_t)__popcll(mask);
     __syncthreads();
     uint32_t before = 0, total = 0;
 #pragma unroll
@@ -593,12 +596,14 @@ __device__ __forceinline__ void issue_fence()
     __builtin_amdgcn_sched_barrier(0);
 }
 
-__device__ __forceinline__ void stage_load_marks(const uint32_t *__restrict__ mark_read, uint4 (&r)[kStageIt], uint32_t cs, uint32_t m_end,
+// (NT: the workgroup's threads, IT: its index loads per thread and pass -- ef_classify's kCandPerBlock and kStageIt, ef_classify_split's own)
+template <int NT = kCandPerBlock, int IT>
+__device__ __forceinline__ void stage_load_marks(const uint32_t *__restrict__ mark_read, uint4 (&r)[IT], uint32_t cs, uint32_t m_end,
                                                  uint32_t tid)
 {
 #pragma unroll
-    for (int it = 0; it < kStageIt; ++it) {
-        const uint32_t m = cs + 4u * (tid + it * kCandPerBlock);
+    for (int it = 0; it < IT; ++it) {
+        const uint32_t m = cs + 4u * (tid + it * NT);
         r[it] = *reinterpret_cast<const uint4 *>(mark_read + (m < m_end ? m : cs));
     }
     issue_fence();
@@ -611,11 +616,12 @@ __device__ __forceinline__ void stage_load_marks(const uint32_t *__restrict__ ma
 // mark where this takes 4 -- the counters put this kernel at 80 % vector issue.)  The compare also covers the indices a 16-byte load
 // picks up behind the last mark of the array (anything below the table's size is a harmless gather into an LDS slot nobody reads).
 // (a scheduling barrier behind every group of four: the groups leave in the order of the index loads they wait for)
+template <int IT>
 __device__ __forceinline__ void stage_gather(const uint64_t *__restrict__ read_tag, const uint64_t *__restrict__ untagged, uint32_t n_reads,
-                                             uint64_t (&t)[4 * kStageIt], const uint4 (&r)[kStageIt])
+                                             uint64_t (&t)[4 * IT], const uint4 (&r)[IT])
 {
 #pragma unroll
-    for (int it = 0; it < kStageIt; ++it) {
+    for (int it = 0; it < IT; ++it) {
         // the wait for index load `it` stands here and nowhere earlier (the asm takes the four indices and hands them back: whatever
         // is computed from them comes behind it, and it comes behind the previous group's gathers)
         uint32_t idx[4] = {r[it].x, r[it].y, r[it].z, r[it].w};
@@ -629,13 +635,15 @@ __device__ __forceinline__ void stage_gather(const uint64_t *__restrict__ read_t
     }
 }
 
-__device__ __forceinline__ void stage_store(uint64_t *s_tag, const uint64_t (&t)[4 * kStageIt], uint32_t tid)
+template <int NT = kCandPerBlock, int IT4>
+__device__ __forceinline__ void stage_store(uint64_t *s_tag, const uint64_t (&t)[IT4], uint32_t tid)
 {
 #pragma unroll
-    for (int it = 0; it < kStageIt; ++it) {
-        // unconditional, like the loads: a thread's slots i .. i + 3 lie inside s_tag whatever m_end is (i + 3 <= 4 * 767 + 3 = kChunk - 1),
-        // and the walk reads s_tag[m - cs] for cs <= m < m_end only -- what lands behind the tile's last mark is never looked at
-        const uint32_t i = 4u * (tid + it * kCandPerBlock);
+    for (int it = 0; it < IT4 / 4; ++it) {
+        // unconditional, like the loads: a thread's slots i .. i + 3 lie inside s_tag whatever m_end is (i + 3 <= 4 * 767 + 3 = kChunk - 1;
+        // in general 4 * (NT * IT4 / 4 - 1) + 3, the pass's last slot), and the walk reads s_tag[m - cs] for cs <= m < m_end only -- what
+        // lands behind the tile's last mark is never looked at
+        const uint32_t i = 4u * (tid + it * NT);
 #pragma unroll
         for (int j = 0; j < 4; ++j) s_tag[i + j] = t[4 * it + j];
     }
@@ -821,6 +829,223 @@ __global__ __launch_bounds__(kCandPerBlock, 6) void ef_classify(const Params p)
         if (!DYN) break;
         __syncthreads();                                           // the tile's LDS is reused
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// kernel 1, small problems (round 9): kSplit lanes per candidate
+// ---------------------------------------------------------------------------------------------
+// Where the two launches are taken the chip is nearly empty (configs[1]: 391 tiles, 1,564 wavefronts on 1,024 SIMDs) and a tile's
+// time is a chain of latencies.  The longest link was the walk: a wavefront loops as often as its longest candidate has marks, an
+// LDS read and ~25 dependent instructions per iteration.  Here a candidate's marks are cut into kSplit contiguous parts and every
+// part has a lane of its own: threads 0 .. 255 are the candidates' owners, exactly ef_classify's threads, thread 256 * k + t helps
+// candidate t with part k.  Each part's state starts empty and is carried across the staging passes by its lane; behind the last
+// pass the helpers hand theirs over through LDS and the owner folds them, left to right, into the state the serial walk would have
+// produced.  Everything behind the state -- decide_store, the pool, seeds_tile -- is ef_classify's, run by the owners.
+//
+// The fold (CandState over a range of marks is a monoid; L = state of [lo, mid), R = state of [mid, hi), both from empty):
+//   * first_ps is the minimum (any tagged mark's PS serves while there is one phase set); multi = either half's, or both halves
+//     have a PS and they differ.  nv and n_b add.
+//   * R's groups are taken in R's first-seen order, A then B, each if it exists: into A if A is empty or has its PS, else into B if
+//     B is empty or has its PS, else `more`; R.more carries over.  n_a is restated as consume_range ends.
+//   * `more` is exact: the serial walk's is false exactly when [lo, hi) has at most two distinct voter PS; then R saw at most two
+//     (R.more false) and each of its groups matches A or B or fills an empty one.  With three or more, either a half has `more`
+//     already or one of R's groups finds both slots taken by other PS.
+//   * counts and sums are exact when `more` is false -- and when it is true nobody reads them (no summary: c2_fast is false, and
+//     ef_finalize* re-gathers the vote from the marks; a class-0 / class-1 candidate has one PS and never sets it).
+//   * what depends on order -- the seed, class 1's PS: the first voter's PS -- is L.A if L has voters, else R.A: group A of the fold.
+//   * widths: a lane's part is at most 255 marks (longer candidates are the owner's wavefront's, consume_heavy, and their helpers
+//     walk nothing), so a helper's counts fit a byte and its PC sums 21 bits: the hand-over is eight words.  Group B's sums stay 32
+//     bits wide: what moves from R.A into B is a helper's.
+// The fold is associative; kSplit = 4 is a left fold over three partners.  tests/test_split_edge_cases.py restates walk and fold
+// and checks fold(walk(a), walk(b)) == walk(a + b) for every short sequence over an alphabet of marks.
+// lanes per candidate.  Measured, plain bench.py at configs[1], us per step, three alternating runs each: ef_classify 15.51-15.57,
+// 2 lanes 15.18-15.20, 4 lanes (1,024 threads) 21.40-21.48 (profiles/history/r09_ef_classify_four_lanes_per_candidate_REJECTED.txt)
+constexpr int kSplit = 2;
+constexpr int kSplitThreads = kSplit * kCandPerBlock;
+constexpr int kSplitChunk = kChunk;                       // marks staged per pass, as in ef_classify: a configs[1] tile (2,560 on average) is one pass
+constexpr int kSplitStagers = 384;                        // threads that stage (six of the eight wavefronts, two index loads each)
+constexpr int kSplitStageIt = kSplitChunk / (kSplitStagers * 4);   // 16-byte index loads per staging thread and pass
+// the two-launch path takes ef_classify_split up to this many tiles.  Measured (tools/own_sweep.py 200, profiles/r09_own_sweep.txt;
+// us per step on the two launches, ef_classify / ef_classify_split): configs[1], 391 tiles, 14.63 / 14.42; the 24-contig genome at
+// 98 tiles 88.3 / 88.0, 391 tiles 73.3 / 71.9, 782 tiles 26.2 / 27.7, 1,563 tiles 34.8 / 37.4, 3,126 tiles 48.3 / 55.0 -- ahead or
+// level while no CU holds more than two tiles, behind from three on.
+constexpr uint32_t kSplitMaxTiles = 512;
+static_assert(kSplit == 2 || kSplit == 4, "the parts are halves, or halves of halves");
+static_assert(kSplitStageIt >= 1 && kSplitStageIt * kSplitStagers * 4 == kSplitChunk, "a pass is whole 16-byte loads");
+static_assert(kSplitStagers % 64 == 0 && kSplitStagers <= kSplitThreads, "whole wavefronts stage");
+
+// part `part` of kSplit of the marks [b, e): halves at b + (n + 1) / 2, for kSplit = 4 each half halved the same way
+__device__ __forceinline__ void split_bounds(uint32_t b, uint32_t e, uint32_t part, uint32_t &lo, uint32_t &hi)
+{
+    lo = b; hi = e;
+#pragma unroll
+    for (uint32_t bit = kSplit >> 1; bit != 0; bit >>= 1) {
+        const uint32_t mid = lo + (hi - lo + 1u) / 2u;
+        if (part & bit) lo = mid; else hi = mid;
+    }
+}
+
+__device__ __forceinline__ void fold(CandState &l, const CandState &r)
+{
+    l.multi = l.multi || r.multi || (l.first_ps != kEmpty && r.first_ps != kEmpty && l.first_ps != r.first_ps);
+    l.first_ps = min(l.first_ps, r.first_ps);
+    l.nv += r.nv;
+    // R's group: its PS, its voters, hap-1 / hap-2 counts and PC sums
+    auto take = [&](uint32_t ps, uint32_t n, uint32_t h1, uint32_t h2, uint32_t t1, uint32_t t2) {
+        const bool is = ps != kEmpty;
+        const bool to_a = is && (l.ps_a == kEmpty || l.ps_a == ps);
+        const bool to_b = is && !to_a && (l.ps_b == kEmpty || l.ps_b == ps);
+        l.ps_a = to_a ? ps : l.ps_a;
+        l.a1 += to_a ? h1 : 0u; l.a2 += to_a ? h2 : 0u;
+        l.TA1 += to_a ? t1 : 0u; l.TA2 += to_a ? t2 : 0u;
+        l.ps_b = to_b ? ps : l.ps_b;
+        l.n_b += to_b ? n : 0u;
+        l.b1 += to_b ? h1 : 0u; l.b2 += to_b ? h2 : 0u;
+        l.tb1 += to_b ? t1 : 0u; l.tb2 += to_b ? t2 : 0u;
+        l.more = l.more || (is && !to_a && !to_b);
+    };
+    take(r.ps_a, r.nv - r.n_b, r.a1, r.a2, (uint32_t)r.TA1, (uint32_t)r.TA2);     // (R.A's voters: those that are not R.B's, exact unless R.more)
+    take(r.ps_b, r.n_b, r.b1, r.b2, r.tb1, r.tb2);
+    l.more = l.more || r.more;
+    l.n_a = l.more ? (l.ps_a != kEmpty ? 1u : 0u) : l.nv - l.n_b;
+}
+
+// a helper's state in eight words: {first_ps, ps_a, ps_b, nv | n_b << 8 | multi << 16 | more << 17} and count << 24 | PC sum of A1, A2, B1, B2
+__device__ __forceinline__ void hand_store(uint4 (*s_hand)[(kSplit - 1) * kCandPerBlock], uint32_t slot, const CandState &st)
+{
+    s_hand[0][slot] = make_uint4(st.first_ps, st.ps_a, st.ps_b, st.nv | st.n_b << 8 | (st.multi ? 1u << 16 : 0u) | (st.more ? 1u << 17 : 0u));
+    s_hand[1][slot] = make_uint4(st.a1 << 24 | (uint32_t)st.TA1, st.a2 << 24 | (uint32_t)st.TA2, st.b1 << 24 | st.tb1, st.b2 << 24 | st.tb2);
+}
+
+__device__ __forceinline__ CandState hand_load(const uint4 (*s_hand)[(kSplit - 1) * kCandPerBlock], uint32_t slot)
+{
+    const uint4 x = s_hand[0][slot], y = s_hand[1][slot];
+    CandState st;
+    st.first_ps = x.x; st.ps_a = x.y; st.ps_b = x.z;
+    st.nv = x.w & 0xFFu; st.n_b = (x.w >> 8) & 0xFFu; st.multi = (x.w >> 16 & 1u) != 0; st.more = (x.w >> 17 & 1u) != 0;
+    st.a1 = y.x >> 24; st.a2 = y.y >> 24; st.b1 = y.z >> 24; st.b2 = y.w >> 24;
+    st.TA1 = y.x & 0xFFFFFFu; st.TA2 = y.y & 0xFFFFFFu; st.tb1 = y.z & 0xFFFFFFu; st.tb2 = y.w & 0xFFFFFFu;
+    return st;
+}
+
+// One tile (256 candidates) per workgroup of kSplitThreads; host-planned runs only (where ef_finalize_own follows).  The prologue keeps
+// ef_classify's round-8 properties: arguments at entry, every load unconditional at a clamped address (a helper loads its candidate's
+// offsets and columns as the owner does: it needs `kept` and the split point), one wait; the staging pass keeps its order of loads.
+// Every wavefront reaches every barrier: the helpers run the tail's barriers with the owners.
+// (registers for six waves per SIMD, three workgroups per CU, as ef_classify; LDS -- 24 KiB of tags, 8 KiB of hand-over -- allows four)
+template <bool VEC>
+__global__ __launch_bounds__(kSplitThreads, 6) void ef_classify_split(const Params p)
+{
+    __shared__ uint64_t s_tag[kSplitChunk];
+    __shared__ uint4 s_hand[2][(kSplit - 1) * kCandPerBlock];
+    __shared__ TileShared sh;
+
+    const uint32_t tid = threadIdx.x, j = tid % kCandPerBlock, part = tid / kCandPerBlock;
+    const bool owner = part == 0;
+    STAMP(0, 0);
+    const uint32_t C = p.C, n_reads = p.n_reads, svlen_thres = p.svlen_thres, suppread_thres = p.suppread_thres;
+    const uint32_t heavy_t = min(p.heavy_t, 255u);             // (the lane walk packs counts into bytes)
+    const uint32_t *__restrict__ const cand_off = p.cand_off, *__restrict__ const mark_read = p.mark_read;
+    const uint64_t *__restrict__ const read_tag = p.read_tag, *__restrict__ const untagged = p.untagged;
+    const uint32_t *__restrict__ const cand_svlen = p.cand_svlen, *__restrict__ const cand_svread = p.cand_svread;
+    const uint32_t *__restrict__ const cand_refread = p.cand_refread;
+    const uint8_t *__restrict__ const cand_gt_ok = p.cand_gt_ok, *__restrict__ const ctg_start = p.ctg_start;
+    asm volatile("" ::"s"(C), "s"(n_reads), "s"(svlen_thres), "s"(suppread_thres), "s"(heavy_t), "s"(cand_off), "s"(mark_read),
+                 "s"(read_tag), "s"(untagged), "s"(cand_svlen), "s"(cand_svread), "s"(cand_refread), "s"(cand_gt_ok), "s"(ctg_start));
+    asm volatile("" ::"s"(p.dbg), "s"(p.out_pred), "s"(p.out_ps), "s"(p.blk_rec), "s"(p.seed_ent), "s"(p.c2rec), "s"(p.status),
+                 "s"(p.c2_fixed), "s"(p.c2_cap));
+    const uint32_t tile = blockIdx.x, c0 = tile * kCandPerBlock, c = c0 + j;
+    // ---- ONE round trip: offsets and candidate scalars of candidate c0 + j, as in ef_classify (same clamps: cand_off has C + 1
+    // entries, the columns C; c0 < C in a host-planned grid) ----
+    const uint32_t ic = min(c, C - 1u);
+    const uint32_t o0_ld = cand_off[min(c, C)], o1_ld = cand_off[min(c + 1u, C)];
+    const uint32_t svlen_ld = cand_svlen[ic], svread_ld = cand_svread[ic], refread_ld = cand_refread[ic], gt_ld = cand_gt_ok[ic];
+    const uint32_t start_ld = ctg_start[ic];
+    const uint32_t mb_ld = cand_off[c0], me_ld = cand_off[min(c0 + (uint32_t)kCandPerBlock, C)];
+    const uint32_t nc = min((uint32_t)kCandPerBlock, C - c0);
+    asm volatile("" ::"v"(o0_ld), "v"(o1_ld), "v"(svlen_ld), "v"(svread_ld), "v"(refread_ld), "v"(gt_ld), "v"(start_ld));
+    // (ordered against decide_store's atomicAdd as in ef_classify: only a tile with a staging pass ever gets there)
+    if (tid == 0) sh.c2n = 0;
+    const bool live = j < nc;
+    const uint32_t svlen = svlen_ld, svread = svread_ld, refread = refread_ld, gt_ok = gt_ld;
+    const uint32_t is_start = (owner && live) ? start_ld : 0u;
+    const bool kept = live && svlen >= svlen_thres && svread >= suppread_thres && gt_ok != 0;     // :189-190
+    const bool divzero = kept && ((uint64_t)svread + (uint64_t)refread == 0);
+    const uint32_t m_begin = (uint32_t)__builtin_amdgcn_readfirstlane((int)mb_ld);
+    const uint32_t m_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)me_ld);
+    STAMP(0, 1);
+
+    const bool active = kept && !divzero;
+    const uint32_t my_b = live ? o0_ld : 0, my_e = live ? o1_ld : 0;
+    // this lane's part of the candidate.  A candidate above heavy_t is walked whole by its owner's wavefront (consume_heavy), its
+    // helpers walk nothing; a candidate that is not kept is walked by nobody
+    const bool heavy_c = my_e - my_b > heavy_t;
+    uint32_t w_b, w_e;
+    split_bounds(my_b, my_e, part, w_b, w_e);
+    if (heavy_c) { w_b = my_b; w_e = owner ? my_e : my_b; }
+    if (!kept) w_e = w_b;
+    CandState st;
+
+    const uint32_t base = VEC ? (m_begin & ~3u) : m_begin;
+    for (uint32_t cs = base; cs < m_end; cs += kSplitChunk) {
+        // ---- stage: LDS[i] = tag of mark cs+i ----
+        if (VEC) {
+            if (tid < kSplitStagers) {                         // (whole wavefronts: the others go straight to the barrier)
+                uint4 r[kSplitStageIt];
+                uint64_t t[4 * kSplitStageIt];
+                stage_load_marks<kSplitStagers>(mark_read, r, cs, m_end, tid);
+                stage_gather(read_tag, untagged, n_reads, t, r);
+                stage_store<kSplitStagers>(s_tag, t, tid);
+            }
+        } else {
+            for (uint32_t i = tid; i < kSplitChunk && cs + i < m_end; i += kSplitThreads) {
+                const uint32_t r = mark_read[cs + i];
+                s_tag[i] = r < n_reads ? read_tag[r] : kUntagged;
+            }
+        }
+        __syncthreads();
+        STAMP(0, 2);
+        // ---- consume: each lane walks its part's share of this chunk (an empty range when the part lies in front of or behind it) ----
+        const uint32_t lo = max(w_b, cs), hi = min(w_e, cs + (uint32_t)kSplitChunk);
+        const bool heavy = heavy_c && lo < hi;
+        unsigned long long hm = __ballot(heavy);
+        consume_range(st, s_tag, heavy ? hi : lo, hi, cs);
+        while (hm) {
+            const uint32_t h = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)__ffsll((long long)hm) - 1u));
+            hm &= hm - 1ull;
+            const uint32_t lo_h = (uint32_t)__builtin_amdgcn_readlane((int)lo, h), hi_h = (uint32_t)__builtin_amdgcn_readlane((int)hi, h);
+            consume_heavy(st, s_tag, lo_h, hi_h, cs, tid & 63u, h);
+        }
+        STAMP(0, 3);
+        // the last pass's closing barrier is the hand-over's
+        if (!owner && cs + (uint32_t)kSplitChunk >= m_end) hand_store(s_hand, tid - kCandPerBlock, st);
+        __syncthreads();
+    }
+    STAMP(0, 4);
+    uint32_t c2_rank = kEmpty;
+    if (owner) {
+        if (base < m_end) {                                    // (a tile without a pass: nothing was walked and nothing handed over)
+#pragma unroll
+            for (int k = 1; k < kSplit; ++k) fold(st, hand_load(s_hand, (k - 1) * kCandPerBlock + j));
+        }
+        sh.seed[j] = decide_store(p, sh, tile, live, c, active, divzero, st, my_e - my_b, svread, refread, c2_rank);
+    }
+    __syncthreads();
+    if (sh.c2n > kC2Quota) {
+        // (ef_classify's pool branch)
+        if (tid == 0) sh.c2base = atomicAdd(&p.status[1], sh.c2n - kC2Quota);
+        __syncthreads();
+        if (owner && live && c2_rank != kEmpty && c2_rank >= kC2Quota) {
+            const uint32_t at = sh.c2base + (c2_rank - kC2Quota);
+            if (at < p.c2_cap - p.c2_fixed) {
+                store_summary(p, p.c2_fixed + at, st);
+                p.out_pred[c] = kClass2;
+                p.out_ps[c] = p.c2_fixed + at;
+            }
+        }
+    }
+    seeds_tile(p, sh, tile, tid, c, is_start, owner);
+    STAMP(0, 6);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2514,8 +2739,14 @@ int duet_ef_run_device(duet_ctx *ctx, const duet_ef_problem *pr, uint8_t *out_pr
     // (the diagnostic bits that select a variant of ef_seed_sort / ef_finalize select the three launches with it)
     const uint32_t three = DUET_DBG_EF_OWN_OFF | DUET_DBG_EF_FIN_TPB2 | DUET_DBG_EF_FIN_TPB4 | DUET_DBG_EF_NO_SEED_HASH;
     const bool own = p.n_small && !(ctx->dbg & three) && (blocks <= kOwnMaxTiles || (ctx->dbg & DUET_DBG_EF_OWN_ALL));
+    // ... and there, while the chip is far from full, kSplit lanes walk a candidate (round 9: ef_classify_split)
+    const bool split = own && blocks <= kSplitMaxTiles && !(ctx->dbg & DUET_DBG_EF_SPLIT_OFF);
     if (prof) ctx->ev_kmask.push_back(own ? 0x5 : 0x7);
-    if (((uintptr_t)pr->mark_read & 15) == 0)
+    if (split && ((uintptr_t)pr->mark_read & 15) == 0)
+        hipExtLaunchKernelGGL(ef_classify_split<true>, dim3(blocks), dim3(kSplitThreads), 0, stream, ev[0], ev[1], 0, p);
+    else if (split)
+        hipExtLaunchKernelGGL(ef_classify_split<false>, dim3(blocks), dim3(kSplitThreads), 0, stream, ev[0], ev[1], 0, p);
+    else if (((uintptr_t)pr->mark_read & 15) == 0)
         hipExtLaunchKernelGGL(ef_classify<true>, dim3(blocks), dim3(kCandPerBlock), 0, stream, ev[0], ev[1], 0, p);
     else
         hipExtLaunchKernelGGL(ef_classify<false>, dim3(blocks), dim3(kCandPerBlock), 0, stream, ev[0], ev[1], 0, p);

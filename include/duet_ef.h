@@ -139,13 +139,15 @@ DUET_API int duet_ef_profile_collect(duet_ctx *ctx, duet_ef_stats *stats);
 /* Diagnostics: each bit forces a kernel path or launch structure other than the one the input would take (the outputs
  * are identical; tests use them to exercise every path), e.g. DUET_DBG_CLUSTER_EXACT sends every A0 partition through the exact linkage
  * instead of the bounding-box / threshold-graph fast paths.  0 in production.  The bit values 0x1, 0x2, 0x4,
- * 0x200000 and 0x10000000 are unused and have no effect. */
+ * and 0x10000000 are unused and have no effect. */
 #define DUET_DBG_EF_NO_SEED_HASH 0x40u   /* E/F: ef_seed_sort orders an unsorted seed list itself instead of taking its distinct values through a hash set first */
 #define DUET_DBG_EF_FIN_TPB2 0x20u       /* E/F: ef_finalize takes two tiles of 256 candidates per workgroup whatever the size (default from 1 M candidates on) */
 #define DUET_DBG_EF_FIN_TPB4 0x80u       /* ... four (default from 8 M candidates on) */
 #define DUET_DBG_EF_HEAVY_ALL 0x80000u   /* E/F: ef_classify walks EVERY kept candidate wave-cooperatively (64 marks per step; default: those with more than 32 marks) */
 #define DUET_DBG_EF_HEAVY_OFF 0x100000u  /* ... only those of more than 255 marks (the lane walk keeps its counts in bytes): every other candidate by its own lane, mark after mark */
-#define DUET_DBG_EF_FP_DECIDE 0x400000u  /* E/F: ef_classify takes every class-0 / class-1 decision through the binary64 expressions (rounds 1-4) instead of the
+#define DUET_DBG_EF_SPLIT_OFF 0x200000u  /* E/F: the two-launch path keeps ef_classify, one lane per candidate (default up to 512 tiles: ef_classify_split, two lanes
+                                            per candidate; the bits that force three launches force ef_classify with them) */
+#define DUET_DBG_EF_FP_DECIDE 0x400000u /* E/F: ef_classify takes every class-0 / class-1 decision through the binary64 expressions (rounds 1-4) instead of the
                                             integer form with the binary64 fallback */
 #define DUET_DBG_EF_OWN_OFF 0x800000u     /* E/F: three launches (ef_classify, ef_seed_sort, ef_finalize) at every size; default up to 2048 tiles of 256 candidates
                                           * and 64 contigs: two -- every finalize tile builds its contig's seed set itself (ef_finalize_own) */

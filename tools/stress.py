@@ -28,8 +28,10 @@ for i in range(n_ef):
     if rc:
         continue
     # (E/F paths in turn: default = two launches, every finalize tile with its own seed set; that with a seed set of 8 entries -- the
-    # array-free walk; three launches; ef_finalize with two / four tiles per workgroup; the seed sort without its hash set)
-    ctx.set_debug([0, 0x3000000, 0x800000, 0x20, 0x80, 0x40][i % 6])
+    # array-free walk; three launches; ef_finalize with two / four tiles per workgroup; the seed sort without its hash set; the two
+    # launches with one lane per candidate (ef_classify instead of ef_classify_split); two lanes for every candidate up to 255 marks;
+    # none, every candidate by its owner's wavefront)
+    ctx.set_debug([0, 0x3000000, 0x800000, 0x20, 0x80, 0x40, 0x200000, 0x100000, 0x80000][i % 9])
     p, s = ctx.run_host(soa, sl, sr)
     ctx.set_debug(0)
     if not (np.array_equal(p, wp) and np.array_equal(s, ws)):
