@@ -41,7 +41,8 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_tune_leaf_census_device', 'duet_tune_leaf_census_host', 'duet_tune_leaves_device', 'duet_tune_leaves_host',
            'duet_evidence_rows_device', 'duet_evidence_rows_host',
            'duet_ps_links_device', 'duet_ps_links_host', 'duet_svim_ps_links_device', 'duet_svim_ps_links_host',
-           'duet_read_tags_device', 'duet_read_tags_host', 'duet_read_tags_rows_device', 'duet_read_tags_rows_host')
+           'duet_read_tags_device', 'duet_read_tags_host', 'duet_read_tags_rows_device', 'duet_read_tags_rows_host',
+           'duet_prims_sort_host', 'duet_prims_scan_host', 'duet_prims_local_sort_host')
 
 
 class EfProblem(ctypes.Structure):
@@ -394,6 +395,12 @@ def load():
                        ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
     lib.duet_tune_cap_line_host.argtypes = lib.duet_tune_cap_line_device.argtypes[:-1]
     lib.duet_svim_cap_line_host.argtypes = lib.duet_svim_cap_line_device.argtypes[:-1]
+    lib.duet_prims_sort_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                         ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    lib.duet_prims_scan_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+    lib.duet_prims_local_sort_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
     _lib = lib
     return lib
 
@@ -1245,6 +1252,49 @@ class Context(object):
         if n < 0:
             self._raise(n)
         return out[:min(n, cap)].copy()
+
+    # -- diagnostics: the shared device primitives on host arrays (include/duet_ef.h, "Diagnostics") ---------------
+    def prims_sort(self, keys, vals=None, key_bits=64, first_shift=0, force_scan=False):
+        """duet_prims_sort_host: radix_sort_pairs over keys u64[n] (and vals u32[n]) by the key bits [first_shift, key_bits)
+        -> (sorted keys, sorted vals or None)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        out_keys = np.zeros(len(keys), dtype=np.uint64)
+        out_vals = None
+        if vals is not None:
+            vals = np.ascontiguousarray(vals, dtype=np.uint32)
+            if len(vals) != len(keys):
+                raise ValueError('prims_sort: %d keys, %d values' % (len(keys), len(vals)))
+            out_vals = np.zeros(len(vals), dtype=np.uint32)
+        rc = self.lib.duet_prims_sort_host(self.handle, _ptr(keys), _ptr(vals), len(keys), int(key_bits), int(first_shift),
+                                           1 if force_scan else 0, _ptr(out_keys), _ptr(out_vals))
+        if rc:
+            self._raise(rc)
+        return out_keys, out_vals
+
+    def prims_scan(self, values, op, n_dyn=None, force_spine=False, prefill=0xA5A5A5A5, zero14=True):
+        """duet_prims_scan_host: launch_scan over values u32[n], op 0 the exclusive sum / 1 the inclusive maximum; n_dyn: the real
+        count on the device, n being its bound.  -> (out u32[n], pre-filled with `prefill` before the scan; total; the 14 words
+        the scan zeroes, pre-filled with ones, or None)."""
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        out = np.full(len(values), prefill, dtype=np.uint32)
+        total = ctypes.c_uint32(0)
+        z = np.ones(14, dtype=np.uint32) if zero14 else None
+        rc = self.lib.duet_prims_scan_host(self.handle, _ptr(values), len(values), int(op), 0xFFFFFFFF if n_dyn is None else int(n_dyn),
+                                           1 if force_spine else 0, _ptr(out), ctypes.byref(total), _ptr(z))
+        if rc:
+            self._raise(rc)
+        return out, total.value, z
+
+    def prims_local_sort(self, keys, key_bits, lo, cap=256, threads=1024):
+        """duet_prims_local_sort_host: global passes over the key bits [lo, key_bits), rx_local<threads> and rx_big over the low
+        ones -> keys u64[n] in the stable order of their low key_bits."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.zeros(len(keys), dtype=np.uint64)
+        rc = self.lib.duet_prims_local_sort_host(self.handle, _ptr(keys), len(keys), int(key_bits), int(lo), int(cap), int(threads),
+                                                 _ptr(out))
+        if rc:
+            self._raise(rc)
+        return out
 
 
 def check_pc_cap(pc_cap):

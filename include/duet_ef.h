@@ -939,6 +939,29 @@ DUET_API int duet_read_tags_rows_host(duet_ctx *ctx, const duet_read_tag_rec *re
                                       const uint64_t *read_tag, uint32_t n_reads, char *out_text, uint64_t out_cap, uint64_t *out_len);
 
 /* ---------------------------------------------------------------------------------------------
+ * Diagnostics: the shared device primitives (duet_amd/csrc/duet_prims.hip.h) on host arrays, each run unchanged on the
+ * context's own stream with a workspace sized as the primitive's comments prescribe (duet_amd/csrc/duet_prims_check.hip).  No
+ * product path calls these; tests/test_gpu_prims.py compares them with numpy at every plan boundary.  n == 0: DUET_OK, nothing is
+ * launched.  A null array or an argument outside the primitive's documented preconditions: DUET_ERR_INVALID, nothing is launched.
+ *
+ * duet_prims_sort_host: radix_sort_pairs -- the stable sort of n keys (with vals: of n (key, value) pairs) by the key bits
+ *   [first_shift, key_bits); the bits above key_bits travel untouched.  1 <= key_bits <= 64, first_shift < key_bits; vals and
+ *   out_vals are both given or both null; force_scan != 0: the tile offsets by the generic scan, as above 1024 tiles.
+ * duet_prims_scan_host: launch_scan<op> over in[n] -- op 0 the exclusive sum (mod 2^32), op 1 the inclusive maximum; n_dyn: the
+ *   real element count on the device, n being its bound (UINT32_MAX: none is passed); force_spine != 0: the path with a spine
+ *   launch.  out[n] is uploaded before the scan and downloaded after it, so the caller sees what was left untouched; *total: the
+ *   combination of every element; zero14 (may be null): 14 words uploaded before the scan, which zeroes them, and downloaded.
+ * duet_prims_local_sort_host: the hybrid sort of the key-only clustering path -- global passes over the bits [lo, key_bits), then
+ *   rx_local<threads> and rx_big over the low bits, groups of more than cap keys going to rx_big; the result is the stable sort
+ *   by the bits [0, key_bits).  1 <= key_bits <= 64, 1 <= lo < 32, lo < key_bits, 1 <= cap <= 256, threads 256 or 1024. */
+DUET_API int duet_prims_sort_host(duet_ctx *ctx, const uint64_t *keys, const uint32_t *vals, uint32_t n, uint32_t key_bits,
+                                  uint32_t first_shift, int force_scan, uint64_t *out_keys, uint32_t *out_vals);
+DUET_API int duet_prims_scan_host(duet_ctx *ctx, const uint32_t *in, uint32_t n, int op, uint32_t n_dyn, int force_spine,
+                                  uint32_t *out, uint32_t *total, uint32_t *zero14);
+DUET_API int duet_prims_local_sort_host(duet_ctx *ctx, const uint64_t *keys, uint32_t n, uint32_t key_bits, uint32_t lo, uint32_t cap,
+                                        uint32_t threads, uint64_t *out_keys);
+
+/* ---------------------------------------------------------------------------------------------
  * The collective of the contig-sharded path: candidates shard by contig over the GPUs of one node,
  * one process and one context per GPU, and ONE all-gather of fixed-size record blocks reassembles the call set
  * (src/duet/sv_phasing_fn.py:15-18, 195-210: nothing crosses contigs before the final sort at :229).  RCCL over xGMI,
