@@ -20,36 +20,40 @@ def ctx():
     c.close()
 
 
-def check(ctx, marks, **kw):
+# hints on/off (sort key width), fast paths on/off (DUET_DBG_CLUSTER_EXACT = 0x100: everything through the exact linkage)
+# ... the launch structure of large inputs (DUET_DBG_CLUSTER_LARGE = 0x200), the pair sort (DUET_DBG_CLUSTER_PAIRS = 0x400),
+# no bounding-box test (DUET_DBG_CLUSTER_NOBOX = 0x800: every partition through the threshold-graph pair loops);
+# DUET_DBG_CLUSTER_KC2 = 0x1000: partitions with more than two groups left take the second tier;
+# DUET_DBG_CLUSTER_TIERS = 0x2000: the two tiers in their fused (small-input) launches; DUET_DBG_CLUSTER_SMALLCAP = 0x4000 /
+# DUET_DBG_CLUSTER_LSD = 0x8000: where the low bits are sorted locally, groups of more than 3 keys through the
+# one-workgroup-per-group path / plain LSD passes instead
+# DUET_DBG_CLUSTER_KEYSORT = 0x10000: the key-only sort of rounds 1-3 (+ the gather through the permutation) where the
+# default now carries the 16-byte record with the key; DUET_DBG_CLUSTER_NOSYM = 0x20000: the pair tests of one-partition units column
+# by column (every ordered pair) instead of every unordered pair once; DUET_DBG_CLUSTER_RECSORT = 0x40000: the record sort also
+# below 1.25 M marks (the default there is the key-only sort; DUET_DBG_CLUSTER_LARGE implies it)
+MODES = ((True, 0), (False, 0), (True, 0x100), (True, 0x200), (True, 0x400), (False, 0x600), (True, 0x800),
+         (True, 0xA00), (True, 0x300), (True, 0x1000), (True, 0x1800), (False, 0x1A00), (True, 0x2000), (True, 0x3800), (True, 0x4000), (False, 0x8000),
+         (True, 0x10000), (False, 0x10200), (True, 0x14000), (False, 0x4200), (True, 0x10800),
+         (True, 0x20000), (False, 0x20200), (True, 0x21200),
+         (True, 0x40000), (False, 0x40000), (True, 0x40100), (True, 0x40800), (True, 0x44000), (True, 0x41000), (True, 0x42000), (True, 0x60000),
+         # DUET_DBG_CLUSTER_EVENT_FORKS = 0x4000000 (round 6): the side streams behind events instead of signal / gate kernels
+         (True, 0x4000000), (False, 0x4040000), (True, 0x4002000),
+         # DUET_DBG_CLUSTER_WIDE_OFF = 0x8000000: small inputs keep one wavefront per partition of more than 64 marks (the default
+         # since round 6: eight, cl_wide_big)
+         (True, 0x8000000), (False, 0x8000800), (True, 0x8000100), (True, 0xC000000))
+
+
+def check(ctx, marks, modes=MODES, **kw):
+    """every (hints, debug word) combination of `modes` against the oracle, field for field; -> the oracle's result"""
     want = c_oracle.cluster(marks['contig'], marks['type'], marks['pos'], marks['span'], **kw)
-    # hints on/off (sort key width), fast paths on/off (DUET_DBG_CLUSTER_EXACT = 0x100: everything through the exact linkage)
-    # ... the launch structure of large inputs (DUET_DBG_CLUSTER_LARGE = 0x200), the pair sort (DUET_DBG_CLUSTER_PAIRS = 0x400),
-    # no bounding-box test (DUET_DBG_CLUSTER_NOBOX = 0x800: every partition through the threshold-graph pair loops);
-    # DUET_DBG_CLUSTER_KC2 = 0x1000: partitions with more than two groups left take the second tier;
-    # DUET_DBG_CLUSTER_TIERS = 0x2000: the two tiers in their fused (small-input) launches; DUET_DBG_CLUSTER_SMALLCAP = 0x4000 /
-    # DUET_DBG_CLUSTER_LSD = 0x8000: where the low bits are sorted locally, groups of more than 3 keys through the
-    # one-workgroup-per-group path / plain LSD passes instead
-    # DUET_DBG_CLUSTER_KEYSORT = 0x10000: the key-only sort of rounds 1-3 (+ the gather through the permutation) where the
-    # default now carries the 16-byte record with the key; DUET_DBG_CLUSTER_NOSYM = 0x20000: the pair tests of one-partition units column
-    # by column (every ordered pair) instead of every unordered pair once; DUET_DBG_CLUSTER_RECSORT = 0x40000: the record sort also
-    # below 1.25 M marks (the default there is the key-only sort; DUET_DBG_CLUSTER_LARGE implies it)
-    for hints, dbg in ((True, 0), (False, 0), (True, 0x100), (True, 0x200), (True, 0x400), (False, 0x600), (True, 0x800),
-                       (True, 0xA00), (True, 0x300), (True, 0x1000), (True, 0x1800), (False, 0x1A00), (True, 0x2000), (True, 0x3800), (True, 0x4000), (False, 0x8000),
-                       (True, 0x10000), (False, 0x10200), (True, 0x14000), (False, 0x4200), (True, 0x10800),
-                       (True, 0x20000), (False, 0x20200), (True, 0x21200),
-                       (True, 0x40000), (False, 0x40000), (True, 0x40100), (True, 0x40800), (True, 0x44000), (True, 0x41000), (True, 0x42000), (True, 0x60000),
-                       # DUET_DBG_CLUSTER_EVENT_FORKS = 0x4000000 (round 6): the side streams behind events instead of signal / gate kernels
-                       (True, 0x4000000), (False, 0x4040000), (True, 0x4002000),
-                       # DUET_DBG_CLUSTER_WIDE_OFF = 0x8000000: small inputs keep one wavefront per partition of more than 64 marks (the default
-                       # since round 6: eight, cl_wide_big)
-                       (True, 0x8000000), (False, 0x8000800), (True, 0x8000100), (True, 0xC000000)):
+    for hints, dbg in modes:
         ctx.set_debug(dbg)
         try:
             got = ctx.cluster_host(marks['contig'], marks['type'], marks['pos'], marks['span'], hints=hints, **kw)
         finally:
             ctx.set_debug(0)
         for f in FIELDS:
-            assert got[f].shape == want[f].shape, (f, got[f].shape, want[f].shape)
+            assert got[f].shape == want[f].shape, (f, hex(dbg), hints, got[f].shape, want[f].shape)
             bad = np.nonzero(got[f] != want[f])[0]
             assert bad.size == 0, (f, dbg, bad[:5], got[f][bad[:5]], want[f][bad[:5]])
     return want
@@ -248,8 +252,10 @@ def test_between_two_and_four_million_marks(ctx):
 def test_wide_keys_few_marks(ctx, M):
     """Positions next to 2^32 with contig ids next to 65535 and many types: 33 + 16 + 8 = 57 key bits.  With few marks the
     index still fits the key's spare bits, and the local ordering of the low bits (32-bit words) must not be offered more
-    than 31 of them: such keys take more global passes (round-3 advisor finding); contig + type + index do not fit one record
-    word either, so this is the key-only sort."""
+    than 31 of them: such keys take more global passes (round-3 advisor finding).  At M = 5000 and 70000 contig + type + index do
+    not fit one record word (16 + 8 + 13 bits and more), so every combination takes the key-only sort; at M = 3 and M = 200 they
+    do (16 + 8 + 2 and 16 + 8 + 8 <= 32), and the combinations with DUET_DBG_CLUSTER_RECSORT or DUET_DBG_CLUSTER_LARGE take the
+    record sort."""
     rng = synth.SplitMix(9100 + M)
     pos = (0xFFFFFFFF - 3000000 + rng.between(M, 0, 40) * 70000 + rng.between(M, 0, 900)).astype(np.uint32)
     span = rng.between(M, 30, 3000).astype(np.uint32)
