@@ -42,6 +42,7 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_evidence_rows_device', 'duet_evidence_rows_host',
            'duet_ps_links_device', 'duet_ps_links_host', 'duet_svim_ps_links_device', 'duet_svim_ps_links_host',
            'duet_read_tags_device', 'duet_read_tags_host', 'duet_read_tags_rows_device', 'duet_read_tags_rows_host',
+           'duet_ps_join_tags_device', 'duet_ps_join_tags_host', 'duet_ps_join_diff_device', 'duet_ps_join_diff_host',
            'duet_prims_sort_host', 'duet_prims_scan_host', 'duet_prims_local_sort_host')
 
 
@@ -227,6 +228,11 @@ def read_tags_bound(n_recs, name_off, chrom_texts):
     return int(n_recs) * (chrom + longest + READ_TAG_ROW_MAX)
 
 
+# joined phase sets (include/duet_ef.h, "Joined phase sets"; duet_amd/ps_join.py): the table's rows, the change codes
+PS_BLOCK_DTYPE = np.dtype([(n, '<u4') for n in ('contig', 'ps', 'block', 'flip')])      # duet_ps_block (16 bytes)
+JOIN_CHANGE_NAMES = ('none', 'gained', 'lost', 'same', 'relabelled', 'to_het', 'to_hom', 'other')   # DUET_PS_JOIN_NONE .. _OTHER
+
+
 class TuneTruth(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ('n_uid', 'n_groups', 'n_pairs', 'reserved')] + \
                [(n, ctypes.c_void_p) for n in ('cand_flags', 'cand_group', 'cand_uid', 'cand_pair', 'group_pair_off', 'pair_uid')]
@@ -380,6 +386,14 @@ def load():
                                                ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
                                                ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
     lib.duet_read_tags_rows_host.argtypes = lib.duet_read_tags_rows_device.argtypes[:-1]
+    lib.duet_ps_join_tags_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+                                             ctypes.c_void_p]
+    lib.duet_ps_join_tags_host.argtypes = lib.duet_ps_join_tags_device.argtypes[:-1]
+    lib.duet_ps_join_diff_device.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6 + \
+                                            [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p]
+    lib.duet_ps_join_diff_host.argtypes = lib.duet_ps_join_diff_device.argtypes[:-1]
     lib.duet_tune_line_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
@@ -1117,6 +1131,75 @@ class Context(object):
         if rc:
             self._raise(rc)
         return n.value
+
+    # -- joined phase sets (duet_psjoin.hip) -------------------------------------------------------------------------------------
+    @staticmethod
+    def _ps_blocks(blocks):
+        return np.ascontiguousarray(blocks, dtype=PS_BLOCK_DTYPE)
+
+    def ps_join_tags_host(self, read_tag, read_off, blocks, out=None):
+        """duet_ps_join_tags_host: the read tags (uint64) under the table `blocks` (PS_BLOCK_DTYPE; duet_amd/ps_join.py: table);
+        read_off: the reads of contig k are read_off[k] .. read_off[k + 1].  out: the array written (None: a new one; read_tag itself
+        is allowed) -> (out, n_changed)"""
+        read_tag = np.ascontiguousarray(read_tag, dtype=np.uint64)
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint32)
+        blocks = self._ps_blocks(blocks)
+        if out is None:
+            out = np.zeros(len(read_tag), dtype=np.uint64)
+        n = ctypes.c_uint32(0)
+        rc = self.lib.duet_ps_join_tags_host(self.handle, _ptr(read_tag), _ptr(read_off), max(len(read_off), 1) - 1, len(read_tag),
+                                             _ptr(blocks), len(blocks), _ptr(out), ctypes.byref(n))
+        if rc:
+            self._raise(rc)
+        return out, n.value
+
+    def ps_join_tags_device(self, read_tag_ptr, read_off, n_reads, blocks, out_ptr, stream=0):
+        """duet_ps_join_tags_device on resident tag words (read_off and blocks host arrays); out_ptr may be read_tag_ptr
+        -> n_changed"""
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint32)
+        blocks = self._ps_blocks(blocks)
+        n = ctypes.c_uint32(0)
+        rc = self.lib.duet_ps_join_tags_device(self.handle, ctypes.c_void_p(read_tag_ptr), _ptr(read_off), max(len(read_off), 1) - 1,
+                                               int(n_reads), _ptr(blocks), len(blocks), ctypes.c_void_p(out_ptr), ctypes.byref(n),
+                                               ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return n.value
+
+    def ps_join_diff_host(self, pred0, ps0, pred1, ps1, blocks, n_contigs, cand_ctg_off=None, cand_contig=None):
+        """duet_ps_join_diff_host: the change code of every candidate between the calls (pred0, ps0) and (pred1, ps1) under the
+        table `blocks`.  Exactly one of cand_ctg_off / cand_contig names the candidates' contigs -> (change u8[C], counts u32[8])"""
+        conv = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)
+        pred0, pred1, ps0, ps1 = conv(pred0, np.uint8), conv(pred1, np.uint8), conv(ps0, np.uint32), conv(ps1, np.uint32)
+        off, col = conv(cand_ctg_off, np.uint32), conv(cand_contig, np.uint16)
+        blocks = self._ps_blocks(blocks)
+        C = len(pred0)
+        change, counts = np.zeros(C, dtype=np.uint8), np.zeros(8, dtype=np.uint32)
+        spare = np.zeros(1, dtype=np.uint64)
+        # (an empty column still has an address: which contig form is meant must not depend on the candidate count)
+        ptr = lambda a: None if a is None else a.ctypes.data if a.size else spare.ctypes.data
+        rc = self.lib.duet_ps_join_diff_host(self.handle, C, ptr(pred0), ptr(ps0), ptr(pred1), ptr(ps1), ptr(off), ptr(col), int(n_contigs),
+                                             _ptr(blocks), len(blocks), ptr(change), counts.ctypes.data)
+        if rc:
+            self._raise(rc)
+        return change, counts
+
+    def ps_join_diff_device(self, n_cands, pred0_ptr, ps0_ptr, pred1_ptr, ps1_ptr, blocks, n_contigs, change_ptr, cand_ctg_off=None,
+                            cand_contig_ptr=None, stream=0):
+        """duet_ps_join_diff_device on resident calls; cand_ctg_off a host array, or cand_contig_ptr the resident uint16 column;
+        change_ptr: device room for n_cands bytes -> counts u32[8]"""
+        off = None if cand_ctg_off is None else np.ascontiguousarray(cand_ctg_off, dtype=np.uint32)
+        blocks = self._ps_blocks(blocks)
+        counts = np.zeros(8, dtype=np.uint32)
+        rc = self.lib.duet_ps_join_diff_device(self.handle, int(n_cands), ctypes.c_void_p(pred0_ptr), ctypes.c_void_p(ps0_ptr),
+                                               ctypes.c_void_p(pred1_ptr), ctypes.c_void_p(ps1_ptr),
+                                               None if off is None else off.ctypes.data,
+                                               None if cand_contig_ptr is None else ctypes.c_void_p(cand_contig_ptr), int(n_contigs),
+                                               _ptr(blocks), len(blocks), ctypes.c_void_p(change_ptr), counts.ctypes.data,
+                                               ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return counts
 
     def strata_build_device(self, prob, truth, chrom_stratum_ptr, n_strata, cand_stratum_ptr, group_stratum_ptr, stream=0):
         """duet_tune_strata_build_device on resident arrays (devmem.DeviceTune), after truth_build_device on the same prob / truth."""

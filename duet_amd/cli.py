@@ -22,6 +22,9 @@ def pipeline(a):
     extra = {'ps_links': True} if getattr(a, 'write_ps_links', False) else {}
     if getattr(a, 'write_read_tags', False):
         extra['read_tags'] = True                           # (--write_read_tags: a keyword too)
+    if getattr(a, 'join_ps', False):
+        extra['join_ps'] = True                             # (--join_ps [--join_min_sv N]: two keywords)
+        extra['join_min_sv'] = 2 if getattr(a, 'join_min_sv', None) is None else a.join_min_sv
     if a.sv_caller == 'svim-gpu':
         from duet_amd.svim_mode import sv_phasing_from_bams
         last = (lambda *args: sv_phasing_from_bams(*args, **extra)) if extra else sv_phasing_from_bams
@@ -82,6 +85,15 @@ def main(argv):
         # decision keeps whatever route the other flags give it)
         if a.gpus > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
             raise SystemExit('duet: --write_read_tags works on the single-GPU path only (not with --gpus > 1)')
+    if a.join_min_sv is not None and not a.join_ps:
+        raise SystemExit('duet: --join_min_sv needs --join_ps')
+    if a.join_ps:
+        # (additive: the second run over the joined phase sets, OUTPUT/phased_sv.joined.vcf with its two tables -- built from the
+        # problem one GPU holds; both runs keep whatever route the other flags give the decision)
+        if a.gpus > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise SystemExit('duet: --join_ps works on the single-GPU path only (not with --gpus > 1)')
+        if a.join_min_sv is not None and a.join_min_sv < 1:
+            raise SystemExit('duet: --join_min_sv takes an integer >= 1')
     check_envs(a.REFERENCE, a.BAM)
     os.makedirs(a.OUTPUT, exist_ok=True)
     set_logging(a.OUTPUT)

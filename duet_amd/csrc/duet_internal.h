@@ -94,7 +94,8 @@ struct duet_ctx {
     DuetOwnedBufs pslinks_ws;              // phase-set links (duet_pslinks.hip): per-candidate workspace 0, per-voter workspace 1; host-run staging of the records 2
     DuetOwnedBufs readtags_ws;             // read tags (duet_readtags.hip): per-candidate workspace 0, per-mark workspace 1, the records before they are released 2; host-run staging 3-11
     DuetOwnedBufs readtags_rows_ws;        // ... its rows: row lengths 0, row offsets 1, tile sums 2, status words and CHROM texts 3; host-run staging 4-7, text 8
-    DuetOwnedBufs prims_ws;                // diagnostics of the shared primitives (duet_prims_check.hip): one arena, 0
+    DuetOwnedBufs psjoin_ws;               // joined phase sets (duet_psjoin.hip): the header words, the offsets and the staged table 0, the change codes before they are released 1; host-run staging of the read tags 2, of pred0, ps0, pred1, ps1, cand_contig 3-7
+    DuetOwnedBufs prims_ws;               // diagnostics of the shared primitives (duet_prims_check.hip): one arena, 0
 };
 
 extern thread_local std::string duet_g_last_error;

@@ -308,9 +308,53 @@ class DeviceSvim(DeviceCluster):
         n = ctx.svim_vcf_rows_device(self.sv_problem, self.result, N, nm, out.data_ptr(), cap, stream)
         return out[:n].cpu().numpy()
 
-    def phased_rows(self, ctx, chrom_texts, stream=None):
+    def run_joined(self, ctx, blocks, read_off, thresholds=None, pc_cap=None, stream=None):
+        """The last run again over joined phase sets (--join_ps): the read tags remapped under the table `blocks`
+        (_lib.PS_BLOCK_DTYPE; duet_ps_join_tags_device) into a second tensor, the fused pipeline -- run_fused, or with thresholds /
+        pc_cap run_thresholds -- on it, and the change code of every candidate between the two runs (duet_ps_join_diff_device).
+        read_off: the reads of contig k are read_off[k] .. read_off[k + 1].  The object keeps the first run's (pred, ps), features and
+        tags; clustering reads no tag, so the cluster result comes out byte for byte what it was (checked) and the candidates line up.
+        Raises ZeroDivisionError where the joined run does.
+        -> dict(pred, ps: device tensors of the joined run, change u8[N], counts u32[8], n_changed)."""
+        torch = self.torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.n_found is None:
+            self.n_found = self.n_cands()
+        N = self.n_found
+        if thresholds is None and pc_cap is not None:
+            thresholds = _lib.TUNE_DEFAULTS
+        tags = torch.empty_like(self.keep['sv_tag'])
+        n_changed = ctx.ps_join_tags_device(self.keep['sv_tag'].data_ptr(), read_off, self.sv_problem.n_reads, blocks, tags.data_ptr(),
+                                            stream)
+        names = ('order', 'cand_off', 'cand_contig', 'cand_type', 'cand_pos', 'cand_span', 'n_cands')
+        before = [self.keep['out_' + k].clone() for k in names]
+        mine = (self.out_pred, self.out_ps, self.feat, self.vector)
+        self.out_pred, self.out_ps = torch.zeros_like(self.out_pred), torch.zeros_like(self.out_ps)
+        self.sv_problem.read_tag = tags.data_ptr()
+        try:
+            if thresholds is not None:
+                self.run_thresholds(ctx, thresholds, stream, pc_cap=pc_cap)
+            else:
+                self.run_fused(ctx, stream)
+                ctx.check(stream)
+            pred, ps = self.out_pred, self.out_ps
+        finally:
+            self.sv_problem.read_tag = self.keep['sv_tag'].data_ptr()
+            self.out_pred, self.out_ps, self.feat, self.vector = mine
+        if self.n_found != N or not all(torch.equal(a, self.keep['out_' + k]) for a, k in zip(before, names)):
+            raise RuntimeError('run_joined: the cluster result changed between the two runs')
+        change = torch.zeros(N + 64, dtype=torch.uint8, device=self.device)
+        counts = ctx.ps_join_diff_device(N, self.out_pred.data_ptr(), self.out_ps.data_ptr(), pred.data_ptr(), ps.data_ptr(), blocks,
+                                         self.sv_problem.n_contigs, change.data_ptr(), cand_contig_ptr=self.result.cand_contig,
+                                         stream=stream)
+        torch.cuda.current_stream(self.device).synchronize()
+        return dict(pred=pred, ps=ps, change=change[:N].cpu().numpy(), counts=counts, n_changed=n_changed)
+
+    def phased_rows(self, ctx, chrom_texts, stream=None, pred=None, ps=None):
         """Rows of phased_sv.vcf for the last run_fused's candidates, sorted and formatted on the device from the resident
-        cluster result and (pred, ps) (duet_svim_phased_rows_device).  chrom_texts: CHROM text per contig.
+        cluster result and (pred, ps) (duet_svim_phased_rows_device).  chrom_texts: CHROM text per contig.  pred, ps: device
+        tensors of another run's calls over the same candidates (run_joined; default: the object's own).
         -> (uint8 numpy array of the text, number of rows)."""
         torch = self.torch
         if stream is None:
@@ -322,8 +366,8 @@ class DeviceSvim(DeviceCluster):
             return np.zeros(0, dtype=np.uint8), 0
         cap = _lib.phased_rows_bound(N, chrom_texts)
         out = torch.empty(cap, dtype=torch.uint8, device=self.device)
-        n, n_rows = ctx.svim_phased_rows_device(self.result, N, self.out_pred.data_ptr(), self.out_ps.data_ptr(), chrom_texts,
-                                                out.data_ptr(), cap, stream)
+        pred, ps = self.out_pred if pred is None else pred, self.out_ps if ps is None else ps
+        n, n_rows = ctx.svim_phased_rows_device(self.result, N, pred.data_ptr(), ps.data_ptr(), chrom_texts, out.data_ptr(), cap, stream)
         return out[:n].cpu().numpy(), n_rows
 
     def fetch(self):

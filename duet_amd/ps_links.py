@@ -50,8 +50,9 @@ def rows_text(records, chrom_texts):
     return ''.join(out)
 
 
-def blocks(records):
-    """A maximum spanning forest per contig over the links whose verdict is not '.': the links are taken in the order
+def blocks(records, min_sv=1):
+    """A maximum spanning forest per contig over the links whose verdict is not '.' and whose winning side counts at least min_sv
+    candidates (1: every verdict link; the other links still name their phase sets): the links are taken in the order
     (-n_win, -w_win, row index), win being the verdict's side; a link joins two components or agrees with the sense they already
     imply; one that contradicts it is not applied.
     -> (rows, conflicts): rows = one (contig, ps, block, flip) per phase set that occurs in any link, ascending by (contig, ps),
@@ -63,6 +64,8 @@ def blocks(records):
         if v == '.':
             continue
         side = 'same' if v == 'same' else 'flip'
+        if int(r['n_' + side]) < min_sv:
+            continue
         order.append((-int(r['n_' + side]), -int(r['w_' + side]), i, 0 if v == 'same' else 1))
     order.sort()
     parent, parity = {}, {}                     # union-find: parity[x] = sense of x relative to parent[x]

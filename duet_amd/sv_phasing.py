@@ -10,7 +10,10 @@ fields ...) and the Python path then takes over, so the observable behaviour is 
 Set DUET_NATIVE_INGEST=0 to force the Python path; DUET_DEVICE_ROWS=0 keeps the native path but formats the rows on
 the host instead of on the device.
 
-Seven additive keyword arguments (upstream's five positionals are unchanged): `read_tags` = also write
+Nine additive keyword arguments (upstream's five positionals are unchanged): `join_ps`, `join_min_sv` = also phase the SVs again
+over the phase sets that the links of at least join_min_sv candidates tie into one block, into <home>/phased_sv.joined.vcf, with
+<home>/phased_sv.join_blocks.tsv and <home>/phased_sv.join_report.tsv (duet_amd/ps_join.py; single-GPU native path, by the route
+the other keywords give the decision), `read_tags` = also write
 <home>/phased_sv.read_tags.tsv, the haplotype the heterozygous calls place each of their supporting reads on, per read and phase
 set (duet_amd/read_tags.py; single-GPU native path, with or without `thresholds`; under `pc_cap` a read's own tag is usable under
 that cap), `ps_links` = also write
@@ -124,9 +127,47 @@ def write_read_tags(home, tags):
     logging.info('  ' + read_tags.summary_text(tags[0]))
 
 
-def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, ps_links=False, read_tags=False):
+def native_join(home, ing, chrom_list, include_all_ctgs, svlen_thres, suppread_thres, ctx, min_sv, run, pc_cap=None):
+    """--join_ps on the ingest's problem, while the ingest is still open and after phased_sv.vcf has been written in full: the
+    links' blocks (duet_amd/ps_links.py: blocks, min_sv), the read tags under them (duet_ps_join_tags_host), `run` -- soa ->
+    (pred, ps), the route the first run took -- on both tag tables, the change codes (duet_ps_join_diff_host), the three files.
+    phased_sv.joined.vcf is created with its header before the joined run: a ZeroDivisionError there leaves it header-only, with no
+    report beside it."""
+    from duet_amd import ps_join, ps_links as links_mod
+    import numpy as np
+    soa = ing.soa
+    texts = contig_texts(ing, chrom_list, '--join_ps')
+    logging.info('phase the SVs again over the joined phase sets (--join_ps, links of at least %d SVs)' % min_sv)
+    with open(ps_join.path_vcf(home), 'wb') as out:
+        out.write(ing.header(include_all_ctgs))
+    records = ctx.ps_links_host(soa, svlen_thres, suppread_thres, pc_cap=pc_cap) if soa.n_cands else links_mod.empty()
+    rows, _ = links_mod.blocks(records, min_sv=min_sv)
+    ps_join.write_blocks(home, rows, texts)
+    table = ps_join.table(rows)
+    body, report, n_changed = b'', '', 0
+    counts = np.zeros(8, dtype=np.uint32)
+    if soa.n_cands:
+        pred0, ps0 = run(soa)
+        tags, n_changed = ctx.ps_join_tags_host(soa.read_tag, soa.read_off, table)
+        kw = {name: getattr(soa, name) for name, _ in engine.EfSoA.FIELDS}
+        kw['read_tag'] = tags
+        pred1, ps1 = run(engine.EfSoA(read_off=soa.read_off, **kw))
+        change, counts = ctx.ps_join_diff_host(pred0, ps0, pred1, ps1, table, soa.n_contigs, cand_ctg_off=soa.cand_ctg_off)
+        body = ing.emit_rows(pred1, ps1)
+        contig = np.repeat(np.arange(soa.n_contigs), np.diff(soa.cand_ctg_off.astype(np.int64)))
+        report = ps_join.report_text(texts, contig, soa.cand_pos, soa.cand_svlen, change, pred0, ps0, pred1, ps1)
+    with open(ps_join.path_vcf(home), 'ab') as out:
+        out.write(body)
+    ps_join.write_report(home, report)
+    logging.info('  ' + ps_join.summary_text(counts, n_changed, len(rows)))
+
+
+def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, ps_links=False, read_tags=False,
+            join_min_sv=None):
     ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf, names=read_tags)
     if ing is None:
+        if join_min_sv is not None:
+            raise RuntimeError('--join_ps needs the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
         if read_tags:
             raise RuntimeError('--write_read_tags needs the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
         if ps_links:
@@ -138,6 +179,8 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
             contig_texts(ing, chrom_list)           # (before the output file is created: a refusal leaves nothing behind)
         if read_tags:
             contig_texts(ing, chrom_list, '--write_read_tags')
+        if join_min_sv is not None:
+            contig_texts(ing, chrom_list, '--join_ps')
         write_header(ing, include_all_ctgs, out_vcf)
         log_ingest(ing, chrom_list)
         logging.info('integrate read weight information')
@@ -158,6 +201,13 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
             pred, ps = engine.run_ef(ing.soa, svlen_thres, suppread_thres, ctx=ctx) if ing.soa.n_cands else ((), ())
             tags = native_read_tags(ing, chrom_list, pred, ps, ctx)
         logging.info('write phased callset into .vcf file')
+        if join_min_sv is not None:
+            # (phased_sv.vcf first and in full: whatever the joined run does, it is what it is without the flag)
+            with open(out_vcf, 'ab') as out:
+                out.write(body)
+            body = b''
+            native_join(home, ing, chrom_list, include_all_ctgs, svlen_thres, suppread_thres, ctx, join_min_sv,
+                        lambda soa: engine.run_ef(soa, svlen_thres, suppread_thres, ctx=ctx))
     except BaseException:
         ing.close()
         raise
@@ -176,18 +226,20 @@ def evidence_path(home):
 
 
 def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, vec, pc_cap=None,
-                       evidence=False, ps_links=False, read_tags=False):
+                       evidence=False, ps_links=False, read_tags=False, join_min_sv=None):
     """The native path with the decision's constants taken from `vec` (duet_amd/tune.py): ingest, the feature export (pc_cap:
     under that PC cap, duet_ef_features_cap_host), a sweep of one vector that keeps its (pred, ps), the rows.
     evidence: also <home>/phased_sv.evidence.tsv, one row per candidate formatted on the device (duet_evidence_rows_host, the text
     form over the ingest's string pool).  ps_links: also the two phase-set link tables, the voters under the same PC cap.
-    read_tags: also <home>/phased_sv.read_tags.tsv from this route's (pred, ps), a read's own tag usable under the same PC cap."""
+    read_tags: also <home>/phased_sv.read_tags.tsv from this route's (pred, ps), a read's own tag usable under the same PC cap.
+    join_min_sv (not None: --join_ps): also the run over the joined phase sets, by this route again (native_join)."""
     from duet_amd import _lib, tune
     ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf, names=read_tags)
     if ing is None:
         raise RuntimeError('--thresholds / --pc_cap / --write_evidence%s need the native ingest, which declined this input '
                            '(or DUET_NATIVE_INGEST=0)' % ((' / --write_ps_links' if ps_links else '') +
-                                                          (' / --write_read_tags' if read_tags else '')))
+                                                          (' / --write_read_tags' if read_tags else '') +
+                                                          (' / --join_ps' if join_min_sv is not None else '')))
     table, links, tags = None, None, None
     try:
         rows = None
@@ -195,6 +247,8 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
             contig_texts(ing, chrom_list)           # (before the output file is created: a refusal leaves nothing behind)
         if read_tags:
             contig_texts(ing, chrom_list, '--write_read_tags')
+        if join_min_sv is not None:
+            contig_texts(ing, chrom_list, '--join_ps')
         if evidence and ing.soa.n_cands:
             rows = ing.rows()                       # (before the output file is created: a refusal leaves nothing behind)
             if rows is None:
@@ -223,6 +277,14 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
             tags = native_read_tags(ing, chrom_list, pred, ps, ctx, pc_cap=pc_cap) if ing.soa.n_cands else \
                 native_read_tags(ing, chrom_list, (), (), ctx)
         logging.info('write phased callset into .vcf file')
+        if join_min_sv is not None:
+            # (phased_sv.vcf first and in full: whatever the joined run does, it is what it is without the flag)
+            with open(out_vcf, 'ab') as out:
+                out.write(body)
+            body = b''
+            native_join(home, ing, chrom_list, include_all_ctgs, svlen_thres, suppread_thres, ctx, join_min_sv,
+                        lambda soa: tune.apply(dict(feat=ctx.features_host(soa, svlen_thres, suppread_thres, pc_cap=pc_cap)), vec,
+                                               ctx=ctx), pc_cap=pc_cap)
     finally:
         ing.close()
     with open(out_vcf, 'ab') as out:
@@ -239,7 +301,15 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
 
 
 def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, device=0, gpus=1, thresholds=None, pc_cap=None,
-               evidence=False, ps_links=False, read_tags=False):
+               evidence=False, ps_links=False, read_tags=False, join_ps=False, join_min_sv=2):
+    if join_ps:
+        # (additive: the run over the joined phase sets -- the native single-GPU path, whichever route the decision takes)
+        from duet_amd import ps_join
+        if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise ValueError('join_ps: single-GPU path only')
+        join_min_sv = ps_join.check_min_sv(join_min_sv)
+    else:
+        join_min_sv = None
     if read_tags and (int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1'):
         # (additive: the read tags -- the native single-GPU path, whichever route the decision takes)
         raise ValueError('read_tags: single-GPU path only')
@@ -273,7 +343,7 @@ def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, devi
             raise ValueError('thresholds: single-GPU path only')
         _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf,
                            engine.default_context(int(device)), thresholds, pc_cap, evidence=bool(evidence), ps_links=bool(ps_links),
-                           read_tags=bool(read_tags))
+                           read_tags=bool(read_tags), join_min_sv=join_min_sv)
         done = True
     # (DUET_FORCE_RANKS=1: the one-process-per-GPU path even with one GPU -- rank 0 of 1 over RCCL; tests use it to take the
     # collective through the real backend on a one-GPU box)
@@ -283,7 +353,7 @@ def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, devi
     if not done:
         ctx = engine.default_context(int(device))
         if not _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, ps_links=bool(ps_links),
-                       read_tags=bool(read_tags)):
+                       read_tags=bool(read_tags), join_min_sv=join_min_sv):
             print_sv_header(caller_vcf, out_vcf, include_all_ctgs)
             rows = generate_phased_callset(caller_vcf, home + '/snp_phasing/', svlen_thres, suppread_thres, thread,
                                            include_all_ctgs, ctx=ctx)

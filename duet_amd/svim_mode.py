@@ -18,7 +18,7 @@ from duet_amd.read_file import init_chrom_list
 
 
 def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_cap=None, evidence_texts=None, ps_links=False,
-                   read_tag_texts=None):
+                   read_tag_texts=None, join_min_sv=None):
     """-> compute(extracted arrays, svlen_thres, suppread_thres, max_dist, depth_bin) -> dict of result arrays, on ctx's GPU:
     stage A0 -> adapter -> step E/F in one device pipeline (duet_svim_phase_device).  chrom_texts (CHROM text per contig): the
     extracted arrays carry the marks' read names, and the result also holds `calls`, the rows of sv_calling/variants.vcf formatted
@@ -30,9 +30,14 @@ def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_ca
     also holds `evidence`, the data rows of the evidence table, one per candidate (duet_evidence_rows_device).  ps_links: the result
     also holds `ps_links`, the phase-set link records of the candidates (duet_svim_ps_links_device; the voters under pc_cap).
     read_tag_texts (CHROM text per contig; the extracted arrays carry the marks' read names): the result also holds `read_tags`,
-    (records, rows) of the read tags of the calls just made (duet_read_tags_device and its rows; a tag usable under pc_cap)."""
+    (records, rows) of the read tags of the calls just made (duet_read_tags_device and its rows; a tag usable under pc_cap).
+    join_min_sv (--join_ps; needs row_texts): the result also holds `join`, the run over the phase sets that the links of at least
+    that many candidates join (DeviceSvim.run_joined): dict(blocks, pred, ps, change, counts, n_changed, rows, n_rows), or
+    dict(blocks, error) when the joined run raised ZeroDivisionError."""
     if evidence_texts is not None and thresholds is None:
         raise ValueError('the evidence table needs a threshold vector')
+    if join_min_sv is not None and row_texts is None:
+        raise ValueError('the joined run needs the CHROM texts of its rows')
 
     def compute(got, svlen_thres, suppread_thres, max_dist, depth_bin):
         from duet_amd.devmem import DeviceSvim
@@ -54,8 +59,22 @@ def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_ca
             res['evidence'] = ds.evidence_rows(ctx, evidence_texts)
         if read_tag_texts is not None:
             res['read_tags'] = ds.read_tags(ctx, got, read_tag_texts, pc_cap=pc_cap)
+        links = None
+        if ps_links or join_min_sv is not None:
+            links = ds.ps_links(ctx, pc_cap=pc_cap)                 # (last: it clusters again, into the same result arrays)
         if ps_links:
-            res['ps_links'] = ds.ps_links(ctx, pc_cap=pc_cap)       # (last: it clusters again, into the same result arrays)
+            res['ps_links'] = links
+        if join_min_sv is not None:
+            from duet_amd import ps_join, ps_links as links_mod
+            blocks = links_mod.blocks(links, min_sv=join_min_sv)[0]
+            res['join'] = join = dict(blocks=blocks)
+            try:
+                join.update(ds.run_joined(ctx, ps_join.table(blocks), got['read_off'], thresholds=thresholds, pc_cap=pc_cap))
+                join['rows'], join['n_rows'] = ds.phased_rows(ctx, row_texts, pred=join['pred'], ps=join['ps'])
+                N = len(join['change'])
+                join['pred'], join['ps'] = join['pred'][:N].cpu().numpy(), join['ps'][:N].cpu().numpy().view(np.uint32)
+            except ZeroDivisionError as e:
+                join['error'] = e                                   # (raised once phased_sv.vcf has been written in full)
         return res
     return compute
 
@@ -442,7 +461,8 @@ def rank_main(argv):
 
 
 def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, cluster_max_distance=0.9, device=0,
-                         gpus=1, write_sv_calls=False, thresholds=None, pc_cap=None, evidence=False, ps_links=False, read_tags=False):
+                         gpus=1, write_sv_calls=False, thresholds=None, pc_cap=None, evidence=False, ps_links=False, read_tags=False,
+                         join_ps=False, join_min_sv=2):
     """`duet ... -b svim-gpu -c <max distance>`: SV calling (signatures + clustering, what `-b svim` delegates to the
     external `svim alignment ... --cluster_max_distance c`, sv_calling.py:13-15) AND SV phasing on the GPU, from the
     haplotagged BAMs of <home>/snp_phasing -> <home>/phased_sv.vcf.  The clustering half is this repository's own rule
@@ -458,7 +478,18 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
     ps_links (--write_ps_links): also <home>/phased_sv.ps_links.tsv and <home>/phased_sv.ps_blocks.tsv, how the clustered candidates
     tie neighbouring phase sets together (duet_amd/ps_links.py); single-GPU path only, whichever route the decision takes.
     read_tags (--write_read_tags): also <home>/phased_sv.read_tags.tsv, the haplotype the heterozygous calls place each supporting
-    read on (duet_amd/read_tags.py), from the resident cluster result and calls; single-GPU path only."""
+    read on (duet_amd/read_tags.py), from the resident cluster result and calls; single-GPU path only.
+    join_ps, join_min_sv (--join_ps [--join_min_sv N]): also the same pipeline again on the read tags remapped over the phase sets
+    that the links of at least N candidates tie into one block -> <home>/phased_sv.joined.vcf, with
+    <home>/phased_sv.join_blocks.tsv and <home>/phased_sv.join_report.tsv (duet_amd/ps_join.py); single-GPU path only, by the
+    route the other keywords give the decision.  phased_sv.vcf is written first and in full."""
+    if join_ps:
+        from duet_amd import ps_join
+        if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise ValueError('join_ps: single-GPU path only')
+        join_min_sv = ps_join.check_min_sv(join_min_sv)
+    else:
+        join_min_sv = None
     if read_tags and (int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1'):
         raise ValueError('read_tags: single-GPU path only')
     if ps_links and (int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1'):
@@ -522,7 +553,7 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
         texts = spelled_contigs(home, chroms)
         return device_compute(ctx if ctx is not None else engine.default_context(int(device)), texts if write_sv_calls else None,
                               row_texts=texts, thresholds=thresholds, pc_cap=pc_cap, evidence_texts=texts if evidence else None,
-                              ps_links=bool(ps_links), read_tag_texts=texts if read_tags else None)(*args)
+                              ps_links=bool(ps_links), read_tag_texts=texts if read_tags else None, join_min_sv=join_min_sv)(*args)
     res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
                           min_sv_size=max(int(svlen_thres), 1), names=bool(write_sv_calls), compute=compute,
                           keep_names=bool(read_tags))
@@ -554,11 +585,36 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
             out.write(rows)
         logging.info('write the clustered SV calls into sv_calling/variants.vcf')
         write_callset(home, chroms, res['calls'])
-        logging.info('%s SV CALLING + PHASING COMPLETED IN %ss %s' % (bar, round(time.time() - t0, 3), bar))
-        return
-    with open(out_vcf, 'ab') as out:
-        out.write(rows)
+    else:
+        with open(out_vcf, 'ab') as out:
+            out.write(rows)
+    if join_min_sv is not None:
+        write_join(home, chroms, res, join_min_sv)
     logging.info('%s SV CALLING + PHASING COMPLETED IN %ss %s' % (bar, round(time.time() - t0, 3), bar))
+
+
+def write_join(home, chroms, res, min_sv):
+    """The three files of --join_ps from the result's `join` (device_compute), after phased_sv.vcf has been written in full.
+    phased_sv.joined.vcf is created with its header first: where the joined run raised ZeroDivisionError it stays header-only, no
+    report is written and the error is raised here.  Without a single mark nothing ran: the header lines alone."""
+    from duet_amd import ps_join
+    logging.info('phase the SVs again over the joined phase sets (--join_ps, links of at least %d SVs)' % min_sv)
+    texts = spelled_contigs(home, chroms)
+    join = res.get('join', dict(blocks=[]))
+    with open(ps_join.path_vcf(home), 'w') as out:
+        out.write(header_text(home, chroms))
+    ps_join.write_blocks(home, join['blocks'], texts)
+    if 'error' in join:
+        raise join['error']
+    with open(ps_join.path_vcf(home), 'ab') as out:
+        out.write(bytes(memoryview(np.ascontiguousarray(join.get('rows', np.zeros(0, dtype=np.uint8))))))
+    report = ''
+    if 'change' in join:
+        report = ps_join.report_text(texts, res['cand_contig'], res['cand_pos'], res['cand_span'], join['change'], res['pred'],
+                                     res['ps'], join['pred'], join['ps'])
+    ps_join.write_report(home, report)
+    logging.info('  ' + ps_join.summary_text(join.get('counts', np.zeros(8, dtype=np.uint32)), join.get('n_changed', 0),
+                                             len(join['blocks'])))
 
 
 if __name__ == '__main__':

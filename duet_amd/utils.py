@@ -5,7 +5,8 @@ Flag names, defaults, help texts and the positional order are upstream's (utils.
 existing command line works unchanged.  Two additive options select the device (--device) or shard the contigs
 over several GPUs (--gpus); --thresholds and --pc_cap replace the decision's constants on the single-GPU path,
 --write_evidence adds the per-candidate evidence table there, --write_ps_links the phase-set link tables, --write_read_tags the
-per-read table of the haplotypes the phased SVs place their supporting reads on.
+per-read table of the haplotypes the phased SVs place their supporting reads on, --join_ps [--join_min_sv N] a second run over the
+phase sets that the SVs tie into one block.
 """
 
 import argparse
@@ -76,6 +77,13 @@ def build_parser():
                     help='also write OUTPUT/phased_sv.read_tags.tsv: one row per supporting read and phase set of the heterozygous '
                          'calls, with the haplotype the calls place the read on, its own tag, and whether they agree; one GPU only '
                          '(the native path, or -b svim-gpu)')
+    ap.add_argument('--join_ps', action='store_true',
+                    help='also phase the SVs again over the phase sets that the SV candidates themselves tie into one block: writes '
+                         'OUTPUT/phased_sv.joined.vcf, OUTPUT/phased_sv.join_blocks.tsv (the blocks used) and '
+                         'OUTPUT/phased_sv.join_report.tsv (the calls that changed); phased_sv.vcf stays what it is; one GPU only (the '
+                         'native path, or -b svim-gpu)')
+    ap.add_argument('--join_min_sv', type=int, default=None,
+                    help='with --join_ps: a link joins two phase sets only when at least this many SV candidates agree on it [2]')
     ap.add_argument('--write_sv_calls', action='store_true',
                     help='with -b svim-gpu, also write the clustered SV calls to OUTPUT/sv_calling/variants.vcf')
     for name, text in _POSITIONALS:

@@ -939,6 +939,72 @@ DUET_API int duet_read_tags_rows_host(duet_ctx *ctx, const duet_read_tag_rec *re
                                       const uint64_t *read_tag, uint32_t n_reads, char *out_text, uint64_t out_cap, uint64_t *out_len);
 
 /* ---------------------------------------------------------------------------------------------
+ * Joined phase sets (duet_psjoin.hip): the phase-set links say which phase sets are one block and in which
+ * sense; duet_amd/ps_links.py: blocks turns them into a table (contig, PS) -> (BLOCK, FLIP).  Here the table is applied to the read
+ * tags -- a joined run is the ordinary run on the remapped tags -- and the calls of the two runs are compared candidate by
+ * candidate.  tests/ps_join_ref.py states both rules in plain Python.
+ *
+ *   Table       n_blocks rows of duet_ps_block, ALWAYS host memory (like cand_ctg_off: thousands of rows; the library checks and
+ *               stages them): strictly ascending by (contig, ps), PS compared as a full unsigned 32-bit number; contig < n_contigs;
+ *               flip 0 or 1.  Otherwise DUET_ERR_INVALID, nothing written.  The same PS on two contigs: two keys.
+ *   Tag word    read r of contig k (read_off[k] <= r < read_off[k + 1]) with tag word t.  The all-ones word is untouched,
+ *               whatever the table holds.  (k, ps(t)) in the table: ps becomes BLOCK, and with FLIP == 1 hap 1 becomes 2 and 2
+ *               becomes 1; hap 0 and 3 stay; pc is kept bit for bit.  A word whose key is not in the table is unchanged.
+ *   Change      of a candidate called (p0, s0) before and (p1, s1) after (pred, ps of duet_ef_run_*), the first rule that holds:
+ *                 DUET_PS_JOIN_NONE        p0 == 0 and p1 == 0
+ *                 DUET_PS_JOIN_GAINED      p0 == 0
+ *                 DUET_PS_JOIN_LOST        p1 == 0
+ *                 DUET_PS_JOIN_SAME        (p1, s1) == (p0, s0)
+ *                 DUET_PS_JOIN_RELABELLED  (p1, s1) == (p', s'): s' = BLOCK of (contig, s0), or s0 when the key is not in the table;
+ *                                          p' = 3 - p0 when that row's FLIP is 1 and p0 is 1 or 2, else p0
+ *                 DUET_PS_JOIN_TO_HET      p0 == 3 and p1 is 1 or 2
+ *                 DUET_PS_JOIN_TO_HOM      p0 is 1 or 2 and p1 == 3
+ *                 DUET_PS_JOIN_OTHER       everything else
+ * Integers only.  The counts are sums of per-wavefront popcounts, added with integer atomics to words of the call's own: nothing
+ * depends on the order of arrival, two runs give identical bytes.
+ *
+ * duet_ps_join_tags_*: out_tag[r] = the remapped read_tag[r] for every r < n_reads; out_tag may be read_tag itself.  *n_changed =
+ * the number of words whose bits changed.  read_off is HOST memory, [n_contigs + 1], ascending from 0 to n_reads (empty contigs
+ * are allowed); otherwise DUET_ERR_INVALID.  n_contigs == 0 is refused unless n_reads and n_blocks are 0 too.  Every refusal is
+ * decided on the host before anything is written.  n_reads == 0 or n_blocks == 0: DUET_OK, out_tag a copy, *n_changed = 0.
+ * _device: read_tag and out_tag device memory, n_changed host memory; ONE host round trip (the count).  _host: host arrays.
+ *
+ * duet_ps_join_diff_*: change[c] = the code of candidate c, counts[i] = the candidates with code i.  Exactly one of cand_ctg_off
+ * (HOST, [n_contigs + 1], ascending from 0 to n_cands) and cand_contig ([n_cands], each < n_contigs) names the candidates' contigs;
+ * both or neither: DUET_ERR_INVALID.  A pred above 3 or a cand_contig >= n_contigs is found on the device, through a word of its
+ * own: DUET_ERR_INVALID, nothing written to change, counts zero.  n_cands == 0: DUET_OK, zero counts.
+ * _device: pred0, ps0, pred1, ps1, cand_contig and change device memory, counts[8] host memory; ONE host round trip (the counts
+ * and the refusals), after which the codes are copied to change asynchronously on `stream`.  _host: host arrays.
+ * The workspace is the entries' own (16 bytes per table row, 1 per candidate; grown, never shrunk): a call changes nothing that
+ * a later duet_ef_run_*, duet_ef_features_*, duet_tune_*, duet_ps_links_* or duet_read_tags_* returns. */
+#define DUET_PS_JOIN_NONE 0u
+#define DUET_PS_JOIN_GAINED 1u
+#define DUET_PS_JOIN_LOST 2u
+#define DUET_PS_JOIN_SAME 3u
+#define DUET_PS_JOIN_RELABELLED 4u
+#define DUET_PS_JOIN_TO_HET 5u
+#define DUET_PS_JOIN_TO_HOM 6u
+#define DUET_PS_JOIN_OTHER 7u
+#define DUET_PS_JOIN_CHANGE_NAMES {"none", "gained", "lost", "same", "relabelled", "to_het", "to_hom", "other"}
+typedef struct duet_ps_block {           /* 16 bytes */
+    uint32_t contig, ps, block, flip;
+} duet_ps_block;
+DUET_API int duet_ps_join_tags_device(duet_ctx *ctx, const uint64_t *read_tag, const uint32_t *read_off, uint32_t n_contigs,
+                                      uint32_t n_reads, const duet_ps_block *blocks, uint32_t n_blocks, uint64_t *out_tag,
+                                      uint32_t *n_changed, void *stream);
+DUET_API int duet_ps_join_tags_host(duet_ctx *ctx, const uint64_t *read_tag, const uint32_t *read_off, uint32_t n_contigs,
+                                    uint32_t n_reads, const duet_ps_block *blocks, uint32_t n_blocks, uint64_t *out_tag,
+                                    uint32_t *n_changed);
+DUET_API int duet_ps_join_diff_device(duet_ctx *ctx, uint32_t n_cands, const uint8_t *pred0, const uint32_t *ps0, const uint8_t *pred1,
+                                      const uint32_t *ps1, const uint32_t *cand_ctg_off, const uint16_t *cand_contig,
+                                      uint32_t n_contigs, const duet_ps_block *blocks, uint32_t n_blocks, uint8_t *change,
+                                      uint32_t *counts, void *stream);
+DUET_API int duet_ps_join_diff_host(duet_ctx *ctx, uint32_t n_cands, const uint8_t *pred0, const uint32_t *ps0, const uint8_t *pred1,
+                                    const uint32_t *ps1, const uint32_t *cand_ctg_off, const uint16_t *cand_contig,
+                                    uint32_t n_contigs, const duet_ps_block *blocks, uint32_t n_blocks, uint8_t *change,
+                                    uint32_t *counts);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics: the shared device primitives (duet_amd/csrc/duet_prims.hip.h) on host arrays, each run unchanged on the
  * context's own stream with a workspace sized as the primitive's comments prescribe (duet_amd/csrc/duet_prims_check.hip).  No
  * product path calls these; tests/test_gpu_prims.py compares them with numpy at every plan boundary.  n == 0: DUET_OK, nothing is
