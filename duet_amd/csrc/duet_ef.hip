@@ -1826,6 +1826,9 @@ __global__ __launch_bounds__(256) void ef_finalize(const Params p)
 // questions -- is this PS a seed, which seed is nearest -- by walking the contig's entries where they lie.  The ascending array
 // the ABI can hand out (duet_ef_get_seed_ps, duet_ef_stats.n_seed_ps) is made on demand by ef_seed_sort from the same entries.
 constexpr uint32_t kOwnMaxTiles = 2048;            // (measured, tools/own_sweep.py: ahead up to ~1,600 tiles on the 24-contig genome, level at 3,100, behind beyond)
+constexpr uint32_t kOwnWideMaxTiles = 512;         // ef_finalize_own_wide up to here: 256 workgroups, ONE per CU -- with 144 VGPRs a CU holds one workgroup of 512 threads
+                                                   // or three of 256 (measured, tools/own_sweep.py 200 8e6 one: one contig of 300 .. 512 tiles 0.5 - 0.7 us ahead of
+                                                   // ef_finalize_own, of 513 .. 768 tiles 2.3 - 2.9 us behind)
 constexpr uint32_t kOwnTab = 2048;                 // hash-set slots (open addressing; the hash takes the product's top 11 bits)
 constexpr uint32_t kOwnKeys = 1024;                // distinct seeds kept in LDS
 
@@ -1966,14 +1969,16 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
 
 // (rare path of ef_finalize_own: candidates out of position order) the hash set's values, ascending, into s_one[0 .. u): compacted,
 // every wavefront orders blocks of 64 in its registers, a value's place is the sum of its lower bounds in all blocks (its own
-// included: the values are distinct) -- ef_seed_sort's scheme.  Every thread of the workgroup calls it.
+// included: the values are distinct) -- ef_seed_sort's scheme.  Every one of the workgroup's NT threads calls it.
+template <uint32_t NT>
 __device__ __forceinline__ void own_sort_set(const uint32_t *s_tab, uint32_t *s_key, uint32_t *s_one, uint32_t *s_part, uint32_t u)
 {
+    constexpr uint32_t NW = NT / 64u;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint32_t mv[kOwnTab / 256u], cnt = 0;
+    uint32_t mv[kOwnTab / NT], cnt = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < kOwnTab / 256u; ++j) {
-        mv[j] = s_tab[tid + 256u * j];
+    for (uint32_t j = 0; j < kOwnTab / NT; ++j) {
+        mv[j] = s_tab[tid + NT * j];
         cnt += mv[j] != kEmpty ? 1u : 0u;
     }
     uint32_t x = cnt;                                               // inclusive running count inside the wavefront
@@ -1986,16 +1991,16 @@ __device__ __forceinline__ void own_sort_set(const uint32_t *s_tab, uint32_t *s_
     __syncthreads();
     uint32_t at = x - cnt;
 #pragma unroll
-    for (uint32_t w = 0; w < 4; ++w) at += w < wave ? s_part[w] : 0u;
+    for (uint32_t w = 0; w < NW; ++w) at += w < wave ? s_part[w] : 0u;
 #pragma unroll
-    for (uint32_t j = 0; j < kOwnTab / 256u; ++j)
+    for (uint32_t j = 0; j < kOwnTab / NT; ++j)
         if (mv[j] != kEmpty) s_key[at++] = mv[j];
     const uint32_t U = (u + 63u) & ~63u, nblk = U >> 6;
     if (tid < U - u) s_key[u + tid] = kEmpty;                       // (pads the last block: sorts behind every seed)
     __syncthreads();
-    for (uint32_t b = wave; b < nblk; b += 4u) s_key[b * 64u + lane] = wave_sort64(s_key[b * 64u + lane], lane);
+    for (uint32_t b = wave; b < nblk; b += NW) s_key[b * 64u + lane] = wave_sort64(s_key[b * 64u + lane], lane);
     __syncthreads();
-    for (uint32_t i = tid; i < U; i += 256u) {
+    for (uint32_t i = tid; i < U; i += NT) {
         const uint32_t me = s_key[i];
         uint32_t rank = 0;
         // (four blocks side by side: their seven dependent reads each overlap)
@@ -2094,18 +2099,24 @@ __device__ __forceinline__ bool own_probe(uint32_t *s_tab, uint32_t key, uint32_
 
 constexpr uint32_t kOwnWin = 64;                   // seeds strictly inside the tile's range of asking positions that are kept as a list
 
-// host-planned runs only: one tile per workgroup
-__global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
+// host-planned runs only: T tiles per workgroup of NT = 256 T threads, one candidate per thread (the body of ef_finalize_own, T = 1,
+// and of ef_finalize_own_wide, T = 2).  What the workgroup does once -- the contig's records into the hash set, the window, the
+// reductions -- it then does once per T tiles, and a contig of up to NT tiles is ONE record per lane: the insert phase's chain of
+// `group` rounds is as long as the records per lane are many.
+template <uint32_t T>
+__device__ __forceinline__ void finalize_own_tiles(const Params &p)
 {
+    constexpr uint32_t NT = 256u * T, NW = 4u * T;             // threads and wavefronts of the workgroup
+    static_assert(kOwnTab % NT == 0 && NT <= 1024u, "the clear and own_sort_set deal the table out evenly");
     __shared__ uint32_t s_tab[kOwnTab];                        // the hash set of the contig's seeds
     __shared__ uint32_t s_key[kOwnKeys];                       // (rare path) the distinct seeds, compacted, then in sorted blocks of 64
     __shared__ uint32_t s_one[kOwnKeys];                       // (rare path) ... ascending
     __shared__ uint32_t s_win[kOwnWin];
-    __shared__ uint32_t s_mm[4][2];                            // per wavefront: ~min and max + 1 of the asking positions
-    __shared__ uint32_t s_red[4][3];                           // per wavefront: left seed + 1, ~right seed, seeds new to the set
-    __shared__ uint32_t s_part[4];
+    __shared__ uint32_t s_mm[NW][2];                           // per wavefront: ~min and max + 1 of the asking positions
+    __shared__ uint32_t s_red[NW][3];                          // per wavefront: left seed + 1, ~right seed, seeds new to the set
+    __shared__ uint32_t s_part[NW];
     __shared__ uint32_t s_nwin;
-    __shared__ __align__(8) uint32_t s_c2[kC2Quota * kC2Words];      // the tile's own group-summary slots
+    __shared__ __align__(8) uint32_t s_c2[T * kC2Quota * kC2Words];  // the tiles' own group-summary slots (contiguous in c2rec)
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     STAMP(2, 0);
     if (blockIdx.x == 0 && tid == 0) p.status[1] = 0;          // the summary pool's counter, for the next run's ef_classify
@@ -2113,29 +2124,29 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
     const uint32_t nK = p.n_small;
     // contig k's first candidate: out of the kernel arguments (scalar loads, no memory)
     auto coff = [&](uint32_t kk) -> uint32_t { return p.ctg_small[kk]; };
-    const uint32_t tile = blockIdx.x;
-    const uint32_t c0 = tile * 256u, c = c0 + tid;
+    const uint32_t tile = blockIdx.x * T;                      // the workgroup's first tile (its last workgroup may hold fewer than T)
+    const uint32_t c0 = blockIdx.x * NT, c = c0 + tid;
     const bool live = c < n_cands;
     const uint32_t cl = live ? c : n_cands - 1u;               // (a clamped address: every load of the first trip is unconditional)
-    const uint32_t last = min(c0 + 255u, n_cands - 1);
+    const uint32_t last = min(c0 + (NT - 1u), n_cands - 1);
     const uint32_t keys_cap = (p.dbg & DUET_DBG_EF_OWN_SMALLTAB) ? 8u : kOwnKeys;
     const uint32_t win_cap = (p.dbg & DUET_DBG_EF_OWN_SMALLTAB) ? 2u : kOwnWin;
     const TileRecs recs{reinterpret_cast<const ulonglong4 *>(p.blk_rec)};
     // ONE round trip in front of everything.  It carries the candidate's code, PS, position, mark range and read counts, up to four
-    // tiles' seed records of the tile's first contig, and the tile's own kC2Quota group-summary slots (3.5 KB: the candidates of this
-    // very tile put theirs there) -- whether or not anybody will look at them: what a multi-PS candidate needs (:85-105, :148-155)
+    // tiles' seed records of the tile's first contig, and the tiles' own kC2Quota group-summary slots each (3.5 KB a tile: the
+    // candidates of these very tiles put theirs there; behind the last tile's come the pool's first slots, which are as readable) -- whether or not anybody will look at them: what a multi-PS candidate needs (:85-105, :148-155)
     // would otherwise be a SECOND, dependent trip, as its summary sits at a slot that only its PS word names.  Only a summary in the
     // shared pool (a tile with more than 64 multi-PS candidates) is fetched once the slot is known.
     // Every load below is unconditional, at a clamped address, and nothing is looked at before the last one has left: a conditional
     // load is a branch, and the compiler waits for a load's value where it is first used -- both split the trip into several.
     // The records stay in registers with constant indices only: a register array indexed at run time lives in scratch memory.
-    constexpr uint32_t kPre = 2;                               // records per thread that leave with the first trip: 512 tiles of a contig
+    constexpr uint32_t kPre = 2;                               // records per thread that leave with the first trip: 512 T tiles of a contig
     static_assert(kPre == 2, "the overflow loop selects between rec[0] and rec[1]");
     ulonglong4 rec[kPre], ext[kPre];                           // a tile's count + entries 0 .. 2; entries 3 .. 6
     auto load_recs = [&](uint32_t b_lo, uint32_t b_hi) {       // (beyond b_hi: tile b_hi again; its count is masked where it is read)
 #pragma unroll
         for (uint32_t i = 0; i < kPre; ++i) {
-            const uint32_t b = min(b_lo + tid + 256u * i, b_hi);
+            const uint32_t b = min(b_lo + tid + NT * i, b_hi);
             rec[i] = recs[b];
             ext[i] = recs.second(b);
         }
@@ -2143,9 +2154,10 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
     const uint32_t code_ld = p.out_pred[cl], ps_ld = p.out_ps[cl], pos_ld = p.cand_pos[cl];
     const uint32_t o0_ld = p.cand_off[cl], o1_ld = p.cand_off[cl + 1u];
     const uint32_t sv_ld = p.cand_svread[cl], rf_ld = p.cand_refread[cl];
-    constexpr uint32_t kPairs = kC2Quota * kC2Words / 2;       // 448 eight-byte pieces
+    constexpr uint32_t kPairs = T * kC2Quota * kC2Words / 2;   // 448 eight-byte pieces a tile
+    static_assert(kPairs <= 2u * NT, "two pieces per thread");
     const uint2 *c2src = reinterpret_cast<const uint2 *>(p.c2rec + (size_t)tile * kC2Quota * kC2Words);
-    const uint2 a0 = c2src[tid], a1 = c2src[tid + 256u < kPairs ? tid + 256u : tid];
+    const uint2 a0 = c2src[tid], a1 = c2src[tid + NT < kPairs ? tid + NT : tid];
     // (the loads above leave before the contig search: its scalar loads of the kernel arguments are a dependent chain of their own)
     uint32_t lo = 0, hi = nK;                                  // the last k with coff(k) <= c0
     while (hi - lo > 1) {
@@ -2165,7 +2177,7 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
     {
         uint2 *dst = reinterpret_cast<uint2 *>(s_c2);
         dst[tid] = a0;
-        if (tid + 256u < kPairs) dst[tid + 256u] = a1;
+        if (tid + NT < kPairs) dst[tid + NT] = a1;
     }
     const uint32_t code = live ? code_ld : 0u, ps_in = live ? ps_ld : 0u, c_pos = live ? pos_ld : 0u;
     const uint32_t c_o0 = live ? o0_ld : 0u, c_o1 = live ? o1_ld : 0u;
@@ -2176,7 +2188,7 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
         const uint32_t b_lo = c_lo / kCandPerBlock, b_hi = (c_hi - 1) / kCandPerBlock;
         if (k != k_first) load_recs(b_lo, b_hi);               // (in flight while the table is cleared)
 #pragma unroll
-        for (uint32_t i = 0; i < kOwnTab / 256u; ++i) s_tab[tid + 256u * i] = kEmpty;
+        for (uint32_t i = 0; i < kOwnTab / NT; ++i) s_tab[tid + NT * i] = kEmpty;
         if (tid == 0) s_nwin = 0;
         // the range of positions for which this tile will ask "which seed is nearest" (:106-111): candidates of this contig that
         // need the nearest seed outright, or may (a multi-PS candidate without a winner)
@@ -2193,14 +2205,20 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
         asm volatile("" ::"v"(rec[0].x), "v"(rec[1].x), "v"(rec[0].y), "v"(rec[1].y), "v"(rec[0].z), "v"(rec[1].z), "v"(rec[0].w),
                      "v"(rec[1].w), "v"(ext[0].x), "v"(ext[1].x), "v"(ext[0].y), "v"(ext[1].y), "v"(ext[0].z), "v"(ext[1].z),
                      "v"(ext[0].w), "v"(ext[1].w));
+        STAMP(2, 3);                                                        // (the records are here: what follows is the LDS chain)
         // ---- every entry of the contig: into the hash set (is this PS a seed, :91), and -- in the same sweep, from the registers
         // it sits in -- what the tile needs to answer "which seed is nearest" for positions in [pmin, pmax]: the largest seed
         // <= pmin, the smallest seed >= pmax, and the seeds strictly inside (with position-ordered candidates a handful; repeats
         // from neighbouring tiles do not hurt a minimum).
         uint32_t pmin, pmax;
         {
-            const uint32_t a0 = max(max(s_mm[0][0], s_mm[1][0]), max(s_mm[2][0], s_mm[3][0]));
-            const uint32_t a1 = max(max(s_mm[0][1], s_mm[1][1]), max(s_mm[2][1], s_mm[3][1]));
+            uint32_t a0 = max(max(s_mm[0][0], s_mm[1][0]), max(s_mm[2][0], s_mm[3][0]));
+            uint32_t a1 = max(max(s_mm[0][1], s_mm[1][1]), max(s_mm[2][1], s_mm[3][1]));
+#pragma unroll
+            for (uint32_t w = 4; w < NW; w += 4) {             // (T > 1: the other tiles' wavefronts -- the range is the workgroup's)
+                a0 = max(a0, max(max(s_mm[w][0], s_mm[w + 1][0]), max(s_mm[w + 2][0], s_mm[w + 3][0])));
+                a1 = max(a1, max(max(s_mm[w][1], s_mm[w + 1][1]), max(s_mm[w + 2][1], s_mm[w + 3][1])));
+            }
             pmin = a1 ? ~a0 : 0u;                                           // (nobody asks: any range serves)
             pmax = a1 ? a1 - 1u : 0u;
         }
@@ -2247,7 +2265,7 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
         };
 #pragma unroll
         for (uint32_t i = 0; i < kPre; ++i) {
-            const uint32_t cnt = b_lo + tid + 256u * i <= b_hi ? (uint32_t)rec[i].x : 0u;
+            const uint32_t cnt = b_lo + tid + NT * i <= b_hi ? (uint32_t)rec[i].x : 0u;
             if (__any(cnt > 0u)) {
                 const uint64_t e[4] = {rec[i].y, rec[i].z, rec[i].w, 0ull};
                 group(e, 0u, 3u, cnt, 7u * i);
@@ -2302,10 +2320,10 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
                 for (uint32_t j = from + lane; j < cnt_h; j += 64u) insert(ov[j]);
             }
         };
-        // the overflow slots of the records above, then (a contig of more than 512 tiles) the others' records one more trip later
+        // the overflow slots of the records above, then (a contig of more than 512 T tiles) the others' records one more trip later
         // (one loop: a single copy of the rare paths; the count of rec[i] by a select, not by a run-time index)
 #pragma unroll 1
-        for (uint32_t i = 0, b0 = b_lo; b0 <= b_hi; ++i, b0 += 256u) {
+        for (uint32_t i = 0, b0 = b_lo; b0 <= b_hi; ++i, b0 += NT) {
             const uint32_t b = b0 + tid;
             uint32_t cnt, from = 7u;
             if (i < kPre) {
@@ -2327,13 +2345,19 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
         }
         lds_barrier();
         STAMP(2, 2);
-        const uint32_t u = s_red[0][2] + s_red[1][2] + s_red[2][2] + s_red[3][2];                   // distinct seeds (a full table loses some: over)
-        const uint32_t Lp = max(max(s_red[0][0], s_red[1][0]), max(s_red[2][0], s_red[3][0]));       // left seed + 1, 0: none
-        const uint32_t Ri = max(max(s_red[0][1], s_red[1][1]), max(s_red[2][1], s_red[3][1]));       // ~right seed, 0: none
+        uint32_t u = s_red[0][2] + s_red[1][2] + s_red[2][2] + s_red[3][2];                         // distinct seeds (a full table loses some: over)
+        uint32_t Lp = max(max(s_red[0][0], s_red[1][0]), max(s_red[2][0], s_red[3][0]));             // left seed + 1, 0: none
+        uint32_t Ri = max(max(s_red[0][1], s_red[1][1]), max(s_red[2][1], s_red[3][1]));             // ~right seed, 0: none
+#pragma unroll
+        for (uint32_t w = 4; w < NW; w += 4) {
+            u += s_red[w][2] + s_red[w + 1][2] + s_red[w + 2][2] + s_red[w + 3][2];
+            Lp = max(Lp, max(max(s_red[w][0], s_red[w + 1][0]), max(s_red[w + 2][0], s_red[w + 3][0])));
+            Ri = max(Ri, max(max(s_red[w][1], s_red[w + 1][1]), max(s_red[w + 2][1], s_red[w + 3][1])));
+        }
         const uint32_t n_win = s_nwin;
         const bool over = u > keys_cap;                                     // (a full table: u == kOwnTab > keys_cap)
         const bool sorted = !over && n_win > win_cap;                       // candidates out of position order: the whole set, ascending
-        if (sorted) own_sort_set(s_tab, s_key, s_one, s_part, u);      // (rare: inlined behind this branch)
+        if (sorted) own_sort_set<NT>(s_tab, s_key, s_one, s_part, u);  // (rare: inlined behind this branch)
         STAMP(2, 5);
         // ---- this tile's candidates of contig k ------------------------------------------------------
         // :107-111 -- ties go to the larger seed
@@ -2382,7 +2406,7 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
                 } else if (code & kClass2) {                                // :85-105, :148-155 from the summary that is already here
                     uint32_t w[kC2Words];
                     const uint32_t own0 = tile * kC2Quota;
-                    if (ps_in >= own0 && ps_in < own0 + kC2Quota) {
+                    if (ps_in >= own0 && ps_in < own0 + T * kC2Quota) {
 #pragma unroll
                         for (int i = 0; i < kC2Words; ++i) w[i] = s_c2[(ps_in - own0) * kC2Words + i];
                     } else {                                                // (a slot of the shared pool)
@@ -2417,6 +2441,16 @@ __global__ __launch_bounds__(256) void ef_finalize_own(const Params p)
         __syncthreads();                                                    // the set is reused
     }
 }
+
+// one tile per workgroup: where no contig spans more than 256 tiles its records are one per lane already
+__global__ __launch_bounds__(256) void ef_finalize_own(const Params p) { finalize_own_tiles<1>(p); }
+
+// two tiles per workgroup (round 10): a contig of up to 512 tiles is one record per lane -- at BASELINE configs[1] (391 tiles, one
+// contig) every wavefront runs two `group` rounds where ef_finalize_own's first three run four, 196 workgroups stand where 391
+// stood (no CU holds two), and the chip reads and inserts the contig's records half as often.  Selected where some contig spans
+// more than 256 tiles and the problem has at most kOwnWideMaxTiles (duet_ef_run_device).  Four tiles per workgroup were measured and not kept:
+// profiles/history/r10_ef_finalize_own_four_tiles_REJECTED.txt.
+__global__ __launch_bounds__(512) void ef_finalize_own_wide(const Params p) { finalize_own_tiles<2>(p); }
 
 // plan time: ctg_start[c] = 1 for the first candidate of every non-empty contig
 __global__ void plan_mark_starts(const uint32_t *ctg_off, uint32_t K, uint8_t *ctg_start)
@@ -2533,6 +2567,11 @@ int ensure_plan(duet_ctx *ctx, const duet_ef_problem *pr, hipStream_t stream)
             h_blk[b] = k;
         }
     }
+    uint32_t max_span = 0;                                     // tiles that the longest contig touches: its seed records
+    for (uint32_t k = 0; k < K; ++k) {
+        const uint32_t c_lo = pr->cand_ctg_off[k], c_hi = pr->cand_ctg_off[k + 1];
+        if (c_lo < c_hi) max_span = std::max(max_span, (c_hi - 1) / kCandPerBlock - c_lo / kCandPerBlock + 1);
+    }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ctg_off, h_off, sizeof(uint32_t) * (K + 1), hipMemcpyHostToDevice, stream));
     if (B) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_blk_ctg, h_blk, sizeof(uint32_t) * B, hipMemcpyHostToDevice, stream));
     HIP_TRY(ctx, hipEventRecord(ctx->plan_ev, stream));
@@ -2544,6 +2583,7 @@ int ensure_plan(duet_ctx *ctx, const duet_ef_problem *pr, hipStream_t stream)
     ctx->ef_seeds_stale = false;                               // (the saved kernel arguments describe the previous workspace)
     ctx->plan_off.assign(pr->cand_ctg_off, pr->cand_ctg_off + K + 1);
     ctx->plan_C = C;
+    ctx->plan_max_span = max_span;
     ctx->plan_stream = stream;
     return DUET_OK;
 }
@@ -2751,7 +2791,13 @@ int duet_ef_run_device(duet_ctx *ctx, const duet_ef_problem *pr, uint8_t *out_pr
     else
         hipExtLaunchKernelGGL(ef_classify<false>, dim3(blocks), dim3(kCandPerBlock), 0, stream, ev[0], ev[1], 0, p);
     if (own) {
-        hipExtLaunchKernelGGL(ef_finalize_own, dim3(blocks), dim3(256), 0, stream, ev[4], ev[5], 0, p);
+        // two tiles per workgroup (round 10) where some contig spans more than 256 tiles -- its records are then one per lane in the
+        // wide kernel and two in ef_finalize_own; up to 256 tiles they are one per lane in either, and the wide kernel is 0.6 us
+        // behind -- and the wide workgroups all run at once (kOwnWideMaxTiles)
+        const bool wide = !(ctx->dbg & DUET_DBG_EF_OWN_NARROW) &&
+                          ((ctx->plan_max_span > 256u && blocks <= kOwnWideMaxTiles) || (ctx->dbg & DUET_DBG_EF_OWN_WIDE));
+        if (wide) hipExtLaunchKernelGGL(ef_finalize_own_wide, dim3((blocks + 1) / 2), dim3(512), 0, stream, ev[4], ev[5], 0, p);
+        else hipExtLaunchKernelGGL(ef_finalize_own, dim3(blocks), dim3(256), 0, stream, ev[4], ev[5], 0, p);
         ctx->ef_last_params.assign((const unsigned char *)&p, (const unsigned char *)&p + sizeof(p));
         ctx->ef_last_stream = stream;
         ctx->ef_seeds_stale = true;
@@ -2809,6 +2855,7 @@ int duet_ef_plan_on_device_prepare(duet_ctx *ctx, uint32_t K, uint32_t c_max, hi
     ctx->d_blk_cnt = w;
     ctx->plan_off.clear();                                     // the cached host-side plan no longer describes the workspace
     ctx->plan_C = 0;
+    ctx->plan_max_span = 0;
     ctx->plan_stream = stream;
     if (ctg_off_out) *ctg_off_out = ctx->d_ctg_off;
     if (zero_out) *zero_out = ctx->d_n_one;

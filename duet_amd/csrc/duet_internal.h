@@ -44,6 +44,7 @@ struct duet_ctx {
     // E/F plan (workspace keyed by the contig layout)
     std::vector<uint32_t> plan_off;        // cached cand_ctg_off
     uint32_t plan_C = 0;
+    uint32_t plan_max_span = 0;            // tiles of 256 candidates that the plan's longest contig touches (selects ef_finalize_own_wide)
     hipStream_t plan_stream = (hipStream_t)-1;   // the stream the plan was built on
     uint32_t *plan_stage = nullptr;        // pinned staging block for the plan uploads
     size_t plan_stage_cap = 0;

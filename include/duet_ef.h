@@ -138,8 +138,11 @@ DUET_API int duet_ef_profile_collect(duet_ctx *ctx, duet_ef_stats *stats);
 
 /* Diagnostics: each bit forces a kernel path or launch structure other than the one the input would take (the outputs
  * are identical; tests use them to exercise every path), e.g. DUET_DBG_CLUSTER_EXACT sends every A0 partition through the exact linkage
- * instead of the bounding-box / threshold-graph fast paths.  0 in production.  The bit values 0x1, 0x2, 0x4,
+ * instead of the bounding-box / threshold-graph fast paths.  0 in production.  The bit values 0x4
  * and 0x10000000 are unused and have no effect. */
+#define DUET_DBG_EF_OWN_WIDE 0x1u        /* E/F: the two-launch path finalizes two tiles of 256 candidates per workgroup of 512 threads (ef_finalize_own_wide) whatever
+                                            the size (default: where some contig spans more than 256 tiles and the problem has at most 512) */
+#define DUET_DBG_EF_OWN_NARROW 0x2u      /* ... one tile per workgroup (ef_finalize_own) whatever the size; it wins over DUET_DBG_EF_OWN_WIDE */
 #define DUET_DBG_EF_NO_SEED_HASH 0x40u   /* E/F: ef_seed_sort orders an unsorted seed list itself instead of taking its distinct values through a hash set first */
 #define DUET_DBG_EF_FIN_TPB2 0x20u       /* E/F: ef_finalize takes two tiles of 256 candidates per workgroup whatever the size (default from 1 M candidates on) */
 #define DUET_DBG_EF_FIN_TPB4 0x80u       /* ... four (default from 8 M candidates on) */

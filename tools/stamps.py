@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """GPU-side diagnostic: per-block phase timeline of the three kernels (libduet_ef_stamps.so, -DDUET_STAMPS).
-Not part of the product; run its numbers as SHARES, the stamped build is slower."""
+Not part of the product; run its numbers as SHARES, the stamped build is slower.
+
+    python3 tools/stamps.py [cfg2 | genome | fused] [3k] [wide | narrow]
+        3k: the three launches; wide / narrow: ef_finalize_own_wide / ef_finalize_own whatever the size (DUET_DBG_EF_OWN_WIDE / _NARROW)"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -12,9 +15,13 @@ from duet_amd.devmem import DeviceProblem
 ctx = _lib.Context(0)
 if '3k' in sys.argv:
     ctx.set_debug(0x800000)        # DUET_DBG_EF_OWN_OFF: the three launches of rounds 1-5
+elif 'wide' in sys.argv:
+    ctx.set_debug(0x1)             # DUET_DBG_EF_OWN_WIDE
+elif 'narrow' in sys.argv:
+    ctx.set_debug(0x2)             # DUET_DBG_EF_OWN_NARROW
 lib = _lib.load()
 lib.duet_dbg_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-which = sys.argv[1] if len(sys.argv) > 1 else 'cfg2'
+which = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] not in ('3k', 'wide', 'narrow') else 'cfg2'
 if which == 'fused':
     # the E/F problem that stage A0 hands over in the fused pipeline (candidates ordered by type, then centre)
     from oracle import c_oracle
@@ -47,7 +54,10 @@ st = buf[:3 * 65536 * 8].reshape(3, 65536, 8).astype(np.int64)
 t0 = st[0][st[0][:, 0] > 0][:, 0].min()
 names = [['start', 'offsets', 'staged', 'consumed', 'loop_end', 'decided', 'end'],
          ['start', 'gathered', 'sorted', 'end', 'recs', 'counted', 'written', 'runs'],
-         ['start', 'meta', 'staged'] if '3k' in sys.argv else ['start', 'cleared', 'inserted', 'swept', 'sorted64', 'ranked', 'end']]
+         ['start', 'meta', 'staged'] if '3k' in sys.argv else ['start', 'cleared', 'inserted', 'records', 'sorted64', 'ranked', 'end']]
+# stamp indices in program order, for the phase durations (ef_finalize_own: `records` -- the seed records have arrived, behind the
+# wait in front of the insert phase -- lies between `cleared` and `inserted`; index 4 is no longer written)
+order_of = [list(range(7)), None, [0, 1, 2] if '3k' in sys.argv else [0, 1, 3, 2, 5, 6]]
 for k in range(3):
     blk = st[k][st[k][:, 0] > 0]
     nb = len(blk)
@@ -63,7 +73,8 @@ for k in range(3):
         for b in range(nb):
             print('  contig block %d:' % b, ' '.join('%s@%.2f' % (names[1][i], rel[b, i]) for i in order if blk[b, i] > 0))
         continue
-    d = np.diff(rel[:, :len(names[k])], axis=1)
-    print('  phase durations (median us):', ' '.join('%s=%.2f' % (names[k][i + 1], np.median(d[:, i])) for i in range(d.shape[1])))
+    cols = [i for i in order_of[k] if (blk[:, i] > 0).all()]
+    d = np.diff(rel[:, cols], axis=1)
+    print('  phase durations (median us):', ' '.join('%s=%.2f' % (names[k][cols[i + 1]], np.median(d[:, i])) for i in range(d.shape[1])))
 if st[1][1][0] > 0:                         # (a diagnostic build may leave (n << 32 | distinct) of contig 0's seed list there)
     print('seed list of contig 0: n %d distinct %d' % (int(st[1][1][0]) >> 32, int(st[1][1][0]) & 0xFFFFFFFF))
