@@ -1533,16 +1533,26 @@ struct ArraySeeds {
     __device__ __forceinline__ uint32_t nearest(uint32_t pos) const { return nearest_seed(one, n, pos); }
 };
 
+// Which marks have no tag is stated here once: kEmpty (no read), an index at or beyond the table's n_reads entries, or a word that
+// is all ones.  tagged_index folds the first two into kEmpty; tag_of is the whole lookup.  The batched loops below fold the index
+// as they load it and then load unconditionally, at word 0 for kEmpty (read_tag always has >= 1 readable word), so that their
+// eight loads stay in flight.
+__device__ __forceinline__ uint32_t tagged_index(uint32_t n_reads, uint32_t r) { return r < n_reads ? r : kEmpty; }
+__device__ __forceinline__ uint64_t tag_of(const uint64_t *read_tag, uint32_t n_reads, uint32_t r)
+{
+    return r < n_reads ? read_tag[r] : kUntagged;
+}
+
 // f(tag) for every mark of [b, e) in list order, the marks' two dependent loads (read index, then tag) eight marks at a time:
 // one pair of round trips per eight marks instead of one per mark
 template <class F>
-__device__ __forceinline__ void for_each_tag(const uint32_t *mark_read, const uint64_t *read_tag, uint32_t b, uint32_t e, F f)
+__device__ __forceinline__ void for_each_tag(const uint32_t *mark_read, const uint64_t *read_tag, uint32_t n_reads, uint32_t b, uint32_t e, F f)
 {
     for (uint32_t m0 = b; m0 < e; m0 += 8) {
         uint32_t r[8];
         uint64_t t[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = mark_read[m0 + j < e ? m0 + j : b];
+        for (int j = 0; j < 8; ++j) r[j] = tagged_index(n_reads, mark_read[m0 + j < e ? m0 + j : b]);  // (a padded lane: mark b again, folded alike)
 #pragma unroll
         for (int j = 0; j < 8; ++j) t[j] = read_tag[r[j] == kEmpty ? 0u : r[j]];         // (read_tag always has >= 1 readable word)
 #pragma unroll
@@ -1553,15 +1563,15 @@ __device__ __forceinline__ void for_each_tag(const uint32_t *mark_read, const ui
 
 // multi-PS vote straight from the marks [b, e) (:85-105): only for candidates without a group summary
 template <class Seeds>
-__device__ __forceinline__ void vote_from_marks(const Seeds &sd, const uint32_t *mark_read, const uint64_t *read_tag, uint32_t b,
-                                                uint32_t e, Vote &v, uint32_t &ps)
+__device__ __forceinline__ void vote_from_marks(const Seeds &sd, const uint32_t *mark_read, const uint64_t *read_tag, uint32_t n_reads,
+                                                uint32_t b, uint32_t e, Vote &v, uint32_t &ps)
 {
     uint32_t best = 0;
-    for_each_tag(mark_read, read_tag, b, e, [&](uint64_t t) {
+    for_each_tag(mark_read, read_tag, n_reads, b, e, [&](uint64_t t) {
         if (t != kUntagged && tag_pc(t) <= kPcMax) ++v.allhap;
     });
     uint32_t done_ps = kEmpty;                                 // last group evaluated (cheap duplicate skip)
-    for_each_tag(mark_read, read_tag, b, e, [&](uint64_t t) {
+    for_each_tag(mark_read, read_tag, n_reads, b, e, [&](uint64_t t) {
         if (t == kUntagged || tag_pc(t) > kPcMax) return;
         const uint32_t g = tag_ps(t);
         if (g == done_ps || (g == ps && best)) return;
@@ -1570,7 +1580,7 @@ __device__ __forceinline__ void vote_from_marks(const Seeds &sd, const uint32_t 
         // evaluated group reproduces the same n and cannot beat it (strict '>', :101)
         uint32_t n = 0, n1 = 0, n2 = 0;
         uint64_t s1 = 0, s2 = 0;
-        for_each_tag(mark_read, read_tag, b, e, [&](uint64_t u) {
+        for_each_tag(mark_read, read_tag, n_reads, b, e, [&](uint64_t u) {
             if (u == kUntagged || tag_pc(u) > kPcMax || tag_ps(u) != g) return;
             ++n;
             const uint32_t hap = tag_hap(u), pc = tag_pc(u);
@@ -1614,6 +1624,7 @@ struct CandCols {
 struct FinalizeIo {
     const uint32_t *mark_read;
     const uint64_t *read_tag;
+    uint32_t n_reads;                                          // entries of read_tag (tag_of)
     uint32_t *status;
     uint8_t *out_pred;
     uint32_t *out_ps;
@@ -1645,7 +1656,7 @@ __device__ __forceinline__ void finalize_rule(const Seeds &sd, const CandCols &c
             load_summary(w);
             vote_from_summary(sd, w, v, ps);
         } else {
-            vote_from_marks(sd, io.mark_read, io.read_tag, cd.o0, cd.o1, v, ps);
+            vote_from_marks(sd, io.mark_read, io.read_tag, io.n_reads, cd.o0, cd.o1, v, ps);
         }
         if (v.hap1 == 0 && v.hap2 == 0) ps = sd.nearest(cd.pos);                         // :106
         io.out_pred[c] = (uint8_t)decide(2, v, cd.o1 - cd.o0, cd.svread, cd.refread);
@@ -1680,7 +1691,7 @@ __device__ __forceinline__ void finalize_candidate(const Params &p, uint32_t c, 
         const uint32_t *rec = p.c2rec + (size_t)ps_in * kC2Words;
 #pragma unroll
         for (int i = 0; i < kC2Words; ++i) w[i] = rec[i];
-    }, FinalizeIo{p.mark_read, p.read_tag, p.status, p.out_pred, p.out_ps});
+    }, FinalizeIo{p.mark_read, p.read_tag, p.n_reads, p.status, p.out_pred, p.out_ps});
 }
 
 // TPB: tiles of 256 candidates per workgroup (host-planned runs with the contig offsets in the kernel arguments only)
@@ -1841,6 +1852,7 @@ struct OwnArgs {
     uint32_t *out_ps, *status;
     uint8_t *out_pred;
     uint32_t c_lo, c_hi;
+    uint32_t n_reads;                              // entries of read_tag (tag_of)
 };
 
 // f(ps) for every seed entry of contig [c_lo, c_hi), tiles dealt out with a stride
@@ -1884,7 +1896,7 @@ __device__ __forceinline__ void own_each_tag(const OwnArgs &a, uint32_t b, uint3
 {
     for (uint32_t m = b; m < e; ++m) {
         const uint32_t r = a.mark_read[m];
-        f(r == kEmpty ? kUntagged : a.read_tag[r]);
+        f(tag_of(a.read_tag, a.n_reads, r));
     }
 }
 
@@ -2028,15 +2040,15 @@ __device__ __forceinline__ void own_sort_set(const uint32_t *s_tab, uint32_t *s_
 
 // (rare path of ef_finalize_own) the multi-PS vote of a candidate without a group summary, straight from its marks (:85-105,
 // vote_from_marks); "is this PS a seed" (:91) from the hash set in LDS
-__device__ __forceinline__ void own_vote_from_marks(const uint32_t *mark_read, const uint64_t *read_tag, uint32_t mb, uint32_t me_,
-                                                 const uint32_t *s_tab, Vote *vo, uint32_t *pso)
+__device__ __forceinline__ void own_vote_from_marks(const uint32_t *mark_read, const uint64_t *read_tag, uint32_t n_reads, uint32_t mb,
+                                                 uint32_t me_, const uint32_t *s_tab, Vote *vo, uint32_t *pso)
 {
     auto each = [&](auto f) {                                      // (eight marks' two dependent loads at a time, as for_each_tag)
         for (uint32_t m0 = mb; m0 < me_; m0 += 8) {
             uint32_t r[8];
             uint64_t t[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) r[j] = mark_read[m0 + j < me_ ? m0 + j : mb];
+            for (int j = 0; j < 8; ++j) r[j] = tagged_index(n_reads, mark_read[m0 + j < me_ ? m0 + j : mb]);  // (a padded lane: mark mb again)
 #pragma unroll
             for (int j = 0; j < 8; ++j) t[j] = read_tag[r[j] == kEmpty ? 0u : r[j]];       // (read_tag always has >= 1 readable word)
 #pragma unroll
@@ -2394,12 +2406,12 @@ __device__ __forceinline__ void finalize_own_tiles(const Params &p)
                     p.out_ps[c] = 0;
                 } else if (over) {
                     const OwnArgs a = {recs, p.seed_ent, p.read_tag, p.cand_pos, p.cand_off, p.cand_svread, p.cand_refread, p.mark_read, p.c2rec,
-                                       p.out_ps, p.status, p.out_pred, c_lo, c_hi};
+                                       p.out_ps, p.status, p.out_pred, c_lo, c_hi, p.n_reads};
                     finalize_candidate_walk(a, c, code, ps_in);
                 } else if (code & kClass2Slow) {                            // no group summary: the vote from the marks (:85-105)
                     Vote v;
                     uint32_t ps;
-                    own_vote_from_marks(p.mark_read, p.read_tag, c_o0, c_o1, s_tab, &v, &ps);
+                    own_vote_from_marks(p.mark_read, p.read_tag, p.n_reads, c_o0, c_o1, s_tab, &v, &ps);
                     if (v.hap1 == 0 && v.hap2 == 0) ps = nearest(c_pos);    // :106
                     p.out_pred[c] = (uint8_t)decide(2, v, c_o1 - c_o0, c_svread, c_refread);
                     p.out_ps[c] = ps;

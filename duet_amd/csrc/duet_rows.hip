@@ -33,6 +33,7 @@ namespace {
 #include "duet_text.hip.h"
 
 constexpr uint32_t kAbsentRead = 0xFFFFFFFFu;
+constexpr uint32_t kNoPs = 0xFFFFFFFFu;            // PS field of a tag word that says "no tag" (duet_ef.hip: kEmpty)
 
 struct RowParams {
     uint32_t C, K, n_rows;
@@ -46,6 +47,7 @@ struct RowParams {
     const uint32_t *ctg_off;                 // device copy, [K + 1]
     const uint32_t *cand_off, *mark_read;    // the E/F problem's CSR
     const uint64_t *read_tag;
+    uint32_t n_reads;                        // entries of read_tag; 0xFFFFFFFF: the caller vouches for every index (duet_rows_problem)
     uint32_t sh_rank, sh_pos;                // key = rank << sh_rank | pos << sh_pos | contig << 2 | class
     const uint32_t *sorted;                  // candidate of each row
     const uint32_t *row_off;                 // [n_rows] byte offset of each row
@@ -63,8 +65,9 @@ __global__ void rows_keys(const RowParams p, const uint32_t *idx, uint64_t *keys
     uint32_t n_ps = 0, first = 0;
     for (uint32_t m = p.cand_off[c]; m < p.cand_off[c + 1]; ++m) {
         const uint32_t r = p.mark_read[m];
-        if (r == kAbsentRead) continue;
+        if (r >= p.n_reads) continue;                                       // (kAbsentRead too: n_reads <= 0xFFFFFFFF)
         const uint32_t ps = (uint32_t)p.read_tag[r];
+        if (ps == kNoPs) continue;                                          // ef_classify's tagged test: an all-ones PS field is no tag
         if (n_ps == 0) { n_ps = 1; first = ps; }
         else if (ps != first) { n_ps = 2; break; }
     }
@@ -165,12 +168,9 @@ __global__ __launch_bounds__(256) void rows_write(const RowParams p)
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int duet_rows_run_device(duet_ctx *ctx, const duet_rows_problem *pr, char *out_text, uint64_t out_cap, uint64_t *out_len,
-                         uint32_t *n_rows, void *stream_)
+// duet_rows_run_device with the read table's size: a mark whose index is at or beyond n_reads has no tag
+int rows_run(duet_ctx *ctx, const duet_rows_problem *pr, uint32_t n_reads, char *out_text, uint64_t out_cap, uint64_t *out_len,
+             uint32_t *n_rows, void *stream_)
 {
     if (!ctx) return duet_fail(nullptr, DUET_ERR_INVALID, "null context");
     if (!pr || !out_len || !n_rows) return duet_fail(ctx, DUET_ERR_INVALID, "null argument");
@@ -216,6 +216,7 @@ int duet_rows_run_device(duet_ctx *ctx, const duet_rows_problem *pr, char *out_t
     p.pred = pr->pred; p.ps = pr->ps; p.cand_pos = pr->cand_pos; p.cand_svlen = pr->cand_svlen; p.cand_plus = pr->cand_plus;
     p.chrom_rank = pr->cand_chrom_rank; p.pool = pr->pool; p.str_off = pr->str_off; p.ctg_off = d_ctg;
     p.cand_off = pr->cand_off; p.mark_read = pr->mark_read; p.read_tag = pr->read_tag;
+    p.n_reads = n_reads;
     const uint32_t contig_bits = bits_for(K - 1), pos_bits = bits_for(pr->max_pos ? pr->max_pos : 0xFFFFFFFFu);
     const uint32_t rank_bits = bits_for(pr->n_chrom_texts - 1);
     p.sh_pos = 2 + contig_bits;
@@ -241,6 +242,16 @@ int duet_rows_run_device(duet_ctx *ctx, const duet_rows_problem *pr, char *out_t
     *out_len = fin[0];
     if (fin[1]) return duet_fail(ctx, DUET_ERR_INVALID, "output buffer too small for the rows");
     return DUET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int duet_rows_run_device(duet_ctx *ctx, const duet_rows_problem *pr, char *out_text, uint64_t out_cap, uint64_t *out_len,
+                         uint32_t *n_rows, void *stream_)
+{
+    return rows_run(ctx, pr, 0xFFFFFFFFu, out_text, out_cap, out_len, n_rows, stream_);      // (the caller vouches: duet_ef.h)
 }
 
 int duet_ef_rows_run_host(duet_ctx *ctx, const duet_ef_problem *pr, const duet_rows_problem *rows, char *out_text, uint64_t out_cap,
@@ -280,7 +291,7 @@ int duet_ef_rows_run_host(duet_ctx *ctx, const duet_ef_problem *pr, const duet_r
     r.cand_plus = (const uint8_t *)dev[3];
     r.cand_off = d.cand_off; r.mark_read = d.mark_read; r.read_tag = d.read_tag;
     uint64_t len = 0;
-    if ((rc = duet_rows_run_device(ctx, &r, (char *)ctx->rows_in[4].ptr, cap, &len, n_rows, s))) return rc;
+    if ((rc = rows_run(ctx, &r, pr->n_reads, (char *)ctx->rows_in[4].ptr, cap, &len, n_rows, s))) return rc;
     if (len > out_cap) return duet_fail(ctx, DUET_ERR_INVALID, "output buffer too small for the rows");
     if (len) HIP_TRY(ctx, hipMemcpy(out_text, ctx->rows_in[4].ptr, len, hipMemcpyDeviceToHost));
     *out_len = len;

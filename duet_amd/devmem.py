@@ -24,7 +24,9 @@ class DeviceProblem(object):
     """An EfSoA uploaded once to HBM, plus output buffers, ready for repeated duet_ef_run_device."""
 
     def __init__(self, soa, svlen_thres, suppread_thres, device='cuda:0', misalign_marks=0, n_cands_max=None,
-                 n_out=1, trailer=0):
+                 n_out=1, trailer=0, tag_guard=None):
+        """tag_guard: tag words written directly behind read_tag, inside the same allocation (at most 8: the 64 bytes that
+        follow every array) -- a kernel that reads the table at n_reads .. n_reads + 7 then reads these, not zeros."""
         import torch
         self.torch = torch
         self.soa = soa
@@ -37,6 +39,10 @@ class DeviceProblem(object):
             raw = torch.zeros(a.nbytes + pad + 64, dtype=torch.uint8, device=self.device)
             if a.nbytes:
                 raw[pad:pad + a.nbytes] = torch.from_numpy(np.frombuffer(a.tobytes(), dtype=np.uint8).copy()).to(self.device)
+            if name == 'read_tag' and tag_guard is not None:
+                g = np.ascontiguousarray(tag_guard, dtype=np.uint64)
+                assert g.nbytes <= 64
+                raw[a.nbytes:a.nbytes + g.nbytes] = torch.from_numpy(g.view(np.uint8).copy()).to(self.device)
             self.buffers[name] = raw
             ptrs[name] = raw.data_ptr() + pad
         # results live in ONE block -- ps u32[n_max] then pred u8[n_max] -- so that a multi-GPU job can

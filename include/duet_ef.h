@@ -66,6 +66,10 @@ typedef enum duet_status {
  * (duplicates kept), each an index into read_tag (already resolved against the candidate's OWN
  * contig table, sv_phasing_fn.py:47-48) or DUET_MARK_ABSENT.  Every candidate has >= 1 mark.
  *
+ * A mark has no tag when its index is DUET_MARK_ABSENT, when its index is >= n_reads, or when its tag
+ * word is all-ones: the three mean the same, for every entry that takes this problem, and no entry
+ * reads read_tag at an index >= n_reads.
+ *
  * cand_ctg_off is ALWAYS a host pointer (K+1 small integers; the library stages it).  The other
  * arrays are device pointers for duet_ef_run_device and host pointers for duet_ef_run_host.
  */
@@ -347,7 +351,11 @@ DUET_API int duet_svim_phased_rows_host(duet_ctx *ctx, const duet_cluster_result
  * All pointers are device memory except cand_ctg_off.  The texts of candidate c are
  * pool[str_off[4c] .. str_off[4c+1]) = CHROM, then REF, ALT and SVTYPE up to str_off[4c+4].
  * cand_chrom_rank[c] = rank of c's CHROM text among the n_chrom_texts distinct CHROM texts in byte order
- * (shorter text first on a common prefix), which is how Python compares the strings at :229. */
+ * (shorter text first on a common prefix), which is how Python compares the strings at :229.
+ *
+ * The struct carries no n_reads: the caller of duet_rows_run_device vouches that every mark_read entry is
+ * DUET_MARK_ABSENT or a valid index into read_tag (duet_ef_rows_run_host takes the size from *prob instead and
+ * treats an index >= n_reads as no tag).  A tag word whose PS field is all-ones is no tag, as for duet_ef_problem. */
 typedef struct duet_rows_problem {
     uint32_t n_contigs, n_cands;
     const uint32_t *cand_ctg_off;        /* HOST [K+1] */

@@ -69,6 +69,7 @@ int duet_oracle_ef(uint32_t K, uint32_t C,
 {
     uint8_t *cls = (uint8_t *)malloc(C ? C : 1);        /* 0,1,2 or 255 = filtered out */
     uint32_t *seeds = (uint32_t *)malloc(sizeof(uint32_t) * (C ? C : 1));
+    uint32_t *done = (uint32_t *)malloc(sizeof(uint32_t) * (C ? C : 1));   /* groups of one candidate already evaluated: seeds, so <= C */
     int rc = 0;
     memset(out_pred, 0, C);
     memset(out_ps, 0, sizeof(uint32_t) * (size_t)C);
@@ -120,6 +121,7 @@ int duet_oracle_ef(uint32_t K, uint32_t C,
                 allhap = hap1 + hap2;
             } else if (cls[c] == 2) {                   /* :85-105 */
                 uint64_t best = 0;
+                uint32_t n_done = 0;
                 for (uint32_t m = b; m < e; ++m) {
                     if (mark_read[m] == ABSENT) continue;
                     if (tag_pc(read_tag[mark_read[m]]) <= PC_MAX) allhap++;
@@ -128,13 +130,12 @@ int duet_oracle_ef(uint32_t K, uint32_t C,
                     if (mark_read[m] == ABSENT) continue;
                     uint64_t t = read_tag[mark_read[m]];
                     if (tag_pc(t) > PC_MAX || !member(one, n_one, tag_ps(t))) continue;
+                    /* an earlier voter of the same PS: that group was evaluated then (a list of the evaluated ones, not a scan
+                     * of the marks in front -- candidates of 500,000 marks) */
                     int seen = 0;
-                    for (uint32_t j = b; j < m && !seen; ++j) {
-                        if (mark_read[j] == ABSENT) continue;
-                        uint64_t u = read_tag[mark_read[j]];
-                        if (tag_pc(u) <= PC_MAX && tag_ps(u) == tag_ps(t)) seen = 1;
-                    }
+                    for (uint32_t j = 0; j < n_done && !seen; ++j) seen = done[j] == tag_ps(t);
                     if (seen) continue;
+                    done[n_done++] = tag_ps(t);
                     uint64_t n = 0, n1 = 0, n2 = 0, s1 = 0, s2 = 0;
                     for (uint32_t j = m; j < e; ++j) {
                         if (mark_read[j] == ABSENT) continue;
@@ -190,5 +191,6 @@ int duet_oracle_ef(uint32_t K, uint32_t C,
     }
     free(cls);
     free(seeds);
+    free(done);
     return rc;
 }

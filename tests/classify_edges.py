@@ -117,8 +117,9 @@ def _no_reads():
 
 def _beyond_table():
     """every third candidate: the marks of ONE read, and between them indices at or beyond the table's size that are not all ones
-    (n_reads, n_reads + 1, 2^31, 2^32 - 2).  Such a candidate sees at most one phase set, so no kernel behind ef_classify walks its
-    marks again (ef_finalize re-gathers only multi-PS candidates)."""
+    (n_reads, n_reads + 1, 2^31, 2^32 - 2).  Such a candidate sees at most one phase set, so this case is ef_classify's alone; the
+    kernels behind it, which walk the marks of multi-PS candidates again, follow the same rule and have their own cases in
+    tests/tag_lookup_edges.py."""
     d = degrees(81, 300, 4, 12)
     s = dealt(81, d)
     R = s.n_reads

@@ -39,8 +39,12 @@ def cands(C, **over):
     return d
 
 
+BLANK = 0xFFFFFFFFFFFFFFFF                      # a read whose tag word is all ones: no tag, as ef_classify reads it
+
+
 def ps_class(marks):
-    return min(len(set(t for t in marks if t is not ABSENT)), 2)
+    """distinct PS over the tagged marks, capped at 2; a word whose PS field is all ones is no tag"""
+    return min(len(set(t & BIG for t in marks if t is not ABSENT and t & BIG != BIG)), 2)
 
 
 def rows_of(d):
@@ -207,6 +211,42 @@ def test_ties_across_ps_classes_and_contigs_stay_in_file_order(ctx):
     got = [int(l.rsplit(b':', 1)[1]) for l in want]
     assert got == [i for p in (20, 500) for k in (0, 1) for c in (0, 1, 2) for i in range(C)
                    if d['pos'][i] == p and d['contig'][i] == k and ps_class(d['marks'][i]) == c]
+
+
+def test_an_all_ones_word_is_no_phase_set(ctx):
+    """equal CHROM, POS and contig: the class alone orders the two.  The second in file order has one real PS and a valid index
+    whose word is all ones -- class 1, in front of the class-2 candidate; counted as a phase set it would stay behind it."""
+    d = cands(4, pos=[300, 500, 500, 700], marks=[[4], [4, 9], [4, BLANK], [BLANK]], ps=[10, 11, 12, 13], pred=[1, 3, 2, 3])
+    want = check(ctx, d).split(b'\n')[:-1]
+    assert [int(l.rsplit(b':', 1)[1]) for l in want] == [10, 12, 11, 13]
+
+
+def test_an_index_beyond_the_table_is_no_phase_set_host_entry(ctx):
+    """the same pair through duet_ef_rows_run_host, which knows n_reads: the second candidate has one real PS and the indices
+    n_reads and 2^31"""
+    from oracle import c_oracle
+    from tests.classify_edges import Soa, as_absent
+    tags = engine.pack_tags([1, 1], [20, 30], [1000, 1010])
+    R = len(tags)
+    marks = [[0, 0], [1, 1], [0, 1], [0, R, 1 << 31]]                             # two seeds, class 2, class 1
+    soa = Soa(cand_ctg_off=[0, 4], read_tag=tags, cand_pos=[1000, 1010, 2000, 2000], cand_svlen=[100] * 4, cand_svread=[5] * 4,
+              cand_refread=[1] * 4, cand_gt_ok=[1] * 4, cand_off=np.cumsum([0] + [len(m) for m in marks]),
+              mark_read=[r for m in marks for r in m])
+    rc, pred, ps = c_oracle.ef(as_absent(soa), 50, 2)
+    assert rc == 0 and pred.all()
+    d = cands(4, pos=soa.cand_pos, svlen=100, pred=pred, ps=ps,
+              marks=[[int(tags[r]) if r < R else ABSENT for r in m] for m in marks])
+    assert [ps_class(m) for m in d['marks']] == [1, 1, 2, 1]
+    texts = [t for i in range(4) for t in (d['chrom'][i], d['ref'][i], d['alt'][i], d['svtype'][i])]
+    pool = np.frombuffer(b''.join(texts), dtype=np.uint8)
+    rows = dict(pool=pool, pool_bytes=len(pool), str_off=np.cumsum([0] + [len(t) for t in texts]), chrom_rank=np.zeros(4),
+                plus=np.ones(4), n_chrom_texts=1, max_pos=2000)
+    want, n_rows = rows_of(d)
+    assert ctx.ef_rows_host(soa, rows, 50, 2) == (want, n_rows)
+    assert [l.split(b'\t')[2] for l in want.split(b'\n')[:-1]] == [b'Duet.1', b'Duet.2', b'Duet.3', b'Duet.4']
+    assert [int(l.split(b'\t')[1]) for l in want.split(b'\n')[:-1]] == [1000, 1010, 2000, 2000]
+    order = sorted(range(4), key=lambda i: (d['pos'][i], ps_class(d['marks'][i])))
+    assert order == [0, 1, 3, 2]                                                 # (the class-1 candidate of POS 2000 first)
 
 
 def test_chrom_texts_sort_as_text(ctx):
