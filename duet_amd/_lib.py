@@ -43,6 +43,7 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_ps_links_device', 'duet_ps_links_host', 'duet_svim_ps_links_device', 'duet_svim_ps_links_host',
            'duet_read_tags_device', 'duet_read_tags_host', 'duet_read_tags_rows_device', 'duet_read_tags_rows_host',
            'duet_ps_join_tags_device', 'duet_ps_join_tags_host', 'duet_ps_join_diff_device', 'duet_ps_join_diff_host',
+           'duet_sv_tags_device', 'duet_sv_tags_host',
            'duet_prims_sort_host', 'duet_prims_scan_host', 'duet_prims_local_sort_host')
 
 
@@ -394,6 +395,8 @@ def load():
                                             [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p]
     lib.duet_ps_join_diff_host.argtypes = lib.duet_ps_join_diff_device.argtypes[:-1]
+    lib.duet_sv_tags_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(ReadTagsProblem)] + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 4
+    lib.duet_sv_tags_host.argtypes = lib.duet_sv_tags_device.argtypes[:-1]
     lib.duet_tune_line_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
@@ -1200,6 +1203,54 @@ class Context(object):
         if rc:
             self._raise(rc)
         return counts
+
+    # -- tags from other SVs (duet_svtags.hip) -------------------------------------------------------------------------------------
+    def sv_tags_host(self, cand_off, mark_read, mark_name, n_names, pred, ps, read_tag, cand_ctg_off=None, cand_contig=None,
+                     mark_order=None, cand_pos=None, pc_cap=None, min_votes=1, pc_new=0, out_tag=None, out_index=None):
+        """duet_sv_tags_host over host arrays (those of read_tags_host; cand_pos is not read) -> (out_tag u64[M], out_index u32[M],
+        counts): one tag word per raw mark, the identity index of the second run, and (n_untagged, n_given, n_own_only).  out_tag /
+        out_index: the arrays written (None: new ones, all-ones and zeros) -- a refused call leaves them as they were."""
+        conv = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)
+        arrays = dict(cand_off=conv(cand_off, np.uint32), mark_order=conv(mark_order, np.uint32), mark_read=conv(mark_read, np.uint32),
+                      mark_name=conv(mark_name, np.uint32), pred=conv(pred, np.uint8), ps=conv(ps, np.uint32),
+                      cand_pos=conv(cand_pos, np.uint32), cand_ctg_off=conv(cand_ctg_off, np.uint32),
+                      cand_contig=conv(cand_contig, np.uint16), read_tag=conv(read_tag, np.uint64))
+        prob = ReadTagsProblem()
+        prob.n_cands, prob.n_marks = len(arrays['pred']), len(arrays['mark_read'])
+        prob.n_reads, prob.n_names = len(arrays['read_tag']), int(n_names)
+        prob.n_contigs = len(arrays['cand_ctg_off']) - 1 if cand_ctg_off is not None else 0
+        spare = np.zeros(1, dtype=np.uint64)
+        for k, a in arrays.items():
+            # (an empty array still has an address: which contig form is meant must not depend on the candidate count)
+            setattr(prob, k, None if a is None else a.ctypes.data if a.size else spare.ctypes.data)
+        M = prob.n_marks
+        if out_tag is None:
+            out_tag = np.full(M, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        if out_index is None:
+            out_index = np.zeros(M, dtype=np.uint32)
+        assert out_tag.dtype == np.uint64 and out_index.dtype == np.uint32 and len(out_tag) == M and len(out_index) == M
+        counts = np.zeros(3, dtype=np.uint32)
+        args = [PC_MAX if pc_cap is None else pc_cap, min_votes, pc_new]
+        if not all(0 <= int(x) <= 0xFFFFFFFF for x in args):
+            raise ValueError('pc_cap, min_votes, pc_new: %r' % (args,))
+        rc = self.lib.duet_sv_tags_host(self.handle, ctypes.byref(prob), int(args[0]), int(args[1]), int(args[2]),
+                                        out_tag.ctypes.data if M else spare.ctypes.data, out_index.ctypes.data if M else spare.ctypes.data,
+                                        counts.ctypes.data)
+        del arrays
+        if rc:
+            self._raise(rc)
+        return out_tag, out_index, tuple(int(x) for x in counts)
+
+    def sv_tags_device(self, prob, out_tag_ptr, out_index_ptr, pc_cap=None, min_votes=1, pc_new=0, stream=0):
+        """duet_sv_tags_device on a resident ReadTagsProblem (cand_ctg_off host memory); out_tag_ptr / out_index_ptr: device room for
+        n_marks words of 8 / 4 bytes -> (n_untagged, n_given, n_own_only)"""
+        counts = np.zeros(3, dtype=np.uint32)
+        rc = self.lib.duet_sv_tags_device(self.handle, ctypes.byref(prob), PC_MAX if pc_cap is None else int(pc_cap), int(min_votes),
+                                          int(pc_new), ctypes.c_void_p(out_tag_ptr), ctypes.c_void_p(out_index_ptr), counts.ctypes.data,
+                                          ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return tuple(int(x) for x in counts)
 
     def strata_build_device(self, prob, truth, chrom_stratum_ptr, n_strata, cand_stratum_ptr, group_stratum_ptr, stream=0):
         """duet_tune_strata_build_device on resident arrays (devmem.DeviceTune), after truth_build_device on the same prob / truth."""

@@ -25,6 +25,9 @@ def pipeline(a):
     if getattr(a, 'join_ps', False):
         extra['join_ps'] = True                             # (--join_ps [--join_min_sv N]: two keywords)
         extra['join_min_sv'] = 2 if getattr(a, 'join_min_sv', None) is None else a.join_min_sv
+    if getattr(a, 'vote_sv_tags', False):
+        extra['vote_sv_tags'] = True                        # (--vote_sv_tags [--sv_tag_min N] [--sv_tag_pc P]: three keywords)
+        extra['sv_tag_min'], extra['sv_tag_pc'] = getattr(a, 'sv_tag_min', None), getattr(a, 'sv_tag_pc', None)
     if a.sv_caller == 'svim-gpu':
         from duet_amd.svim_mode import sv_phasing_from_bams
         last = (lambda *args: sv_phasing_from_bams(*args, **extra)) if extra else sv_phasing_from_bams
@@ -94,6 +97,20 @@ def main(argv):
             raise SystemExit('duet: --join_ps works on the single-GPU path only (not with --gpus > 1)')
         if a.join_min_sv is not None and a.join_min_sv < 1:
             raise SystemExit('duet: --join_min_sv takes an integer >= 1')
+    if (a.sv_tag_min is not None or a.sv_tag_pc is not None) and not a.vote_sv_tags:
+        raise SystemExit('duet: --sv_tag_min and --sv_tag_pc need --vote_sv_tags')
+    if a.vote_sv_tags:
+        # (additive: the second run with the tags of the other SVs, OUTPUT/phased_sv.sv_tags.vcf with its report -- built from the
+        # problem one GPU holds; both runs keep whatever route the other flags give the decision)
+        from duet_amd import sv_tags
+        if a.gpus > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
+            raise SystemExit('duet: --vote_sv_tags works on the single-GPU path only (not with --gpus > 1)')
+        if a.join_ps:
+            raise SystemExit('duet: --vote_sv_tags and --join_ps do not work together')
+        if a.sv_tag_min is not None and a.sv_tag_min < 1:
+            raise SystemExit('duet: --sv_tag_min takes an integer >= 1')
+        if a.sv_tag_pc is not None and not 0 <= a.sv_tag_pc <= sv_tags.PC_LIMIT:
+            raise SystemExit('duet: --sv_tag_pc takes an integer in 0 .. %d' % sv_tags.PC_LIMIT)
     check_envs(a.REFERENCE, a.BAM)
     os.makedirs(a.OUTPUT, exist_ok=True)
     set_logging(a.OUTPUT)

@@ -96,6 +96,7 @@ struct duet_ctx {
     DuetOwnedBufs readtags_ws;             // read tags (duet_readtags.hip): per-candidate workspace 0, per-mark workspace 1, the records before they are released 2; host-run staging 3-11
     DuetOwnedBufs readtags_rows_ws;        // ... its rows: row lengths 0, row offsets 1, tile sums 2, status words and CHROM texts 3; host-run staging 4-7, text 8
     DuetOwnedBufs psjoin_ws;               // joined phase sets (duet_psjoin.hip): the header words, the offsets and the staged table 0, the change codes before they are released 1; host-run staging of the read tags 2, of pred0, ps0, pred1, ps1, cand_contig 3-7
+    DuetOwnedBufs svtags_ws;               // tags from other SVs (duet_svtags.hip): per-candidate workspace 0, per-mark workspace and the staged words 1, per-contributing-mark workspace 2, the records 3; host-run staging 4-11
     DuetOwnedBufs prims_ws;               // diagnostics of the shared primitives (duet_prims_check.hip): one arena, 0
 };
 

@@ -357,6 +357,60 @@ class DeviceSvim(DeviceCluster):
         torch.cuda.current_stream(self.device).synchronize()
         return dict(pred=pred, ps=ps, change=change[:N].cpu().numpy(), counts=counts, n_changed=n_changed)
 
+    def run_sv_tags(self, ctx, names, min_votes=1, pc_new=0, thresholds=None, pc_cap=None, stream=None):
+        """The last run again with the untagged reads voting (--vote_sv_tags): one tag word per raw mark from the last run's calls
+        (duet_sv_tags_device on the resident cluster result, marks and tags; names: dict(mark_name, ...) of
+        NativeIngest.extract(..., names=True)), the problem pointed at those words through the identity index, the fused pipeline
+        -- run_fused, or with thresholds / pc_cap run_thresholds -- on it, and the change code of every candidate between the two
+        runs (duet_ps_join_diff_device under an empty table).  The object keeps the first run's (pred, ps), features and tags;
+        clustering reads no tag, so the cluster result comes out byte for byte what it was (checked) and the candidates line up.
+        Raises ZeroDivisionError where the second run does.
+        -> dict(pred, ps: device tensors of the second run, change u8[N], counts u32[8], marks (n_untagged, n_given, n_own_only))."""
+        torch = self.torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.n_found is None:
+            self.n_found = self.n_cands()
+        N = self.n_found
+        if thresholds is None and pc_cap is not None:
+            thresholds = _lib.TUNE_DEFAULTS
+        if N == 0:
+            return dict(pred=torch.zeros_like(self.out_pred), ps=torch.zeros_like(self.out_ps), change=np.zeros(0, dtype=np.uint8),
+                        counts=np.zeros(8, dtype=np.uint32), marks=(0, 0, 0))
+        mark_name = upload(torch, self.device, names['mark_name'], np.uint32)
+        p = _lib.ReadTagsProblem()
+        p.n_cands, p.n_marks, p.n_reads, p.n_names = N, self.M, self.sv_problem.n_reads, len(names['name_off']) - 1
+        p.cand_off, p.mark_order, p.cand_pos, p.cand_contig = self.result.cand_off, self.result.order, self.result.cand_pos, self.result.cand_contig
+        p.mark_read, p.mark_name, p.read_tag = self.keep['sv_read'].data_ptr(), mark_name.data_ptr(), self.keep['sv_tag'].data_ptr()
+        p.pred, p.ps = self.out_pred.data_ptr(), self.out_ps.data_ptr()
+        tags = torch.zeros(max(self.M, 1) * 8, dtype=torch.uint8, device=self.device)
+        index = torch.zeros(max(self.M, 1) * 4, dtype=torch.uint8, device=self.device)
+        marks = ctx.sv_tags_device(p, tags.data_ptr(), index.data_ptr(), pc_cap=pc_cap, min_votes=min_votes, pc_new=pc_new, stream=stream)
+        fields = ('order', 'cand_off', 'cand_contig', 'cand_type', 'cand_pos', 'cand_span', 'n_cands')
+        before = [self.keep['out_' + k].clone() for k in fields]
+        mine = (self.out_pred, self.out_ps, self.feat, self.vector)
+        self.out_pred, self.out_ps = torch.zeros_like(self.out_pred), torch.zeros_like(self.out_ps)
+        sp = self.sv_problem
+        sp.read_tag, sp.mark_read, sp.n_reads = tags.data_ptr(), index.data_ptr(), self.M
+        try:
+            if thresholds is not None:
+                self.run_thresholds(ctx, thresholds, stream, pc_cap=pc_cap)
+            else:
+                self.run_fused(ctx, stream)
+                ctx.check(stream)
+            pred, ps = self.out_pred, self.out_ps
+        finally:
+            sp.read_tag, sp.mark_read, sp.n_reads = self.keep['sv_tag'].data_ptr(), self.keep['sv_read'].data_ptr(), p.n_reads
+            self.out_pred, self.out_ps, self.feat, self.vector = mine
+        if self.n_found != N or not all(torch.equal(a, self.keep['out_' + k]) for a, k in zip(before, fields)):
+            raise RuntimeError('run_sv_tags: the cluster result changed between the two runs')
+        change = torch.zeros(N + 64, dtype=torch.uint8, device=self.device)
+        counts = ctx.ps_join_diff_device(N, self.out_pred.data_ptr(), self.out_ps.data_ptr(), pred.data_ptr(), ps.data_ptr(),
+                                         np.zeros(0, dtype=_lib.PS_BLOCK_DTYPE), self.sv_problem.n_contigs, change.data_ptr(),
+                                         cand_contig_ptr=self.result.cand_contig, stream=stream)
+        torch.cuda.current_stream(self.device).synchronize()
+        return dict(pred=pred, ps=ps, change=change[:N].cpu().numpy(), counts=counts, marks=marks)
+
     def phased_rows(self, ctx, chrom_texts, stream=None, pred=None, ps=None):
         """Rows of phased_sv.vcf for the last run_fused's candidates, sorted and formatted on the device from the resident
         cluster result and (pred, ps) (duet_svim_phased_rows_device).  chrom_texts: CHROM text per contig.  pred, ps: device

@@ -10,7 +10,10 @@ fields ...) and the Python path then takes over, so the observable behaviour is 
 Set DUET_NATIVE_INGEST=0 to force the Python path; DUET_DEVICE_ROWS=0 keeps the native path but formats the rows on
 the host instead of on the device.
 
-Nine additive keyword arguments (upstream's five positionals are unchanged): `join_ps`, `join_min_sv` = also phase the SVs again
+Twelve additive keyword arguments (upstream's five positionals are unchanged): `vote_sv_tags`, `sv_tag_min`, `sv_tag_pc` = also
+phase the SVs again with the untagged reads voting by the haplotype the other heterozygous calls give them, into
+<home>/phased_sv.sv_tags.vcf with <home>/phased_sv.sv_tags_report.tsv (duet_amd/sv_tags.py; single-GPU native path, by the route
+the other keywords give the decision; not together with `join_ps`), `join_ps`, `join_min_sv` = also phase the SVs again
 over the phase sets that the links of at least join_min_sv candidates tie into one block, into <home>/phased_sv.joined.vcf, with
 <home>/phased_sv.join_blocks.tsv and <home>/phased_sv.join_report.tsv (duet_amd/ps_join.py; single-GPU native path, by the route
 the other keywords give the decision), `read_tags` = also write
@@ -162,10 +165,49 @@ def native_join(home, ing, chrom_list, include_all_ctgs, svlen_thres, suppread_t
     logging.info('  ' + ps_join.summary_text(counts, n_changed, len(rows)))
 
 
+def native_sv_tags(home, ing, chrom_list, include_all_ctgs, ctx, settings, run, pc_cap=None, first=None):
+    """--vote_sv_tags on the ingest's problem, while the ingest is still open and after phased_sv.vcf has been written in full:
+    the first run's calls -- `first` = (pred, ps) where the caller has them, else `run`, soa -> (pred, ps), the route the first run
+    took (the fused rows entry keeps its calls on the device) --, one tag word per mark from those calls
+    (duet_sv_tags_host; settings = (min_votes, pc_new)), `run` again on the expanded problem (read_tag = the words, mark_read = the
+    identity), the change codes (duet_ps_join_diff_host under an empty table), the two files.  phased_sv.sv_tags.vcf is created
+    with its header before the second run: a ZeroDivisionError there leaves it header-only, with no report beside it."""
+    from duet_amd import _lib, sv_tags
+    import numpy as np
+    soa = ing.soa
+    texts = contig_texts(ing, chrom_list, '--vote_sv_tags')
+    logging.info('phase the SVs again with the tags of the other SVs (--vote_sv_tags, at least %d votes, PC %d)' % settings)
+    with open(sv_tags.path_vcf(home), 'wb') as out:
+        out.write(ing.header(include_all_ctgs))
+    body, report, marks = b'', '', (0, 0, 0)
+    counts = np.zeros(8, dtype=np.uint32)
+    if soa.n_cands:
+        pred0, ps0 = first if first is not None else run(soa)
+        nm = ing.mark_names()
+        tags, index, marks = ctx.sv_tags_host(soa.cand_off, soa.mark_read, nm['mark_name'], len(nm['name_off']) - 1, pred0, ps0,
+                                              soa.read_tag, cand_ctg_off=soa.cand_ctg_off, pc_cap=pc_cap, min_votes=settings[0],
+                                              pc_new=settings[1])
+        kw = {name: getattr(soa, name) for name, _ in engine.EfSoA.FIELDS}
+        kw['read_tag'], kw['mark_read'] = tags, index
+        # (a mark is its own read now: the "reads" of contig k are the marks of its candidates)
+        pred1, ps1 = run(engine.EfSoA(read_off=soa.cand_off[soa.cand_ctg_off], **kw))
+        change, counts = ctx.ps_join_diff_host(pred0, ps0, pred1, ps1, np.zeros(0, dtype=_lib.PS_BLOCK_DTYPE), soa.n_contigs,
+                                               cand_ctg_off=soa.cand_ctg_off)
+        body = ing.emit_rows(pred1, ps1)
+        contig = np.repeat(np.arange(soa.n_contigs), np.diff(soa.cand_ctg_off.astype(np.int64)))
+        report = sv_tags.report_text(texts, contig, soa.cand_pos, soa.cand_svlen, change, pred0, ps0, pred1, ps1)
+    with open(sv_tags.path_vcf(home), 'ab') as out:
+        out.write(body)
+    sv_tags.write_report(home, report)
+    logging.info('  ' + sv_tags.summary_text(marks, counts))
+
+
 def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, ps_links=False, read_tags=False,
-            join_min_sv=None):
-    ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf, names=read_tags)
+            join_min_sv=None, sv_tags=None):
+    ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf, names=read_tags or sv_tags is not None)
     if ing is None:
+        if sv_tags is not None:
+            raise RuntimeError('--vote_sv_tags needs the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
         if join_min_sv is not None:
             raise RuntimeError('--join_ps needs the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
         if read_tags:
@@ -181,17 +223,20 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
             contig_texts(ing, chrom_list, '--write_read_tags')
         if join_min_sv is not None:
             contig_texts(ing, chrom_list, '--join_ps')
+        if sv_tags is not None:
+            contig_texts(ing, chrom_list, '--vote_sv_tags')
         write_header(ing, include_all_ctgs, out_vcf)
         log_ingest(ing, chrom_list)
         logging.info('integrate read weight information')
         logging.info('calculate read weight statistics')
         logging.info('predict SV haplotypes in the callset')
         rows = None if os.environ.get('DUET_DEVICE_ROWS') == '0' else ing.rows()
+        calls = None                                # (the first run's (pred, ps), where they came back to the host)
         if rows is not None and ing.soa.n_cands:
             # (pred, ps) stay on the device; it also orders and formats the rows (duet_ef_rows_run_host)
             body = ctx.ef_rows_host(ing.soa, rows, svlen_thres, suppread_thres)[0]
         else:
-            pred, ps = engine.run_ef(ing.soa, svlen_thres, suppread_thres, ctx=ctx)
+            pred, ps = calls = engine.run_ef(ing.soa, svlen_thres, suppread_thres, ctx=ctx)
             body = ing.emit_rows(pred, ps)
         if ps_links:
             links = native_ps_links(ing, chrom_list, svlen_thres, suppread_thres, ctx)
@@ -199,6 +244,7 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
             # (the rows above keep their route, so phased_sv.vcf is what it is without the flag; the calls themselves come from
             # one more E/F run on the same problem)
             pred, ps = engine.run_ef(ing.soa, svlen_thres, suppread_thres, ctx=ctx) if ing.soa.n_cands else ((), ())
+            calls = (pred, ps) if ing.soa.n_cands else calls
             tags = native_read_tags(ing, chrom_list, pred, ps, ctx)
         logging.info('write phased callset into .vcf file')
         if join_min_sv is not None:
@@ -208,6 +254,13 @@ def _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_
             body = b''
             native_join(home, ing, chrom_list, include_all_ctgs, svlen_thres, suppread_thres, ctx, join_min_sv,
                         lambda soa: engine.run_ef(soa, svlen_thres, suppread_thres, ctx=ctx))
+        if sv_tags is not None:
+            # (phased_sv.vcf first and in full: whatever the second run does, it is what it is without the flag)
+            with open(out_vcf, 'ab') as out:
+                out.write(body)
+            body = b''
+            native_sv_tags(home, ing, chrom_list, include_all_ctgs, ctx, sv_tags,
+                           lambda soa: engine.run_ef(soa, svlen_thres, suppread_thres, ctx=ctx), first=calls)
     except BaseException:
         ing.close()
         raise
@@ -226,20 +279,23 @@ def evidence_path(home):
 
 
 def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, vec, pc_cap=None,
-                       evidence=False, ps_links=False, read_tags=False, join_min_sv=None):
+                       evidence=False, ps_links=False, read_tags=False, join_min_sv=None, sv_tags=None):
     """The native path with the decision's constants taken from `vec` (duet_amd/tune.py): ingest, the feature export (pc_cap:
     under that PC cap, duet_ef_features_cap_host), a sweep of one vector that keeps its (pred, ps), the rows.
     evidence: also <home>/phased_sv.evidence.tsv, one row per candidate formatted on the device (duet_evidence_rows_host, the text
     form over the ingest's string pool).  ps_links: also the two phase-set link tables, the voters under the same PC cap.
     read_tags: also <home>/phased_sv.read_tags.tsv from this route's (pred, ps), a read's own tag usable under the same PC cap.
-    join_min_sv (not None: --join_ps): also the run over the joined phase sets, by this route again (native_join)."""
+    join_min_sv (not None: --join_ps): also the run over the joined phase sets, by this route again (native_join).
+    sv_tags (not None: --vote_sv_tags, (min_votes, pc_new)): also the run with the tags of the other SVs, by this route again
+    (native_sv_tags)."""
     from duet_amd import _lib, tune
-    ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf, names=read_tags)
+    ing, chrom_list = load_native(home, thread, include_all_ctgs, caller_vcf, names=read_tags or sv_tags is not None)
     if ing is None:
         raise RuntimeError('--thresholds / --pc_cap / --write_evidence%s need the native ingest, which declined this input '
                            '(or DUET_NATIVE_INGEST=0)' % ((' / --write_ps_links' if ps_links else '') +
                                                           (' / --write_read_tags' if read_tags else '') +
-                                                          (' / --join_ps' if join_min_sv is not None else '')))
+                                                          (' / --join_ps' if join_min_sv is not None else '') +
+                                                          (' / --vote_sv_tags' if sv_tags is not None else '')))
     table, links, tags = None, None, None
     try:
         rows = None
@@ -249,6 +305,8 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
             contig_texts(ing, chrom_list, '--write_read_tags')
         if join_min_sv is not None:
             contig_texts(ing, chrom_list, '--join_ps')
+        if sv_tags is not None:
+            contig_texts(ing, chrom_list, '--vote_sv_tags')
         if evidence and ing.soa.n_cands:
             rows = ing.rows()                       # (before the output file is created: a refusal leaves nothing behind)
             if rows is None:
@@ -285,6 +343,14 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
             native_join(home, ing, chrom_list, include_all_ctgs, svlen_thres, suppread_thres, ctx, join_min_sv,
                         lambda soa: tune.apply(dict(feat=ctx.features_host(soa, svlen_thres, suppread_thres, pc_cap=pc_cap)), vec,
                                                ctx=ctx), pc_cap=pc_cap)
+        if sv_tags is not None:
+            # (phased_sv.vcf first and in full: whatever the second run does, it is what it is without the flag)
+            with open(out_vcf, 'ab') as out:
+                out.write(body)
+            body = b''
+            native_sv_tags(home, ing, chrom_list, include_all_ctgs, ctx, sv_tags,
+                           lambda soa: tune.apply(dict(feat=ctx.features_host(soa, svlen_thres, suppread_thres, pc_cap=pc_cap)), vec,
+                                                  ctx=ctx), pc_cap=pc_cap, first=(pred, ps) if ing.soa.n_cands else None)
     finally:
         ing.close()
     with open(out_vcf, 'ab') as out:
@@ -301,7 +367,12 @@ def _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ct
 
 
 def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, device=0, gpus=1, thresholds=None, pc_cap=None,
-               evidence=False, ps_links=False, read_tags=False, join_ps=False, join_min_sv=2):
+               evidence=False, ps_links=False, read_tags=False, join_ps=False, join_min_sv=2, vote_sv_tags=False, sv_tag_min=None,
+               sv_tag_pc=None):
+    # (additive: the second run with the tags of the other SVs -- the native single-GPU path, whichever route the decision takes;
+    # refused before anything is opened)
+    from duet_amd import sv_tags as sv_tags_mod
+    sv_tags = sv_tags_mod.check_settings(vote_sv_tags, sv_tag_min, sv_tag_pc, gpus=gpus, join_ps=join_ps)
     if join_ps:
         # (additive: the run over the joined phase sets -- the native single-GPU path, whichever route the decision takes)
         from duet_amd import ps_join
@@ -343,7 +414,7 @@ def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, devi
             raise ValueError('thresholds: single-GPU path only')
         _native_thresholds(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf,
                            engine.default_context(int(device)), thresholds, pc_cap, evidence=bool(evidence), ps_links=bool(ps_links),
-                           read_tags=bool(read_tags), join_min_sv=join_min_sv)
+                           read_tags=bool(read_tags), join_min_sv=join_min_sv, sv_tags=sv_tags)
         done = True
     # (DUET_FORCE_RANKS=1: the one-process-per-GPU path even with one GPU -- rank 0 of 1 over RCCL; tests use it to take the
     # collective through the real backend on a one-GPU box)
@@ -353,7 +424,7 @@ def sv_phasing(home, svlen_thres, suppread_thres, thread, include_all_ctgs, devi
     if not done:
         ctx = engine.default_context(int(device))
         if not _native(home, svlen_thres, suppread_thres, thread, include_all_ctgs, caller_vcf, out_vcf, ctx, ps_links=bool(ps_links),
-                       read_tags=bool(read_tags), join_min_sv=join_min_sv):
+                       read_tags=bool(read_tags), join_min_sv=join_min_sv, sv_tags=sv_tags):
             print_sv_header(caller_vcf, out_vcf, include_all_ctgs)
             rows = generate_phased_callset(caller_vcf, home + '/snp_phasing/', svlen_thres, suppread_thres, thread,
                                            include_all_ctgs, ctx=ctx)

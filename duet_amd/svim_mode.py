@@ -18,7 +18,7 @@ from duet_amd.read_file import init_chrom_list
 
 
 def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_cap=None, evidence_texts=None, ps_links=False,
-                   read_tag_texts=None, join_min_sv=None):
+                   read_tag_texts=None, join_min_sv=None, sv_tags=None):
     """-> compute(extracted arrays, svlen_thres, suppread_thres, max_dist, depth_bin) -> dict of result arrays, on ctx's GPU:
     stage A0 -> adapter -> step E/F in one device pipeline (duet_svim_phase_device).  chrom_texts (CHROM text per contig): the
     extracted arrays carry the marks' read names, and the result also holds `calls`, the rows of sv_calling/variants.vcf formatted
@@ -33,9 +33,14 @@ def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_ca
     (records, rows) of the read tags of the calls just made (duet_read_tags_device and its rows; a tag usable under pc_cap).
     join_min_sv (--join_ps; needs row_texts): the result also holds `join`, the run over the phase sets that the links of at least
     that many candidates join (DeviceSvim.run_joined): dict(blocks, pred, ps, change, counts, n_changed, rows, n_rows), or
-    dict(blocks, error) when the joined run raised ZeroDivisionError."""
+    dict(blocks, error) when the joined run raised ZeroDivisionError.
+    sv_tags (--vote_sv_tags, (min_votes, pc_new); needs row_texts and the marks' read names): the result also holds `sv_tags`, the
+    run with the untagged reads voting by the tags the other SVs give them (DeviceSvim.run_sv_tags): dict(pred, ps, change, counts,
+    marks, rows, n_rows), or dict(error) when that run raised ZeroDivisionError."""
     if evidence_texts is not None and thresholds is None:
         raise ValueError('the evidence table needs a threshold vector')
+    if sv_tags is not None and row_texts is None:
+        raise ValueError('the run with the tags of the other SVs needs the CHROM texts of its rows')
     if join_min_sv is not None and row_texts is None:
         raise ValueError('the joined run needs the CHROM texts of its rows')
 
@@ -75,6 +80,15 @@ def device_compute(ctx, chrom_texts=None, row_texts=None, thresholds=None, pc_ca
                 join['pred'], join['ps'] = join['pred'][:N].cpu().numpy(), join['ps'][:N].cpu().numpy().view(np.uint32)
             except ZeroDivisionError as e:
                 join['error'] = e                                   # (raised once phased_sv.vcf has been written in full)
+        if sv_tags is not None:
+            res['sv_tags'] = second = dict()
+            try:
+                second.update(ds.run_sv_tags(ctx, got, min_votes=sv_tags[0], pc_new=sv_tags[1], thresholds=thresholds, pc_cap=pc_cap))
+                second['rows'], second['n_rows'] = ds.phased_rows(ctx, row_texts, pred=second['pred'], ps=second['ps'])
+                N = len(second['change'])
+                second['pred'], second['ps'] = second['pred'][:N].cpu().numpy(), second['ps'][:N].cpu().numpy().view(np.uint32)
+            except ZeroDivisionError as e:
+                second['error'] = e                                 # (raised once phased_sv.vcf has been written in full)
         return res
     return compute
 
@@ -462,7 +476,7 @@ def rank_main(argv):
 
 def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, cluster_max_distance=0.9, device=0,
                          gpus=1, write_sv_calls=False, thresholds=None, pc_cap=None, evidence=False, ps_links=False, read_tags=False,
-                         join_ps=False, join_min_sv=2):
+                         join_ps=False, join_min_sv=2, vote_sv_tags=False, sv_tag_min=None, sv_tag_pc=None):
     """`duet ... -b svim-gpu -c <max distance>`: SV calling (signatures + clustering, what `-b svim` delegates to the
     external `svim alignment ... --cluster_max_distance c`, sv_calling.py:13-15) AND SV phasing on the GPU, from the
     haplotagged BAMs of <home>/snp_phasing -> <home>/phased_sv.vcf.  The clustering half is this repository's own rule
@@ -482,7 +496,13 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
     join_ps, join_min_sv (--join_ps [--join_min_sv N]): also the same pipeline again on the read tags remapped over the phase sets
     that the links of at least N candidates tie into one block -> <home>/phased_sv.joined.vcf, with
     <home>/phased_sv.join_blocks.tsv and <home>/phased_sv.join_report.tsv (duet_amd/ps_join.py); single-GPU path only, by the
-    route the other keywords give the decision.  phased_sv.vcf is written first and in full."""
+    route the other keywords give the decision.  phased_sv.vcf is written first and in full.
+    vote_sv_tags, sv_tag_min, sv_tag_pc (--vote_sv_tags [--sv_tag_min N] [--sv_tag_pc P]): also the same pipeline again with the
+    untagged reads voting by the haplotype the other heterozygous calls give them -> <home>/phased_sv.sv_tags.vcf with
+    <home>/phased_sv.sv_tags_report.tsv (duet_amd/sv_tags.py); single-GPU path only, not together with join_ps, by the route the
+    other keywords give the decision.  phased_sv.vcf is written first and in full."""
+    from duet_amd import sv_tags as sv_tags_mod
+    sv_tags = sv_tags_mod.check_settings(vote_sv_tags, sv_tag_min, sv_tag_pc, gpus=gpus, join_ps=join_ps)
     if join_ps:
         from duet_amd import ps_join
         if int(gpus) > 1 or os.environ.get('DUET_FORCE_RANKS') == '1':
@@ -553,10 +573,11 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
         texts = spelled_contigs(home, chroms)
         return device_compute(ctx if ctx is not None else engine.default_context(int(device)), texts if write_sv_calls else None,
                               row_texts=texts, thresholds=thresholds, pc_cap=pc_cap, evidence_texts=texts if evidence else None,
-                              ps_links=bool(ps_links), read_tag_texts=texts if read_tags else None, join_min_sv=join_min_sv)(*args)
+                              ps_links=bool(ps_links), read_tag_texts=texts if read_tags else None, join_min_sv=join_min_sv,
+                              sv_tags=sv_tags)(*args)
     res = phase_from_bams(home, svlen_thres, suppread_thres, thread, include_all_ctgs, max_dist=cluster_max_distance,
                           min_sv_size=max(int(svlen_thres), 1), names=bool(write_sv_calls), compute=compute,
-                          keep_names=bool(read_tags))
+                          keep_names=bool(read_tags) or sv_tags is not None)
     # the data rows come sorted and formatted from the device; without a single mark nothing ran and there are none
     if 'rows' not in res and len(res['pred']):
         raise RuntimeError('svim-gpu: the device pipeline returned candidates without the rows of phased_sv.vcf')
@@ -590,7 +611,31 @@ def sv_phasing_from_bams(home, svlen_thres, suppread_thres, thread, include_all_
             out.write(rows)
     if join_min_sv is not None:
         write_join(home, chroms, res, join_min_sv)
+    if sv_tags is not None:
+        write_sv_tags(home, chroms, res, sv_tags)
     logging.info('%s SV CALLING + PHASING COMPLETED IN %ss %s' % (bar, round(time.time() - t0, 3), bar))
+
+
+def write_sv_tags(home, chroms, res, settings):
+    """The two files of --vote_sv_tags from the result's `sv_tags` (device_compute), after phased_sv.vcf has been written in full.
+    phased_sv.sv_tags.vcf is created with its header first: where the second run raised ZeroDivisionError it stays header-only, no
+    report is written and the error is raised here.  Without a single mark nothing ran: the header lines alone."""
+    from duet_amd import sv_tags
+    logging.info('phase the SVs again with the tags of the other SVs (--vote_sv_tags, at least %d votes, PC %d)' % settings)
+    texts = spelled_contigs(home, chroms)
+    second = res.get('sv_tags', dict())
+    with open(sv_tags.path_vcf(home), 'w') as out:
+        out.write(header_text(home, chroms))
+    if 'error' in second:
+        raise second['error']
+    with open(sv_tags.path_vcf(home), 'ab') as out:
+        out.write(bytes(memoryview(np.ascontiguousarray(second.get('rows', np.zeros(0, dtype=np.uint8))))))
+    report = ''
+    if 'change' in second:
+        report = sv_tags.report_text(texts, res['cand_contig'], res['cand_pos'], res['cand_span'], second['change'], res['pred'],
+                                     res['ps'], second['pred'], second['ps'])
+    sv_tags.write_report(home, report)
+    logging.info('  ' + sv_tags.summary_text(second.get('marks', (0, 0, 0)), second.get('counts', np.zeros(8, dtype=np.uint32))))
 
 
 def write_join(home, chroms, res, min_sv):

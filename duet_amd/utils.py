@@ -6,7 +6,8 @@ existing command line works unchanged.  Two additive options select the device (
 over several GPUs (--gpus); --thresholds and --pc_cap replace the decision's constants on the single-GPU path,
 --write_evidence adds the per-candidate evidence table there, --write_ps_links the phase-set link tables, --write_read_tags the
 per-read table of the haplotypes the phased SVs place their supporting reads on, --join_ps [--join_min_sv N] a second run over the
-phase sets that the SVs tie into one block.
+phase sets that the SVs tie into one block, --vote_sv_tags [--sv_tag_min N] [--sv_tag_pc P] a second run in which the untagged
+reads vote with the haplotype the other SV calls give them.
 """
 
 import argparse
@@ -84,6 +85,16 @@ def build_parser():
                          'native path, or -b svim-gpu)')
     ap.add_argument('--join_min_sv', type=int, default=None,
                     help='with --join_ps: a link joins two phase sets only when at least this many SV candidates agree on it [2]')
+    ap.add_argument('--vote_sv_tags', action='store_true',
+                    help='also phase the SVs again with the untagged reads voting: a read without a WhatsHap tag gets the haplotype '
+                         'that the OTHER heterozygous SV calls listing it place it on; writes OUTPUT/phased_sv.sv_tags.vcf and '
+                         'OUTPUT/phased_sv.sv_tags_report.tsv (the calls that changed); phased_sv.vcf stays what it is; one GPU only '
+                         '(the native path, or -b svim-gpu); not together with --join_ps')
+    ap.add_argument('--sv_tag_min', type=int, default=None,
+                    help='with --vote_sv_tags: a read gets a tag only when the other calls favour one haplotype by at least this many '
+                         'marks [1]')
+    ap.add_argument('--sv_tag_pc', type=int, default=None,
+                    help='with --vote_sv_tags: the PC the derived tags carry, 0 .. 2^30 - 3 [0]')
     ap.add_argument('--write_sv_calls', action='store_true',
                     help='with -b svim-gpu, also write the clustered SV calls to OUTPUT/sv_calling/variants.vcf')
     for name, text in _POSITIONALS:

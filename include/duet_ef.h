@@ -1016,6 +1016,48 @@ DUET_API int duet_ps_join_diff_host(duet_ctx *ctx, uint32_t n_cands, const uint8
                                     uint32_t *counts);
 
 /* ---------------------------------------------------------------------------------------------
+ * Tags from other SVs (duet_svtags.hip): a mark whose read has no tag word is given the haplotype that the
+ * OTHER heterozygous calls listing the read place it on.  A call must not vote for itself, so the tag is per mark and
+ * leave-one-out: the evidence for mark (c, r) is every het call listing r except c.  The output is one tag word per RAW MARK, in
+ * read_tag's layout (hap:2 | pc:30 | ps:32): the second run is the ordinary run with read_tag = out_tag, n_reads = n_marks and
+ * mark_read = out_index (the identity, which the entry also writes).  tests/sv_tags_ref.py states the rule in plain Python.
+ * Nothing here has been tried on real data; which reads get a tag, the PC they get and how ties break are CHOICES.
+ *
+ *   Problem     the duet_read_tags_problem of the section above (cand_pos is not read and may be NULL).  A raw mark belongs to the
+ *               candidate whose CSR slot names it; a raw mark that no slot names belongs to none.
+ *   Kept        a mark that has a tag (index not DUET_MARK_ABSENT, < n_reads, word not all-ones) keeps its word bit for bit,
+ *               whatever hap and pc it holds: only reads without any tag word are given one (the narrow choice: the PS-class of
+ *               every tagged mark stays what it was).
+ *   Evidence    for an untagged mark m of candidate c with name n = mark_name[m]: the section-20 records of n, one per (n, P) over
+ *               the marks of candidates with pred 1 or 2, with n_h1 and n_h2 (a read listed twice counts twice).
+ *   Own part    k = the marks of c whose name is n.  pred[c] == 1: the record (n, ps[c]) loses k from n_h1; pred[c] == 2: from
+ *               n_h2; otherwise nothing is taken out.
+ *   Choice      d_P = n_h1' - n_h2' (signed 64-bit).  The P with the largest |d_P|, ties to the smaller P as a full unsigned
+ *               32-bit number.  |d_P| < min_votes, or no record: out_tag[m] is all-ones.  Otherwise hap = 1 if d_P > 0 else 2,
+ *               pc = pc_new, ps = P.
+ *   Counts      counts[0] n_untagged: the marks without a tag; counts[1] n_given: those that received one; counts[2] n_own_only:
+ *               those that would have received one with the own part left in and receive none without it.  Sums of popcounts
+ *               added with integer atomics: independent of the order of arrival, two runs give identical bytes.
+ *   Refused     DUET_ERR_INVALID, nothing written: pred > 3; a cand_off that descends or passes n_marks; a mark_name >= n_names (every raw mark is checked); a mark_order
+ *               entry >= n_marks, or a raw mark named by two slots (its tag would depend on which slot is asked); a cand_ctg_off
+ *               that does not ascend from 0 to n_cands; both or neither of cand_ctg_off and cand_contig; pc_cap or pc_new above
+ *               2^30 - 3; min_votes == 0; a NULL array that is needed; section 20's contradiction (contributing marks of one
+ *               name on two contigs or with two mark_read values).  pc_cap is the cap of the run the tags are made for; the rule
+ *               itself does not read it.
+ * n_cands == 0 or n_marks == 0: DUET_OK, zero counts, nothing written.  No candidate with pred 1 or 2: every untagged mark is
+ * all-ones.
+ * _device: the arrays of *prob (cand_ctg_off aside: HOST), out_tag[n_marks] and out_index[n_marks] are device memory, counts[3]
+ * host memory.  THREE host round trips of a few words: the contributing marks V and the argument refusals; the record and run
+ * counts; the contradiction words and the counters.  The words wait in the workspace until the last is read, then are copied to
+ * out_tag asynchronously on `stream`.  _host: host arrays; uploads, runs the same kernels, copies back, synchronises.
+ * The workspace is the entry's own (44 bytes per contributing mark + the sort's histogram, 12 per mark, 8 per candidate, 16 per
+ * record; grown, never shrunk): a call changes nothing that any other entry returns. */
+DUET_API int duet_sv_tags_device(duet_ctx *ctx, const duet_read_tags_problem *prob, uint32_t pc_cap, uint32_t min_votes, uint32_t pc_new,
+                                 uint64_t *out_tag, uint32_t *out_index, uint32_t *counts, void *stream);
+DUET_API int duet_sv_tags_host(duet_ctx *ctx, const duet_read_tags_problem *prob, uint32_t pc_cap, uint32_t min_votes, uint32_t pc_new,
+                               uint64_t *out_tag, uint32_t *out_index, uint32_t *counts);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics: the shared device primitives (duet_amd/csrc/duet_prims.hip.h) on host arrays, each run unchanged on the
  * context's own stream with a workspace sized as the primitive's comments prescribe (duet_amd/csrc/duet_prims_check.hip).  No
  * product path calls these; tests/test_gpu_prims.py compares them with numpy at every plan boundary.  n == 0: DUET_OK, nothing is
