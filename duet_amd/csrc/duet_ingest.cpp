@@ -15,6 +15,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <string_view>
 #include <thread>
@@ -179,6 +181,17 @@ struct NameTable {
     }
 };
 
+// Worker threads of one stage.  Every stage joins them itself; the destructor joins whatever is still running when an exception passes
+// through -- std::thread's constructor may throw std::system_error with earlier workers at work, and destroying a joinable
+// std::thread would end the process before guarded() (below) sees the exception.
+struct Pool : std::vector<std::thread> {
+    ~Pool()
+    {
+        for (std::thread &t : *this)
+            if (t.joinable()) t.join();
+    }
+};
+
 // A whole file in memory that nobody has touched before the readers do: malloc, not a vector (whose resize would write every page
 // from ONE thread first -- 30 ms per 100 MB), filled by `threads` readers with pread, each first-touching its own stretch.
 struct RawBuf {
@@ -218,7 +231,7 @@ bool read_file_parallel(const char *path, RawBuf &buf, int threads)
             at += (size_t)got;
         }
     };
-    std::vector<std::thread> pool;
+    Pool pool;
     for (int t = 1; t < T; ++t) pool.emplace_back(work, t);
     work(0);
     for (auto &th : pool) th.join();
@@ -300,6 +313,26 @@ int unsupported(duet_ingest *g, const std::string &why)
     return DUET_INGEST_UNSUPPORTED;
 }
 
+// No exception leaves an extern "C" entry (under ctypes it would end the process): every entry that allocates runs its body
+// through this.  A failed allocation or a length error becomes DUET_INGEST_UNSUPPORTED with a reason, so that the Python host path
+// takes over.  ("out of memory" fits the string's own buffer: reporting it allocates nothing.)
+template <class F>
+int guarded(std::string &err, F &&body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        err = "out of memory";
+    } catch (const std::length_error &) {
+        err = "length error";
+    } catch (const std::exception &e) {
+        try { err = std::string("exception: ") + e.what(); } catch (...) { err = "exception"; }
+    } catch (...) {
+        err = "exception";
+    }
+    return DUET_INGEST_UNSUPPORTED;
+}
+
 // ---------------------------------------------------------------------------------------------
 // BGZF / BAM
 // ---------------------------------------------------------------------------------------------
@@ -307,28 +340,38 @@ struct Block {
     size_t in_off, in_len, out_off, out_len;
 };
 
-int inflate_bgzf(duet_ingest *g, const std::vector<char> &file, std::vector<unsigned char> &out, int threads)
+// A member's ISIZE is what the inflate below is sized by, before a byte is inflated: it has to be one the format allows (at most
+// 65536, SAMv1 4.1) and one the member's deflate body can reach (deflate gives at most 258 bytes per two bits: 1032 per byte).
+constexpr size_t kBgzfMaxIsize = 65536, kDeflateMaxRatio = 1032;
+
+int inflate_bgzf(std::string &err, const std::vector<char> &file, std::vector<unsigned char> &out, int threads)
 {
+    auto decline = [&](const char *why) { err = why; return DUET_INGEST_UNSUPPORTED; };
     std::vector<Block> blocks;
     size_t p = 0, total = 0;
     const unsigned char *d = (const unsigned char *)file.data();
     while (p < file.size()) {
         if (p + 18 > file.size() || d[p] != 31 || d[p + 1] != 139 || d[p + 2] != 8 || !(d[p + 3] & 4))
-            return unsupported(g, "not a BGZF stream");
+            return decline("not a BGZF stream");
         const unsigned xlen = d[p + 10] | (d[p + 11] << 8);
         size_t q = p + 12, xend = p + 12 + xlen;
         int bsize = -1;
+        // (a subfield's payload is read only when all of it lies inside the extra field, the extra field inside the file)
         while (q + 4 <= xend && xend <= file.size()) {
             const unsigned slen = d[q + 2] | (d[q + 3] << 8);
+            if (q + 4 + slen > xend) break;
             if (d[q] == 'B' && d[q + 1] == 'C' && slen == 2) bsize = d[q + 4] | (d[q + 5] << 8);
             q += 4 + slen;
         }
-        if (bsize < 0) return unsupported(g, "gzip member without BGZF block size");
+        if (bsize < 0) return decline("gzip member without BGZF block size");
         const size_t blen = (size_t)bsize + 1;
-        if (p + blen > file.size() || blen < xlen + 20) return unsupported(g, "truncated BGZF block");
+        if (p + blen > file.size() || blen < xlen + 20) return decline("truncated BGZF block");
         const unsigned char *tail = d + p + blen - 4;
         const size_t isize = tail[0] | (tail[1] << 8) | (tail[2] << 16) | ((size_t)tail[3] << 24);
-        blocks.push_back(Block{p + 12 + xlen, blen - xlen - 20, total, isize});
+        const size_t in_len = blen - xlen - 20;
+        if (isize > kBgzfMaxIsize) return decline("BGZF member with ISIZE above 65536");
+        if (isize > kDeflateMaxRatio * in_len) return decline("BGZF member with ISIZE above what its body can inflate to");
+        blocks.push_back(Block{p + 12 + xlen, in_len, total, isize});
         total += isize;
         p += blen;
     }
@@ -341,25 +384,27 @@ int inflate_bgzf(duet_ingest *g, const std::vector<char> &file, std::vector<unsi
             const size_t i = next.fetch_add(1);
             if (i >= blocks.size() || bad.load()) return;
             const Block &b = blocks[i];
-            if (b.out_len == 0) continue;
+            // (a member that claims ISIZE 0 -- the end-of-file marker -- is inflated too, into a spare byte that has to stay
+            // unused: a body that holds data under ISIZE 0 would otherwise drop out of the stream unseen)
+            unsigned char spare;
             memset(&zs, 0, sizeof(zs));
             if (inflateInit2(&zs, -15) != Z_OK) { bad = 1; return; }
             zs.next_in = (Bytef *)(d + b.in_off);
             zs.avail_in = (uInt)b.in_len;
-            zs.next_out = out.data() + b.out_off;
-            zs.avail_out = (uInt)b.out_len;
+            zs.next_out = b.out_len ? out.data() + b.out_off : &spare;
+            zs.avail_out = b.out_len ? (uInt)b.out_len : 1u;
             const int rc = inflate(&zs, Z_FINISH);
             inflateEnd(&zs);
-            if (rc != Z_STREAM_END || zs.avail_out != 0) { bad = 1; return; }
+            if (rc != Z_STREAM_END || zs.total_out != b.out_len) { bad = 1; return; }
         }
     };
     int nt = threads < 1 ? 1 : (threads > 16 ? 16 : threads);
     if (blocks.size() < 8) nt = 1;
-    std::vector<std::thread> pool;
+    Pool pool;
     for (int t = 1; t < nt; ++t) pool.emplace_back(work);
     work();
     for (auto &t : pool) t.join();
-    if (bad.load()) return unsupported(g, "BGZF inflate failed");
+    if (bad.load()) return decline("BGZF inflate failed");
     return DUET_INGEST_OK;
 }
 
@@ -370,10 +415,13 @@ struct Aux {
     size_t next;
 };
 
+inline bool aux_is_int(unsigned char t) { return t == 'c' || t == 'C' || t == 's' || t == 'S' || t == 'i' || t == 'I'; }
+
 // length of one aux field's value; 0 on error
 bool aux_step(const unsigned char *b, size_t p, size_t end, Aux &a)
 {
     if (p + 3 > end) return false;
+    if ((b[p] | b[p + 1]) & 0x80) return false;       // (the Python reader decodes the tag as ASCII and raises)
     a.tag[0] = (char)b[p];
     a.tag[1] = (char)b[p + 1];
     a.type = b[p + 2];
@@ -392,6 +440,7 @@ bool aux_step(const unsigned char *b, size_t p, size_t end, Aux &a)
             if (q + 5 > end) return false;
             const unsigned char sub = b[q];
             const size_t cnt = b[q + 1] | (b[q + 2] << 8) | (b[q + 3] << 16) | ((size_t)b[q + 4] << 24);
+            if (!aux_is_int(sub) && sub != 'f') return false;      // (SAMv1 4.2.4 has seven subtypes)
             const size_t w = (sub == 'c' || sub == 'C') ? 1 : ((sub == 's' || sub == 'S') ? 2 : 4);
             q += 5 + w * cnt;
             break;
@@ -402,8 +451,6 @@ bool aux_step(const unsigned char *b, size_t p, size_t end, Aux &a)
     a.next = q;
     return true;
 }
-
-inline bool aux_is_int(unsigned char t) { return t == 'c' || t == 'C' || t == 's' || t == 'S' || t == 'i' || t == 'I'; }
 
 long long aux_int(const unsigned char *b, const Aux &a)
 {
@@ -459,6 +506,12 @@ void parse_bam_record(const unsigned char *b, size_t p, size_t end, BamRec &o)
     o.name_len = (uint32_t)name_len;
     q += l_name + 4 * (size_t)n_cig + (l_seq + 1) / 2 + l_seq;
     if (q > end) return decline("corrupt BAM record");
+    if (!l_name) return decline("BAM record without a read name");       // (l_read_name counts the terminating NUL)
+    {   // every record's name, tagged or not: the Python reader decodes it as ASCII and raises
+        unsigned char acc = 0;
+        for (size_t i = 0; i < name_len; ++i) acc |= (unsigned char)name[i];
+        if (acc & 0x80) return decline("non-ASCII read name");
+    }
     // SAMv1 section 4.2.2: a CIGAR of more than 65535 operations is stored as the placeholder <l_seq>S<ref_len>N with
     // the real operations in a CG:B:I tag; htslib -- hence the `samtools view` text the reference parses -- moves
     // them back on reading and drops the tag, when the record is placed, its first stored operation soft-clips the
@@ -527,8 +580,6 @@ void parse_bam_record(const unsigned char *b, size_t p, size_t end, BamRec &o)
             return decline("HP/PS neighbours of PC are not integers");
         const long long hap = aux_int(b, last[0]), pc = aux_int(b, t2), ps = aux_int(b, last[2]);
         if (pc < 0 || ps < 0 || ps > 0xFFFFFFFELL) return decline("PC/PS out of range");
-        for (size_t i = 0; i < name_len; ++i)
-            if ((unsigned char)name[i] >= 0x80) return decline("non-ASCII read name");
         const uint64_t code = (hap == 1 || hap == 2) ? (uint64_t)hap : 3ull;
         const uint64_t pcc = pc > (long long)kPcSat ? kPcSat : (uint64_t)pc;
         const uint64_t word = (code << 62) | (pcc << 32) | (uint64_t)ps;
@@ -572,10 +623,9 @@ static int build_header(duet_ingest *g, int include_all_ctgs, std::string &out)
 
 extern "C" {
 
-duet_ingest *duet_ingest_create(int n_contigs, const char *const *contig_names)
+static duet_ingest *create_impl(int n_contigs, const char *const *contig_names)
 {
-    if (n_contigs < 0 || (n_contigs > 0 && !contig_names)) return nullptr;
-    duet_ingest *g = new duet_ingest();
+    std::unique_ptr<duet_ingest> g(new duet_ingest());
     g->contigs.reserve(n_contigs);
     for (int k = 0; k < n_contigs; ++k) {
         g->contigs.emplace_back(contig_names[k] ? contig_names[k] : "");
@@ -589,16 +639,34 @@ duet_ingest *duet_ingest_create(int n_contigs, const char *const *contig_names)
     g->tables.resize(n_contigs);
     g->tags.resize(n_contigs);
     g->bam_has_aln.assign(n_contigs, 0);
-    return g;
+    return g.release();
+}
+
+duet_ingest *duet_ingest_create(int n_contigs, const char *const *contig_names)
+{
+    if (n_contigs < 0 || (n_contigs > 0 && !contig_names)) return nullptr;
+    try { return create_impl(n_contigs, contig_names); } catch (...) { return nullptr; }
 }
 
 void duet_ingest_destroy(duet_ingest *g) { delete g; }
 const char *duet_ingest_error(const duet_ingest *g) { return g ? g->err.c_str() : "null"; }
 void duet_ingest_free(void *p) { free(p); }
 
-int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int threads)
+}  // extern "C"
+
+namespace {
+
+// What an alignment may reach in SVIM mode: mark positions are 1-based uint32_t with 0xFFFFFFFF kept free, the depth offsets of
+// duet_ingest_marks are uint32_t, and the depth vector is sized by the furthest reference end -- so an alignment that ends past
+// 2^32 - 1, a mark at or past 2^32 - 1 and a contig of more than 2^28 depth bins are declined (oracle/svim_oracle.py has no such
+// limits; every input accepted here lies inside them).
+constexpr uint64_t kMaxRefEnd = 0xFFFFFFFFull, kMaxDepthBins = 1ull << 28;
+
+// The body of duet_ingest_add_bam.  It reports through `err`, not g->err, and touches only contig's own table, tags and flag (and,
+// in SVIM mode, the shared mark arrays): duet_ingest_add_bams runs it for several contigs side by side.
+int add_bam_impl(duet_ingest *g, int contig, const char *path, int threads, std::string &err)
 {
-    if (!g || contig < 0 || contig >= (int)g->contigs.size() || !path) return DUET_INGEST_INVALID;
+    auto decline = [&](const std::string &why) { err = why; return DUET_INGEST_UNSUPPORTED; };
     const bool timing = getenv("DUET_INGEST_TIMING") != nullptr;
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
@@ -608,24 +676,29 @@ int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int thread
         t_last = now;
     };
     std::vector<char> file;
-    if (!read_file(path, file)) { g->err = std::string("cannot read ") + path; return DUET_INGEST_IO; }
+    if (!read_file(path, file)) { err = std::string("cannot read ") + path; return DUET_INGEST_IO; }
     if (file.empty()) return DUET_INGEST_OK;                       // an empty file prints nothing (no alignments)
     lap("read");
     std::vector<unsigned char> buf;
-    int rc = inflate_bgzf(g, file, buf, threads);
+    int rc = inflate_bgzf(err, file, buf, threads);
     if (rc) return rc;
     lap("inflate");
     const unsigned char *b = buf.data();
     const size_t n = buf.size();
     auto u32 = [&](size_t p) { return (uint32_t)(b[p] | (b[p + 1] << 8) | (b[p + 2] << 16) | ((uint32_t)b[p + 3] << 24)); };
-    if (n < 12 || memcmp(b, "BAM\1", 4) != 0) return unsupported(g, "not a BAM file");
+    if (n < 12 || memcmp(b, "BAM\1", 4) != 0) return decline("not a BAM file");
     size_t p = 8 + (size_t)u32(4);
-    if (p + 4 > n) return unsupported(g, "truncated BAM header");
+    if (p + 4 > n) return decline("truncated BAM header");
     const uint32_t n_ref = u32(p);
     p += 4;
     for (uint32_t r = 0; r < n_ref; ++r) {
-        if (p + 4 > n) return unsupported(g, "truncated BAM header");
-        p += 4 + (size_t)u32(p) + 4;
+        if (p + 4 > n) return decline("truncated BAM header");
+        const size_t l_name = u32(p);
+        if (p + 8 + l_name > n) return decline("truncated BAM header");
+        unsigned char acc = 0;                        // (the Python reader decodes the reference names as ASCII and raises)
+        for (size_t i = 0; i < l_name; ++i) acc |= b[p + 4 + i];
+        if (acc & 0x80) return decline("non-ASCII reference name");
+        p += 8 + l_name;
     }
     NameTable &tab = g->tables[contig];
     std::vector<uint64_t> &tags = g->tags[contig];
@@ -642,7 +715,7 @@ int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int thread
     std::vector<size_t> at;
     while (p + 4 <= n) {
         const size_t bs = u32(p), end = p + 4 + bs;
-        if (end > n || bs < 32) return unsupported(g, "truncated BAM record");
+        if (end > n || bs < 32) return decline("truncated BAM record");
         at.push_back(p);
         p = end;
     }
@@ -659,13 +732,13 @@ int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int thread
         auto work = [&](int t) {
             for (size_t i = NR * t / T, hi = NR * (t + 1) / T; i < hi; ++i) parse_bam_record(b, at[i], rec_end(i), recs[i]);
         };
-        std::vector<std::thread> pool;
+        Pool pool;
         for (int t = 1; t < T; ++t) pool.emplace_back(work, t);
         work(0);
         for (auto &th : pool) th.join();
         size_t tagged = 0;
         for (size_t i = 0; i < NR; ++i) {
-            if (recs[i].why) return unsupported(g, recs[i].why);
+            if (recs[i].why) return decline(recs[i].why);
             tagged += recs[i].tagged;
         }
         tab.reserve(tagged);
@@ -675,7 +748,7 @@ int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int thread
         BamRec one;
         if (!batch) {
             parse_bam_record(b, p, rec_end(ri), one);
-            if (one.why) return unsupported(g, one.why);
+            if (one.why) return decline(one.why);
         }
         const BamRec &rec = batch ? recs[ri] : one;
         const char *name = rec.name;
@@ -718,7 +791,8 @@ int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int thread
                 for (uint32_t i = 0; i < n_ops; ++i) {
                     const uint32_t v = u32(cg + 4 * (size_t)i), op = v & 15u, len = v >> 4;
                     if (op == 1 || op == 2) {
-                        if (len >= g->min_sv_size && ref < 0xFFFFFFFEull) {
+                        if (len >= g->min_sv_size) {
+                            if (ref >= 0xFFFFFFFEull) return decline("SV mark at or past reference position 2^32 - 1");
                             pend.push_back({name, (uint32_t)name_len, (uint8_t)(op == 1 ? 1 : 0), (uint32_t)ref + 1u, len});
                         }
                         if (op == 2) ref += len;
@@ -728,9 +802,11 @@ int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int thread
                 }
                 // depth[b] counts the alignments that cover the middle of bin b
                 const uint64_t w = g->depth_bin, half = w / 2, s0 = (uint64_t)pos0, e0 = ref;
+                if (e0 > kMaxRefEnd) return decline("alignment ends past reference position 2^32 - 1");
                 if (e0 > s0) {
                     const uint64_t lo = s0 <= half ? 0 : (s0 - half + w - 1) / w;            // first b with b*w + half >= s0
                     const uint64_t hi = e0 <= half ? 0 : (e0 - half + w - 1) / w;            // first b with b*w + half >= e0
+                    if (hi > kMaxDepthBins) return decline("more than 2^28 depth bins on one contig");
                     if (hi > lo) {
                         if (dep.size() < hi + 1) dep.resize(hi + 1, 0);
                         dep[lo] += 1;
@@ -761,6 +837,7 @@ int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int thread
             groups[it.first->second].push_back(i);
         }
         const int64_t tol = 5, max_del = 100000, min_sv = (int64_t)g->min_sv_size;
+        const char *const past = "SV mark at or past reference position 2^32 - 1";
         for (auto &gr : groups) {
             if (gr.size() < 2) continue;
             std::sort(gr.begin(), gr.end(), [&](uint32_t x, uint32_t y) {
@@ -777,7 +854,10 @@ int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int thread
                     if (dread < -tol) continue;
                     const int64_t p1 = a.rev ? (int64_t)a.rs : (int64_t)a.re, p2 = a.rev ? (int64_t)c.rs : (int64_t)c.re;
                     const int64_t lo = p1 < p2 ? p1 : p2, sp = p1 < p2 ? p2 - p1 : p1 - p2;
-                    if (sp >= min_sv && sp <= max_del && lo < 0xFFFFFFFEll) pend.push_back({a.name, a.len, 2, (uint32_t)lo + 1u, (uint32_t)sp});
+                    if (sp >= min_sv && sp <= max_del) {
+                        if (lo >= 0xFFFFFFFEll) return decline(past);
+                        pend.push_back({a.name, a.len, 2, (uint32_t)lo + 1u, (uint32_t)sp});
+                    }
                     continue;
                 }
                 const int64_t dref = a.rev ? (int64_t)a.rs - (int64_t)c.re : (int64_t)c.rs - (int64_t)a.re;
@@ -785,15 +865,20 @@ int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int thread
                 if (dref < -tol) {
                     // the read goes back on the reference: a tandem duplication of the stretch both segments cover: DUP
                     const int64_t s0 = a.rev ? (int64_t)a.rs : (int64_t)c.rs, e0 = a.rev ? (int64_t)c.re : (int64_t)a.re;
-                    if (e0 - s0 >= min_sv && e0 - s0 <= max_del && s0 < 0xFFFFFFFEll) pend.push_back({a.name, a.len, 3, (uint32_t)s0 + 1u, (uint32_t)(e0 - s0)});
+                    if (e0 - s0 >= min_sv && e0 - s0 <= max_del) {
+                        if (s0 >= 0xFFFFFFFEll) return decline(past);
+                        pend.push_back({a.name, a.len, 3, (uint32_t)s0 + 1u, (uint32_t)(e0 - s0)});
+                    }
                     continue;
                 }
                 const int64_t dev = dread - dref;
                 const uint64_t anchor = a.rev ? c.re : a.re;
-                if (anchor >= 0xFFFFFFFEull) continue;
-                if (dev >= min_sv && dev <= 0xFFFFFFFFll)
+                const bool ins = dev >= min_sv, del = -dev >= min_sv && -dev <= max_del;
+                if ((ins || del) && anchor >= 0xFFFFFFFEull) return decline(past);
+                if (ins && dev > 0xFFFFFFFFll) return decline("split-read insertion longer than 2^32 - 1");
+                if (ins)
                     pend.push_back({a.name, a.len, 1, (uint32_t)anchor + 1u, (uint32_t)dev});
-                else if (-dev >= min_sv && -dev <= max_del)
+                else if (del)
                     pend.push_back({a.name, a.len, 0, (uint32_t)anchor + 1u, (uint32_t)(-dev)});
             }
         }
@@ -829,20 +914,51 @@ int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int thread
     return DUET_INGEST_OK;
 }
 
+// a contig whose BAM failed keeps nothing of it (the records before the one that declined had been applied already)
+void forget_contig(duet_ingest *g, int contig)
+{
+    g->tables[(size_t)contig] = NameTable();
+    g->tags[(size_t)contig] = std::vector<uint64_t>();
+    g->bam_has_aln[(size_t)contig] = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int duet_ingest_add_bam(duet_ingest *g, int contig, const char *path, int threads)
+{
+    if (!g || contig < 0 || contig >= (int)g->contigs.size() || !path) return DUET_INGEST_INVALID;
+    return guarded(g->err, [&] { return add_bam_impl(g, contig, path, threads, g->err); });
+}
+
 // Several contigs' BAMs at once (round 6).  A contig's tag table, tag words and "has alignments" flag are its own, so whole
 // contigs go to the workers -- the largest files first, a shared counter hands them out -- instead of one contig after the other with
 // the workers meeting at every stage of each (inflate, records, then ONE thread filling that contig's name table in file order: with
 // 24 contigs that serial part was what the BAM side cost).  With fewer contigs than workers every contig keeps `threads / n`
 // workers of its own.  SVIM-mode extraction appends to shared arrays in contig order: it takes the contigs one by one as before.
-// Returns the status of the first contig (in the caller's order) that failed, with that contig's message.
-int duet_ingest_add_bams(duet_ingest *g, int n, const int *contigs, const char *const *paths, int threads)
+// A list that names a contig twice takes them one by one too: two workers would fill one table (and the later file's words win).
+// Every contig reports into a status and a message of its own; returns the status of the first contig (in the caller's order) that
+// failed, with that contig's message, nothing run again.  Every failing contig is left without table and tags.
+static int add_bams_impl(duet_ingest *g, int n, const int *contigs, const char *const *paths, int threads)
 {
-    if (!g || n < 0 || (n && (!contigs || !paths))) return DUET_INGEST_INVALID;
     if (threads < 1) threads = 1;
-    if (n <= 1 || threads == 1 || g->extract) {
+    bool twice = false;
+    {
+        std::vector<uint8_t> named(g->contigs.size(), 0);
+        for (int i = 0; i < n; ++i) {
+            if (contigs[i] < 0 || contigs[i] >= (int)g->contigs.size()) continue;        // (refused below, as before)
+            twice = twice || named[(size_t)contigs[i]];
+            named[(size_t)contigs[i]] = 1;
+        }
+    }
+    if (n <= 1 || threads == 1 || g->extract || twice) {
         for (int i = 0; i < n; ++i) {
             const int rc = duet_ingest_add_bam(g, contigs[i], paths[i], threads);
-            if (rc) return rc;
+            if (rc) {
+                if (rc != DUET_INGEST_INVALID) forget_contig(g, contigs[i]);
+                return rc;
+            }
         }
         return DUET_INGEST_OK;
     }
@@ -858,29 +974,35 @@ int duet_ingest_add_bams(duet_ingest *g, int n, const int *contigs, const char *
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bytes[(size_t)a] > bytes[(size_t)b]; });
     const int outer = n < threads ? n : threads, inner = threads / outer > 1 ? threads / outer : 1;
     std::vector<int> rcs((size_t)n, DUET_INGEST_OK);
+    std::vector<std::string> errs((size_t)n);
     std::atomic<int> next(0);
     auto work = [&]() {
         for (;;) {
             const int j = next.fetch_add(1);
             if (j >= n) return;
             const int i = order[(size_t)j];
-            rcs[(size_t)i] = duet_ingest_add_bam(g, contigs[i], paths[i], inner);
+            std::string &err = errs[(size_t)i];
+            rcs[(size_t)i] = guarded(err, [&] { return add_bam_impl(g, contigs[i], paths[i], inner, err); });
         }
     };
     {
-        std::vector<std::thread> pool;
+        Pool pool;
         for (int t = 1; t < outer; ++t) pool.emplace_back(work);
         work();
         for (auto &th : pool) th.join();
     }
-    for (int i = 0; i < n; ++i)
-        if (rcs[(size_t)i]) {
-            // (failing contigs may have written the message side by side: the first one's again, alone)
-            g->tables[(size_t)contigs[i]] = NameTable();
-            g->tags[(size_t)contigs[i]].clear();
-            return duet_ingest_add_bam(g, contigs[i], paths[i], threads);
-        }
-    return DUET_INGEST_OK;
+    int first = -1;
+    for (int i = n - 1; i >= 0; --i)
+        if (rcs[(size_t)i]) { forget_contig(g, contigs[i]); first = i; }
+    if (first < 0) return DUET_INGEST_OK;
+    g->err = errs[(size_t)first];
+    return rcs[(size_t)first];
+}
+
+int duet_ingest_add_bams(duet_ingest *g, int n, const int *contigs, const char *const *paths, int threads)
+{
+    if (!g || n < 0 || (n && (!contigs || !paths))) return DUET_INGEST_INVALID;
+    return guarded(g->err, [&] { return add_bams_impl(g, n, contigs, paths, threads); });
 }
 
 namespace {
@@ -985,7 +1107,7 @@ int vcf_begin(duet_ingest *g, const char *path, int threads, VcfStage &st)
             }
         };
         {
-            std::vector<std::thread> pool;
+            Pool pool;
             for (int t = 1; t < T; ++t) pool.emplace_back(scan, t);
             scan(0);
             for (auto &th : pool) th.join();
@@ -1020,7 +1142,7 @@ int vcf_begin(duet_ingest *g, const char *path, int threads, VcfStage &st)
                 }
             };
             {
-                std::vector<std::thread> pool;
+                Pool pool;
                 for (int t = 1; t < T; ++t) pool.emplace_back(fill, t);
                 fill(0);
                 for (auto &th : pool) th.join();
@@ -1095,7 +1217,7 @@ int vcf_begin(duet_ingest *g, const char *path, int threads, VcfStage &st)
         }
     };
     {
-        std::vector<std::thread> pool;
+        Pool pool;
         for (int t = 1; t < T; ++t) pool.emplace_back(work_a, t);
         work_a(0);
         for (auto &th : pool) th.join();
@@ -1280,7 +1402,7 @@ int vcf_finish(duet_ingest *g, VcfStage &st)
         }
     };
     {
-        std::vector<std::thread> pool;
+        Pool pool;
         for (int t = 1; t < TB; ++t) pool.emplace_back(work_b, t);
         work_b(0);
         for (auto &th : pool) th.join();
@@ -1334,7 +1456,7 @@ int vcf_finish(duet_ingest *g, VcfStage &st)
 
 duet_ingest::~duet_ingest() { delete (VcfStage *)stage; }
 
-int duet_ingest_parse_vcf(duet_ingest *g, const char *path, int threads)
+static int parse_vcf_impl(duet_ingest *g, const char *path, int threads)
 {
     if (!g || !path) return DUET_INGEST_INVALID;
     VcfStage st;
@@ -1347,22 +1469,24 @@ int duet_ingest_parse_vcf_begin(duet_ingest *g, const char *path, int threads)
 {
     if (!g || !path) return DUET_INGEST_INVALID;
     delete (VcfStage *)g->stage;
-    VcfStage *st = new VcfStage;
+    g->stage = nullptr;
+    VcfStage *st = new (std::nothrow) VcfStage;
+    if (!st) return DUET_INGEST_UNSUPPORTED;          // (_finish then returns DUET_INGEST_INVALID: no first half to finish)
     g->stage = st;
-    st->rc = vcf_begin(g, path, threads, *st);
+    // (it may run beside duet_ingest_add_bams: an exception's message goes where the first half's own messages go, not to g->err)
+    st->rc = guarded(st->err, [&] { return vcf_begin(g, path, threads, *st); });
     return st->rc;
 }
 
 int duet_ingest_parse_vcf_finish(duet_ingest *g)
 {
     if (!g || !g->stage) return DUET_INGEST_INVALID;
-    VcfStage *st = (VcfStage *)g->stage;
+    std::unique_ptr<VcfStage> st((VcfStage *)g->stage);
     g->stage = nullptr;
-    int rc = st->rc;
-    if (rc) g->err = st->err;
-    else rc = vcf_finish(g, *st);
-    delete st;
-    return rc;
+    return guarded(g->err, [&] {
+        if (st->rc) { g->err = st->err; return st->rc; }
+        return vcf_finish(g, *st);
+    });
 }
 
 int duet_ingest_get_arrays(const duet_ingest *g, duet_ingest_arrays *o)
@@ -1484,7 +1608,7 @@ static int hand_over(const std::string &out, char **text, uint64_t *len)
     return DUET_INGEST_OK;
 }
 
-int duet_ingest_emit(duet_ingest *g, const uint8_t *pred, const uint32_t *ps, int include_all_ctgs, char **text,
+static int emit_impl(duet_ingest *g, const uint8_t *pred, const uint32_t *ps, int include_all_ctgs, char **text,
                      uint64_t *len)
 {
     if (!g || !g->parsed || !text || !len) return DUET_INGEST_INVALID;
@@ -1530,7 +1654,7 @@ int duet_ingest_cand_slots(duet_ingest *g, uint32_t *slot)
     return DUET_INGEST_OK;
 }
 
-int duet_ingest_emit_blocks(duet_ingest *g, const uint8_t *pred, const uint32_t *ps, const uint64_t *id_base, char **text,
+static int emit_blocks_impl(duet_ingest *g, const uint8_t *pred, const uint32_t *ps, const uint64_t *id_base, char **text,
                             uint64_t *len, uint64_t *slot_off, uint64_t *slot_len)
 {
     if (!g || !g->parsed || !text || !len || !id_base || !slot_off || !slot_len) return DUET_INGEST_INVALID;
@@ -1543,7 +1667,7 @@ int duet_ingest_emit_blocks(duet_ingest *g, const uint8_t *pred, const uint32_t 
     return hand_over(out, text, len);
 }
 
-int duet_ingest_set_owned(duet_ingest *g, const uint8_t *owned)
+static int set_owned_impl(duet_ingest *g, const uint8_t *owned)
 {
     if (!g || g->parsed) return DUET_INGEST_INVALID;
     g->skip.clear();
@@ -1554,7 +1678,7 @@ int duet_ingest_set_owned(duet_ingest *g, const uint8_t *owned)
     return DUET_INGEST_OK;
 }
 
-int duet_ingest_vcf_precount(duet_ingest *g, const char *path, uint64_t *n_records, uint64_t *n_bytes)
+static int vcf_precount_impl(duet_ingest *g, const char *path, uint64_t *n_records, uint64_t *n_bytes)
 {
     if (!g || !path || !n_records || !n_bytes) return DUET_INGEST_INVALID;
     if (g->vcf_path != path || g->vcf.empty()) {
@@ -1592,7 +1716,7 @@ int duet_ingest_vcf_precount(duet_ingest *g, const char *path, uint64_t *n_recor
     return DUET_INGEST_OK;
 }
 
-int duet_ingest_header(duet_ingest *g, int include_all_ctgs, char **text, uint64_t *len)
+static int header_impl(duet_ingest *g, int include_all_ctgs, char **text, uint64_t *len)
 {
     if (!g || !g->parsed || !text || !len) return DUET_INGEST_INVALID;
     std::string out;
@@ -1607,7 +1731,7 @@ int duet_ingest_header(duet_ingest *g, int include_all_ctgs, char **text, uint64
     return DUET_INGEST_OK;
 }
 
-int duet_ingest_get_rows(duet_ingest *g, duet_ingest_rows *o)
+static int get_rows_impl(duet_ingest *g, duet_ingest_rows *o)
 {
     if (!g || !g->parsed || !o) return DUET_INGEST_INVALID;
     const size_t C = g->cand_pos.size();
@@ -1624,7 +1748,7 @@ int duet_ingest_get_rows(duet_ingest *g, duet_ingest_rows *o)
         // candidates they were 120 ms of a 640 ms run on one thread, the pool's zero-fill included)
         const int T = (int)std::min<size_t>((size_t)std::max(1, g->threads), std::max<size_t>(1, C / 4096));
         auto run = [&](auto work) {
-            std::vector<std::thread> pool;
+            Pool pool;
             for (int t = 1; t < T; ++t) pool.emplace_back(work, t);
             work(0);
             for (auto &th : pool) th.join();
@@ -1774,7 +1898,7 @@ int duet_ingest_get_mark_names(duet_ingest *g, duet_ingest_mark_names *o)
     return DUET_INGEST_OK;
 }
 
-int duet_ingest_get_marks(duet_ingest *g, duet_ingest_marks *o)
+static int get_marks_impl(duet_ingest *g, duet_ingest_marks *o)
 {
     if (!g || !o || !g->extract) return DUET_INGEST_INVALID;
     const size_t K = g->contigs.size(), M = g->m_pos.size();
@@ -1790,6 +1914,11 @@ int duet_ingest_get_marks(duet_ingest *g, duet_ingest_marks *o)
     g->depth.resize(K);
     g->depth_off.assign(K + 1, 0);
     g->depth_flat.clear();
+    {
+        uint64_t bins = 0;
+        for (size_t k = 0; k < K; ++k) bins += g->depth[k].size();
+        if (bins > 0xFFFFFFFFull) return unsupported(g, "more than 2^32 - 1 depth bins over all contigs");
+    }
     for (size_t k = 0; k < K; ++k) {
         g->depth_off[k + 1] = g->depth_off[k] + (uint32_t)g->depth[k].size();
         g->depth_flat.insert(g->depth_flat.end(), g->depth[k].begin(), g->depth[k].end());
@@ -1808,6 +1937,56 @@ int duet_ingest_get_marks(duet_ingest *g, duet_ingest_marks *o)
     o->depth = g->depth_flat.data();
     o->depth_off = g->depth_off.data();
     return DUET_INGEST_OK;
+}
+
+// the entries whose bodies allocate, each through guarded() (see there)
+int duet_ingest_parse_vcf(duet_ingest *g, const char *path, int threads)
+{
+    if (!g || !path) return DUET_INGEST_INVALID;
+    return guarded(g->err, [&] { return parse_vcf_impl(g, path, threads); });
+}
+
+int duet_ingest_emit(duet_ingest *g, const uint8_t *pred, const uint32_t *ps, int include_all_ctgs, char **text, uint64_t *len)
+{
+    if (!g) return DUET_INGEST_INVALID;
+    return guarded(g->err, [&] { return emit_impl(g, pred, ps, include_all_ctgs, text, len); });
+}
+
+int duet_ingest_emit_blocks(duet_ingest *g, const uint8_t *pred, const uint32_t *ps, const uint64_t *id_base, char **text,
+                            uint64_t *len, uint64_t *slot_off, uint64_t *slot_len)
+{
+    if (!g) return DUET_INGEST_INVALID;
+    return guarded(g->err, [&] { return emit_blocks_impl(g, pred, ps, id_base, text, len, slot_off, slot_len); });
+}
+
+int duet_ingest_set_owned(duet_ingest *g, const uint8_t *owned)
+{
+    if (!g) return DUET_INGEST_INVALID;
+    return guarded(g->err, [&] { return set_owned_impl(g, owned); });
+}
+
+int duet_ingest_vcf_precount(duet_ingest *g, const char *path, uint64_t *n_records, uint64_t *n_bytes)
+{
+    if (!g) return DUET_INGEST_INVALID;
+    return guarded(g->err, [&] { return vcf_precount_impl(g, path, n_records, n_bytes); });
+}
+
+int duet_ingest_header(duet_ingest *g, int include_all_ctgs, char **text, uint64_t *len)
+{
+    if (!g) return DUET_INGEST_INVALID;
+    return guarded(g->err, [&] { return header_impl(g, include_all_ctgs, text, len); });
+}
+
+int duet_ingest_get_rows(duet_ingest *g, duet_ingest_rows *o)
+{
+    if (!g) return DUET_INGEST_INVALID;
+    return guarded(g->err, [&] { return get_rows_impl(g, o); });
+}
+
+int duet_ingest_get_marks(duet_ingest *g, duet_ingest_marks *o)
+{
+    if (!g) return DUET_INGEST_INVALID;
+    return guarded(g->err, [&] { return get_marks_impl(g, o); });
 }
 
 }  // extern "C"
