@@ -43,6 +43,7 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_ps_links_device', 'duet_ps_links_host', 'duet_svim_ps_links_device', 'duet_svim_ps_links_host',
            'duet_read_tags_device', 'duet_read_tags_host', 'duet_read_tags_rows_device', 'duet_read_tags_rows_host',
            'duet_ps_join_tags_device', 'duet_ps_join_tags_host', 'duet_ps_join_diff_device', 'duet_ps_join_diff_host',
+           'duet_ps_blocks_device', 'duet_ps_blocks_host', 'duet_ps_join_links_device',
            'duet_sv_tags_device', 'duet_sv_tags_host',
            'duet_prims_sort_host', 'duet_prims_scan_host', 'duet_prims_local_sort_host')
 
@@ -234,6 +235,13 @@ PS_BLOCK_DTYPE = np.dtype([(n, '<u4') for n in ('contig', 'ps', 'block', 'flip')
 JOIN_CHANGE_NAMES = ('none', 'gained', 'lost', 'same', 'relabelled', 'to_het', 'to_hom', 'other')   # DUET_PS_JOIN_NONE .. _OTHER
 
 
+class PsBlocksCounts(ctypes.Structure):     # duet_ps_blocks_counts
+    _fields_ = [(n, ctypes.c_uint32) for n in ('n_rows', 'n_trusted', 'n_conflicts', 'n_components')]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class TuneTruth(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ('n_uid', 'n_groups', 'n_pairs', 'reserved')] + \
                [(n, ctypes.c_void_p) for n in ('cand_flags', 'cand_group', 'cand_uid', 'cand_pair', 'group_pair_off', 'pair_uid')]
@@ -395,6 +403,13 @@ def load():
                                             [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p]
     lib.duet_ps_join_diff_host.argtypes = lib.duet_ps_join_diff_device.argtypes[:-1]
+    lib.duet_ps_blocks_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                          ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                          ctypes.POINTER(PsBlocksCounts), ctypes.c_void_p]
+    lib.duet_ps_blocks_host.argtypes = lib.duet_ps_blocks_device.argtypes[:-1]
+    lib.duet_ps_join_links_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                              ctypes.POINTER(PsBlocksCounts), ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
     lib.duet_sv_tags_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(ReadTagsProblem)] + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 4
     lib.duet_sv_tags_host.argtypes = lib.duet_sv_tags_device.argtypes[:-1]
     lib.duet_tune_line_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
@@ -1203,6 +1218,47 @@ class Context(object):
         if rc:
             self._raise(rc)
         return counts
+
+    # -- blocks of the phase-set links, on the device (duet_psblocks.hip) -------------------------------------------------------
+    def ps_blocks_host(self, records, n_contigs, min_sv=1, rows=None, conflicts=None):
+        """duet_ps_blocks_host: the table of ps_links.blocks(records, min_sv) from host records (PS_LINK_DTYPE)
+        -> (rows PS_BLOCK_DTYPE, conflicts u32 in rank order, counts dict).  rows / conflicts: the arrays written (None: new ones
+        with room for everything) -- a refused call leaves them as they were."""
+        records = np.ascontiguousarray(records, dtype=PS_LINK_DTYPE)
+        n = len(records)
+        if rows is None:
+            rows = np.zeros(2 * n, dtype=PS_BLOCK_DTYPE)
+        if conflicts is None:
+            conflicts = np.zeros(n, dtype=np.uint32)
+        c = PsBlocksCounts()
+        rc = self.lib.duet_ps_blocks_host(self.handle, _ptr(records), n, int(n_contigs), int(min_sv), _ptr(rows), len(rows),
+                                          _ptr(conflicts), len(conflicts), ctypes.byref(c))
+        if rc:
+            self._raise(rc)
+        return rows[:c.n_rows].copy(), conflicts[:c.n_conflicts].copy(), c.as_dict()
+
+    def ps_blocks_device(self, links_ptr, n_links, n_contigs, min_sv, rows_ptr, rows_cap, conflicts_ptr=0, conflicts_cap=0, stream=0):
+        """duet_ps_blocks_device on resident records (as ps_links_device left them); rows_ptr: device room for rows_cap rows
+        (2 * n_links always suffice), conflicts_ptr: device room for conflicts_cap indices, or 0 -> counts dict."""
+        c = PsBlocksCounts()
+        rc = self.lib.duet_ps_blocks_device(self.handle, ctypes.c_void_p(links_ptr), int(n_links), int(n_contigs), int(min_sv),
+                                            ctypes.c_void_p(rows_ptr), int(rows_cap), ctypes.c_void_p(conflicts_ptr), int(conflicts_cap),
+                                            ctypes.byref(c), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return c.as_dict()
+
+    def ps_join_links_device(self, links_ptr, n_links, min_sv, read_tag_ptr, read_off, n_reads, out_ptr, stream=0):
+        """duet_ps_join_links_device: the table of the resident records built on the device and applied to the resident tag
+        words (read_off a host array); out_ptr may be read_tag_ptr -> (n_changed, counts dict)."""
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint32)
+        c, n = PsBlocksCounts(), ctypes.c_uint32(0)
+        rc = self.lib.duet_ps_join_links_device(self.handle, ctypes.c_void_p(links_ptr), int(n_links), int(min_sv),
+                                                ctypes.c_void_p(read_tag_ptr), _ptr(read_off), max(len(read_off), 1) - 1, int(n_reads),
+                                                ctypes.c_void_p(out_ptr), ctypes.byref(c), ctypes.byref(n), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return n.value, c.as_dict()
 
     # -- tags from other SVs (duet_svtags.hip) -------------------------------------------------------------------------------------
     def sv_tags_host(self, cand_off, mark_read, mark_name, n_names, pred, ps, read_tag, cand_ctg_off=None, cand_contig=None,

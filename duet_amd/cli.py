@@ -52,7 +52,7 @@ def pipeline(a):
 
 def main(argv):
     a = parse_args(argv)
-    a.threshold_vector, a.pc_cap_value = None, None
+    a.threshold_vector, a.pc_cap_value, a.join_min_sv_file = None, None, None
     if a.write_sv_calls and a.sv_caller != 'svim-gpu':
         # (additive: the clustered calls exist only in the svim-gpu mode; every other caller writes sv_calling/variants.vcf itself)
         raise SystemExit('duet: --write_sv_calls works with -b svim-gpu only')
@@ -63,7 +63,7 @@ def main(argv):
             raise SystemExit('duet: --thresholds works on the single-GPU path with an external SV caller only '
                              '(not with --gpus > 1 or -b svim-gpu)')
         from duet_amd import tune
-        a.threshold_vector, a.pc_cap_value = tune.load_vector(a.thresholds, with_cap=True)
+        a.threshold_vector, a.pc_cap_value, a.join_min_sv_file = tune.load_vector(a.thresholds, with_cap=True, with_join=True)
     if a.pc_cap is not None:
         # (additive: the PC cap of the vote, sv_phasing_fn.py:76,88,201 -- the flag wins over a pc_cap key of the thresholds file;
         # without --thresholds the vector is the defaults)
@@ -97,6 +97,8 @@ def main(argv):
             raise SystemExit('duet: --join_ps works on the single-GPU path only (not with --gpus > 1)')
         if a.join_min_sv is not None and a.join_min_sv < 1:
             raise SystemExit('duet: --join_min_sv takes an integer >= 1')
+        if a.join_min_sv is None:
+            a.join_min_sv = a.join_min_sv_file              # (a join_min_sv key of the thresholds file, what `tune --fit --join_ps` writes; the flag wins)
     if (a.sv_tag_min is not None or a.sv_tag_pc is not None) and not a.vote_sv_tags:
         raise SystemExit('duet: --sv_tag_min and --sv_tag_pc need --vote_sv_tags')
     if a.vote_sv_tags:

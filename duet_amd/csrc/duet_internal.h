@@ -96,6 +96,7 @@ struct duet_ctx {
     DuetOwnedBufs readtags_ws;             // read tags (duet_readtags.hip): per-candidate workspace 0, per-mark workspace 1, the records before they are released 2; host-run staging 3-11
     DuetOwnedBufs readtags_rows_ws;        // ... its rows: row lengths 0, row offsets 1, tile sums 2, status words and CHROM texts 3; host-run staging 4-7, text 8
     DuetOwnedBufs psjoin_ws;               // joined phase sets (duet_psjoin.hip): the header words, the offsets and the staged table 0, the change codes before they are released 1; host-run staging of the read tags 2, of pred0, ps0, pred1, ps1, cand_contig 3-7
+    DuetOwnedBufs psblocks_ws;             // blocks of the links (duet_psblocks.hip): the header words and the whole workspace 0; host-run staging of the records 1
     DuetOwnedBufs svtags_ws;               // tags from other SVs (duet_svtags.hip): per-candidate workspace 0, per-mark workspace and the staged words 1, per-contributing-mark workspace 2, the records 3; host-run staging 4-11
     DuetOwnedBufs prims_ws;               // diagnostics of the shared primitives (duet_prims_check.hip): one arena, 0
 };
@@ -138,6 +139,14 @@ int duet_ef_upload(duet_ctx *ctx, const duet_ef_problem *pr, duet_ef_problem *d,
 // out_on_host host memory (the records are staged and copied, the stream synchronised).  For the SVIM drivers in duet_svim.hip.
 int duet_ps_links_run(duet_ctx *ctx, const duet_ef_problem *pr, uint32_t pc_cap, duet_ps_link *out, uint32_t out_cap, uint32_t *n_links,
                       hipStream_t st, bool out_on_host);
+
+// pj_tags (duet_psjoin.hip) over a table that is already on the device in its staged layout, for duet_psblocks.hip: slice k of the
+// keys (PS, ascending) and values (flip << 32 | block) is d_slice_off[k] .. d_slice_off[k + 1]; n_bound: an index no row has (the
+// row count or above); d_read_off: the device copy of read_off; d_hdr: 16 zeroed words, word 0 receives the changed tag words.
+// K >= 1, R >= 1, the arguments checked by the caller; nothing is read back.
+int duet_ps_join_tags_staged(duet_ctx *ctx, const uint64_t *read_tag, const uint32_t *d_read_off, uint32_t K, uint32_t R,
+                             const uint32_t *d_slice_off, const uint32_t *d_key, const uint64_t *d_val, uint32_t n_bound, uint64_t *out_tag,
+                             uint32_t *d_hdr, hipStream_t st);
 
 inline int duet_reserve(duet_ctx *ctx, DevBuf &b, size_t bytes)
 {

@@ -294,6 +294,18 @@ int diff_run(duet_ctx *ctx, uint32_t C, const uint8_t *pred0, const uint32_t *ps
 
 }  // namespace
 
+int duet_ps_join_tags_staged(duet_ctx *ctx, const uint64_t *read_tag, const uint32_t *d_read_off, uint32_t K, uint32_t R,
+                             const uint32_t *d_slice_off, const uint32_t *d_key, const uint64_t *d_val, uint32_t n_bound, uint64_t *out_tag,
+                             uint32_t *d_hdr, hipStream_t st)
+{
+    Table t;
+    t.K = K; t.n = n_bound;
+    t.slice_off = d_slice_off; t.key = d_key; t.val = d_val;
+    hipLaunchKernelGGL(pj_tags, dim3((R + kThreads - 1) / kThreads), dim3(kThreads), 0, st, read_tag, out_tag, R, d_read_off, t, d_hdr);
+    HIP_TRY(ctx, hipGetLastError());
+    return DUET_OK;
+}
+
 extern "C" {
 
 int duet_ps_join_tags_device(duet_ctx *ctx, const uint64_t *read_tag, const uint32_t *read_off, uint32_t n_contigs, uint32_t n_reads,

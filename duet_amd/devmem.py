@@ -64,6 +64,19 @@ class DeviceProblem(object):
         ctx.run_device(self.problem, blk.data_ptr() + 4 * self.n_max, blk.data_ptr(), stream)
         return stream
 
+    def joined_tags(self, ctx, min_sv, pc_cap=None, stream=None):
+        """The read tags over joined phase sets, all on the device: the links under the problem's -s / -r and pc_cap (None: 8100;
+        duet_ps_links_device), their blocks and the remap (duet_ps_join_links_device) into a second tag tensor -- no table visits
+        the host.  -> (the tensor, dict(n_links, n_changed, n_rows, n_trusted, n_conflicts, n_components)).  The problem keeps its
+        own tags: pointed_at(tensor) runs something on the remapped ones.  The tensor is the object's and is written again by the next
+        call."""
+        return _joined_tags(self, ctx, self.problem, self.buffers['read_tag'], self.soa.read_off, self.soa.n_marks, min_sv, stream,
+                            lambda out, room, st: ctx.ps_links_device(self.problem, out, room, st, pc_cap=pc_cap))
+
+    def pointed_at(self, tags):
+        """Context manager: the problem reads `tags` (joined_tags) as its read tags; its own come back whatever happens inside."""
+        return _pointed_at(self.problem, tags)
+
     def load_results(self, pred, ps, slot=0):
         """Put host (pred, ps) -- e.g. the merged records of a multi-GPU run -- into result block `slot`, so that the
         device-side row emission can read them."""
@@ -77,6 +90,40 @@ class DeviceProblem(object):
         """-> (pred u8[C], ps u32[C]) on the host (synchronises)."""
         from duet_amd.dist import unpack_block
         return unpack_block(self.out_blocks[slot].cpu().numpy(), self.n_max, self.soa.n_cands)
+
+
+def _joined_tags(obj, ctx, problem, own_tags, read_off, n_marks, min_sv, stream, links_into):
+    torch = obj.torch
+    if stream is None:
+        stream = torch.cuda.current_stream(obj.device).cuda_stream
+    if read_off is None:
+        raise ValueError('joined_tags: the reads per contig (read_off) are not known to this object')
+    # both tensors are kept across calls (the fit's cap axis calls this per line value): the records' room is not cleared, only
+    # the records a call announces are read; the second tag tensor starts as a copy, so the words behind the reads are the same
+    room = _lib.ps_links_room(n_marks)
+    kept = getattr(obj, '_joined', None)
+    if kept is None or kept[2] != own_tags.data_ptr():
+        kept = obj._joined = (torch.empty(max(room, 1) * _lib.PS_LINK_DTYPE.itemsize, dtype=torch.uint8, device=obj.device),
+                              own_tags.clone(), own_tags.data_ptr())
+    links, tags = kept[0], kept[1]
+    n_links = links_into(links.data_ptr(), room, stream)
+    n_changed, counts = ctx.ps_join_links_device(links.data_ptr(), n_links, min_sv, own_tags.data_ptr(), read_off, problem.n_reads,
+                                                 tags.data_ptr(), stream)
+    return tags, dict(counts, n_links=n_links, n_changed=n_changed)
+
+
+class _pointed_at(object):
+    def __init__(self, problem, tags):
+        self.problem, self.tags, self.mine = problem, tags, None
+
+    def __enter__(self):
+        self.mine = self.problem.read_tag
+        self.problem.read_tag = self.tags.data_ptr()
+        return self.tags
+
+    def __exit__(self, *exc):
+        self.problem.read_tag = self.mine
+        return False
 
 
 def device_rows(ctx, dp, rows, slot=0, stream=None):
@@ -150,10 +197,12 @@ class DeviceSvim(DeviceCluster):
     """Fused SVIM-mode pipeline on resident inputs: raw marks (+ their read indices), read tags, binned depth."""
 
     def __init__(self, marks, read_tag, depth, depth_off, depth_bin=1000, svlen_thres=50, suppread_thres=2,
-                 max_dist=0.9, part_gap=1000, part_max=100, normalizer=900.0, device='cuda:0'):
+                 max_dist=0.9, part_gap=1000, part_max=100, normalizer=900.0, device='cuda:0', read_off=None):
+        """read_off: the reads of contig k are read_off[k] .. read_off[k + 1] (only joined_tags needs them)."""
         DeviceCluster.__init__(self, marks, max_dist=max_dist, part_gap=part_gap, part_max=part_max, normalizer=normalizer,
                                device=device)
         torch = self.torch
+        self.read_off = None if read_off is None else np.ascontiguousarray(read_off, dtype=np.uint32)
 
         self.keep['sv_read'] = upload(torch, self.device, marks['read'], np.uint32)
         self.keep['sv_tag'] = upload(torch, self.device, read_tag, np.uint64)
@@ -313,6 +362,19 @@ class DeviceSvim(DeviceCluster):
         out = torch.empty(cap, dtype=torch.uint8, device=self.device)
         n = ctx.svim_vcf_rows_device(self.sv_problem, self.result, N, nm, out.data_ptr(), cap, stream)
         return out[:n].cpu().numpy()
+
+    def joined_tags(self, ctx, min_sv, pc_cap=None, stream=None):
+        """DeviceProblem.joined_tags for the fused pipeline: the links of the candidates the resident marks cluster into under the
+        problem's -c / -s / -r and pc_cap (duet_svim_ps_links_device: it clusters again), their blocks and the remap
+        (duet_ps_join_links_device).  Needs read_off.  -> (the second tag tensor, dict of counts)."""
+        def links_into(out, room, st):
+            n, self.n_found = ctx.svim_ps_links_device(self.sv_problem, self.result, out, room, st, pc_cap=pc_cap)
+            return n
+        return _joined_tags(self, ctx, self.sv_problem, self.keep['sv_tag'], self.read_off, self.M, min_sv, stream, links_into)
+
+    def pointed_at(self, tags):
+        """Context manager: the pipeline reads `tags` (joined_tags) as its read tags; its own come back whatever happens inside."""
+        return _pointed_at(self.sv_problem, tags)
 
     def run_joined(self, ctx, blocks, read_off, thresholds=None, pc_cap=None, stream=None):
         """The last run again over joined phase sets (--join_ps): the read tags remapped under the table `blocks`

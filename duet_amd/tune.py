@@ -482,10 +482,18 @@ def _cap_list(pc_cap):
     return [_lib.check_pc_cap(v) for v in vals]
 
 
-def _lead(c_=None, s_=None, r_=None, p_=None):
+def _lead(c_=None, s_=None, r_=None, p_=None, j_=None):
     """The setting columns in front of a row, in LEAD's order."""
-    vals = dict(pc_cap=p_, svlen_thres=s_, suppread_thres=r_, cluster_max_distance=c_)
+    vals = dict(pc_cap=p_, svlen_thres=s_, suppread_thres=r_, cluster_max_distance=c_, join_min_sv=j_)
     return {n: vals[n] for n in LEAD if vals[n] is not None}
+
+
+JOIN = 'join_min_sv'         # the setting of --join_ps: the features over the phase sets joined by links of at least N candidates; 0: not joined
+
+
+def _join_list(join_min_sv):
+    """join_min_sv of sweep_settings / fit: None -> no such setting (and no column), else a non-empty list of integers >= 0."""
+    return None if join_min_sv is None else _int_list(JOIN, join_min_sv)
 
 
 def _int_list(name, v):
@@ -506,14 +514,14 @@ class _Callset(object):
     n_max (the most candidates a setting can have), texts (the CHROM text per candidate or contig, for chrom_strata), key(dt),
     features(dt, setting, cap), result, cap_line(dt, max_values) and host(dt)."""
 
-    def __init__(self, ctx, home, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread):
+    def __init__(self, ctx, home, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js=None):
         self.ctx, self.home, self.bed, self.skip_phasing, self.ingest = ctx, home, bed, skip_phasing, (include_all_ctgs, thread)
-        self.settings = [(None,) + t for t in itertools.product(ss, rs, ps)]
+        self.settings = [(None,) + t for t in itertools.product(ss, rs, ps, *([js] if js is not None else []))]
         self.result = None                                  # (the per-candidate form: build() reads no cluster result)
 
     def ingests(self):
         from duet_amd.devmem import DeviceProblem
-        _, s_, r_, _ = self.settings[0]
+        _, s_, r_, _ = self.settings[0][:4]
         self.soa, txt = _candidates(self.home, s_, r_, *self.ingest)
         self.cands = dict(pos=self.soa.cand_pos, svlen=self.soa.cand_svlen, **txt)
         self.n_max, self.texts = self.soa.n_cands, self.cands['chrom']
@@ -529,10 +537,19 @@ class _Callset(object):
         if self.n_max:
             p = self.dp.problem
             p.svlen_thres, p.suppread_thres = _lib.clamp_u32(setting['svlen_thres']), _lib.clamp_u32(setting['suppread_thres'])
-            self.ctx.features_device(p, dt.feat.data_ptr(), dt.stream(), pc_cap=cap)
+            if setting.get(JOIN):
+                # (a joined run is the ordinary run on remapped tags: the links under this -s, -r and cap, their blocks and the remap,
+                # all on the device; the problem gets its own tags back whatever the features call does)
+                self.joined, _ = self.dp.joined_tags(self.ctx, setting[JOIN], pc_cap=cap, stream=dt.stream())
+                with self.dp.pointed_at(self.joined):
+                    self.ctx.features_device(p, dt.feat.data_ptr(), dt.stream(), pc_cap=cap)
+            else:
+                self.ctx.features_device(p, dt.feat.data_ptr(), dt.stream(), pc_cap=cap)
         return self.n_max
 
     def cap_line(self, dt, max_values):
+        # (the same line with and without a join: the remap keeps pc bit for bit and leaves untagged words alone, so the problem's
+        # own tags give the pc values of the marks that can vote)
         return dt.cap_line(self.ctx, self.dp.problem, max_values) if self.n_max else _NO_CAP_LINE
 
     def host(self, dt):
@@ -546,9 +563,9 @@ class _Bams(object):
     per-contig tables (contig_tables, bed_tables); a setting's features are DeviceSvim.run_features', which clusters again on
     every call (the entry keeps no state between calls).  Each distinct setting is computed once, in c, r, cap order per -s."""
 
-    def __init__(self, ctx, home, cs, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread):
+    def __init__(self, ctx, home, cs, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js=None):
         self.ctx, self.home, self.bed, self.skip_phasing, self.ingest = ctx, home, bed, skip_phasing, (include_all_ctgs, thread)
-        self.settings = list(itertools.product(cs, ss, rs, ps))
+        self.settings = list(itertools.product(cs, ss, rs, ps, *([js] if js is not None else [])))
 
     def ingests(self):
         from duet_amd import svim_mode
@@ -567,9 +584,9 @@ class _Bams(object):
             ing.close()
             self.n_max = len(got['pos'])
             todo = list(dict.fromkeys(t for t in self.settings if t[1] == s_))
-            c_, _, r_, _ = todo[0]
+            c_, _, r_, _ = todo[0][:4]
             self.ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, s_, r_, max_dist=c_,
-                                 device='cuda:%d' % self.ctx.device_id) if self.n_max else None
+                                 device='cuda:%d' % self.ctx.device_id, read_off=got['read_off']) if self.n_max else None
             yield todo
 
     @property
@@ -585,10 +602,14 @@ class _Bams(object):
         p = self.ds.sv_problem
         p.marks.max_dist = setting['cluster_max_distance']
         p.svlen_thres, p.suppread_thres = _lib.clamp_u32(setting['svlen_thres']), _lib.clamp_u32(setting['suppread_thres'])
+        if setting.get(JOIN):
+            self.joined, _ = self.ds.joined_tags(self.ctx, setting[JOIN], pc_cap=cap)       # (as _Callset.features)
+            with self.ds.pointed_at(self.joined):
+                return self.ds.run_features(self.ctx, dt.feat.data_ptr(), pc_cap=cap)
         return self.ds.run_features(self.ctx, dt.feat.data_ptr(), pc_cap=cap)
 
     def cap_line(self, dt, max_values):
-        return dt.cap_line(self.ctx, self.ds.sv_problem, max_values) if self.n_max else _NO_CAP_LINE
+        return dt.cap_line(self.ctx, self.ds.sv_problem, max_values) if self.n_max else _NO_CAP_LINE     # (as _Callset.cap_line)
 
     def host(self, dt):
         from duet_amd.svim_mode import SV_TYPE_NAMES
@@ -598,11 +619,12 @@ class _Bams(object):
                     pos=res['cand_pos'], svlen=res['cand_span'], svtype=[SV_TYPE_NAMES[int(t) & 3] for t in res['cand_type']])
 
 
-def _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_bams, pc_cap, bed, skip_phasing, include_all_ctgs, thread):
+def _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_bams, pc_cap, bed, skip_phasing, include_all_ctgs, thread,
+            join_min_sv=None):
     """The candidate source of sweep_settings / fit for their -s, -r, -c and pc_cap arguments (nothing is read yet); its ctx is
     `ctx`, or the default context, opened once the arguments have passed."""
     ss, rs = _int_list('svlen_thres', svlen_thres), _int_list('suppread_thres', suppread_thres)
-    ps = _cap_list(pc_cap)
+    ps, js = _cap_list(pc_cap), _join_list(join_min_sv)
     if cluster_max_distance is not None and not from_bams:
         raise ValueError('cluster_max_distance only acts on candidates clustered from the BAMs: it needs from_bams')
     cs = [float(c) for c in (cluster_max_distance if cluster_max_distance is not None else (0.9,))]
@@ -610,8 +632,8 @@ def _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_b
         raise ValueError('cluster_max_distance: an empty list')
     ctx = ctx or engine.default_context()
     if from_bams:
-        return _Bams(ctx, home, cs, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread)
-    return _Callset(ctx, home, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread)
+        return _Bams(ctx, home, cs, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js)
+    return _Callset(ctx, home, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js)
 
 
 def _make_resident(src, dt, setting, cap, passes):
@@ -648,7 +670,7 @@ def _settings(src, vecs, base, passes, refdist, pctsim, on_features=None):
 
 def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,), cluster_max_distance=None, from_bams=False,
                    refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False, thread=4, ctx=None, on_features=None,
-                   holdout=None, by_contig=None, pc_cap=None, by_leaf=None):
+                   holdout=None, by_contig=None, pc_cap=None, by_leaf=None, join_min_sv=None):
     """sweep() for every setting of -s (svlen_thres), -r (suppread_thres) and, with from_bams, -c (cluster_max_distance; default
     (0.9,)): -> list of rows, settings outermost in the order c, s, r, each row a dict of svlen_thres, suppread_thres
     [, cluster_max_distance], the 14 thresholds and the ten numbers.  from_bams: the candidates come from <home>/snp_phasing/*.bam
@@ -672,9 +694,16 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     from_bams, no host work.  None: the features of the entries without a cap, and rows without the column.
     by_leaf: a list that receives leaf_rows() per setting: one row per vector, stratum (`all`; with holdout also `train`, `test`)
     and leaf -- one more pass per setting over what is already resident (duet_tune_leaf_census_device), after the plain sweep
-    and after the holdout pass's; every other row and count stays what it is without it."""
+    and after the holdout pass's; every other row and count stays what it is without it.
+    join_min_sv: a list of N >= 0 (--join_ps --join_min_sv) -- the innermost setting, behind pc_cap, because the links depend on
+    -c, -s, -r and the cap; every row then gains a join_min_sv column behind the other setting columns.  N >= 1: the setting's
+    features are those of the joined run -- the links under the setting (duet_ps_links_device / duet_svim_ps_links_device), their
+    blocks built and applied to the read tags on the device (duet_ps_join_links_device), the features call on the remapped tags,
+    whose PS column holds block names; everything downstream runs unchanged on that record.  0: not joined, the rows of a run
+    without the argument.  None: no such setting and no column."""
     vecs = grid if isinstance(grid, np.ndarray) else expand_grid(grid)
-    src = _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_bams, pc_cap, bed, skip_phasing, include_all_ctgs, thread)
+    src = _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_bams, pc_cap, bed, skip_phasing, include_all_ctgs, thread,
+                  join_min_sv)
     ctx = src.ctx
     base = truth_side(truth_vcf, bed, skip_phasing)
     passes = _strata_passes(truth_vcf, bed, skip_phasing, holdout, by_contig)
@@ -845,7 +874,7 @@ def _nan_row(holdout):
 
 def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max_values=0, svlen_thres=(50,), suppread_thres=(2,),
         cluster_max_distance=None, from_bams=False, refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False,
-        thread=4, ctx=None, holdout=None, pc_cap=None, fit_cap=False, by_leaf=None):
+        thread=4, ctx=None, holdout=None, pc_cap=None, fit_cap=False, by_leaf=None, join_min_sv=None):
     """Fit the vector to the truth set by exact per-threshold line search (see the module text), per setting of -s, -r, -c and
     pc_cap as sweep_settings takes them.  The cap is a setting, fitted per value given; with the name pc_cap among the axes (at any
     place), or fit_cap=True (appended behind the axes in force), it is also an axis: each given value -- else the pc_cap key of a
@@ -865,7 +894,10 @@ def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max
     None and (division by zero) its trace is one row of nan.
     by_leaf: a list that receives, per setting, leaf_rows() of the start vector (vector = 'start', on the features the fit starts
     from) and of the vector the fit ends on (vector = 'fitted', under the fitted cap where the cap moved): where the fit moved the
-    calls.  A setting without a trace has nan rows for both."""
+    calls.  A setting without a trace has nan rows for both.
+    join_min_sv: as sweep_settings takes it -- each listed N is a setting of its own, fitted on the features of its joined run
+    (0: not joined); on the cap axis every value of the line builds the links, the blocks and the remap again under that value
+    before its features call (all on the device); the line itself is the same with and without a join."""
     if objective not in SCORES:
         raise ValueError('objective: %r is not one of %s' % (objective, ', '.join(SCORES)))
     rounds, max_values = int(rounds), int(max_values)
@@ -887,7 +919,8 @@ def fit(home, truth_vcf, objective='hp_f1', start=None, axes=None, rounds=8, max
     base = truth_side(truth_vcf, bed, skip_phasing)
     passes = _strata_passes(truth_vcf, bed, skip_phasing, holdout, None)
     n_base, n_base_hold = base['n_base'], passes[0][2]['n_base_strata'] if passes else None
-    src = _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_bams, pc_cap, bed, skip_phasing, include_all_ctgs, thread)
+    src = _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_bams, pc_cap, bed, skip_phasing, include_all_ctgs, thread,
+                  join_min_sv)
 
     def one(setting, dt, n_cands, resident):
         """The fit of one setting (n_cands None: its features report a division by zero) -> its dict of `fits`"""
@@ -948,9 +981,11 @@ def explain(cands, thresholds, ctx=None):
     return ctx.leaves_host(cands['feat'], np.asarray(thresholds, dtype=np.float64).reshape(-1))
 
 
-def load_vector(path, with_cap=False):
+def load_vector(path, with_cap=False, with_join=False):
     """--thresholds FILE.json: one partial vector (JSON object) -> float64[14].  The object may carry a 15th key, pc_cap (what
-    `tune --fit --pc_cap` writes): with_cap: -> (float64[14], the cap or None); without, the key is accepted and left out."""
+    `tune --fit --pc_cap` writes): with_cap: -> (float64[14], the cap or None); without, the key is accepted and left out.
+    Likewise the key join_min_sv, an integer >= 1 (what `tune --fit --join_ps` writes): with_join: the tuple gains it (or None)
+    as its last element."""
     with open(path) as f:
         obj = json.load(f)
     if not isinstance(obj, dict):
@@ -962,8 +997,13 @@ def load_vector(path, with_cap=False):
             cap = _lib.check_pc_cap(cap)
         except ValueError as e:
             raise ValueError('%s: %s' % (path, e))
+    join = obj.pop(JOIN, None)
+    if join is not None:
+        if isinstance(join, bool) or not isinstance(join, int) or join < 1:
+            raise ValueError('%s: join_min_sv: an integer >= 1, not %r' % (path, join))
     vec = vector(obj)
-    return (vec, cap) if with_cap else vec
+    out = (vec,) + ((cap,) if with_cap else ()) + ((join,) if with_join else ())
+    return out if len(out) > 1 else vec
 
 
 def _write_tsv(path, names, rows):
@@ -1028,6 +1068,14 @@ def parse_args(argv):
     ap.add_argument('--pc_cap', type=_caps, default=None,
                     help='reads with a PC tag above the cap do not vote; a comma-separated list sweeps it, innermost, and every '
                          'row gains a leading pc_cap column [8100, without the column]')
+    ap.add_argument('--join_ps', action='store_true',
+                    help='score the run over joined phase sets (duet --join_ps): --join_min_sv becomes the innermost setting and '
+                         'every row gains a join_min_sv column')
+    ap.add_argument('--join_min_sv', type=_csv(int, '--join_min_sv'), default=None,
+                    help='with --join_ps: a link joins two phase sets only when at least this many SV candidates agree on it; a '
+                         'comma-separated list sweeps it; 0 = not joined [2].  With --fit, --out_vector carries the best '
+                         'setting\'s value when it is at least 1; when 0 (not joined) fits best the file has no such key, and '
+                         'duet --thresholds FILE is then meant to run without --join_ps (with it, it joins with its default 2)')
     ap.add_argument('-a', '--include_all_ctgs', action='store_true', help='all contigs, not only chr{1..22,X,Y}')
     ap.add_argument('-t', '--thread', type=int, default=4, help='threads of the ingest [%(default)s]')
     ap.add_argument('--refdist', type=int, default=1000, help="the evaluator's --refdist [%(default)s]")
@@ -1062,17 +1110,20 @@ def parse_args(argv):
         ap.error('-c / --cluster_max_distance needs --from_bams: it only acts on candidates clustered from the BAMs')
     if a.holdout is not None and (not a.holdout or not all(a.holdout)):
         ap.error('--holdout: an empty list (or an empty CHROM text in it)')
+    if a.join_min_sv is not None and not a.join_ps:
+        ap.error('--join_min_sv needs --join_ps')
+    a.join = (a.join_min_sv if a.join_min_sv is not None else [2]) if a.join_ps else None
     return a
 
 
-LEAD = ('pc_cap', 'svlen_thres', 'suppread_thres', 'cluster_max_distance')      # the setting columns in front of a row, in this order
+LEAD = ('pc_cap', 'svlen_thres', 'suppread_thres', 'cluster_max_distance', 'join_min_sv')   # the setting columns in front of a row, in this order
 
 
 def features_path(path, setting):
-    """--features with several settings: FILE.ext -> FILE[.c<c>].s<s>.r<r>[.p<cap>].ext"""
+    """--features with several settings: FILE.ext -> FILE[.c<c>].s<s>.r<r>[.p<cap>][.j<join_min_sv>].ext"""
     root, ext = os.path.splitext(path)
     tag = ''.join('.%s%s' % (t, setting[n]) for t, n in (('c', 'cluster_max_distance'), ('s', 'svlen_thres'), ('r', 'suppread_thres'),
-                                                         ('p', 'pc_cap')) if n in setting)
+                                                         ('p', 'pc_cap'), ('j', JOIN)) if n in setting)
     return root + tag + ext
 
 
@@ -1092,7 +1143,7 @@ def main_fit(a):
     got = fit(a.workdir, a.truthset, a.fit, start, a.axes, a.rounds, a.max_values, a.sv_min_size, a.min_support_read,
               a.cluster_max_distance if a.from_bams else None, a.from_bams, a.refdist, a.pctsim, a.bed_file, a.skip_phasing,
               a.include_all_ctgs, a.thread, ctx=engine.default_context(a.device), holdout=a.holdout, pc_cap=a.pc_cap, fit_cap=a.fit_cap,
-              by_leaf=leaf if a.by_leaf else None)
+              by_leaf=leaf if a.by_leaf else None, join_min_sv=a.join)
     if a.by_leaf:
         cols = tuple(n for n in LEAD if n in leaf[0]) + LEAF_COLS
         _write_tsv(a.by_leaf, cols, ([r[n] for n in cols] for r in leaf))
@@ -1112,6 +1163,10 @@ def main_fit(a):
             obj['pc_cap'] = int(best[CAP_AXIS])                     # (the fitted cap)
         elif a.pc_cap is not None:
             obj['pc_cap'] = int(best['setting']['pc_cap'])          # (the 15th key: duet --thresholds applies it)
+        if a.join is not None and best['setting'][JOIN] >= 1:
+            obj[JOIN] = int(best['setting'][JOIN])                  # (duet --thresholds --join_ps joins with it)
+        # (join_min_sv 0 fitted best: no key -- the file's key is an integer >= 1; the printed line says join_min_sv=0, and the
+        # vector is meant for a run without --join_ps)
         json.dump(obj, f, indent=1)
         f.write('\n')
     at = ' '.join('%s=%s' % (n, best['setting'][n]) for n in LEAD if n in best['setting'])
@@ -1129,7 +1184,7 @@ def main(argv):
     ctx = engine.default_context(a.device)
     cs = a.cluster_max_distance if a.from_bams else None
     single = not a.from_bams and len(a.sv_min_size) == 1 and len(a.min_support_read) == 1
-    plain = single and a.pc_cap is None
+    plain = single and a.pc_cap is None and a.join is None
 
     def write_features(setting, cands):
         f = cands['feat']
@@ -1142,9 +1197,10 @@ def main(argv):
     rows = sweep_settings(a.workdir, a.truthset, vecs, a.sv_min_size, a.min_support_read, cs, a.from_bams, a.refdist, a.pctsim,
                           a.bed_file, a.skip_phasing, a.include_all_ctgs, a.thread, ctx=ctx,
                           on_features=write_features if a.features else None, holdout=a.holdout,
-                          by_contig=contig_rows if a.by_contig else None, pc_cap=a.pc_cap, by_leaf=leaf if a.by_leaf else None)
+                          by_contig=contig_rows if a.by_contig else None, pc_cap=a.pc_cap, by_leaf=leaf if a.by_leaf else None,
+                          join_min_sv=a.join)
     # (one -s and one -r, not from the BAMs: their columns stay away, as without --pc_cap)
-    lead = tuple(n for n in LEAD if n in rows[0] and (n == 'pc_cap' or not single))
+    lead = tuple(n for n in LEAD if n in rows[0] and (n in ('pc_cap', JOIN) or not single))
     cols = lead + NAMES + SCORES
     if a.holdout is not None:
         cols += tuple('%s_%s' % (part, n) for part in ('train', 'test') for n in SCORES)

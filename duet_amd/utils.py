@@ -84,7 +84,8 @@ def build_parser():
                          'OUTPUT/phased_sv.join_report.tsv (the calls that changed); phased_sv.vcf stays what it is; one GPU only (the '
                          'native path, or -b svim-gpu)')
     ap.add_argument('--join_min_sv', type=int, default=None,
-                    help='with --join_ps: a link joins two phase sets only when at least this many SV candidates agree on it [2]')
+                    help='with --join_ps: a link joins two phase sets only when at least this many SV candidates agree on it '
+                         '[the join_min_sv key of the --thresholds file, else 2]')
     ap.add_argument('--vote_sv_tags', action='store_true',
                     help='also phase the SVs again with the untagged reads voting: a read without a WhatsHap tag gets the haplotype '
                          'that the OTHER heterozygous SV calls listing it place it on; writes OUTPUT/phased_sv.sv_tags.vcf and '

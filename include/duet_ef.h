@@ -1016,6 +1016,56 @@ DUET_API int duet_ps_join_diff_host(duet_ctx *ctx, uint32_t n_cands, const uint8
                                     uint32_t *counts);
 
 /* ---------------------------------------------------------------------------------------------
+ * Blocks of the phase-set links, on the device (duet_psblocks.hip): the table that duet_amd/ps_links.py:
+ * blocks(records, min_sv) builds on the host -- that function is the normative text -- built from resident records, and applied
+ * to the read tags without a host table in between.  For callers that rebuild it many times (duet_amd.tune under --join_ps).
+ * tests/ps_blocks_ref.py states the round-based build in plain Python.
+ *
+ *   Nodes       every (contig, ps) that occurs as ps_a or ps_b of any record, trusted or not; one row per node, ascending by
+ *               (contig, ps), PS compared as a full unsigned 32-bit number.
+ *   Trusted     a record whose verdict is same or flip -- (n_same, w_same) against (n_flip, w_flip), lexicographically -- and
+ *               whose winning side has n_win >= min_sv.
+ *   Order       strict: (-n_win, -w_win, row index).
+ *   Forest      Kruskal in that order: a link joins two components or is checked against the sense they imply; one that
+ *               contradicts it is not applied and its row index goes to the conflicts, in the order met.  BLOCK = the smallest
+ *               PS of the component, FLIP = the node's sense relative to that PS.
+ * The device builds the same forest in rounds: every component takes its best-ranked outgoing link (the order is strict, so the
+ * forest is unique); a trusted link outside the forest is a conflict exactly when the parities of its ends differ from its sense.
+ * Integers only; the atomics are minima and sums, so two runs give identical bytes.
+ *
+ * duet_ps_blocks_*: links as duet_ps_links_* writes them (n_links records, strictly ascending by (contig, ps_a, ps_b), ps_a < ps_b,
+ * contig < n_contigs).  out_rows: n_rows rows, 2 * n_links always suffice.  out_conflicts: the conflicting row indices in rank
+ * order; it may be NULL (with conflicts_cap 0): none is written, counts->n_conflicts is still exact.  *counts (HOST): the rows, the
+ * trusted records, the conflicts, the components (distinct BLOCK values per contig, summed).
+ * DUET_ERR_INVALID, nothing written to either output, *counts zero: min_sv < 1; n_links >= 2^30; a record with ps_a >= ps_b, with
+ * contig >= n_contigs, or not strictly above the record before it (found on the device, through a word of the call's own; the
+ * results wait in the workspace until that word has been read); n_rows > rows_cap; out_conflicts given and n_conflicts >
+ * conflicts_cap.  n_links == 0: DUET_OK, zero counts, no array is read.
+ * _device: links, out_rows and out_conflicts device memory; ONE host round trip (the counts and the refusal word), after which the
+ * results are copied out asynchronously on `stream`.  The number of rounds and of pointer jumps per round is fixed on the host
+ * from the bound 2 * n_links on the nodes.  _host: host arrays.
+ *
+ * duet_ps_join_links_device: out_tag and *n_changed are what duet_ps_join_tags_device gives for the table of blocks(records,
+ * min_sv); the table never visits the host.  read_tag, out_tag device memory (out_tag may be read_tag), read_off HOST as for
+ * duet_ps_join_tags_*, counts and n_changed host memory.  ONE host round trip in all.  A refusal of the arguments is decided
+ * before anything is written; a refusal found on the device (the three record checks) returns DUET_ERR_INVALID with zero counts
+ * and *n_changed = 0, and out_tag then holds an unchanged copy of read_tag.  n_links == 0: out_tag a copy.
+ * The workspace is the entries' own (about 110 bytes per record; grown, never shrunk): a call changes nothing that any other
+ * entry later returns. */
+typedef struct duet_ps_blocks_counts {
+    uint32_t n_rows, n_trusted, n_conflicts, n_components;
+} duet_ps_blocks_counts;
+DUET_API int duet_ps_blocks_device(duet_ctx *ctx, const duet_ps_link *links, uint32_t n_links, uint32_t n_contigs, uint32_t min_sv,
+                                   duet_ps_block *out_rows, uint32_t rows_cap, uint32_t *out_conflicts, uint32_t conflicts_cap,
+                                   duet_ps_blocks_counts *counts, void *stream);
+DUET_API int duet_ps_blocks_host(duet_ctx *ctx, const duet_ps_link *links, uint32_t n_links, uint32_t n_contigs, uint32_t min_sv,
+                                 duet_ps_block *out_rows, uint32_t rows_cap, uint32_t *out_conflicts, uint32_t conflicts_cap,
+                                 duet_ps_blocks_counts *counts);
+DUET_API int duet_ps_join_links_device(duet_ctx *ctx, const duet_ps_link *links, uint32_t n_links, uint32_t min_sv,
+                                       const uint64_t *read_tag, const uint32_t *read_off, uint32_t n_contigs, uint32_t n_reads,
+                                       uint64_t *out_tag, duet_ps_blocks_counts *counts, uint32_t *n_changed, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Tags from other SVs (duet_svtags.hip): a mark whose read has no tag word is given the haplotype that the
  * OTHER heterozygous calls listing the read place it on.  A call must not vote for itself, so the tag is per mark and
  * leave-one-out: the evidence for mark (c, r) is every het call listing r except c.  The output is one tag word per RAW MARK, in
