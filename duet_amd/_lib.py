@@ -45,6 +45,7 @@ EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last
            'duet_ps_join_tags_device', 'duet_ps_join_tags_host', 'duet_ps_join_diff_device', 'duet_ps_join_diff_host',
            'duet_ps_blocks_device', 'duet_ps_blocks_host', 'duet_ps_join_links_device',
            'duet_sv_tags_device', 'duet_sv_tags_host',
+           'duet_sv_tags_plan_device', 'duet_sv_tags_plan_host', 'duet_sv_tags_apply_device', 'duet_sv_tags_apply_host',
            'duet_prims_sort_host', 'duet_prims_scan_host', 'duet_prims_local_sort_host')
 
 
@@ -242,6 +243,13 @@ class PsBlocksCounts(ctypes.Structure):     # duet_ps_blocks_counts
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class SvTagsPlanInfo(ctypes.Structure):     # duet_sv_tags_plan_info
+    _fields_ = [(n, ctypes.c_uint32) for n in ('n_untagged', 'n_records', 'n_runs', 'n_contributing')]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class TuneTruth(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ('n_uid', 'n_groups', 'n_pairs', 'reserved')] + \
                [(n, ctypes.c_void_p) for n in ('cand_flags', 'cand_group', 'cand_uid', 'cand_pair', 'group_pair_off', 'pair_uid')]
@@ -412,6 +420,11 @@ def load():
                                               ctypes.POINTER(PsBlocksCounts), ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
     lib.duet_sv_tags_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(ReadTagsProblem)] + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 4
     lib.duet_sv_tags_host.argtypes = lib.duet_sv_tags_device.argtypes[:-1]
+    lib.duet_sv_tags_plan_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(ReadTagsProblem), ctypes.c_void_p, ctypes.c_uint32,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SvTagsPlanInfo), ctypes.c_void_p]
+    lib.duet_sv_tags_plan_host.argtypes = lib.duet_sv_tags_plan_device.argtypes[:-1]
+    lib.duet_sv_tags_apply_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 3
+    lib.duet_sv_tags_apply_host.argtypes = lib.duet_sv_tags_apply_device.argtypes[:-1]
     lib.duet_tune_line_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
@@ -1308,6 +1321,78 @@ class Context(object):
             self._raise(rc)
         return tuple(int(x) for x in counts)
 
+    # -- tags from other SVs, planned (duet_svtags_plan.hip) ------------------------------------------------------------------------
+    def sv_tags_plan_host(self, cand_off, mark_read, mark_name, n_names, ps, read_tag, cand_mask=None, cand_ctg_off=None, cand_contig=None,
+                          mark_order=None, cand_pos=None, pred=None, pc_cap=None, out_tag=None, out_index=None):
+        """duet_sv_tags_plan_host over host arrays (those of sv_tags_host; pred and cand_pos are not read; cand_mask u8[C] or None =
+        every candidate) -> (out_tag u64[M] the base words, out_index u32[M], info dict(n_untagged, n_records, n_runs,
+        n_contributing)).  The plan stays on the context for sv_tags_apply_*.  out_tag / out_index: the arrays written (None: new
+        ones) -- a refused call leaves them as they were."""
+        conv = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)
+        arrays = dict(cand_off=conv(cand_off, np.uint32), mark_order=conv(mark_order, np.uint32), mark_read=conv(mark_read, np.uint32),
+                      mark_name=conv(mark_name, np.uint32), ps=conv(ps, np.uint32), cand_ctg_off=conv(cand_ctg_off, np.uint32),
+                      cand_contig=conv(cand_contig, np.uint16), read_tag=conv(read_tag, np.uint64))
+        mask = conv(cand_mask, np.uint8)
+        prob = ReadTagsProblem()
+        prob.n_cands, prob.n_marks = len(arrays['ps']), len(arrays['mark_read'])
+        prob.n_reads, prob.n_names = len(arrays['read_tag']), int(n_names)
+        prob.n_contigs = len(arrays['cand_ctg_off']) - 1 if cand_ctg_off is not None else 0
+        assert mask is None or len(mask) == prob.n_cands
+        spare = np.zeros(1, dtype=np.uint64)
+        ptr = lambda a: None if a is None else a.ctypes.data if a.size else spare.ctypes.data
+        for k, a in arrays.items():
+            setattr(prob, k, ptr(a))
+        M = prob.n_marks
+        if out_tag is None:
+            out_tag = np.full(M, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        if out_index is None:
+            out_index = np.zeros(M, dtype=np.uint32)
+        assert out_tag.dtype == np.uint64 and out_index.dtype == np.uint32 and len(out_tag) == M and len(out_index) == M
+        cap = PC_MAX if pc_cap is None else int(pc_cap)
+        if not 0 <= cap <= 0xFFFFFFFF:
+            raise ValueError('pc_cap: %r' % (pc_cap,))
+        info = SvTagsPlanInfo()
+        rc = self.lib.duet_sv_tags_plan_host(self.handle, ctypes.byref(prob), ptr(mask), cap, ptr(out_tag), ptr(out_index),
+                                             ctypes.byref(info))
+        del arrays
+        if rc:
+            self._raise(rc)
+        return out_tag, out_index, info.as_dict()
+
+    def sv_tags_plan_device(self, prob, out_tag_ptr, out_index_ptr, cand_mask_ptr=None, pc_cap=None, stream=0):
+        """duet_sv_tags_plan_device on a resident ReadTagsProblem (cand_ctg_off host memory; pred is not read); cand_mask_ptr:
+        the resident u8[n_cands] mask, or None = every candidate; out_tag_ptr / out_index_ptr: device room for n_marks words of 8 /
+        4 bytes -> info dict"""
+        info = SvTagsPlanInfo()
+        rc = self.lib.duet_sv_tags_plan_device(self.handle, ctypes.byref(prob), None if not cand_mask_ptr else ctypes.c_void_p(cand_mask_ptr),
+                                               PC_MAX if pc_cap is None else int(pc_cap), ctypes.c_void_p(out_tag_ptr),
+                                               ctypes.c_void_p(out_index_ptr), ctypes.byref(info), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+        return info.as_dict()
+
+    def sv_tags_apply_host(self, pred, out_tag, min_votes=1, pc_new=0):
+        """duet_sv_tags_apply_host: one vector's first-run calls on the context's plan; out_tag (u64[M], holding the plan's base
+        words at the tagged marks) is written in place at the untagged marks -> (out_tag, counts u32[4]: n_untagged, n_given,
+        n_own_only, and the candidates the plan cannot serve -- non-zero: the words are not to be used)"""
+        pred = np.ascontiguousarray(pred, dtype=np.uint8)
+        assert out_tag.dtype == np.uint64 and out_tag.flags['C_CONTIGUOUS']
+        if not all(0 <= int(x) <= 0xFFFFFFFF for x in (min_votes, pc_new)):
+            raise ValueError('min_votes, pc_new: %r' % ((min_votes, pc_new),))
+        spare, counts = np.zeros(1, dtype=np.uint64), np.zeros(4, dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data if a.size else spare.ctypes.data
+        rc = self.lib.duet_sv_tags_apply_host(self.handle, ptr(pred), int(min_votes), int(pc_new), ptr(out_tag), counts.ctypes.data)
+        if rc:
+            self._raise(rc)
+        return out_tag, tuple(int(x) for x in counts)
+
+    def sv_tags_apply_device(self, pred_ptr, out_tag_ptr, counts_ptr, min_votes=1, pc_new=0, stream=0):
+        """duet_sv_tags_apply_device: asynchronous on `stream`, nothing is read back; counts_ptr: device room for four uint32"""
+        rc = self.lib.duet_sv_tags_apply_device(self.handle, ctypes.c_void_p(pred_ptr), int(min_votes), int(pc_new),
+                                                ctypes.c_void_p(out_tag_ptr), ctypes.c_void_p(counts_ptr), ctypes.c_void_p(stream))
+        if rc:
+            self._raise(rc)
+
     def strata_build_device(self, prob, truth, chrom_stratum_ptr, n_strata, cand_stratum_ptr, group_stratum_ptr, stream=0):
         """duet_tune_strata_build_device on resident arrays (devmem.DeviceTune), after truth_build_device on the same prob / truth."""
         rc = self.lib.duet_tune_strata_build_device(self.handle, ctypes.byref(prob), ctypes.byref(truth), ctypes.c_void_p(chrom_stratum_ptr),
@@ -1355,10 +1440,13 @@ class Context(object):
             self._raise(rc)
         return n.value
 
-    def sweep_device(self, feat_ptr, n_cands, vec_ptr, n_vec, truth, counts_ptr, stream=0):
+    def sweep_device(self, feat_ptr, n_cands, vec_ptr, n_vec, truth, counts_ptr, stream=0, out_pred_ptr=None, out_ps_ptr=None):
+        """duet_tune_sweep_device; out_pred_ptr: device room for n_vec * n_cands bytes (vector-major), out_ps_ptr: for n_cands
+        uint32; without a truth counts_ptr may be 0"""
+        opt = lambda p: ctypes.c_void_p(p) if p else None
         rc = self.lib.duet_tune_sweep_device(self.handle, ctypes.c_void_p(feat_ptr), int(n_cands), ctypes.c_void_p(vec_ptr), int(n_vec),
-                                             ctypes.byref(truth) if truth is not None else None, ctypes.c_void_p(counts_ptr), None, None,
-                                             ctypes.c_void_p(stream))
+                                             ctypes.byref(truth) if truth is not None else None, opt(counts_ptr), opt(out_pred_ptr),
+                                             opt(out_ps_ptr), ctypes.c_void_p(stream))
         if rc:
             self._raise(rc)
 

@@ -29,6 +29,14 @@ struct DuetOwnedBufs {
     }
 };
 
+// the plan of duet_sv_tags_plan_* (duet_svtags_plan.hip): counts, and where its pieces lie in svplan_ws
+struct DuetSvPlan {
+    bool valid = false;
+    uint32_t C = 0, M = 0, U = 0, N = 0, R = 0, V = 0;       // candidates, marks, untagged marks, records, runs, contributing marks
+    void *runs = nullptr, *rec_h = nullptr, *ps = nullptr, *mask = nullptr;
+    uint32_t *rec_first = nullptr, *rec_ps = nullptr, *u_mark = nullptr, *u_cand = nullptr, *u_k = nullptr, *u_lo = nullptr, *u_hi = nullptr;
+};
+
 struct duet_ctx {
     int device = 0;
     std::string err;
@@ -98,6 +106,9 @@ struct duet_ctx {
     DuetOwnedBufs psjoin_ws;               // joined phase sets (duet_psjoin.hip): the header words, the offsets and the staged table 0, the change codes before they are released 1; host-run staging of the read tags 2, of pred0, ps0, pred1, ps1, cand_contig 3-7
     DuetOwnedBufs psblocks_ws;             // blocks of the links (duet_psblocks.hip): the header words and the whole workspace 0; host-run staging of the records 1
     DuetOwnedBufs svtags_ws;               // tags from other SVs (duet_svtags.hip): per-candidate workspace 0, per-mark workspace and the staged words 1, per-contributing-mark workspace 2, the records 3; host-run staging 4-11
+    DuetOwnedBufs svplan_ws;               // tags from other SVs, planned (duet_svtags_plan.hip): the build's per-candidate workspace 0, per-mark workspace and the staged base words 1, per-contributing-mark workspace 2; KEPT between calls: the runs and records 3, the untagged marks 4, the copies of ps and the mask 5
+    DuetOwnedBufs svplan_in;               // ... host-run staging: the plan's arrays 0-7; the apply's pred, words and counters 8-10
+    DuetSvPlan svplan;                     // ... the one plan of the context
     DuetOwnedBufs prims_ws;               // diagnostics of the shared primitives (duet_prims_check.hip): one arena, 0
 };
 

@@ -48,6 +48,11 @@ callset and the truth set are both restricted to the rows with those CHROM texts
 phase sets inside `for ch in range(24)`, so restricting the rows is all it takes, and a stratum is nan exactly where the restricted
 evaluator would raise.  A truth id is the text ID + CHROM + POS, which rows of two contigs can share: truth_side(strata=..) numbers
 the ids per (stratum, id text), so that such an id counts once in a stratum that holds both rows and once in each otherwise.
+
+Voted runs.  --vote_sv_tags scores the second run of duet --vote_sv_tags for every vector of a grid, each on the tags derived from
+its OWN first-run het calls: per setting one plan over the eligible candidates (duet_sv_tags_plan_device),
+per vector one apply (duet_sv_tags_apply_device), the features call on the problem pointed at the words, and that vector swept
+alone over its own records.  --sv_tag_min and --sv_tag_pc are the innermost settings; not with --fit or --join_ps.
 """
 
 import argparse
@@ -415,9 +420,11 @@ def _strata_passes(truth_vcf, bed, skip_phasing, holdout, by_contig):
 COUNTS = tuple(n for n in _lib.COUNTS_NAMES if n != 'reserved')
 
 
-def _strata_rows(rows, contig_rows, vecs, strata_counts, passes, lead):
+def _strata_rows(rows, contig_rows, vecs, strata_counts, passes, lead, labels=None):
     """Per setting: train_ / test_ scores onto its K rows (holdout); one row per vector and stratum that has a call or a truth
-    record to contig_rows (by_contig).  strata_counts[kind] is COUNTS_DTYPE[K, S], or None where the setting's rows are nan."""
+    record to contig_rows (by_contig).  strata_counts[kind] is COUNTS_DTYPE[K, S], or None where the setting's rows are nan.
+    labels[k]: the `vector` column of vector k (None: k itself)."""
+    labels = range(len(vecs)) if labels is None else labels
     for kind, st, base_s in passes:
         counts, n_base = strata_counts.get(kind), base_s['n_base_strata']
         for k in range(len(vecs)):
@@ -427,7 +434,7 @@ def _strata_rows(rows, contig_rows, vecs, strata_counts, passes, lead):
                 if kind == 'holdout':
                     rows[k].update(('%s_%s' % (name, n), x) for n, x in zip(SCORES, ten))
                 elif int(rec['n_calls']) or n_base[s]:
-                    row = dict(lead, vector=k, contig=name, n_base=n_base[s])
+                    row = dict(lead, vector=labels[k], contig=name, n_base=n_base[s])
                     row.update((n, int(rec[n])) for n in COUNTS)
                     row.update(zip(SCORES, ten))
                     contig_rows.append(row)
@@ -482,10 +489,10 @@ def _cap_list(pc_cap):
     return [_lib.check_pc_cap(v) for v in vals]
 
 
-def _lead(c_=None, s_=None, r_=None, p_=None, j_=None):
+def _lead(c_=None, s_=None, r_=None, p_=None, j_=None, m_=None, q_=None):
     """The setting columns in front of a row, in LEAD's order."""
-    vals = dict(pc_cap=p_, svlen_thres=s_, suppread_thres=r_, cluster_max_distance=c_, join_min_sv=j_)
-    return {n: vals[n] for n in LEAD if vals[n] is not None}
+    vals = dict(pc_cap=p_, svlen_thres=s_, suppread_thres=r_, cluster_max_distance=c_, join_min_sv=j_, sv_tag_min=m_, sv_tag_pc=q_)
+    return {n: vals[n] for n in LEAD + SV_TAG if vals[n] is not None}
 
 
 JOIN = 'join_min_sv'         # the setting of --join_ps: the features over the phase sets joined by links of at least N candidates; 0: not joined
@@ -503,6 +510,112 @@ def _int_list(name, v):
     return [int(x) for x in vals]
 
 
+SV_TAG_PC_LIMIT = (1 << 30) - 3
+
+
+def _sv_tag_lists(vote_sv_tags, sv_tag_min, sv_tag_pc, join_min_sv=None):
+    """vote_sv_tags / sv_tag_min / sv_tag_pc of sweep_settings: None without the flag, else (mins, pcs) -- the product's defaults
+    (1,) and (0,); 0 among the mins: no second run."""
+    if not vote_sv_tags:
+        if sv_tag_min is not None or sv_tag_pc is not None:
+            raise ValueError('sv_tag_min / sv_tag_pc need vote_sv_tags')
+        return None
+    if join_min_sv is not None:
+        raise ValueError('vote_sv_tags: not together with join_ps')
+    mins = _int_list('sv_tag_min', (1,) if sv_tag_min is None else sv_tag_min)
+    pcs = _int_list('sv_tag_pc', (0,) if sv_tag_pc is None else sv_tag_pc)
+    if any(q > SV_TAG_PC_LIMIT for q in pcs):
+        raise ValueError('sv_tag_pc: integers in 0 .. %d, not %r' % (SV_TAG_PC_LIMIT, sv_tag_pc))
+    return mins, pcs
+
+
+def _sv_tag_runs(src, dt, n, setting, cap, resident, vecs, sv, want_leaf, on_features=None):
+    """--vote_sv_tags for one outer setting whose first-run features, truth arrays and strata are resident in dt (n candidates):
+    the first-run pred of every vector (duet_tune_sweep_device without a truth, in chunks of vectors), ONE plan with mask =
+    eligible (duet_sv_tags_plan_device), and per (sv_tag_min >= 1, sv_tag_pc) and vector: the apply, the features call on the
+    problem pointed at the words into a second feature tensor, the truth build, every strata build, and that vector swept ALONE
+    over its own record, with its strata sweeps and its census.  The K count records of a setting come back together, with the K
+    counter blocks.  -> {(m, q): dict(counts COUNTS_DTYPE[K], strata {kind: [K, S]}, leaf [(census [K, S, 18] or None per
+    vector, names)], marks int[K, 3], bad bool[K])}; bad[k]: the second run of vector k divides by zero or the plan cannot serve
+    its calls -- nan rows for that vector only.  sv_tag_min 0 is the plain sweep of the first run."""
+    torch, ctx, K, C = dt.torch, src.ctx, dt.K, int(n)
+    mins, pcs = sv
+    rec, VB = _lib.COUNTS_DTYPE.itemsize, dt.VEC_BYTES
+    out = {}
+
+    def census(vectors):
+        leaf = [(dt.leaf_census(ctx, C, vectors), ('all',))]
+        if 'holdout' in resident:
+            leaf.append((dt.leaf_census(ctx, C, vectors, strata=resident['holdout']), ('train', 'test')))
+        return leaf
+
+    todo = [(m, q) for m in mins if m >= 1 for q in pcs]
+    if 0 in mins or C == 0:
+        # (no candidate: nothing can be tagged, the second run IS the first -- the plain rows and marks of 0 for every sv_tag_min)
+        plain = dict(counts=dt.sweep(ctx, C), strata={kind: dt.sweep_strata(ctx, C, p) for kind, p in resident.items()},
+                     leaf=[([c[k:k + 1] for k in range(K)], names) for c, names in census(None)] if want_leaf else [],
+                     marks=np.zeros((K, 3), dtype=np.int64), bad=np.zeros(K, dtype=bool))
+        for m, q in [(0, q) for q in pcs if 0 in mins] + (todo if C == 0 else []):
+            out[(m, q)] = plain
+            if on_features is not None:
+                on_features(dict(setting, sv_tag_min=m, sv_tag_pc=q), src.host(dt))
+    if not todo or C == 0:
+        return out
+    st = dt.stream()
+    first, second = dt.feat, torch.zeros_like(dt.feat)
+    el = _lib.FEATURE_DTYPE.fields['eligible'][1]
+    mask = first[:C * _lib.FEATURE_DTYPE.itemsize].view(C, _lib.FEATURE_DTYPE.itemsize)[:, el].contiguous()
+    ps = torch.zeros(C, dtype=torch.int32, device=dt.device)
+    chunk = max(1, min(K, (64 << 20) // C))                # (K * C bytes stay bounded)
+    pred = torch.zeros(chunk * C, dtype=torch.uint8, device=dt.device)
+    state = {mq: dict(counts=torch.zeros(K * rec, dtype=torch.uint8, device=dt.device),
+                      four=torch.zeros(4 * K, dtype=torch.int32, device=dt.device),
+                      strata={kind: torch.zeros_like(p['counts']) for kind, p in resident.items()},
+                      leaf=None, bad=np.zeros(K, dtype=bool)) for mq in todo}
+    planned = None
+    for k0 in range(0, K, chunk):
+        kn = min(chunk, K - k0)
+        ctx.sweep_device(first.data_ptr(), C, dt.vec_ptr + k0 * VB, kn, None, 0, st, out_pred_ptr=pred.data_ptr(), out_ps_ptr=ps.data_ptr())
+        if planned is None:                                 # (ps is the same for every vector: the first chunk brought it)
+            planned = src.sv_tags_plan(dt, cap, ps, mask, st)
+        for m, q in todo:
+            s_ = state[(m, q)]
+            for k in range(k0, k0 + kn):
+                vec_k = dt.vec_ptr + k * VB
+                ctx.sv_tags_apply_device(pred.data_ptr() + (k - k0) * C, planned['tags'].data_ptr(), s_['four'].data_ptr() + 16 * k,
+                                         min_votes=m, pc_new=q, stream=st)
+                dt.feat = second
+                try:
+                    src.sv_tags_features(planned, second.data_ptr(), st, cap)
+                    dt.build(ctx, C, src.result)
+                    ctx.sweep_device(second.data_ptr(), C, vec_k, 1, dt.truth, s_['counts'].data_ptr() + k * rec, st)
+                    for kind, p in resident.items():
+                        dt.build_strata(ctx, C, src.result, p)
+                        S = p['strata'].n_strata
+                        ctx.sweep_strata_device(second.data_ptr(), C, vec_k, 1, p.get('truth', dt.truth), p['strata'],
+                                                s_['strata'][kind].data_ptr() + k * S * rec, st)
+                    if want_leaf:
+                        got = census(vecs[k:k + 1])
+                        if s_['leaf'] is None:
+                            s_['leaf'] = [([None] * K, names) for _, names in got]
+                        for (per, _), (c, _) in zip(s_['leaf'], got):
+                            per[k] = c
+                    if on_features is not None:
+                        on_features(dict(setting, sv_tag_min=m, sv_tag_pc=q), src.host(dt))
+                except ZeroDivisionError:
+                    s_['bad'][k] = True
+                finally:
+                    dt.feat = first
+    for (m, q), s_ in state.items():
+        four = s_['four'].cpu().numpy().view(np.uint32).reshape(K, 4)
+        bad = s_['bad'] | (four[:, 3] != 0)
+        out[(m, q)] = dict(counts=s_['counts'].cpu().numpy().view(_lib.COUNTS_DTYPE).copy(),
+                           strata={kind: t[:K * resident[kind]['strata'].n_strata * rec].cpu().numpy().view(_lib.COUNTS_DTYPE)
+                                   .reshape(K, resident[kind]['strata'].n_strata).copy() for kind, t in s_['strata'].items()},
+                           leaf=s_['leaf'] or [], marks=four[:, :3].astype(np.int64), bad=bad)
+    return out
+
+
 _NO_CAP_LINE = np.zeros(1, dtype=np.uint32), 0, True        # the cap line of a problem without marks: the one value 0, whole
 
 
@@ -514,15 +627,20 @@ class _Callset(object):
     n_max (the most candidates a setting can have), texts (the CHROM text per candidate or contig, for chrom_strata), key(dt),
     features(dt, setting, cap), result, cap_line(dt, max_values) and host(dt)."""
 
-    def __init__(self, ctx, home, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js=None):
+    def __init__(self, ctx, home, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js=None, names=False):
         self.ctx, self.home, self.bed, self.skip_phasing, self.ingest = ctx, home, bed, skip_phasing, (include_all_ctgs, thread)
         self.settings = [(None,) + t for t in itertools.product(ss, rs, ps, *([js] if js is not None else []))]
         self.result = None                                  # (the per-candidate form: build() reads no cluster result)
+        self.names = names                                  # (--vote_sv_tags: the marks' read names too)
 
     def ingests(self):
         from duet_amd.devmem import DeviceProblem
         _, s_, r_, _ = self.settings[0][:4]
+        if self.names:
+            self.mark_name, self.n_names = _mark_names(self.home, *self.ingest)
         self.soa, txt = _candidates(self.home, s_, r_, *self.ingest)
+        if self.names and len(self.mark_name) != self.soa.n_marks:
+            raise RuntimeError('--vote_sv_tags needs the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
         self.cands = dict(pos=self.soa.cand_pos, svlen=self.soa.cand_svlen, **txt)
         self.n_max, self.texts = self.soa.n_cands, self.cands['chrom']
         self.dp = DeviceProblem(self.soa, s_, r_, device='cuda:%d' % self.ctx.device_id) if self.n_max else None
@@ -547,6 +665,32 @@ class _Callset(object):
                 self.ctx.features_device(p, dt.feat.data_ptr(), dt.stream(), pc_cap=cap)
         return self.n_max
 
+    def sv_tags_plan(self, dt, cap, ps, mask, stream):
+        """(--vote_sv_tags) The plan of the resident problem under the phase sets `ps` (int32[C] tensor) and `mask` (uint8[C] tensor)
+        -> dict(tags, index, info): the base words, the identity index and the plan's counts.  A refusal raises."""
+        from duet_amd.devmem import upload
+        torch, ef, soa = dt.torch, self.dp.problem, self.soa
+        if getattr(self, 'sv', None) is None:
+            self.sv = dict(names=upload(torch, dt.device, self.mark_name, np.uint32),
+                           tags=torch.zeros(max(soa.n_marks, 1), dtype=torch.int64, device=dt.device),
+                           index=torch.zeros(max(soa.n_marks, 1), dtype=torch.int32, device=dt.device),
+                           off=np.ascontiguousarray(soa.cand_ctg_off, dtype=np.uint32))
+        sv = self.sv
+        p = _lib.ReadTagsProblem()
+        p.n_cands, p.n_marks, p.n_reads, p.n_names, p.n_contigs = soa.n_cands, soa.n_marks, soa.n_reads, self.n_names, soa.n_contigs
+        p.cand_off, p.mark_read, p.read_tag, p.mark_name = ef.cand_off, ef.mark_read, ef.read_tag, sv['names'].data_ptr()
+        p.cand_ctg_off, p.ps = sv['off'].ctypes.data, ps.data_ptr()
+        sv['info'] = self.ctx.sv_tags_plan_device(p, sv['tags'].data_ptr(), sv['index'].data_ptr(), cand_mask_ptr=mask.data_ptr(),
+                                                  pc_cap=cap, stream=stream)
+        return sv
+
+    def sv_tags_features(self, planned, out_ptr, stream, cap):
+        """(--vote_sv_tags) The features of the second run: the resident problem reads the plan's words through the identity index
+        (a mark is its own read); its own tags, index and read count come back whatever happens.  Raises ZeroDivisionError where
+        E/F would."""
+        with _pointed_at_marks(self.dp.problem, planned['tags'], planned['index'], self.soa.n_marks):
+            self.ctx.features_device(self.dp.problem, out_ptr, stream, pc_cap=cap)
+
     def cap_line(self, dt, max_values):
         # (the same line with and without a join: the remap keeps pc bit for bit and leaves untagged words alone, so the problem's
         # own tags give the pc values of the marks that can vote)
@@ -563,9 +707,10 @@ class _Bams(object):
     per-contig tables (contig_tables, bed_tables); a setting's features are DeviceSvim.run_features', which clusters again on
     every call (the entry keeps no state between calls).  Each distinct setting is computed once, in c, r, cap order per -s."""
 
-    def __init__(self, ctx, home, cs, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js=None):
+    def __init__(self, ctx, home, cs, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js=None, names=False):
         self.ctx, self.home, self.bed, self.skip_phasing, self.ingest = ctx, home, bed, skip_phasing, (include_all_ctgs, thread)
         self.settings = list(itertools.product(cs, ss, rs, ps, *([js] if js is not None else [])))
+        self.names = names                                  # (--vote_sv_tags: the marks' read names too)
 
     def ingests(self):
         from duet_amd import svim_mode
@@ -578,11 +723,13 @@ class _Bams(object):
         self.tables = contig_tables(self.texts, self.skip_phasing) + (bed_tables(self.bed, self.texts) if self.bed else None,)
         depth_bin = 1000                                    # (phase_from_bams's defaults)
         for s_ in sorted(set(t[1] for t in self.settings)):
-            ing, got = NativeIngest.extract(self.home + '/snp_phasing/', chroms, thread, max(s_, 1), 20, depth_bin)
+            ing, got = NativeIngest.extract(self.home + '/snp_phasing/', chroms, thread, max(s_, 1), 20, depth_bin, names=self.names)
             if ing is None:
                 raise RuntimeError('signature extraction declined the input: %s' % got)
             ing.close()
             self.n_max = len(got['pos'])
+            if self.names:
+                self.mark_name, self.n_names, self.sv = np.array(got['mark_name'], dtype=np.uint32), len(got['name_off']) - 1, None
             todo = list(dict.fromkeys(t for t in self.settings if t[1] == s_))
             c_, _, r_, _ = todo[0][:4]
             self.ds = DeviceSvim(got, got['read_tag'], got['depth'], got['depth_off'], depth_bin, s_, r_, max_dist=c_,
@@ -608,6 +755,34 @@ class _Bams(object):
                 return self.ds.run_features(self.ctx, dt.feat.data_ptr(), pc_cap=cap)
         return self.ds.run_features(self.ctx, dt.feat.data_ptr(), pc_cap=cap)
 
+    def sv_tags_plan(self, dt, cap, ps, mask, stream):
+        """(--vote_sv_tags) As _Callset.sv_tags_plan, on the resident cluster result of the last features() call (its offsets, mark
+        order and contig column), the raw marks' read indices and names, and the resident tags."""
+        from duet_amd.devmem import upload
+        torch, ds = dt.torch, self.ds
+        if self.sv is None:
+            self.sv = dict(names=upload(torch, dt.device, self.mark_name, np.uint32),
+                           tags=torch.zeros(max(ds.M, 1), dtype=torch.int64, device=dt.device),
+                           index=torch.zeros(max(ds.M, 1), dtype=torch.int32, device=dt.device))
+        sv = self.sv
+        sv['n_cands'] = int(ds.n_found)
+        p = _lib.ReadTagsProblem()
+        p.n_cands, p.n_marks, p.n_reads, p.n_names = sv['n_cands'], ds.M, ds.sv_problem.n_reads, self.n_names
+        p.cand_off, p.mark_order, p.cand_contig = ds.result.cand_off, ds.result.order, ds.result.cand_contig
+        p.mark_read, p.mark_name, p.read_tag = ds.keep['sv_read'].data_ptr(), sv['names'].data_ptr(), ds.keep['sv_tag'].data_ptr()
+        p.ps = ps.data_ptr()
+        sv['info'] = self.ctx.sv_tags_plan_device(p, sv['tags'].data_ptr(), sv['index'].data_ptr(), cand_mask_ptr=mask.data_ptr(),
+                                                  pc_cap=cap, stream=stream)
+        return sv
+
+    def sv_tags_features(self, planned, out_ptr, stream, cap):
+        """(--vote_sv_tags) As _Callset.sv_tags_features: the pipeline clusters again (clustering reads no tag, so the candidates
+        line up; their count is checked) and reads the plan's words through the identity index."""
+        with _pointed_at_marks(self.ds.sv_problem, planned['tags'], planned['index'], self.ds.M):
+            n = self.ds.run_features(self.ctx, out_ptr, pc_cap=cap)
+        if n != planned['n_cands']:
+            raise RuntimeError('vote_sv_tags: the cluster result changed between the two runs')
+
     def cap_line(self, dt, max_values):
         return dt.cap_line(self.ctx, self.ds.sv_problem, max_values) if self.n_max else _NO_CAP_LINE     # (as _Callset.cap_line)
 
@@ -619,8 +794,38 @@ class _Bams(object):
                     pos=res['cand_pos'], svlen=res['cand_span'], svtype=[SV_TYPE_NAMES[int(t) & 3] for t in res['cand_type']])
 
 
+class _pointed_at_marks(object):
+    def __init__(self, problem, tags, index, n_marks):
+        self.problem, self.to, self.mine = problem, (tags.data_ptr(), index.data_ptr(), int(n_marks)), None
+
+    def __enter__(self):
+        p = self.problem
+        self.mine = p.read_tag, p.mark_read, p.n_reads
+        p.read_tag, p.mark_read, p.n_reads = self.to
+        return self
+
+    def __exit__(self, *exc):
+        p = self.problem
+        p.read_tag, p.mark_read, p.n_reads = self.mine
+        return False
+
+
+def _mark_names(home, include_all_ctgs, thread):
+    """(--vote_sv_tags) The marks' read names of <home> by the native ingest -> (mark_name u32[M], n_names); refused where the
+    ingest declines, as in duet."""
+    from duet_amd import sv_phasing
+    ing, _ = sv_phasing.load_native(home, thread, include_all_ctgs, home + '/sv_calling/variants.vcf', log=False, names=True)
+    if ing is None:
+        raise RuntimeError('--vote_sv_tags needs the native ingest, which declined this input (or DUET_NATIVE_INGEST=0)')
+    try:
+        nm = ing.mark_names()
+        return np.array(nm['mark_name'], dtype=np.uint32), len(nm['name_off']) - 1
+    finally:
+        ing.close()
+
+
 def _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_bams, pc_cap, bed, skip_phasing, include_all_ctgs, thread,
-            join_min_sv=None):
+            join_min_sv=None, names=False):
     """The candidate source of sweep_settings / fit for their -s, -r, -c and pc_cap arguments (nothing is read yet); its ctx is
     `ctx`, or the default context, opened once the arguments have passed."""
     ss, rs = _int_list('svlen_thres', svlen_thres), _int_list('suppread_thres', suppread_thres)
@@ -632,8 +837,8 @@ def _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_b
         raise ValueError('cluster_max_distance: an empty list')
     ctx = ctx or engine.default_context()
     if from_bams:
-        return _Bams(ctx, home, cs, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js)
-    return _Callset(ctx, home, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js)
+        return _Bams(ctx, home, cs, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js, names=names)
+    return _Callset(ctx, home, ss, rs, ps, bed, skip_phasing, include_all_ctgs, thread, js, names=names)
 
 
 def _make_resident(src, dt, setting, cap, passes):
@@ -670,7 +875,8 @@ def _settings(src, vecs, base, passes, refdist, pctsim, on_features=None):
 
 def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,), cluster_max_distance=None, from_bams=False,
                    refdist=1000, pctsim=0.0, bed='', skip_phasing=False, include_all_ctgs=False, thread=4, ctx=None, on_features=None,
-                   holdout=None, by_contig=None, pc_cap=None, by_leaf=None, join_min_sv=None):
+                   holdout=None, by_contig=None, pc_cap=None, by_leaf=None, join_min_sv=None, vote_sv_tags=False, sv_tag_min=None,
+                   sv_tag_pc=None):
     """sweep() for every setting of -s (svlen_thres), -r (suppread_thres) and, with from_bams, -c (cluster_max_distance; default
     (0.9,)): -> list of rows, settings outermost in the order c, s, r, each row a dict of svlen_thres, suppread_thres
     [, cluster_max_distance], the 14 thresholds and the ten numbers.  from_bams: the candidates come from <home>/snp_phasing/*.bam
@@ -700,13 +906,27 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
     features are those of the joined run -- the links under the setting (duet_ps_links_device / duet_svim_ps_links_device), their
     blocks built and applied to the read tags on the device (duet_ps_join_links_device), the features call on the remapped tags,
     whose PS column holds block names; everything downstream runs unchanged on that record.  0: not joined, the rows of a run
-    without the argument.  None: no such setting and no column."""
+    without the argument.  None: no such setting and no column.
+    vote_sv_tags (--vote_sv_tags), with sv_tag_min (a list of N >= 0, default (1,)) and sv_tag_pc (a list of PCs in 0 .. 2^30 - 3,
+    default (0,)) -- the innermost settings, behind pc_cap: every row scores the SECOND run of duet --vote_sv_tags for its own
+    vector -- the tags derived from that vector's first-run calls (_sv_tag_runs: one plan per outer setting, one apply per
+    vector) -- and gains sv_tag_min, sv_tag_pc and the vector's marks_untagged, marks_given, marks_own_only behind the other
+    setting columns; by_contig rows gain the two settings only.  sv_tag_min 0: no second run, the rows of a call without the
+    argument and marks of 0.  A vector whose second run divides by zero has nan rows for that vector only.  Not together with
+    join_min_sv.  Both candidate sources; from_bams clusters again per features call, as it does without the flag.
+    on_features: one call per (setting, sv_tag_min, sv_tag_pc) with the second run's records, which differ per vector -- so
+    only with a grid of exactly one vector."""
     vecs = grid if isinstance(grid, np.ndarray) else expand_grid(grid)
+    sv = _sv_tag_lists(vote_sv_tags, sv_tag_min, sv_tag_pc, join_min_sv)
+    if sv is not None and on_features is not None and len(vecs) != 1:
+        raise ValueError('vote_sv_tags: the features of the second run differ per vector; on_features needs a grid of exactly one vector')
     src = _source(ctx, home, svlen_thres, suppread_thres, cluster_max_distance, from_bams, pc_cap, bed, skip_phasing, include_all_ctgs, thread,
-                  join_min_sv)
+                  join_min_sv, names=sv is not None)
     ctx = src.ctx
     base = truth_side(truth_vcf, bed, skip_phasing)
     passes = _strata_passes(truth_vcf, bed, skip_phasing, holdout, by_contig)
+    if sv is not None:
+        return _sweep_sv_tags(src, vecs, base, passes, refdist, pctsim, on_features, by_contig, by_leaf, sv)
     done = {}
     for lead, dt, n, resident, _ in _settings(src, vecs, base, passes, refdist, pctsim, on_features):
         counts, strata_counts, leaf = None, {}, _leaf_nan(resident)
@@ -729,6 +949,41 @@ def sweep_settings(home, truth_vcf, grid, svlen_thres=(50,), suppread_thres=(2,)
         if by_leaf is not None:
             for census, names in leaf:
                 by_leaf.extend(leaf_rows(lead, range(len(vecs)), census, names))
+    return out
+
+
+def _sweep_sv_tags(src, vecs, base, passes, refdist, pctsim, on_features, by_contig, by_leaf, sv):
+    """sweep_settings under vote_sv_tags: per outer setting _sv_tag_runs, then the rows -- settings outermost, sv_tag_min, sv_tag_pc,
+    the vectors innermost."""
+    K, done = len(vecs), {}
+    for lead, dt, n, resident, _ in _settings(src, vecs, base, passes, refdist, pctsim):
+        cap = lead.get('pc_cap')
+        done[tuple(lead.values())] = (None if n is None else
+                                      _sv_tag_runs(src, dt, n, lead, cap, resident, vecs, sv, by_leaf is not None, on_features), resident)
+    out = []
+    for t in src.settings:
+        runs, resident = done[tuple(_lead(*t).values())]
+        for m in sv[0]:
+            for q in sv[1]:
+                lead = _lead(*t, m_=m, q_=q)
+                run = runs[(m, q)] if runs is not None else None
+                rows = []
+                for k in range(K):
+                    ok = run is not None and not run['bad'][k]
+                    row = _rows(vecs[k:k + 1], run['counts'][k:k + 1] if ok else None, base['n_base'], lead)[0]
+                    marks = run['marks'][k] if ok else (math.nan,) * 3
+                    row = dict(list(lead.items()) + list(zip(MARKS, (x if x != x else int(x) for x in marks))) +
+                               [(name, row[name]) for name in row if name not in lead])
+                    _strata_rows([row], by_contig, vecs[k:k + 1], {kind: c[k:k + 1] for kind, c in run['strata'].items()} if ok else {},
+                                 passes, lead, labels=[k])
+                    rows.append(row)
+                out.extend(rows)
+                if by_leaf is not None:
+                    kinds = run['leaf'] if run is not None and run['leaf'] else [([None] * K, names) for _, names in _leaf_nan(resident)]
+                    for per, names in kinds:
+                        for k in range(K):
+                            ok = run is not None and not run['bad'][k] and per[k] is not None
+                            by_leaf.extend(leaf_rows(lead, [k], per[k] if ok else None, names))
     return out
 
 
@@ -1076,6 +1331,15 @@ def parse_args(argv):
                          'comma-separated list sweeps it; 0 = not joined [2].  With --fit, --out_vector carries the best '
                          'setting\'s value when it is at least 1; when 0 (not joined) fits best the file has no such key, and '
                          'duet --thresholds FILE is then meant to run without --join_ps (with it, it joins with its default 2)')
+    ap.add_argument('--vote_sv_tags', action='store_true',
+                    help='score the second run of duet --vote_sv_tags, per vector: the untagged reads vote with the haplotype that the '
+                         "vector's own first-run het calls give them; --sv_tag_min and --sv_tag_pc become the innermost settings and "
+                         'every row gains their columns and marks_untagged, marks_given, marks_own_only')
+    ap.add_argument('--sv_tag_min', type=_csv(int, '--sv_tag_min'), default=None,
+                    help='with --vote_sv_tags: a read gets a tag only when the other calls favour one haplotype by at least this many '
+                         'marks; a comma-separated list sweeps it; 0 = no second run [1]')
+    ap.add_argument('--sv_tag_pc', type=_csv(int, '--sv_tag_pc'), default=None,
+                    help='with --vote_sv_tags: the PC the derived tags carry, 0 .. 2^30 - 3; a comma-separated list sweeps it [0]')
     ap.add_argument('-a', '--include_all_ctgs', action='store_true', help='all contigs, not only chr{1..22,X,Y}')
     ap.add_argument('-t', '--thread', type=int, default=4, help='threads of the ingest [%(default)s]')
     ap.add_argument('--refdist', type=int, default=1000, help="the evaluator's --refdist [%(default)s]")
@@ -1113,17 +1377,31 @@ def parse_args(argv):
     if a.join_min_sv is not None and not a.join_ps:
         ap.error('--join_min_sv needs --join_ps')
     a.join = (a.join_min_sv if a.join_min_sv is not None else [2]) if a.join_ps else None
+    if (a.sv_tag_min is not None or a.sv_tag_pc is not None) and not a.vote_sv_tags:
+        ap.error('--sv_tag_min and --sv_tag_pc need --vote_sv_tags')
+    if a.vote_sv_tags and a.fit is not None:
+        ap.error('--vote_sv_tags does not work with --fit: the exact line of an axis rests on the feature records not moving while a '
+                 'constant moves, and the second run\'s records move with the first run\'s calls')
+    if a.vote_sv_tags and a.join_ps:
+        ap.error('--vote_sv_tags and --join_ps do not work together')
+    if a.vote_sv_tags:
+        try:
+            _sv_tag_lists(True, a.sv_tag_min, a.sv_tag_pc)
+        except ValueError as e:
+            ap.error(str(e))
     return a
 
 
 LEAD = ('pc_cap', 'svlen_thres', 'suppread_thres', 'cluster_max_distance', 'join_min_sv')   # the setting columns in front of a row, in this order
+SV_TAG = ('sv_tag_min', 'sv_tag_pc')            # ... and behind them the settings of --vote_sv_tags, innermost; sv_tag_min 0: no second run
+MARKS = ('marks_untagged', 'marks_given', 'marks_own_only')     # ... and what the second run of a row's vector did to the marks
 
 
 def features_path(path, setting):
-    """--features with several settings: FILE.ext -> FILE[.c<c>].s<s>.r<r>[.p<cap>][.j<join_min_sv>].ext"""
+    """--features with several settings: FILE.ext -> FILE[.c<c>].s<s>.r<r>[.p<cap>][.j<join_min_sv>][.v<sv_tag_min>.q<sv_tag_pc>].ext"""
     root, ext = os.path.splitext(path)
     tag = ''.join('.%s%s' % (t, setting[n]) for t, n in (('c', 'cluster_max_distance'), ('s', 'svlen_thres'), ('r', 'suppread_thres'),
-                                                         ('p', 'pc_cap'), ('j', JOIN)) if n in setting)
+                                                         ('p', 'pc_cap'), ('j', JOIN), ('v', 'sv_tag_min'), ('q', 'sv_tag_pc')) if n in setting)
     return root + tag + ext
 
 
@@ -1181,10 +1459,13 @@ def main(argv):
     if a.fit is not None:
         return main_fit(a)
     vecs = load_grid(a.grid)
+    if a.vote_sv_tags and a.features and len(vecs) != 1:
+        raise SystemExit('tune: --features with --vote_sv_tags needs a grid of exactly one vector: the features of the second run '
+                         'differ per vector')
     ctx = engine.default_context(a.device)
     cs = a.cluster_max_distance if a.from_bams else None
     single = not a.from_bams and len(a.sv_min_size) == 1 and len(a.min_support_read) == 1
-    plain = single and a.pc_cap is None and a.join is None
+    plain = single and a.pc_cap is None and a.join is None and not a.vote_sv_tags
 
     def write_features(setting, cands):
         f = cands['feat']
@@ -1198,10 +1479,10 @@ def main(argv):
                           a.bed_file, a.skip_phasing, a.include_all_ctgs, a.thread, ctx=ctx,
                           on_features=write_features if a.features else None, holdout=a.holdout,
                           by_contig=contig_rows if a.by_contig else None, pc_cap=a.pc_cap, by_leaf=leaf if a.by_leaf else None,
-                          join_min_sv=a.join)
+                          join_min_sv=a.join, vote_sv_tags=a.vote_sv_tags, sv_tag_min=a.sv_tag_min, sv_tag_pc=a.sv_tag_pc)
     # (one -s and one -r, not from the BAMs: their columns stay away, as without --pc_cap)
-    lead = tuple(n for n in LEAD if n in rows[0] and (n in ('pc_cap', JOIN) or not single))
-    cols = lead + NAMES + SCORES
+    lead = tuple(n for n in LEAD + SV_TAG if n in rows[0] and (n in ('pc_cap', JOIN) + SV_TAG or not single))
+    cols = lead + (MARKS if a.vote_sv_tags else ()) + NAMES + SCORES
     if a.holdout is not None:
         cols += tuple('%s_%s' % (part, n) for part in ('train', 'test') for n in SCORES)
     _write_tsv(a.out, cols, ([r[n] for n in cols] for r in rows))

@@ -1108,6 +1108,56 @@ DUET_API int duet_sv_tags_host(duet_ctx *ctx, const duet_read_tags_problem *prob
                                uint64_t *out_tag, uint32_t *out_index, uint32_t *counts);
 
 /* ---------------------------------------------------------------------------------------------
+ * Tags from other SVs, planned (duet_svtags_plan.hip): the rule of the section above for MANY vectors of first-run
+ * calls over one problem.  What does not read pred is done once (the plan); what reads it is done per vector (the apply) with no
+ * sort, no allocation and no host round trip.  For callers that score the second run of many vectors (duet_amd.tune under
+ * --vote_sv_tags).  tests/sv_tags_ref.py remains the rule; nothing new is chosen.
+ *
+ * duet_sv_tags_plan_*: prob as for duet_sv_tags_* -- pred is NOT read and may be NULL; ps[c] is read for the masked candidates.
+ * cand_mask: u8[n_cands], non-zero = the candidate may be a het call (pred 1 or 2) under some vector; NULL = every candidate.
+ *   Plan        everything of duet_sv_tags_device that does not read pred, over the masked candidates in place of the het ones: the
+ *               owner of every raw mark; the (name << 32 | ps[c]) keys of the masked candidates' marks sorted stably once; the records
+ *               numbered; the RUNS -- a record's members from one candidate -- kept as (candidate, k), so a candidate with 70,000
+ *               marks under one name is one run; one compact record per UNTAGGED raw mark: the mark, its candidate (where masked),
+ *               its own k, the range of records of its name.
+ *   Base words  out_tag[m] = the word of every tagged mark bit for bit, all-ones for every untagged mark; out_index = the identity.
+ *   Refused     DUET_ERR_INVALID, nothing written, no plan left: what duet_sv_tags_* refuses of the problem and of pc_cap (pred, min_votes
+ *               and pc_new are the apply's).  Section 20's contradiction is checked over the MASKED candidates' marks: STRICTER than
+ *               duet_sv_tags_*, which checks the het ones only -- a masked candidate that no vector calls het can refuse a plan.
+ *   *info       (HOST) the untagged marks, the records, the runs, and the contributing marks V of the masked candidates.
+ * n_cands == 0 or n_marks == 0: DUET_OK, zero info, nothing written; an apply then clears its counters and writes nothing else.
+ * _device: the arrays of *prob (cand_ctg_off aside: HOST), cand_mask, out_tag[n_marks] and out_index[n_marks] device memory.  THREE host
+ * round trips of a few words, as duet_sv_tags_device.  _host: host arrays.
+ * The plan lives in a workspace of the context's own (8 bytes per run, 20 per record, 20 per untagged mark, 5 per candidate, beside the
+ * build's transient 44 per contributing mark and 16 per mark; grown, never shrunk).  One plan per context: a later plan call
+ * replaces it, accepted or not.  The plan holds COPIES (ps and the mask among them): nothing of *prob is read once the work queued
+ * on `stream` has run, so the caller may point the problem at out_tag afterwards.
+ *
+ * duet_sv_tags_apply_*: pred u8[n_cands], one vector's first-run calls.  out_tag must hold the plan's base words at the tagged marks.
+ *   Writes      the word of EVERY untagged mark -- given or all-ones -- on every call, and nothing else of out_tag: the bytes of a
+ *               vector do not depend on the vectors applied before it.
+ *   out_counts  u32[4]: n_untagged, n_given, n_own_only as duet_sv_tags_*; out_counts[3] = the candidates with pred > 3 or with pred 1
+ *               or 2 outside the mask.  Non-zero: the words of this call are not to be used (the tagged marks still hold the base
+ *               words).
+ *   Contract    where the plan accepts and out_counts[3] is 0: out_tag, out_index and the three counters are those of
+ *               duet_sv_tags_device with the same pred, min_votes and pc_new, byte for byte.
+ *   Refused     DUET_ERR_INVALID, nothing written: no plan on the context; min_votes == 0; pc_new above 2^30 - 3; a NULL argument.
+ * _device: pred, out_tag and out_counts device memory; ASYNCHRONOUS on `stream` -- four words cleared and two kernels, nothing read
+ * back; calls on one plan are ordered by the stream (they share the plan's record sums).  _host: host arrays (out_tag is uploaded,
+ * applied to, and copied back), synchronises. */
+typedef struct duet_sv_tags_plan_info {
+    uint32_t n_untagged, n_records, n_runs, n_contributing;
+} duet_sv_tags_plan_info;
+DUET_API int duet_sv_tags_plan_device(duet_ctx *ctx, const duet_read_tags_problem *prob, const uint8_t *cand_mask, uint32_t pc_cap,
+                                      uint64_t *out_tag, uint32_t *out_index, duet_sv_tags_plan_info *info, void *stream);
+DUET_API int duet_sv_tags_plan_host(duet_ctx *ctx, const duet_read_tags_problem *prob, const uint8_t *cand_mask, uint32_t pc_cap,
+                                    uint64_t *out_tag, uint32_t *out_index, duet_sv_tags_plan_info *info);
+DUET_API int duet_sv_tags_apply_device(duet_ctx *ctx, const uint8_t *pred, uint32_t min_votes, uint32_t pc_new, uint64_t *out_tag,
+                                       uint32_t *out_counts, void *stream);
+DUET_API int duet_sv_tags_apply_host(duet_ctx *ctx, const uint8_t *pred, uint32_t min_votes, uint32_t pc_new, uint64_t *out_tag,
+                                     uint32_t *out_counts);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics: the shared device primitives (duet_amd/csrc/duet_prims.hip.h) on host arrays, each run unchanged on the
  * context's own stream with a workspace sized as the primitive's comments prescribe (duet_amd/csrc/duet_prims_check.hip).  No
  * product path calls these; tests/test_gpu_prims.py compares them with numpy at every plan boundary.  n == 0: DUET_OK, nothing is
