@@ -1983,10 +1983,11 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
 // every wavefront orders blocks of 64 in its registers, a value's place is the sum of its lower bounds in all blocks (its own
 // included: the values are distinct) -- ef_seed_sort's scheme.  Every one of the workgroup's NT threads calls it.
 template <uint32_t NT>
-__device__ __forceinline__ void own_sort_set(const uint32_t *s_tab, uint32_t *s_key, uint32_t *s_one, uint32_t *s_part, uint32_t u)
+__device__ __forceinline__ void own_sort_set(const uint32_t *s_tab, uint32_t *s_key, uint32_t *s_one, uint32_t *s_part, uint32_t u,
+                                             uint32_t tid)
 {
     constexpr uint32_t NW = NT / 64u;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
     uint32_t mv[kOwnTab / NT], cnt = 0;
 #pragma unroll
     for (uint32_t j = 0; j < kOwnTab / NT; ++j) {
@@ -2186,6 +2187,7 @@ __device__ __forceinline__ void finalize_own_tiles(const Params &p)
     // records, issued last, are still on their way -- their wait is the insert phase's, behind the barrier
     asm volatile("" ::"v"(code_ld), "v"(ps_ld), "v"(pos_ld), "v"(o0_ld), "v"(o1_ld), "v"(sv_ld), "v"(rf_ld), "v"(a0.x), "v"(a0.y),
                  "v"(a1.x), "v"(a1.y));
+    STAMP(2, 4);                                               // (the columns and summaries are here: the first trip without the clear)
     {
         uint2 *dst = reinterpret_cast<uint2 *>(s_c2);
         dst[tid] = a0;
@@ -2199,6 +2201,15 @@ __device__ __forceinline__ void finalize_own_tiles(const Params &p)
         if (c_lo == c_hi) continue;
         const uint32_t b_lo = c_lo / kCandPerBlock, b_hi = (c_hi - 1) / kCandPerBlock;
         if (k != k_first) load_recs(b_lo, b_hi);               // (in flight while the table is cleared)
+        // The thread's index through an asm, once per contig (round 11).  What the body below derives from it -- the lane predicates
+        // of own_sort_set's sorting network, the later trips' record indices, LDS addresses: most of it for the rare paths -- is the
+        // same for every contig, so the compiler computed all of it in front of this loop, in every wavefront, between the first
+        // trip's wait and the first barrier: 357 instructions stood there, 65 of them v_writelane for the scalar registers the
+        // predicates had spilled, and the stamps put 1.2 us of the 1.76 us "start -> cleared" behind the arrival of the columns.
+        // Derived from a value the compiler cannot see through, each stays where it is used.
+        uint32_t t_k = threadIdx.x;
+        asm volatile("" : "+v"(t_k));
+        const uint32_t tid = t_k, lane = t_k & 63u, wave = t_k >> 6;
 #pragma unroll
         for (uint32_t i = 0; i < kOwnTab / NT; ++i) s_tab[tid + NT * i] = kEmpty;
         if (tid == 0) s_nwin = 0;
@@ -2369,7 +2380,7 @@ __device__ __forceinline__ void finalize_own_tiles(const Params &p)
         const uint32_t n_win = s_nwin;
         const bool over = u > keys_cap;                                     // (a full table: u == kOwnTab > keys_cap)
         const bool sorted = !over && n_win > win_cap;                       // candidates out of position order: the whole set, ascending
-        if (sorted) own_sort_set<NT>(s_tab, s_key, s_one, s_part, u);  // (rare: inlined behind this branch)
+        if (sorted) own_sort_set<NT>(s_tab, s_key, s_one, s_part, u, tid);  // (rare: inlined behind this branch)
         STAMP(2, 5);
         // ---- this tile's candidates of contig k ------------------------------------------------------
         // :107-111 -- ties go to the larger seed

@@ -54,10 +54,11 @@ st = buf[:3 * 65536 * 8].reshape(3, 65536, 8).astype(np.int64)
 t0 = st[0][st[0][:, 0] > 0][:, 0].min()
 names = [['start', 'offsets', 'staged', 'consumed', 'loop_end', 'decided', 'end'],
          ['start', 'gathered', 'sorted', 'end', 'recs', 'counted', 'written', 'runs'],
-         ['start', 'meta', 'staged'] if '3k' in sys.argv else ['start', 'cleared', 'inserted', 'records', 'sorted64', 'ranked', 'end']]
+         ['start', 'meta', 'staged'] if '3k' in sys.argv else ['start', 'cleared', 'inserted', 'records', 'columns', 'ranked', 'end']]
 # stamp indices in program order, for the phase durations (ef_finalize_own: `records` -- the seed records have arrived, behind the
-# wait in front of the insert phase -- lies between `cleared` and `inserted`; index 4 is no longer written)
-order_of = [list(range(7)), None, [0, 1, 2] if '3k' in sys.argv else [0, 1, 3, 2, 5, 6]]
+# wait in front of the insert phase -- lies between `cleared` and `inserted`; `columns` -- the columns and summaries have arrived,
+# behind the first trip's one wait -- splits start -> cleared into the trip and the clear + barrier)
+order_of = [list(range(7)), None, [0, 1, 2] if '3k' in sys.argv else [0, 4, 1, 3, 2, 5, 6]]
 for k in range(3):
     blk = st[k][st[k][:, 0] > 0]
     nb = len(blk)
