@@ -59,6 +59,7 @@ namespace {
 
 #include "duet_prims.hip.h"
 #include "duet_recsort.hip.h"
+#include "duet_cluster_plan.h"
 
 
 typedef float float2v __attribute__((ext_vector_type(2)));
@@ -449,8 +450,6 @@ __global__ __launch_bounds__(kScanThreads) void part_apply(const uint8_t *hbits,
 // A list is kept in kShards pieces, one per run of consecutive scan tiles, each with its own counter (ten thousand workgroups
 // adding to ONE counter queue up behind each other: 40 ns apiece, 0.4 ms at 2e7 marks); the piece of a shard starts at the
 // shard's first position -- it has room, a shard cannot hold more partitions than positions.
-constexpr int kClasses = 5;
-constexpr int kShards = 64;
 struct WorkList {
     const uint32_t *items;          // the class's list, [M]
     const uint32_t *pref;           // (LDS) pref[s] = items in the shards before s, pref[kShards] = all
@@ -2976,6 +2975,91 @@ __global__ __launch_bounds__(256) void cl_emit(const ClParams p)
     }
 }
 
+// host side: ctx->cl_ws by name
+enum ClSlot { kWsKeysA, kWsKeysB, kWsValsA, kWsValsB, kWsHist, kWsTiles, kWsTileFirst, kWsSpart, kWsPartStart, kWsERec, kWsPc, kWsScal, kWsLists,
+              kWsLabels, kWsRecsA, kWsEFirst, kWsSlots };
+// the scalar block (kWsScal), in words: n_parts | cl_maxima's four maxima | big_count | the class counters [kClasses][kShards] | the second
+// lists' counters, the same | big_parts [M / 65 + 1], the partitions of more than 64 marks
+constexpr uint32_t kScalMaxima = 28, kScalBigCount = 40, kScalCnts = 64, kScalOver = kScalCnts + kClasses * kShards, kScalBigParts = kScalOver + kClasses * kShards;
+size_t cl_scal_bytes(uint32_t M) { return 4 * ((size_t)kScalBigParts + M / 64 + 16); }
+// ctx->cl_flags, in words: what the gate kernels wait for
+constexpr uint32_t kFlagFork = 0, kFlagJoin = 4, kFlagTierFork = 8, kFlagTestSignal = 13, kFlagTestGate = 14, kFlagTestOpened = 15;
+
+struct ClWs {
+    uint64_t *keysA, *keysB;
+    uint32_t *valsA, *valsB, *hist;
+    PartSum *tiles;                 // the partition scan's tile summaries: 3 words per 2048 marks
+    uint8_t *hbits;                 // ... and the head flags, a bit per mark
+    uint32_t *tile_first;           // [tiles + 1] first partition starting in each scan tile
+    uint32_t *spart, *part_start, *pc;
+    uint4 *e_rec, *e_first, *recs_a;                            // (recs_a: the record sort's first buffer)
+    uint32_t *scal, *big_count, *cnts, *over, *big_parts;       // scal[0] = n_parts
+    uint32_t *lists;                // [kClasses][M] partitions by size class, each list in kShards pieces
+    uint32_t *cbase;                // (in front of it, kWsLabels' first M + 1 words hold label8 / comp8)
+    unsigned char *recs;            // the marks' records behind them, 16-byte aligned; the record sort's second buffer
+};
+
+// every slot's bytes for this plan, and what is carved out of it
+int cl_reserve(duet_ctx *ctx, const ClPlan &pl, bool rec16, ClWs &ws)
+{
+    static_assert(kWsSlots == sizeof(ctx->cl_ws) / sizeof(ctx->cl_ws[0]), "a name per slot");
+    const size_t M = pl.M, nb_sc = pl.nb_sc;
+    int rc = DUET_OK;
+    auto slot = [&](ClSlot s, size_t bytes) -> unsigned char * {
+        if (!rc) rc = duet_reserve(ctx, ctx->cl_ws[s], bytes);
+        return (unsigned char *)ctx->cl_ws[s].ptr;
+    };
+    ws.keysA = (uint64_t *)slot(kWsKeysA, pl.rec_mode ? 16 : M * 8);
+    ws.keysB = (uint64_t *)slot(kWsKeysB, pl.rec_mode ? 16 : M * 8);
+    ws.valsA = (uint32_t *)slot(kWsValsA, M * 4);
+    ws.valsB = (uint32_t *)slot(kWsValsB, pl.rec_mode ? M * 2 + 16 : M * 4);
+    ws.hist = (uint32_t *)slot(kWsHist, pl.rec_mode ? ((size_t)pl.nb_rs + pl.rs_chunks + 1) * (4u << kRsMaxW) : (size_t)256 * pl.nb_rx * 4);
+    const size_t tiles_bytes = (nb_sc + 1) * sizeof(PartSum);
+    unsigned char *tiles = slot(kWsTiles, tiles_bytes + 16 + nb_sc * kScanThreads);
+    ws.tiles = (PartSum *)tiles;
+    ws.hbits = tiles + ((tiles_bytes + 15) & ~(size_t)15);
+    ws.tile_first = (uint32_t *)slot(kWsTileFirst, (nb_sc + 2) * 4);
+    ws.spart = (uint32_t *)slot(kWsSpart, ((size_t)std::max(pl.nb_sc, pl.nb_hs) + 1) * 4);
+    ws.part_start = (uint32_t *)slot(kWsPartStart, (M + 1) * 4);
+    ws.e_rec = (uint4 *)slot(kWsERec, M * 16);
+    ws.pc = (uint32_t *)slot(kWsPc, M * 4);
+    ws.scal = (uint32_t *)slot(kWsScal, cl_scal_bytes(pl.M));
+    ws.big_count = ws.scal + kScalBigCount; ws.cnts = ws.scal + kScalCnts; ws.over = ws.scal + kScalOver; ws.big_parts = ws.scal + kScalBigParts;
+    ws.lists = (uint32_t *)slot(kWsLists, M * 4 * kClasses);
+    const size_t labels_bytes = (M + 1) * 4, cbase_bytes = (M + 1) * 4;
+    unsigned char *labels = slot(kWsLabels, labels_bytes + cbase_bytes + 16 + M * (rec16 ? 16 : 8));
+    ws.cbase = (uint32_t *)(labels + labels_bytes);
+    ws.recs = labels + ((labels_bytes + cbase_bytes + 15) & ~(size_t)15);
+    ws.recs_a = (uint4 *)slot(kWsRecsA, M * 16);
+    ws.e_first = (uint4 *)slot(kWsEFirst, M * 16);
+    return rc;
+}
+
+// the low bits, group by group, behind the global passes (duet_prims.hip.h): -> the sorted elements, in `out`
+template <class E, class KeyOf>
+void sort_groups(const E *in, E *out, uint32_t lo, const KeyOf keyof, const ClPlan &pl, const ClWs &ws, hipStream_t st)
+{
+    uint32_t *big_list = ws.valsA;                                // (the value buffers are idle when the index rides in the key)
+    if (pl.small_in)
+        hipLaunchKernelGGL((rx_local<1024, E, KeyOf>), dim3(pl.g_loc), dim3(1024), 0, st, in, out, pl.M, lo, keyof, pl.loc_cap, big_list, ws.big_count);
+    else
+        hipLaunchKernelGGL((rx_local<256, E, KeyOf>), dim3(pl.g_loc), dim3(256), 0, st, in, out, pl.M, lo, keyof, pl.loc_cap, big_list, ws.big_count);
+    hipLaunchKernelGGL((rx_big<E, KeyOf>), dim3(256), dim3(256), 0, st, (E *)in, out, pl.M, lo, keyof, (const uint32_t *)big_list, (const uint32_t *)ws.big_count);
+}
+
+// partitions: one composite scan straight off the sorted elements -> each position's partition id, the partition start
+// list and their number (scal[0]); it also zeroes the work-list counters.  apply = false: cl_box is the scan's last stage
+template <class E, class KeyOf>
+void part_scan(const E *sorted, const KeyOf keyof, const ClParams &p, const ClPlan &pl, const ClWs &ws, bool apply, hipStream_t st)
+{
+    const LoadHead<E, KeyOf> heads{sorted, p.centre_bits, p.part_gap, keyof};
+    hipLaunchKernelGGL((part_reduce<E, KeyOf>), dim3(pl.nb_sc), dim3(kScanThreads), 0, st, heads, p.M, p.part_max, ws.tiles, ws.cnts, (uint32_t)(2 * kClasses * kShards), ws.hbits);
+    if (pl.use_spine) hipLaunchKernelGGL(part_spine, dim3(1), dim3(1024), 0, st, ws.tiles, pl.nb_sc, p.part_max);
+    if (!apply) return;
+    hipLaunchKernelGGL(!pl.use_spine ? part_apply<true> : part_apply<false>, dim3(pl.nb_sc), dim3(kScanThreads), 0, st, (const uint8_t *)ws.hbits, p.M, p.part_max,
+                       (const PartSum *)ws.tiles, (uint32_t *)nullptr, ws.part_start, ws.scal, ws.tile_first);
+}
+
 }  // namespace
 
 extern "C" {
@@ -3007,13 +3091,7 @@ int duet_cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_c
         !res->cand_contig || !res->cand_type || !res->cand_pos || !res->cand_span)
         return duet_fail(ctx, DUET_ERR_INVALID, "null array");
 
-    const uint32_t nb_sc = (M + kScanTile - 1) / kScanTile;
-    const uint32_t nb_rx = (M + kRxTile - 1) / kRxTile;
-    const uint32_t nb_hs = (256u * nb_rx + kScanTile - 1) / kScanTile;      // scan tiles of the radix histogram
     int rc;
-    if ((rc = duet_reserve(ctx, ctx->cl_ws[11], 4 * ((size_t)64 + 2 * kClasses * kShards + M / 64 + 16)))) return rc;
-    uint32_t *scal = (uint32_t *)ctx->cl_ws[11].ptr;      // [0] = n_parts
-
     ClParams p;
     memset(&p, 0, sizeof(p));
     p.M = M; p.part_gap = pr->part_gap; p.part_max = pr->part_max;
@@ -3026,7 +3104,8 @@ int duet_cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_c
         contig_bits = bits_for(pr->n_contigs_hint - 1);
     } else {
         // no (or partial) hints: measure -- one small kernel and one host round trip, instead of sorting 58-bit keys
-        uint32_t *d_max = scal + 28;
+        if ((rc = duet_reserve(ctx, ctx->cl_ws[kWsScal], cl_scal_bytes(M)))) return rc;
+        uint32_t *d_max = (uint32_t *)ctx->cl_ws[kWsScal].ptr + kScalMaxima;
         uint32_t h_max[4] = {0, 0, 0, 0};
         HIP_TRY(ctx, hipMemsetAsync(d_max, 0, 16, st));
         hipLaunchKernelGGL(cl_maxima, dim3((M + 2047) / 2048 < 1024u ? (M + 2047) / 2048 : 1024u), dim3(256), 0, st, p, d_max);
@@ -3036,58 +3115,28 @@ int duet_cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_c
         p.type_bits = bits_for(h_max[1]);
         contig_bits = bits_for(h_max[0]);
     }
-    const uint32_t key_bits = p.centre_bits + p.type_bits + contig_bits;
-    if (key_bits > 64) return duet_fail(ctx, DUET_ERR_INVALID, "sort key does not fit 64 bits");
-    p.key_bits = key_bits;
-    p.idx_packed = key_bits + bits_for(M - 1) <= 64 && !(ctx->dbg & DUET_DBG_CLUSTER_PAIRS);
-    // The record travels with the key (duet_recsort.hip.h) when contig, type and mark index fit one word of it
-    const uint32_t idx_bits = bits_for(M - 1);
-    // ... from 1.25 M marks on: below, every pass is launch-latency bound and 8-byte keys are the cheaper thing to move (measured
-    // on the fused pipeline, round 4: 1.0 M marks, one contig 0.277 ms with the key sort against 0.287; 2 M marks over 24 contigs 0.369
-    // against 0.316, 4 M 0.483 / 0.455, 8 M 0.946 / 0.869, 2e7 2.35 / 2.22; round 6, 24 contigs, key sort / record sort: 0.9 M 0.252 / 0.259,
-    // 1.1 M 0.253 / 0.253, 1.2 M 0.229 / 0.227, 1.3 M 0.283 / 0.249, 1.5 M 0.276 / 0.240 -- rounds 4-5 drew the line at 1.5 M);
-    // DUET_DBG_CLUSTER_RECSORT takes it at any size
-    const bool rec_mode = contig_bits + p.type_bits + idx_bits <= 32u &&
-                          (M >= 1250000u || (ctx->dbg & (DUET_DBG_CLUSTER_RECSORT | DUET_DBG_CLUSTER_LARGE))) &&
-                          !(ctx->dbg & (DUET_DBG_CLUSTER_PAIRS | DUET_DBG_CLUSTER_LSD | DUET_DBG_CLUSTER_KEYSORT));
-    p.rec_mode = rec_mode ? 1u : 0u;
-    p.idx_bits = idx_bits;
-    p.idx_mask = rec_mode ? (uint32_t)((1ull << idx_bits) - 1ull) : 0xFFFFFFFFu;
-    // the digits of the record sort: LSD passes of up to kRsMaxW bits over the key's top bits, so many of them that the marks
-    // that agree in them (a GROUP: one type within 2^lo centres) are a few dozen; the low bits are ordered group by group
-    uint32_t rs_lo = 0, rs_np = 0, rs_w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (rec_mode) {
-        // (measured at 2e7 marks, 34-bit keys: 20 top bits in two 10-bit passes leave groups of 53 marks on average and the local
-        // stage takes 285 + 33 us; 21 bits 235 us; 22 bits, two 11-bit passes, 212 us but 33 us more in the second scatter and
-        // its offsets: 21 it is.  1.0 M marks: 16 bits in two 8-bit passes, groups of 32)
-        uint32_t T = std::max(bits_for(M >> 4), 8u);
-        T = std::min(T, key_bits);
-        if (key_bits - T > 31u) T = key_bits - 31u;            // (the local stage holds the low bits in 32-bit words)
-        rs_lo = key_bits - T;
-        rs_np = (T + kRsMaxW - 1u) / kRsMaxW;
-        for (uint32_t i = 0; i < rs_np; ++i) rs_w[i] = T / rs_np + (i < T % rs_np ? 1u : 0u);
+    // The partitions of more than 64 marks go on a side stream that forks through gate kernels: the first small input of a context
+    // finds out whether a gate on one side stream sees the signal queued behind it on the other (-> cl_gates)
+    if (cl_small_in(M, ctx->dbg) && ctx->cl_gates == 0) {
+        const uint32_t e0 = ++ctx->cl_epoch;
+        uint32_t opened = 0;
+        hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, ctx->cl_side[1], ctx->cl_flags + kFlagTestSignal, e0);
+        hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, ctx->cl_side[1], ctx->cl_flags + kFlagTestSignal, e0);
+        hipLaunchKernelGGL(cl_gate_try, dim3(1), dim3(64), 0, ctx->cl_side[0], (const uint32_t *)(ctx->cl_flags + kFlagTestGate), e0, ctx->cl_flags + kFlagTestOpened);
+        hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, ctx->cl_side[1], ctx->cl_flags + kFlagTestGate, e0);
+        HIP_TRY(ctx, hipMemcpyAsync(&opened, ctx->cl_flags + kFlagTestOpened, 4, hipMemcpyDeviceToHost, ctx->cl_side[0]));     // (not the null stream: it would wait for the caller's)
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->cl_side[1]));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->cl_side[0]));
+        ctx->cl_gates = opened ? 1 : -1;
     }
-    const uint32_t nb_rs = (M + kRsTile - 1) / kRsTile, rs_chunks = (nb_rs + kRsChunk - 1) / kRsChunk;
-    {
-        const size_t hist_legacy = (size_t)256 * nb_rx * 4, hist_rec = ((size_t)nb_rs + rs_chunks + 1) * (4u << kRsMaxW);
-        const size_t sizes[16] = {rec_mode ? 16 : (size_t)M * 8, rec_mode ? 16 : (size_t)M * 8, (size_t)M * 4, rec_mode ? (size_t)M * 2 + 16 : (size_t)M * 4,
-                                  rec_mode ? hist_rec : hist_legacy,
-                                  ((size_t)nb_sc + 1) * sizeof(PartSum) + 16 + (size_t)nb_sc * kScanThreads, ((size_t)nb_sc + 2) * 4, ((size_t)(nb_sc > nb_hs ? nb_sc : nb_hs) + 1) * 4,
-                                  ((size_t)M + 1) * 4, (size_t)M * 16, (size_t)M * 4, 4 * ((size_t)64 + 2 * kClasses * kShards + M / 64 + 16), (size_t)M * 4 * kClasses,
-                                  ((size_t)M + 1) * 4 * 2 + 16 + (size_t)M * ((sv || rec_mode) ? 16 : 8), (size_t)M * 16, (size_t)M * 16};
-        for (int i = 0; i < 16; ++i)
-            if ((rc = duet_reserve(ctx, ctx->cl_ws[i], sizes[i]))) return rc;
-    }
-    scal = (uint32_t *)ctx->cl_ws[11].ptr;
-    uint64_t *keysA = (uint64_t *)ctx->cl_ws[0].ptr, *keysB = (uint64_t *)ctx->cl_ws[1].ptr;
-    uint32_t *valsA = (uint32_t *)ctx->cl_ws[2].ptr, *valsB = (uint32_t *)ctx->cl_ws[3].ptr;
-    uint32_t *hist = (uint32_t *)ctx->cl_ws[4].ptr;
-    uint32_t *tmpA = (uint32_t *)ctx->cl_ws[5].ptr;             // the partition scan's tile summaries
-    uint32_t *tile_first = (uint32_t *)ctx->cl_ws[6].ptr;       // [tiles + 1] first partition starting in each scan tile
-    uint32_t *spart = (uint32_t *)ctx->cl_ws[7].ptr;
-    uint32_t *part_start = (uint32_t *)ctx->cl_ws[8].ptr;
-    uint32_t *cbase = (uint32_t *)ctx->cl_ws[13].ptr + (M + 1);      // (the first M + 1 words hold label8 / comp8)
-    uint32_t *pc = (uint32_t *)ctx->cl_ws[10].ptr;
+    const ClPlan pl = cl_plan(M, p.centre_bits, p.type_bits, contig_bits, ctx->dbg, pr->part_max, ctx->cl_gates > 0);
+    if (pl.key_bits > 64) return duet_fail(ctx, DUET_ERR_INVALID, "sort key does not fit 64 bits");
+    const uint32_t key_bits = pl.key_bits, idx_bits = pl.idx_bits, nb_sc = pl.nb_sc;
+    const bool rec_mode = pl.rec_mode, small_in = pl.small_in, gate_forks = pl.gate_forks, box_applies = pl.box_applies;
+    p.key_bits = key_bits; p.idx_packed = pl.idx_packed; p.rec_mode = rec_mode ? 1u : 0u; p.tps = pl.tps;
+    p.idx_bits = idx_bits; p.idx_mask = rec_mode ? (uint32_t)((1ull << idx_bits) - 1ull) : 0xFFFFFFFFu;
+    ClWs ws;
+    if ((rc = cl_reserve(ctx, pl, sv || rec_mode, ws))) return rc;
 
     // outputs (the agglomeration kernels write the marks' output order themselves)
     if (sv) {
@@ -3098,146 +3147,75 @@ int duet_cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_c
     p.order = res->order; p.cand_off = res->cand_off; p.cand_pos = res->cand_pos; p.cand_span = res->cand_span;
     p.cand_contig = res->cand_contig; p.cand_type = res->cand_type;
 
-    const dim3 g256((M + 255) / 256), b256(256);
-    unsigned char *recs = (unsigned char *)ctx->cl_ws[13].ptr + ((8 * ((size_t)M + 1) + 15) & ~(size_t)15);
-    if (sv) p.rec4 = (const uint4 *)recs;
-    else p.ps = (const uint2 *)recs;
-    const bool big_sort = (ctx->dbg & DUET_DBG_CLUSTER_LARGE) != 0;     // (tests: the tile-offset path of > 4 M keys)
-    const bool rx_totals = nb_rx <= kRxTotalsTiles && !big_sort;
-    // Small inputs whose keys would take four passes or more: global passes over the top 16 bits only, then the groups of keys
-    // that agree in them -- the marks of one type within 2^(key_bits - 16) centres, a few dozen -- are put in order by their low
-    // bits locally (rx_local: a rank count in LDS; rx_big for a group of more than 256 keys).  8 launches instead of 13.
-    // (The first attempt at this, earlier in round 3, ordered the groups with three ballot-ranked LDS radix passes and cost
-    // what the global passes it replaced did: 91 against 88 us at 1 M marks; on the uneven groups of 2e7 marks over a whole
-    // genome it was slower, 1010 against 745 us, and large inputs keep the plain LSD passes.)
-    const bool small_in = M <= (4u << 20) && !(ctx->dbg & DUET_DBG_CLUSTER_LARGE);
-    // (the global passes take the top 16 bits of a small input's keys, the top 24 of a large one's: groups of a few keys to a
-    // few dozen either way on a genome; used where that saves two passes or more)
-    const uint32_t top_bits = M <= (2u << 20) ? 16u : 24u;     // (16 bits leave groups of a hundred keys and more beyond 2 M marks)
-    // (rx_local and rx_big hold the low bits in 32-bit words: wider keys than top_bits + 31 take plain LSD passes)
-    const bool hybrid = !rec_mode && p.idx_packed && (key_bits + 7u) / 8u >= top_bits / 8u + 2u && key_bits - top_bits < 32u && !(ctx->dbg & DUET_DBG_CLUSTER_LSD);
-    const uint32_t top_shift = hybrid ? key_bits - top_bits : 0u;
-    uint32_t *big_count = scal + 40, *big_list = valsA;          // (the value buffers are idle when the index rides in the key)
-    const uint32_t loc_cap = (ctx->dbg & DUET_DBG_CLUSTER_SMALLCAP) ? 3u : (uint32_t)kLocHalo;
-    // large inputs, record sort: cl_box is also the partition scan's last stage (no part_apply launch)
-    // (small inputs keep part_apply: there the chain of the partitions of more than 64 marks is the critical path and has to start
-    // beside the box test, not behind it -- measured: 315 us against 287 at 1.0 M marks)
-    // (cl_box<.., true> reads tiles[tile] as the EXCLUSIVE carry part_spine leaves: it applies exactly where the spine launch runs,
-    // i.e. never together with the spine-less part_apply<true> of `nb_sc <= kSelfSpine && !big_sort`)
-    static_assert((4u << 20) == kSelfSpine * (uint32_t)kScanTile, "small_in's bound is the spine-less scan's reach: box_applies needs part_spine's carries");
-    const bool use_spine = nb_sc > kSelfSpine || big_sort;
-    const bool box_applies = rec_mode && (!small_in || big_sort) && use_spine;
-    PartSum *tiles = (PartSum *)tmpA;                             // the partition scan's tile summaries: 3 words per 2048 marks
-    uint8_t *hbits = (uint8_t *)tmpA + ((((size_t)nb_sc + 1) * sizeof(PartSum) + 15) & ~(size_t)15);      // ... and the head flags, a bit per mark
-    p.e_rec = (uint4 *)ctx->cl_ws[9].ptr;
-    p.e_first = (uint4 *)ctx->cl_ws[15].ptr;
+    if (sv) p.rec4 = (const uint4 *)ws.recs;
+    else p.ps = (const uint2 *)ws.recs;
+    p.e_rec = ws.e_rec; p.e_first = ws.e_first;
     if (rec_mode) {
         // the record sort (duet_recsort.hip.h): the first pass reads the caller's arrays, every pass moves 16-byte records
         RsSrc src;
         src.contig = pr->mark_contig; src.type = pr->mark_type; src.pos = pr->mark_pos; src.span = pr->mark_span;
         src.read = sv ? sv->mark_in : nullptr;
         src.type_bits = p.type_bits; src.idx_bits = idx_bits; src.centre_bits = p.centre_bits;
-        uint4 *buf[2] = {(uint4 *)ctx->cl_ws[14].ptr, (uint4 *)recs};
-        const bool rs_small = nb_rs <= kRsSmallTiles && !big_sort;
+        uint4 *buf[2] = {ws.recs_a, (uint4 *)ws.recs};
         uint32_t *dtot = ctx->rx_dtot;                             // [kRsDtotCopies][2048]
         // (every pass's rs_scatter zeroes the totals behind itself; a run cut short between a histogram and its scatter -- a launch
         // failure, an early return on a HIP error -- would leave them dirty for every later sort on this context: ~1 us for not
         // depending on that)
         HIP_TRY(ctx, hipMemsetAsync(dtot, 0, (size_t)kRsDtotCopies * 2048u * sizeof(uint32_t), st));
-        uint32_t *partial = hist + ((size_t)nb_rs << kRsMaxW);
-        uint16_t *dig = (uint16_t *)valsB;                        // the next pass's digit of every record (rs_scatter -> rs_hist_dig)
+        uint32_t *partial = ws.hist + ((size_t)pl.nb_rs << kRsMaxW);
+        uint16_t *dig = (uint16_t *)ws.valsB;                     // the next pass's digit of every record (rs_scatter -> rs_hist_dig)
         const uint4 *rin = nullptr;
         int at = 0;                                               // the buffer the next launch writes
-        uint32_t shift = rs_lo;
-        for (uint32_t ps = 0; ps < rs_np; ++ps) {
-            const uint32_t w = rs_w[ps];
-            uint32_t *htot = rs_small ? dtot : (uint32_t *)nullptr;
-            if (ps == 0) hipLaunchKernelGGL(rs_hist<true>, dim3(nb_rs), dim3(kRsHistThreads), 0, st, src, (const uint4 *)nullptr, M, shift, w, hist, htot, big_count);
-            else hipLaunchKernelGGL(rs_hist_dig, dim3(nb_rs), dim3(kRsDigThreads), 0, st, (const uint16_t *)dig, M, w, hist, htot);
-            uint16_t *dig_out = ps + 1 < rs_np ? dig : (uint16_t *)nullptr;
-            const uint32_t nshift = shift + w, nmask = ps + 1 < rs_np ? (1u << rs_w[ps + 1]) - 1u : 0u;
-            if (rs_small) {
-                hipLaunchKernelGGL(rs_offsets_small, dim3(std::max(1u, (1u << w) / 64u)), dim3(1024), 0, st, hist, nb_rs, w, (const uint32_t *)dtot);
+        uint32_t shift = pl.rs_lo;
+        for (uint32_t ps = 0; ps < pl.rs_np; ++ps) {
+            const uint32_t w = pl.rs_w[ps];
+            uint32_t *htot = pl.rs_small ? dtot : (uint32_t *)nullptr;
+            if (ps == 0) hipLaunchKernelGGL(rs_hist<true>, dim3(pl.nb_rs), dim3(kRsHistThreads), 0, st, src, (const uint4 *)nullptr, M, shift, w, ws.hist, htot, ws.big_count);
+            else hipLaunchKernelGGL(rs_hist_dig, dim3(pl.nb_rs), dim3(kRsDigThreads), 0, st, (const uint16_t *)dig, M, w, ws.hist, htot);
+            uint16_t *dig_out = ps + 1 < pl.rs_np ? dig : (uint16_t *)nullptr;
+            const uint32_t nshift = shift + w, nmask = ps + 1 < pl.rs_np ? (1u << pl.rs_w[ps + 1]) - 1u : 0u;
+            if (pl.rs_small) {
+                hipLaunchKernelGGL(rs_offsets_small, dim3(std::max(1u, (1u << w) / 64u)), dim3(1024), 0, st, ws.hist, pl.nb_rs, w, (const uint32_t *)dtot);
             } else {
-                hipLaunchKernelGGL(rs_col_reduce, dim3(rs_chunks), dim3(256), 0, st, (const uint32_t *)hist, nb_rs, w, partial, dtot);
-                hipLaunchKernelGGL(rs_offsets_small, dim3(std::max(1u, (1u << w) / 64u)), dim3(1024), 0, st, partial, rs_chunks, w, (const uint32_t *)dtot);
+                hipLaunchKernelGGL(rs_col_reduce, dim3(pl.rs_chunks), dim3(256), 0, st, (const uint32_t *)ws.hist, pl.nb_rs, w, partial, dtot);
+                hipLaunchKernelGGL(rs_offsets_small, dim3(std::max(1u, (1u << w) / 64u)), dim3(1024), 0, st, partial, pl.rs_chunks, w, (const uint32_t *)dtot);
             }
-            if (ps == 0) {
-                if (w <= 10u) hipLaunchKernelGGL((rs_scatter<10, true>), dim3(nb_rs), dim3(kRsThreads), 0, st, src, (const uint4 *)nullptr, M, shift, w, nb_rs, (const uint32_t *)hist, buf[at], dtot, dig_out, nshift, nmask, rs_small ? (const uint32_t *)nullptr : (const uint32_t *)partial);
-                else hipLaunchKernelGGL((rs_scatter<kRsMaxW, true>), dim3(nb_rs), dim3(kRsThreads), 0, st, src, (const uint4 *)nullptr, M, shift, w, nb_rs, (const uint32_t *)hist, buf[at], dtot, dig_out, nshift, nmask, rs_small ? (const uint32_t *)nullptr : (const uint32_t *)partial);
-            } else {
-                if (w <= 10u) hipLaunchKernelGGL((rs_scatter<10, false>), dim3(nb_rs), dim3(kRsThreads), 0, st, src, rin, M, shift, w, nb_rs, (const uint32_t *)hist, buf[at], dtot, dig_out, nshift, nmask, rs_small ? (const uint32_t *)nullptr : (const uint32_t *)partial);
-                else hipLaunchKernelGGL((rs_scatter<kRsMaxW, false>), dim3(nb_rs), dim3(kRsThreads), 0, st, src, rin, M, shift, w, nb_rs, (const uint32_t *)hist, buf[at], dtot, dig_out, nshift, nmask, rs_small ? (const uint32_t *)nullptr : (const uint32_t *)partial);
-            }
+            // (the first pass reads the caller's arrays: rin is null there)
+            const auto scatter = ps == 0 ? (w <= 10u ? rs_scatter<10, true> : rs_scatter<kRsMaxW, true>) : (w <= 10u ? rs_scatter<10, false> : rs_scatter<kRsMaxW, false>);
+            hipLaunchKernelGGL(scatter, dim3(pl.nb_rs), dim3(kRsThreads), 0, st, src, rin, M, shift, w, pl.nb_rs, (const uint32_t *)ws.hist, buf[at], dtot, dig_out, nshift, nmask,
+                               pl.rs_small ? (const uint32_t *)nullptr : (const uint32_t *)partial);
             rin = buf[at];
             at ^= 1;
             shift += w;
         }
-        if (rs_lo > 0) {
-            const KeyOfRec keyof{p.centre_bits, idx_bits};
-            if (small_in)
-                hipLaunchKernelGGL((rx_local<1024, uint4, KeyOfRec>), dim3((M + kLocTile - 1) / kLocTile), dim3(1024), 0, st, rin, buf[at], M, rs_lo, keyof, loc_cap, big_list, big_count);
-            else
-                hipLaunchKernelGGL((rx_local<256, uint4, KeyOfRec>), dim3((M + kLocTile - 1) / kLocTile), dim3(256), 0, st, rin, buf[at], M, rs_lo, keyof, loc_cap, big_list, big_count);
-            hipLaunchKernelGGL((rx_big<uint4, KeyOfRec>), dim3(256), dim3(256), 0, st, (uint4 *)rin, buf[at], M, rs_lo, keyof, (const uint32_t *)big_list, (const uint32_t *)big_count);
+        const KeyOfRec keyof{p.centre_bits, idx_bits};
+        if (pl.rs_lo > 0) {
+            sort_groups(rin, buf[at], pl.rs_lo, keyof, pl, ws, st);
             rin = buf[at];
         }
         p.srec = (uint4 *)rin;
         p.rec4 = nullptr; p.ps = nullptr;
-        const LoadHead<uint4, KeyOfRec> heads{rin, p.centre_bits, p.part_gap, KeyOfRec{p.centre_bits, idx_bits}};
-        hipLaunchKernelGGL((part_reduce<uint4, KeyOfRec>), dim3(nb_sc), dim3(kScanThreads), 0, st, heads, M, p.part_max, tiles, scal + 64, (uint32_t)(2 * kClasses * kShards), hbits);
-        if (nb_sc <= kSelfSpine && !big_sort) {
-            if (!box_applies)
-                hipLaunchKernelGGL(part_apply<true>, dim3(nb_sc), dim3(kScanThreads), 0, st, (const uint8_t *)hbits, M, p.part_max, (const PartSum *)tiles, (uint32_t *)nullptr,
-                                   part_start, scal, tile_first);
-        } else {
-            hipLaunchKernelGGL(part_spine, dim3(1), dim3(1024), 0, st, tiles, nb_sc, p.part_max);
-            if (!box_applies)
-                hipLaunchKernelGGL(part_apply<false>, dim3(nb_sc), dim3(kScanThreads), 0, st, (const uint8_t *)hbits, M, p.part_max, (const PartSum *)tiles, (uint32_t *)nullptr,
-                                   part_start, scal, tile_first);
-        }
+        part_scan(rin, keyof, p, pl, ws, !box_applies, st);
     } else {
-    hipLaunchKernelGGL(cl_keys, dim3(nb_rx), dim3(kRxHistThreads), 0, st, p, keysA, valsA, (uint2 *)recs, (uint4 *)recs, top_shift,
-                       key_bits - top_shift >= 8u ? 255u : (1u << (key_bits - top_shift)) - 1u, nb_rx, hist, rx_totals ? ctx->rx_dtot : (uint32_t *)nullptr,
-                       big_count);
-    uint64_t *kin = nullptr, *kout = nullptr;
-    uint32_t *vin = nullptr;
-    if (p.idx_packed) radix_sort_pairs(keysA, keysB, nullptr, nullptr, M, key_bits, hist, spart, ctx->rx_dtot, st, &kin, nullptr, &kout, big_sort, true, top_shift);
-    else radix_sort_pairs(keysA, keysB, valsA, valsB, M, key_bits, hist, spart, ctx->rx_dtot, st, &kin, &vin, &kout, big_sort, true);
-    const KeyOfU64 keyof{key_mask(key_bits)};
-    if (hybrid) {
-        if (small_in)
-            hipLaunchKernelGGL((rx_local<1024, uint64_t, KeyOfU64>), dim3((M + kLocTile - 1) / kLocTile), dim3(1024), 0, st, (const uint64_t *)kin, kout, M, top_shift, keyof, loc_cap,
-                               big_list, big_count);
-        else
-            hipLaunchKernelGGL((rx_local<256, uint64_t, KeyOfU64>), dim3((M + kLocTile - 1) / kLocTile), dim3(256), 0, st, (const uint64_t *)kin, kout, M, top_shift, keyof, loc_cap,
-                               big_list, big_count);
-        hipLaunchKernelGGL((rx_big<uint64_t, KeyOfU64>), dim3(256), dim3(256), 0, st, kin, kout, M, top_shift, keyof, (const uint32_t *)big_list, (const uint32_t *)big_count);
-        uint64_t *t = kin; kin = kout; kout = t;
-    }
-    p.sorted = vin;
-    p.skeys = kin;
-    // partitions: one composite scan straight off the sorted keys -> each position's partition id, the partition start
-    // list and their number (scal[0]); it also zeroes the work-list counters
-    {
-        const LoadHead<uint64_t, KeyOfU64> heads{(const uint64_t *)kin, p.centre_bits, p.part_gap, keyof};
-        hipLaunchKernelGGL((part_reduce<uint64_t, KeyOfU64>), dim3(nb_sc), dim3(kScanThreads), 0, st, heads, M, p.part_max, tiles, scal + 64, (uint32_t)(2 * kClasses * kShards), hbits);
-        if (nb_sc <= kSelfSpine && !big_sort) {
-            hipLaunchKernelGGL(part_apply<true>, dim3(nb_sc), dim3(kScanThreads), 0, st, (const uint8_t *)hbits, M, p.part_max, (const PartSum *)tiles, (uint32_t *)nullptr,
-                               part_start, scal, tile_first);
-        } else {
-            hipLaunchKernelGGL(part_spine, dim3(1), dim3(1024), 0, st, tiles, nb_sc, p.part_max);
-            hipLaunchKernelGGL(part_apply<false>, dim3(nb_sc), dim3(kScanThreads), 0, st, (const uint8_t *)hbits, M, p.part_max, (const PartSum *)tiles, (uint32_t *)nullptr,
-                               part_start, scal, tile_first);
+        hipLaunchKernelGGL(cl_keys, dim3(pl.nb_rx), dim3(kRxHistThreads), 0, st, p, ws.keysA, ws.valsA, (uint2 *)ws.recs, (uint4 *)ws.recs, pl.top_shift,
+                           key_bits - pl.top_shift >= 8u ? 255u : (1u << (key_bits - pl.top_shift)) - 1u, pl.nb_rx, ws.hist, pl.rx_totals ? ctx->rx_dtot : (uint32_t *)nullptr,
+                           ws.big_count);
+        uint64_t *kin = nullptr, *kout = nullptr;
+        uint32_t *vin = nullptr;
+        if (p.idx_packed) radix_sort_pairs(ws.keysA, ws.keysB, nullptr, nullptr, M, key_bits, ws.hist, ws.spart, ctx->rx_dtot, st, &kin, nullptr, &kout, pl.big_sort, true, pl.top_shift);
+        else radix_sort_pairs(ws.keysA, ws.keysB, ws.valsA, ws.valsB, M, key_bits, ws.hist, ws.spart, ctx->rx_dtot, st, &kin, &vin, &kout, pl.big_sort, true);
+        const KeyOfU64 keyof{key_mask(key_bits)};
+        if (pl.hybrid) {
+            sort_groups((const uint64_t *)kin, kout, pl.top_shift, keyof, pl, ws, st);
+            uint64_t *t = kin; kin = kout; kout = t;
         }
+        p.sorted = vin;
+        p.skeys = kin;
+        part_scan((const uint64_t *)kin, keyof, p, pl, ws, true, st);
+        p.srec = ws.recs_a;
     }
-    p.srec = (uint4 *)ctx->cl_ws[14].ptr;
-    }
-    p.part_start = part_start; p.n_parts = scal; p.pc = pc;
-    const uint32_t grid = M < 16384u ? M : 16384u;               // partitions <= marks; kernels stride over them
-    uint32_t *lists = (uint32_t *)ctx->cl_ws[12].ptr;            // [kClasses][M] partitions by size class, each list in kShards pieces
-    uint32_t *cnts = scal + 64;                                  // [kClasses][kShards]
-    p.tps = (nb_sc + kShards - 1) / kShards;
+    p.part_start = ws.part_start; p.n_parts = ws.scal; p.pc = ws.pc;
+    uint32_t *const lists = ws.lists, *const cnts = ws.cnts, *const over = ws.over, *const scal = ws.scal;
     p.inv_norm = (float)(1.0 / pr->normalizer);
     for (int l = 0; l < 3; ++l) {
         p.t_lo[l] = (float)(pr->max_dist / (double)(1 << l) * (1.0 - 1e-5));
@@ -3253,10 +3231,6 @@ int duet_cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_c
     p.kc = (ctx->dbg & DUET_DBG_CLUSTER_KC2) ? 2u : 64u;
     p.sym = (ctx->dbg & DUET_DBG_CLUSTER_NOSYM) ? 0u : 1u;
     p.stamps = ctx->d_stamps;
-    const uint32_t gridw = std::min(32768u, std::max(1024u, M / 256u));     // (a wavefront per virtual block, striding)
-    const bool small = M <= (4u << 20) && !(ctx->dbg & DUET_DBG_CLUSTER_LARGE);
-    const bool cap100 = p.part_max <= 100u;          // no unit has more rows than part_max
-    uint32_t *over = cnts + kClasses * kShards;                  // [kClasses][kShards] the second lists' counters
     uint32_t *l4 = lists + 4 * (size_t)M, *c4 = cnts + 4 * kShards, *o4 = over + 4 * kShards;
     // The partitions of more than 64 marks on the side stream: few, long chains.  They are listed from the partition starts
     // alone and read their rows through the sort permutation themselves (or where the record sort left them), so their launch
@@ -3264,122 +3238,93 @@ int duet_cluster_run(duet_ctx *ctx, const duet_cluster_problem *pr, const duet_c
     // cl_box) -- except where cl_box itself numbers the partitions (large inputs: the chain is far from critical there).
     // (small inputs only: at 2e7 marks the forks' gaps are 15 of 2,100 us, and a side chain that starts 7 us earlier takes compute units
     // from the first tier's first launch -- measured: 2,187 against 2,127 us)
-    if (small && ctx->cl_gates == 0) {
-        const uint32_t e0 = ++ctx->cl_epoch;
-        uint32_t opened = 0;
-        hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, ctx->cl_side[1], ctx->cl_flags + 13, e0);
-        hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, ctx->cl_side[1], ctx->cl_flags + 13, e0);
-        hipLaunchKernelGGL(cl_gate_try, dim3(1), dim3(64), 0, ctx->cl_side[0], (const uint32_t *)(ctx->cl_flags + 14), e0, ctx->cl_flags + 15);
-        hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, ctx->cl_side[1], ctx->cl_flags + 14, e0);
-        HIP_TRY(ctx, hipMemcpyAsync(&opened, ctx->cl_flags + 15, 4, hipMemcpyDeviceToHost, ctx->cl_side[0]));     // (not the null stream: it would wait for the caller's)
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->cl_side[1]));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->cl_side[0]));
-        ctx->cl_gates = opened ? 1 : -1;
-    }
-    const bool gate_forks = small && ctx->cl_gates > 0 && !(ctx->dbg & DUET_DBG_CLUSTER_EVENT_FORKS);
     const uint32_t epoch = ++ctx->cl_epoch;
-    const bool tiers = !small || (ctx->dbg & DUET_DBG_CLUSTER_TIERS);
-    // small inputs: every partition of more than 64 marks on its own workgroup of eight wavefronts (wide_unit), on the side stream beside cl_box and
-    // cl_fast_all
-    // (up to 2 M marks: a wide unit holds 143 KB of LDS, i.e. a CU, for 50 us -- at 4 M marks the 80-odd of them take a third of the chip from
-    // cl_fast_all for that long and the pipeline is 1 % slower with them, 0.423 against 0.419 ms; level at 2 M)
-    // (measured, profiles/history/r06_wide_units.txt: for the listed partitions of up to 64 marks four-wavefront units LOSE -- cl_fast_all is
-    // bound by the chip's throughput there, not by a chain -- so only the partitions of more than 64 marks take wide units)
-    const bool wide = !tiers && M <= (2u << 20) && !(ctx->dbg & DUET_DBG_CLUSTER_WIDE_OFF);
     auto join_signal = [&]() -> int {
         // the join the same way on small inputs: the side stream says when it is through, a gate on the main stream waits for it (the
         // side stream's launches are queued in front of that gate, so even one shared hardware queue would run them first)
-        if (gate_forks) hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, ctx->cl_side[0], ctx->cl_flags + 4, epoch);
+        if (gate_forks) hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, ctx->cl_side[0], ctx->cl_flags + kFlagJoin, epoch);
         else HIP_TRY(ctx, hipEventRecord(ctx->cl_join[0], ctx->cl_side[0]));
         return DUET_OK;
     };
     auto launch_big = [&](bool next_kernel_signals) -> int {
         if (gate_forks) {
-            if (!next_kernel_signals) hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, st, ctx->cl_flags + 0, epoch);
-            hipLaunchKernelGGL(cl_gate, dim3(1), dim3(64), 0, ctx->cl_side[0], (const uint32_t *)(ctx->cl_flags + 0), epoch);
+            if (!next_kernel_signals) hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, st, ctx->cl_flags + kFlagFork, epoch);
+            hipLaunchKernelGGL(cl_gate, dim3(1), dim3(64), 0, ctx->cl_side[0], (const uint32_t *)(ctx->cl_flags + kFlagFork), epoch);
         } else {
             HIP_TRY(ctx, hipEventRecord(ctx->cl_fork, st));
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->cl_side[0], ctx->cl_fork, 0));
         }
         ClParams pb = p;
         pb.gather_rows = rec_mode ? 0u : 1u;                     // (rec_mode: the sorted rows are there already)
-        if (wide) {
-            uint32_t *big_parts = scal + 64 + 2 * kClasses * kShards;           // [M / 65 + 1] the partitions of more than 64 marks; o4[0] counts them
-            hipLaunchKernelGGL(cl_find_big, dim3(std::max(1u, std::min(512u, (M / 8u + 255u) / 256u))), dim3(256), 0, ctx->cl_side[0], pb, big_parts, o4);
-            hipLaunchKernelGGL(cl_wide_big, dim3(256), dim3(512), 0, ctx->cl_side[0], pb, (const uint32_t *)big_parts, (const uint32_t *)o4);
+        if (pl.wide) {
+            // (big_parts: [M / 65 + 1] the partitions of more than 64 marks; o4[0] counts them)
+            hipLaunchKernelGGL(cl_find_big, dim3(pl.g_find_big), dim3(256), 0, ctx->cl_side[0], pb, ws.big_parts, o4);
+            hipLaunchKernelGGL(cl_wide_big, dim3(256), dim3(512), 0, ctx->cl_side[0], pb, (const uint32_t *)ws.big_parts, (const uint32_t *)o4);
             return join_signal();
         }
-        const uint32_t gb = std::min(4096u, std::max(256u, (M / 64u + 63u) / 64u));      // (partitions <= marks; 64 of them per wavefront and step)
-        hipLaunchKernelGGL((cl_tight_big<64>), dim3(gb), dim3(64), 0, ctx->cl_side[0], pb, l4, o4, c4);
-        const uint32_t gl = std::min(gb, 1024u);
-        if (cap100) hipLaunchKernelGGL((cl_link_one<64, 2, 100>), dim3(gl), dim3(64), 0, ctx->cl_side[0], pb, (const uint32_t *)l4, (const uint32_t *)o4);
-        else hipLaunchKernelGGL((cl_link_one<64, 2, 128>), dim3(gl), dim3(64), 0, ctx->cl_side[0], pb, (const uint32_t *)l4, (const uint32_t *)o4);
+        hipLaunchKernelGGL((cl_tight_big<64>), dim3(pl.g_big), dim3(64), 0, ctx->cl_side[0], pb, l4, o4, c4);
+        hipLaunchKernelGGL((pl.cap100 ? cl_link_one<64, 2, 100> : cl_link_one<64, 2, 128>), dim3(pl.g_link), dim3(64), 0, ctx->cl_side[0], pb, (const uint32_t *)l4, (const uint32_t *)o4);
         return join_signal();
     };
     // (small inputs: cl_box itself signals as it starts -- a signal kernel of its own was 5.9 us on the main stream)
-    p.fork_flag = (!box_applies && gate_forks) ? ctx->cl_flags + 0 : nullptr;
+    p.fork_flag = (!box_applies && gate_forks) ? ctx->cl_flags + kFlagFork : nullptr;
     p.fork_epoch = epoch;
     // (the side stream's launches are queued BEHIND cl_box's: were the two streams ever to share a hardware queue, a gate in front of the
     // kernel that opens it would never see it start; an event fork goes in front, as in rounds 1-5)
     if (!box_applies && !gate_forks && (rc = launch_big(false))) return rc;
     // the bounding-box test finishes the partitions it can (on SV-like data: most) and lists the others by size class
     if (box_applies)
-        hipLaunchKernelGGL((cl_box<true, true>), dim3(nb_sc), dim3(kBoxThreads), 0, st, p, (const uint32_t *)nullptr, lists, cnts, (const uint8_t *)hbits, (const PartSum *)tiles, part_start, scal);
-    else if (rec_mode)
-        hipLaunchKernelGGL((cl_box<true, false>), dim3(nb_sc), dim3(kBoxThreads), 0, st, p, (const uint32_t *)tile_first, lists, cnts, (const uint8_t *)nullptr, (const PartSum *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
+        hipLaunchKernelGGL((cl_box<true, true>), dim3(nb_sc), dim3(kBoxThreads), 0, st, p, (const uint32_t *)nullptr, lists, cnts, (const uint8_t *)ws.hbits, (const PartSum *)ws.tiles, ws.part_start, scal);
     else
-        hipLaunchKernelGGL((cl_box<false, false>), dim3(nb_sc), dim3(kBoxThreads), 0, st, p, (const uint32_t *)tile_first, lists, cnts, (const uint8_t *)nullptr, (const PartSum *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
+        hipLaunchKernelGGL((rec_mode ? cl_box<true, false> : cl_box<false, false>), dim3(nb_sc), dim3(kBoxThreads), 0, st, p, (const uint32_t *)ws.tile_first, lists, cnts, (const uint8_t *)nullptr, (const PartSum *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
     if ((box_applies || gate_forks) && (rc = launch_big(!box_applies && gate_forks))) return rc;
-    if (!tiers) {
+    if (!pl.tiers) {
         // one launch for the classes of up to 64 marks, nothing handed on
-        hipLaunchKernelGGL(cl_fast_all, dim3(gridw), dim3(64), 0, st, p, (const uint32_t *)lists, (const uint32_t *)cnts);
-    } else if (small) {
-        hipLaunchKernelGGL(cl_tight_all, dim3(gridw), dim3(64), 0, st, p, lists, (const uint32_t *)cnts, over);
+        hipLaunchKernelGGL(cl_fast_all, dim3(pl.g_waves), dim3(64), 0, st, p, (const uint32_t *)lists, (const uint32_t *)cnts);
+    } else if (small_in) {
+        hipLaunchKernelGGL(cl_tight_all, dim3(pl.g_waves), dim3(64), 0, st, p, lists, (const uint32_t *)cnts, over);
     } else {
         // the first tier, one launch per size class: the registers and the LDS each variant needs, not the largest one's.
         // (Measured and dropped, profiles/history: the tiles in two or four pieces, a piece's box test on a side stream while the
         // first tier takes the piece before -- the box test, 32 KB of LDS per workgroup, then waits for room between the first
         // tier's many small workgroups and takes as long for a piece as it does alone for everything.)
-        hipLaunchKernelGGL((cl_tight_one<64, 1, kK64>), dim3(grid), dim3(64), 0, st, p, lists + 3 * (size_t)M, (const uint32_t *)(cnts + 3 * kShards), over + 3 * kShards);
+        hipLaunchKernelGGL((cl_tight_one<64, 1, kK64>), dim3(pl.g_lists), dim3(64), 0, st, p, lists + 3 * (size_t)M, (const uint32_t *)(cnts + 3 * kShards), over + 3 * kShards);
         // (what this class hands on -- the most of all classes -- has its second tier beside the other classes' first one)
         if (gate_forks) {
-            hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, st, ctx->cl_flags + 8, epoch);
-            hipLaunchKernelGGL(cl_gate, dim3(1), dim3(64), 0, ctx->cl_side[1], (const uint32_t *)(ctx->cl_flags + 8), epoch);
+            hipLaunchKernelGGL(cl_signal, dim3(1), dim3(64), 0, st, ctx->cl_flags + kFlagTierFork, epoch);
+            hipLaunchKernelGGL(cl_gate, dim3(1), dim3(64), 0, ctx->cl_side[1], (const uint32_t *)(ctx->cl_flags + kFlagTierFork), epoch);
         } else {
             HIP_TRY(ctx, hipEventRecord(ctx->cl_join[1], st));
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->cl_side[1], ctx->cl_join[1], 0));
         }
-        hipLaunchKernelGGL((cl_tier2_one<64, 1, 64>), dim3(std::min(grid, 4096u)), dim3(64), 0, ctx->cl_side[1], p, (const uint32_t *)(lists + 3 * (size_t)M), (const uint32_t *)(over + 3 * kShards));
+        hipLaunchKernelGGL((cl_tier2_one<64, 1, 64>), dim3(std::min(pl.g_lists, 4096u)), dim3(64), 0, ctx->cl_side[1], p, (const uint32_t *)(lists + 3 * (size_t)M), (const uint32_t *)(over + 3 * kShards));
         HIP_TRY(ctx, hipEventRecord(ctx->cl_join[2], ctx->cl_side[1]));
-        hipLaunchKernelGGL((cl_tight_one<32, 1, kK32>), dim3(grid), dim3(64), 0, st, p, lists + 2 * (size_t)M, (const uint32_t *)(cnts + 2 * kShards), over + 2 * kShards);
-        hipLaunchKernelGGL((cl_tight_one<16, 1, kK16>), dim3(grid), dim3(64), 0, st, p, lists + 1 * (size_t)M, (const uint32_t *)(cnts + 1 * kShards), over + 1 * kShards);
-        hipLaunchKernelGGL((cl_tight_one<8, 1, kK8>), dim3(grid), dim3(64), 0, st, p, lists, (const uint32_t *)cnts, over);
+        hipLaunchKernelGGL((cl_tight_one<32, 1, kK32>), dim3(pl.g_lists), dim3(64), 0, st, p, lists + 2 * (size_t)M, (const uint32_t *)(cnts + 2 * kShards), over + 2 * kShards);
+        hipLaunchKernelGGL((cl_tight_one<16, 1, kK16>), dim3(pl.g_lists), dim3(64), 0, st, p, lists + 1 * (size_t)M, (const uint32_t *)(cnts + 1 * kShards), over + 1 * kShards);
+        hipLaunchKernelGGL((cl_tight_one<8, 1, kK8>), dim3(pl.g_lists), dim3(64), 0, st, p, lists, (const uint32_t *)cnts, over);
     }
     // what they handed on
-    if (tiers) hipLaunchKernelGGL(cl_tier2_all, dim3(std::min(gridw, 2048u)), dim3(64), 0, st, p, (const uint32_t *)lists, (const uint32_t *)over, small ? 1u : 0u);
-    if (!small) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->cl_join[2], 0));
-    // (the join inside cl_pc_sums: its waiting workgroups hold wave slots -- up to M / 2048 workgroups of four wavefronts when every mark is a partition of its
-    // own -- so only up to 2 M marks, where they cannot take more than half of the chip's from the side stream's kernels; beyond, a one-lane gate kernel)
-    const bool join_in_sums = gate_forks && M <= (2u << 20);
-    if (gate_forks && !join_in_sums) hipLaunchKernelGGL(cl_gate, dim3(1), dim3(64), 0, st, (const uint32_t *)(ctx->cl_flags + 4), epoch);
+    if (pl.tiers) hipLaunchKernelGGL(cl_tier2_all, dim3(std::min(pl.g_waves, 2048u)), dim3(64), 0, st, p, (const uint32_t *)lists, (const uint32_t *)over, small_in ? 1u : 0u);
+    if (!small_in) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->cl_join[2], 0));
+    if (gate_forks && !pl.join_in_sums) hipLaunchKernelGGL(cl_gate, dim3(1), dim3(64), 0, st, (const uint32_t *)(ctx->cl_flags + kFlagJoin), epoch);
     else if (!gate_forks) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->cl_join[0], 0));
     // clusters per partition -> their sums per 64 and per 2048 partitions (cl_emit numbers the candidates from them); with gate forks the launch is
     // also the join of the side stream
-    hipLaunchKernelGGL(cl_pc_sums, dim3((M + 2047u) / 2048u), dim3(256), 0, st, (const uint32_t *)pc, (const uint32_t *)scal, cbase, spart,
-                       join_in_sums ? (const uint32_t *)(ctx->cl_flags + 4) : (const uint32_t *)nullptr, epoch);
-    p.csum = cbase;
-    p.tsum = spart;
+    hipLaunchKernelGGL(cl_pc_sums, dim3(pl.g_sums), dim3(256), 0, st, (const uint32_t *)ws.pc, (const uint32_t *)scal, ws.cbase, ws.spart,
+                       pl.join_in_sums ? (const uint32_t *)(ctx->cl_flags + kFlagJoin) : (const uint32_t *)nullptr, epoch);
+    p.csum = ws.cbase;
+    p.tsum = ws.spart;
     p.n_cands_w = res->n_cands;
     p.n_cands = res->n_cands;
-    hipLaunchKernelGGL(cl_emit, dim3(std::min((M + 16383u) / 16384u * 8u, 4096u)), b256, 0, st, p);        // (a wave per 64 partitions, striding)
+    hipLaunchKernelGGL(cl_emit, dim3(pl.g_emit), dim3(256), 0, st, p);
     HIP_TRY(ctx, hipGetLastError());
     if (getenv("DUET_CL_DEBUG")) {
-        uint32_t h[64 + 2 * kClasses * kShards];
+        uint32_t h[kScalBigParts];
         HIP_TRY(ctx, hipMemcpyAsync(h, scal, sizeof(h), hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
         uint32_t c[2 * kClasses] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int k = 0; k < 2 * kClasses; ++k)
-            for (int sh = 0; sh < kShards; ++sh) c[k] += h[64 + k * kShards + sh];
+            for (int sh = 0; sh < kShards; ++sh) c[k] += h[kScalCnts + k * kShards + sh];
         fprintf(stderr, "[duet_cluster] parts %u; past the box test, by size class: %u %u %u %u %u; handed on by the first tier: %u %u %u %u %u\n",
                 h[0], c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9]);
     }

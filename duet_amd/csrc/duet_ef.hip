@@ -2482,46 +2482,6 @@ __global__ void plan_mark_starts(const uint32_t *ctg_off, uint32_t K, uint8_t *c
     if (k < K && ctg_off[k] < ctg_off[k + 1]) ctg_start[ctg_off[k]] = 1;
 }
 
-// device-planned runs, everything the plan needs in ONE launch: the workspace's copy of the contig offsets, the per-contig
-// seed counts and the status words zeroed, and the contig of the first candidate of every 256-candidate block (binary search)
-__global__ void plan_device(const uint32_t *ctg_off, uint32_t K, uint32_t B, uint32_t *ctg_off_copy, uint32_t *n_one_and_status,
-                            uint32_t *blk_ctg)
-{
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b <= K) ctg_off_copy[b] = ctg_off[b];
-    if (b < K + 8) n_one_and_status[b] = 0;
-    if (b >= B) return;
-    const uint32_t c = b * kCandPerBlock;
-    uint32_t lo = 0, hi = K;                                   // the last k with ctg_off[k] <= c
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ctg_off[mid] <= c) lo = mid; else hi = mid;
-    }
-    blk_ctg[b] = lo;
-}
-
-// the same from the candidates' contig column (sorted by contig): the contig offsets by binary search, the tiles' contigs
-// straight from the column
-__global__ void plan_device_contigs(const uint16_t *cand_contig, const uint32_t *n_cands, uint32_t K, uint32_t B,
-                                    uint32_t *ctg_off_copy, uint32_t *n_one_and_status, uint32_t *blk_ctg)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t N = *n_cands;
-    if (t <= K) {
-        uint32_t lo = 0, hi = N;                               // first candidate whose contig is >= t
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (cand_contig[mid] < t) lo = mid + 1; else hi = mid;
-        }
-        ctg_off_copy[t] = t == K ? N : lo;
-    }
-    if (t < K + 8) n_one_and_status[t] = 0;
-    if (t < B) {
-        const uint32_t c = t * kCandPerBlock;
-        blk_ctg[t] = c < N ? (uint32_t)cand_contig[c] : 0u;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -2535,12 +2495,44 @@ namespace {
 inline int fail(duet_ctx *ctx, int code, const std::string &msg) { return duet_fail(ctx, code, msg); }
 inline int reserve(duet_ctx *ctx, DevBuf &b, size_t bytes) { return duet_reserve(ctx, b, bytes); }
 
-// (re)build the workspace for this contig layout; a no-op when it matches the cached plan.  The rebuild is
-// ordered on `stream` (uploads from a pinned staging block, memsets, one small kernel): the device is only
-// synchronised when a buffer has to grow or the context moves to another stream.
 // group-summary slots: kC2Quota per tile and a pool of an eighth of the candidates for the tiles that need more
 size_t c2_slots(uint32_t B, uint32_t C) { return (size_t)B * kC2Quota + (C / 8u > 256u ? C / 8u : 256u); }
 
+// the workspace of K contigs and C candidates in B tiles: its six buffers and their bytes
+struct WsWant { DevBuf *buf[6]; size_t bytes[6]; };
+WsWant ws_want(duet_ctx *ctx, uint32_t K, uint32_t C, uint32_t B)
+{
+    const size_t small_words = (size_t)(K + 1) + K + 8 + (size_t)B + 16 + (size_t)B * 16;      // (... 64-byte tile records, 64-byte aligned)
+    return WsWant{{&ctx->ws_small, &ctx->ws_start, &ctx->ws_ent, &ctx->ws_one, &ctx->ws_tmp, &ctx->ws_c2},
+                  {small_words * 4, C, (size_t)B * kCandPerBlock * 8, ((size_t)C + K + 1) * 4, ((size_t)C + K + 1) * 4, c2_slots(B, C) * kC2Words * 4}};
+}
+// ... reserved; grow: the caller has to synchronise the device anyway, out: it has been -- only where a buffer has to grow: those of the
+// previous plan may still be in use by queued work
+int ws_reserve(duet_ctx *ctx, const WsWant &w, bool &grow)
+{
+    for (int i = 0; i < 6; ++i) grow = grow || w.bytes[i] > w.buf[i]->cap;
+    if (!grow) return DUET_OK;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    int rc;
+    for (int i = 0; i < 6; ++i)
+        if ((rc = reserve(ctx, *w.buf[i], w.bytes[i]))) return rc;
+    return DUET_OK;
+}
+// ... and ws_small's pieces, in that order
+void carve_small(duet_ctx *ctx, uint32_t K, uint32_t B)
+{
+    uint32_t *w = (uint32_t *)ctx->ws_small.ptr;
+    ctx->d_ctg_off = w;            w += K + 1;
+    ctx->d_n_one = w;              w += K;
+    ctx->d_status = w;             w += 8;
+    ctx->d_blk_ctg = w;            w += B;
+    w += ((uintptr_t)w & 63) ? (64 - ((uintptr_t)w & 63)) / 4 : 0;        // 64-byte aligned tile records
+    ctx->d_blk_cnt = w;            // B records of 4 x u64
+}
+
+// (re)build the workspace for this contig layout; a no-op when it matches the cached plan.  The rebuild is
+// ordered on `stream` (uploads from a pinned staging block, memsets, one small kernel): the device is only
+// synchronised when a buffer has to grow or the context moves to another stream.
 int ensure_plan(duet_ctx *ctx, const duet_ef_problem *pr, hipStream_t stream)
 {
     const uint32_t K = pr->n_contigs, C = pr->n_cands;
@@ -2548,20 +2540,12 @@ int ensure_plan(duet_ctx *ctx, const duet_ef_problem *pr, hipStream_t stream)
         memcmp(ctx->plan_off.data(), pr->cand_ctg_off, sizeof(uint32_t) * (K + 1)) == 0)
         return DUET_OK;
     const uint32_t B = (C + kCandPerBlock - 1) / kCandPerBlock;
-    const size_t small_words = (size_t)(K + 1) + K + 8 + (size_t)B + 16 + (size_t)B * 16;      // (... 64-byte tile records, 64-byte aligned)
-    const size_t want[6] = {small_words * 4, C, (size_t)B * kCandPerBlock * 8, ((size_t)C + K + 1) * 4, ((size_t)C + K + 1) * 4,
-                            c2_slots(B, C) * kC2Words * 4};
-    DevBuf *bufs[6] = {&ctx->ws_small, &ctx->ws_start, &ctx->ws_ent, &ctx->ws_one, &ctx->ws_tmp, &ctx->ws_c2};
-    bool grow = ctx->plan_stream != stream;
-    for (int i = 0; i < 6; ++i) grow = grow || want[i] > bufs[i]->cap;
+    const WsWant want = ws_want(ctx, K, C, B);
     const size_t stage_bytes = ((size_t)K + 1 + B) * 4;
-    grow = grow || stage_bytes > ctx->plan_stage_cap;
+    bool grow = ctx->plan_stream != stream || stage_bytes > ctx->plan_stage_cap;
     int rc;
+    if ((rc = ws_reserve(ctx, want, grow))) return rc;
     if (grow) {
-        // buffers of the previous plan may still be in use by queued work
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        for (int i = 0; i < 6; ++i)
-            if ((rc = reserve(ctx, *bufs[i], want[i]))) return rc;
         if (stage_bytes > ctx->plan_stage_cap) {
             if (ctx->plan_stage) HIP_TRY(ctx, hipHostFree(ctx->plan_stage));
             ctx->plan_stage = nullptr;
@@ -2572,13 +2556,7 @@ int ensure_plan(duet_ctx *ctx, const duet_ef_problem *pr, hipStream_t stream)
     } else {
         HIP_TRY(ctx, hipEventSynchronize(ctx->plan_ev));        // the staging block's previous upload has been read
     }
-    uint32_t *w = (uint32_t *)ctx->ws_small.ptr;
-    ctx->d_ctg_off = w;            w += K + 1;
-    ctx->d_n_one = w;              w += K;
-    ctx->d_status = w;             w += 8;
-    ctx->d_blk_ctg = w;            w += B;
-    w += ((uintptr_t)w & 63) ? (64 - ((uintptr_t)w & 63)) / 4 : 0;        // 32-byte aligned tile records
-    ctx->d_blk_cnt = w;            // B records of 4 x u64
+    carve_small(ctx, K, B);
     // staging: ctg_off, then the contig of the first candidate of every 256-candidate block
     uint32_t *h_off = ctx->plan_stage, *h_blk = ctx->plan_stage + (K + 1);
     memcpy(h_off, pr->cand_ctg_off, sizeof(uint32_t) * (K + 1));
@@ -2629,6 +2607,30 @@ int validate(duet_ctx *ctx, const duet_ef_problem *pr, const void *out_pred, con
         if (pr->n_reads && !pr->read_tag) return fail(ctx, DUET_ERR_INVALID, "read_tag is null");
     }
     return DUET_OK;
+}
+
+// what both runs pass the kernels, over the planned workspace: K contigs and C candidates (or their bound) in B tiles
+void shared_params(Params &p, duet_ctx *ctx, const duet_ef_problem *pr, uint32_t C, uint32_t B, uint8_t *out_pred, uint32_t *out_ps)
+{
+    memset(&p, 0, sizeof(p));
+    p.K = pr->n_contigs; p.C = C; p.M = pr->n_marks;
+    p.read_tag = pr->n_reads ? pr->read_tag : (const uint64_t *)ctx->d_n_one;   // always >= 1 readable word
+    p.n_reads = pr->n_reads; p.untagged = ctx->d_untagged;
+    p.cand_pos = pr->cand_pos; p.cand_svlen = pr->cand_svlen; p.cand_svread = pr->cand_svread;
+    p.cand_refread = pr->cand_refread; p.cand_gt_ok = pr->cand_gt_ok;
+    p.cand_off = pr->cand_off; p.mark_read = pr->mark_read;
+    p.svlen_thres = pr->svlen_thres; p.suppread_thres = pr->suppread_thres;
+    p.ctg_off = ctx->d_ctg_off; p.ctg_start = (const uint8_t *)ctx->ws_start.ptr; p.blk_ctg = ctx->d_blk_ctg;
+    p.blk_rec = (uint64_t *)ctx->d_blk_cnt; p.seed_ent = (uint64_t *)ctx->ws_ent.ptr;
+    p.one_cap = C + pr->n_contigs;
+    p.onebuf = (uint32_t *)ctx->ws_one.ptr; p.tmpbuf = (uint32_t *)ctx->ws_tmp.ptr;
+    p.n_one = ctx->d_n_one; p.c2rec = (uint32_t *)ctx->ws_c2.ptr; p.status = ctx->d_status;
+    p.c2_fixed = B * kC2Quota;
+    p.c2_cap = (uint32_t)c2_slots(B, C);
+    p.out_pred = out_pred; p.out_ps = out_ps;
+    p.dbg = ctx->dbg;
+    p.heavy_t = (ctx->dbg & DUET_DBG_EF_HEAVY_ALL) ? 0u : ((ctx->dbg & DUET_DBG_EF_HEAVY_OFF) ? 0xFFFFFFFFu : ctx->ef_heavy_t);
+    p.stamps = ctx->d_stamps;
 }
 
 }  // namespace
@@ -2758,28 +2760,12 @@ int duet_ef_run_device(duet_ctx *ctx, const duet_ef_problem *pr, uint8_t *out_pr
     if (pr->n_cands == 0) return DUET_OK;
     if ((rc = ensure_plan(ctx, pr, stream))) return rc;
 
+    const uint32_t blocks = (pr->n_cands + kCandPerBlock - 1) / kCandPerBlock;
+    const bool aligned = ((uintptr_t)pr->mark_read & 15) == 0;
     Params p;
-    memset(&p, 0, sizeof(p));
-    p.K = pr->n_contigs; p.C = pr->n_cands; p.M = pr->n_marks;
-    p.read_tag = pr->n_reads ? pr->read_tag : (const uint64_t *)ctx->d_n_one;   // always >= 1 readable word
-    p.n_reads = pr->n_reads; p.untagged = ctx->d_untagged;
-    p.cand_pos = pr->cand_pos; p.cand_svlen = pr->cand_svlen; p.cand_svread = pr->cand_svread;
-    p.cand_refread = pr->cand_refread; p.cand_gt_ok = pr->cand_gt_ok;
-    p.cand_off = pr->cand_off; p.mark_read = pr->mark_read;
-    p.svlen_thres = pr->svlen_thres; p.suppread_thres = pr->suppread_thres;
-    p.ctg_off = ctx->d_ctg_off; p.ctg_start = (const uint8_t *)ctx->ws_start.ptr; p.blk_ctg = ctx->d_blk_ctg;
-    p.blk_rec = (uint64_t *)ctx->d_blk_cnt; p.seed_ent = (uint64_t *)ctx->ws_ent.ptr;
-    p.one_cap = pr->n_cands + pr->n_contigs;
+    shared_params(p, ctx, pr, pr->n_cands, blocks, out_pred, out_ps);
     p.n_small = pr->n_contigs <= (uint32_t)kSmallK ? pr->n_contigs : 0;
     for (uint32_t k = 0; k <= p.n_small && p.n_small; ++k) p.ctg_small[k] = pr->cand_ctg_off[k];
-    p.onebuf = (uint32_t *)ctx->ws_one.ptr; p.tmpbuf = (uint32_t *)ctx->ws_tmp.ptr;
-    p.n_one = ctx->d_n_one; p.c2rec = (uint32_t *)ctx->ws_c2.ptr; p.status = ctx->d_status;
-    p.c2_fixed = ((p.C + kCandPerBlock - 1) / kCandPerBlock) * kC2Quota;
-    p.c2_cap = (uint32_t)c2_slots((p.C + kCandPerBlock - 1) / kCandPerBlock, p.C);
-    p.out_pred = out_pred; p.out_ps = out_ps;
-    p.dbg = ctx->dbg;
-    p.heavy_t = (ctx->dbg & DUET_DBG_EF_HEAVY_ALL) ? 0u : ((ctx->dbg & DUET_DBG_EF_HEAVY_OFF) ? 0xFFFFFFFFu : ctx->ef_heavy_t);
-    p.stamps = ctx->d_stamps;
 
     // Profiling: the start/stop events ride on the kernel's own dispatch packet (hipExtLaunchKernelGGL),
     // so hipEventElapsedTime is the kernel's execution time as rocprofv3 --kernel-trace reports it.
@@ -2797,7 +2783,6 @@ int duet_ef_run_device(duet_ctx *ctx, const duet_ef_problem *pr, uint8_t *out_pr
         for (int i = 0; i < (prof == 2 ? 6 : 2); ++i) ev[i] = ctx->ev_pool[ctx->ev_used + i];
         ctx->ev_used += 6;
     }
-    const uint32_t blocks = (pr->n_cands + kCandPerBlock - 1) / kCandPerBlock;
     // two launches where the problem is small (round 6): ef_finalize_own builds every tile's seed set itself, no ef_seed_sort
     // (the diagnostic bits that select a variant of ef_seed_sort / ef_finalize select the three launches with it)
     const uint32_t three = DUET_DBG_EF_OWN_OFF | DUET_DBG_EF_FIN_TPB2 | DUET_DBG_EF_FIN_TPB4 | DUET_DBG_EF_NO_SEED_HASH;
@@ -2805,11 +2790,11 @@ int duet_ef_run_device(duet_ctx *ctx, const duet_ef_problem *pr, uint8_t *out_pr
     // ... and there, while the chip is far from full, kSplit lanes walk a candidate (round 9: ef_classify_split)
     const bool split = own && blocks <= kSplitMaxTiles && !(ctx->dbg & DUET_DBG_EF_SPLIT_OFF);
     if (prof) ctx->ev_kmask.push_back(own ? 0x5 : 0x7);
-    if (split && ((uintptr_t)pr->mark_read & 15) == 0)
+    if (split && aligned)
         hipExtLaunchKernelGGL(ef_classify_split<true>, dim3(blocks), dim3(kSplitThreads), 0, stream, ev[0], ev[1], 0, p);
     else if (split)
         hipExtLaunchKernelGGL(ef_classify_split<false>, dim3(blocks), dim3(kSplitThreads), 0, stream, ev[0], ev[1], 0, p);
-    else if (((uintptr_t)pr->mark_read & 15) == 0)
+    else if (aligned)
         hipExtLaunchKernelGGL(ef_classify<true>, dim3(blocks), dim3(kCandPerBlock), 0, stream, ev[0], ev[1], 0, p);
     else
         hipExtLaunchKernelGGL(ef_classify<false>, dim3(blocks), dim3(kCandPerBlock), 0, stream, ev[0], ev[1], 0, p);
@@ -2846,7 +2831,7 @@ int duet_ef_run_device(duet_ctx *ctx, const duet_ef_problem *pr, uint8_t *out_pr
 }  // extern "C"
 
 // Device-planned run (used by duet_svim_phase_device): the candidate count and the contig offsets exist only on the
-// device (d_n_cands, d_ctg_off[K+1]); every buffer and grid is sized for c_max candidates and the kernels read the real
+// device (d_n_cands, the workspace's ctg_off[K+1]); every buffer and grid is sized for c_max candidates and the kernels read the real
 // count.  Nothing here waits for the device.
 //
 // The workspace first: a producer that knows the candidates' contigs as it writes them (stage A0's cl_emit) fills in the
@@ -2855,27 +2840,12 @@ int duet_ef_run_device(duet_ctx *ctx, const duet_ef_problem *pr, uint8_t *out_pr
 int duet_ef_plan_on_device_prepare(duet_ctx *ctx, uint32_t K, uint32_t c_max, hipStream_t stream, uint32_t **ctg_off_out,
                                    uint32_t **zero_out)
 {
-    const uint32_t C = c_max;
-    const uint32_t B = (C + kCandPerBlock - 1) / kCandPerBlock;
-    const size_t small_words = (size_t)(K + 1) + K + 8 + (size_t)B + 16 + (size_t)B * 16;      // (... 64-byte tile records, 64-byte aligned)
-    const size_t want[6] = {small_words * 4, C, (size_t)B * kCandPerBlock * 8, ((size_t)C + K + 1) * 4, ((size_t)C + K + 1) * 4,
-                            c2_slots(B, C) * kC2Words * 4};
-    DevBuf *bufs[6] = {&ctx->ws_small, &ctx->ws_start, &ctx->ws_ent, &ctx->ws_one, &ctx->ws_tmp, &ctx->ws_c2};
+    const uint32_t B = (c_max + kCandPerBlock - 1) / kCandPerBlock;
+    const WsWant want = ws_want(ctx, K, c_max, B);
     bool grow = ctx->plan_stream != stream;
-    for (int i = 0; i < 6; ++i) grow = grow || want[i] > bufs[i]->cap;
     int rc;
-    if (grow) {
-        HIP_TRY(ctx, hipDeviceSynchronize());                  // buffers of the previous plan may still be in use
-        for (int i = 0; i < 6; ++i)
-            if ((rc = reserve(ctx, *bufs[i], want[i]))) return rc;
-    }
-    uint32_t *w = (uint32_t *)ctx->ws_small.ptr;
-    ctx->d_ctg_off = w;            w += K + 1;
-    ctx->d_n_one = w;              w += K;
-    ctx->d_status = w;             w += 8;
-    ctx->d_blk_ctg = w;            w += B;
-    w += ((uintptr_t)w & 63) ? (64 - ((uintptr_t)w & 63)) / 4 : 0;
-    ctx->d_blk_cnt = w;
+    if ((rc = ws_reserve(ctx, want, grow))) return rc;
+    carve_small(ctx, K, B);
     ctx->plan_off.clear();                                     // the cached host-side plan no longer describes the workspace
     ctx->plan_C = 0;
     ctx->plan_max_span = 0;
@@ -2886,47 +2856,19 @@ int duet_ef_plan_on_device_prepare(duet_ctx *ctx, uint32_t K, uint32_t c_max, hi
 }
 
 int duet_ef_run_planned_on_device(duet_ctx *ctx, const duet_ef_problem *pr, uint32_t c_max, const uint32_t *d_n_cands,
-                                  const uint32_t *d_ctg_off, const uint16_t *d_cand_contig, uint8_t *out_pred, uint32_t *out_ps,
-                                  hipStream_t stream, bool planned)
+                                  const uint16_t *d_cand_contig, uint8_t *out_pred, uint32_t *out_ps, hipStream_t stream)
 {
     const uint32_t K = pr->n_contigs, C = c_max;
     if (K == 0 || C == 0) return DUET_OK;
     const uint32_t B = (C + kCandPerBlock - 1) / kCandPerBlock;
     int rc;
     if ((rc = duet_ef_plan_on_device_prepare(ctx, K, c_max, stream, nullptr, nullptr))) return rc;
-    if (!planned) {
-        const uint32_t nthr = B > K + 8 ? B : K + 8;
-        if (d_cand_contig)      // no contig offsets yet: they come out of the same launch
-            hipLaunchKernelGGL(plan_device_contigs, dim3((nthr + 255) / 256), dim3(256), 0, stream, d_cand_contig, d_n_cands, K, B,
-                               ctx->d_ctg_off, ctx->d_n_one, ctx->d_blk_ctg);
-        else
-            hipLaunchKernelGGL(plan_device, dim3((nthr + 255) / 256), dim3(256), 0, stream, d_ctg_off, K, B, ctx->d_ctg_off,
-                               ctx->d_n_one, ctx->d_blk_ctg);
-    }
 
     Params p;
-    memset(&p, 0, sizeof(p));
-    p.K = K; p.C = C; p.M = pr->n_marks;
+    shared_params(p, ctx, pr, C, B, out_pred, out_ps);
     p.dyn_c = d_n_cands;
     p.cand_contig = d_cand_contig;
-    p.read_tag = pr->n_reads ? pr->read_tag : (const uint64_t *)ctx->d_n_one;
-    p.n_reads = pr->n_reads; p.untagged = ctx->d_untagged;
-    p.cand_pos = pr->cand_pos; p.cand_svlen = pr->cand_svlen; p.cand_svread = pr->cand_svread;
-    p.cand_refread = pr->cand_refread; p.cand_gt_ok = pr->cand_gt_ok;
-    p.cand_off = pr->cand_off; p.mark_read = pr->mark_read;
-    p.svlen_thres = pr->svlen_thres; p.suppread_thres = pr->suppread_thres;
-    p.ctg_off = ctx->d_ctg_off; p.ctg_start = (const uint8_t *)ctx->ws_start.ptr; p.blk_ctg = ctx->d_blk_ctg;
-    p.blk_rec = (uint64_t *)ctx->d_blk_cnt; p.seed_ent = (uint64_t *)ctx->ws_ent.ptr;
-    p.one_cap = C + K;
     p.n_small = 0;
-    p.onebuf = (uint32_t *)ctx->ws_one.ptr; p.tmpbuf = (uint32_t *)ctx->ws_tmp.ptr;
-    p.n_one = ctx->d_n_one; p.c2rec = (uint32_t *)ctx->ws_c2.ptr; p.status = ctx->d_status;
-    p.c2_fixed = ((p.C + kCandPerBlock - 1) / kCandPerBlock) * kC2Quota;
-    p.c2_cap = (uint32_t)c2_slots((p.C + kCandPerBlock - 1) / kCandPerBlock, p.C);
-    p.out_pred = out_pred; p.out_ps = out_ps;
-    p.dbg = ctx->dbg;
-    p.heavy_t = (ctx->dbg & DUET_DBG_EF_HEAVY_ALL) ? 0u : ((ctx->dbg & DUET_DBG_EF_HEAVY_OFF) ? 0xFFFFFFFFu : ctx->ef_heavy_t);
-    p.stamps = ctx->d_stamps;
     // the kernels stride over the real tiles: an eighth of the bound's tiles (SV-like data: ~10 marks per candidate), at least 512
     const uint32_t G = B < 512u ? B : (B / 8u > 512u ? B / 8u : 512u);
     if (((uintptr_t)pr->mark_read & 15) == 0)
@@ -2939,7 +2881,7 @@ int duet_ef_run_planned_on_device(duet_ctx *ctx, const duet_ef_problem *pr, uint
     // 269.1 us for the pipeline (in position order the same candidates take 23.4 against 28.8).
     hipLaunchKernelGGL(ef_seed_sort, dim3(K), dim3(kSortThreads), 0, stream, p);
     // (two tiles per workgroup where the bound says millions of candidates: the per-workgroup round trips once per 512)
-    if (d_cand_contig && (C >= 8000000u || (ctx->dbg & DUET_DBG_EF_FIN_TPB2)))
+    if (C >= 8000000u || (ctx->dbg & DUET_DBG_EF_FIN_TPB2))
         hipLaunchKernelGGL((ef_finalize<true, 2>), dim3(G), dim3(256), 0, stream, p);
     else
         hipLaunchKernelGGL(ef_finalize<true>, dim3(G), dim3(256), 0, stream, p);

@@ -130,13 +130,13 @@ inline int duet_fail(duet_ctx *ctx, int code, const std::string &msg)
     } while (0)
 
 // device-planned E/F run (duet_ef.hip), for the fused pipeline in duet_svim.hip.  _prepare sizes the workspace for the bound
-// and names the plan's place in it: ctg_off[K + 1], and K + 8 words to zero (seeds per contig, status words) -- a producer that
-// writes both itself passes planned = true and no plan kernel is launched
+// and names the plan's place in it: ctg_off[K + 1], and K + 8 words to zero (seeds per contig, status words) -- the producer
+// (stage A0's cl_emit) writes both itself, and the run launches no plan kernel
 int duet_ef_plan_on_device_prepare(duet_ctx *ctx, uint32_t K, uint32_t c_max, hipStream_t stream, uint32_t **ctg_off_out,
                                    uint32_t **zero_out);
 int duet_ef_run_planned_on_device(duet_ctx *ctx, const duet_ef_problem *pr, uint32_t c_max, const uint32_t *d_n_cands,
-                                  const uint32_t *d_ctg_off /* or null ... */, const uint16_t *d_cand_contig /* ... then the candidates' contig column */,
-                                  uint8_t *out_pred, uint32_t *out_ps, hipStream_t stream, bool planned);
+                                  const uint16_t *d_cand_contig /* the candidates' contig column */, uint8_t *out_pred, uint32_t *out_ps,
+                                  hipStream_t stream);
 
 int duet_ef_materialise_seeds(duet_ctx *ctx);
 

@@ -273,8 +273,7 @@ int duet_svim_phase_device(duet_ctx *ctx, const duet_svim_problem *pr, const due
         // fully asynchronous: E/F is planned on the device from the candidates' contig column; buffers and grids are
         // sized for the upper bound (a candidate has at least one mark) and the kernels read the real count
         ef.n_cands = ef.n_marks;
-        return duet_ef_run_planned_on_device(ctx, &ef, ef.n_marks, (const uint32_t *)res->n_cands, nullptr, (const uint16_t *)res->cand_contig,
-                                             out_pred, out_ps, st, true);
+        return duet_ef_run_planned_on_device(ctx, &ef, ef.n_marks, (const uint32_t *)res->n_cands, (const uint16_t *)res->cand_contig, out_pred, out_ps, st);
     }
     std::vector<uint32_t> ctg_off;
     if ((rc = svim_host_plan(ctx, res, st, ctg_off, ef))) return rc;

@@ -1,8 +1,10 @@
 # coding=utf-8
 """TEST INFRASTRUCTURE ONLY -- what stage A0's host driver DECIDES for an input, not what its kernels compute: a transcription of
-the plan code of duet_cluster_run (csrc/duet_cluster.hip) and of rule 2 of oracle/cluster_oracle.c (the partitions), in numpy.
+the driver's plan function (cl_plan, csrc/duet_cluster_plan.h) and of rule 2 of oracle/cluster_oracle.c (the partitions), in numpy.
 It is used for one thing: to show that a named case of tests/cluster_cases.py sits on the edge it is named for
-(tests/test_cluster_case_edges.py).  Expected results never come from here: they come from the oracle."""
+(tests/test_cluster_case_edges.py).  Expected results never come from here: they come from the oracle.  The plan is not taken on
+trust: tests/test_cluster_plan_host.py compiles cl_plan itself (tools/cluster_plan_check.hip) and holds plan_from_counts to it, field
+for field, on every named case and on a grid of sizes, key widths and debug words."""
 import numpy as np
 
 # include/duet_ef.h
@@ -24,15 +26,25 @@ def centres(marks):
     return marks['pos'].astype(np.int64) + marks['span'].astype(np.int64) // 2
 
 
-def plan(marks, dbg=0, hints=True, part_max=100):
-    """duet_cluster_run's switches for these marks under debug word dbg; hints as _lib.fill_cluster_problem sets them (without
-    them, or with max_pos_hint == 0, the bit counts come from the true maxima, as cl_maxima measures them)."""
-    M = len(marks['pos'])
-    assert M > 0
+def bit_counts(marks, hints=True):
+    """-> (centre_bits, type_bits, contig_bits, hinted): hints as _lib.fill_cluster_problem sets them (without them, or with
+    max_pos_hint == 0, the bit counts come from the true maxima, as cl_maxima measures them)."""
     max_pos, max_span = int(marks['pos'].max()), max(int(marks['span'].max()), 1)
     hinted = bool(hints) and max_pos != 0                 # (the other three hints are never 0)
     centre_bits = bits_for(max_pos + max_span // 2) if hinted else bits_for(int(centres(marks).max()))
-    type_bits, contig_bits = bits_for(int(marks['type'].max())), bits_for(int(marks['contig'].max()))
+    return centre_bits, bits_for(int(marks['type'].max())), bits_for(int(marks['contig'].max())), hinted
+
+
+def plan(marks, dbg=0, hints=True, part_max=100):
+    """duet_cluster_run's switches for these marks under debug word dbg"""
+    M = len(marks['pos'])
+    assert M > 0
+    centre_bits, type_bits, contig_bits, hinted = bit_counts(marks, hints)
+    return dict(plan_from_counts(M, centre_bits, type_bits, contig_bits, dbg, part_max), hinted=hinted)
+
+
+def plan_from_counts(M, centre_bits, type_bits, contig_bits, dbg=0, part_max=100):
+    """cl_plan (csrc/duet_cluster_plan.h) for M marks whose keys have these widths"""
     key_bits = centre_bits + type_bits + contig_bits
     assert key_bits <= 64
     idx_bits = bits_for(M - 1)
@@ -65,7 +77,7 @@ def plan(marks, dbg=0, hints=True, part_max=100):
                 rs_small=rs_small, rs_chunks=rs_chunks, small_in=bool(small_in), top_bits=top_bits, hybrid=bool(hybrid),
                 top_shift=top_shift, nb_sc=nb_sc, use_spine=use_spine, box_applies=bool(box_applies),
                 tps=(nb_sc + SHARDS - 1) // SHARDS, tiers=tiers,
-                wide=not tiers and M <= (2 << 20) and not dbg & WIDE_OFF, cap100=part_max <= 100, hinted=hinted)
+                wide=not tiers and M <= (2 << 20) and not dbg & WIDE_OFF, cap100=part_max <= 100)
 
 
 def partitions(marks, part_gap=1000, part_max=100):

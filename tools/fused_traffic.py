@@ -33,7 +33,7 @@ wt, wc = per_kernel(write_csv, 'WRITE_SIZE')
 pipeline = [k for k in ft if k.split('<')[0] in ('rs_hist', 'rs_hist_dig', 'rs_offsets_small', 'rs_col_reduce', 'rs_scatter',
                                                   'rx_local', 'rx_big', 'part_reduce', 'part_spine', 'part_apply', 'cl_box', 'cl_tight_big',
                                                   'cl_link_one', 'cl_fast_all', 'cl_tight_all', 'cl_tight_one', 'cl_tier2_one', 'cl_tier2_all',
-                                                  'scan_reduce', 'scan_spine', 'scan_apply', 'cl_emit', 'plan_device_contigs', 'ef_classify',
+                                                  'scan_reduce', 'scan_spine', 'scan_apply', 'cl_emit', 'ef_classify',
                                                   'ef_seed_sort', 'ef_finalize', 'cl_keys', 'rx_hist', 'rx_offsets', 'rx_scatter', 'cl_find_big', 'cl_wide_big', 'cl_signal',
                                                   'cl_gate', 'cl_pc_sums')]
 def runs_of(c):       # one first-pass histogram (record sort) or one cl_keys (key-only sort) per run
