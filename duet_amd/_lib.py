@@ -28,7 +28,7 @@ KERNEL_NAMES = ('ef_classify', 'ef_seed_sort', 'ef_finalize')
 EXPORTS = ('duet_abi_version', 'duet_ctx_create', 'duet_ctx_destroy', 'duet_last_error',
            'duet_ctx_set_profiling', 'duet_ctx_set_debug', 'duet_ef_run_device', 'duet_ef_check', 'duet_ef_run_host',
            'duet_ef_profile_collect', 'duet_ef_get_seed_ps', 'duet_cluster_run_device', 'duet_cluster_run_host', 'duet_svim_phase_device', 'duet_svim_phase_host', 'duet_rows_run_device',
-           'duet_ef_rows_run_host', 'duet_eval_run_host', 'duet_comm_unique_id', 'duet_comm_create', 'duet_comm_allgather_device',
+           'duet_ef_rows_run_host', 'duet_eval_run_host', 'duet_eval_details_host', 'duet_comm_unique_id', 'duet_comm_create', 'duet_comm_allgather_device',
            'duet_comm_allgather_host', 'duet_comm_destroy', 'duet_comm_set_timeout', 'duet_comm_block_bytes',
            'duet_comm_ef_allgather', 'duet_comm_rccl_version', 'duet_comm_info', 'duet_comm_selftest',
            'duet_ef_features_device', 'duet_ef_features_host', 'duet_tune_sweep_device', 'duet_tune_sweep_host',
@@ -146,6 +146,15 @@ class EvalProblem(ctypes.Structure):
 class EvalCounts(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ('call_tp', 'base_tp', 'call_gt', 'base_gt', 'call_hp', 'base_hp')]
 
+
+# the evaluator's per-record outcome (include/duet_ef.h: duet_eval_call_rec, 12 bytes; duet_eval_base_rec, 24 bytes)
+EVAL_CALL_DTYPE = np.dtype([('base', '<u4'), ('dist', '<u4'), ('bits', '<u4')])
+EVAL_BASE_DTYPE = np.dtype([('n_calls', '<u4'), ('n_gt', '<u4'), ('n_hp', '<u4'), ('nearest', '<u4'), ('nearest_dist', '<u4'),
+                            ('reason', 'u1'), ('reserved', 'u1', (3,))])
+EVAL_NEAR, EVAL_SIZE, EVAL_MATCHED, EVAL_GT, EVAL_SAME, EVAL_FLIP, EVAL_LABEL, EVAL_HP = (1 << i for i in range(8))   # DUET_EVAL_NEAR ..
+EVAL_REASON_NAMES = ('no_call', 'far', 'size', 'elsewhere')                        # DUET_EVAL_NO_CALL .. DUET_EVAL_ELSEWHERE
+EVAL_HIT = 255                                                                     # DUET_EVAL_HIT
+EVAL_NONE = 0xFFFFFFFF
 
 # threshold sweep (include/duet_ef.h, "Threshold sweep"; duet_amd/tune.py)
 TUNE_NAMES = ('c0_min_sv_num', 'c2_min_sv_ratio', 'c2_max_avgsc_diff', 'c2_min_sv_num', 'c2_min_hap0', 'c1_onehap_sv_ratio_lo',
@@ -282,6 +291,22 @@ TRUTH_ARRAYS = (('cand_flags', np.uint16), ('cand_group', np.uint32), ('cand_uid
                 ('group_pair_off', np.uint32), ('pair_uid', np.uint32))
 
 
+def eval_problem(arrays, refdist, ratio):
+    """The flat host arrays of duet_amd/evaluation.py's flatten -> (EvalProblem, what must outlive the call)."""
+    p = EvalProblem()
+    keep = {}
+    for name, dt in (('base_off', np.uint32), ('base_pos', np.uint32), ('base_len', np.uint32), ('base_uid', np.uint32),
+                     ('base_hp', np.uint8), ('call_key', np.uint32), ('call_pos', np.uint32), ('call_len', np.uint32),
+                     ('call_uid', np.uint32), ('call_group', np.uint32), ('call_hp', np.uint8)):
+        keep[name] = np.ascontiguousarray(arrays[name], dtype=dt)
+        setattr(p, name, keep[name].ctypes.data if keep[name].size else None)
+    p.n_base, p.n_calls = len(keep['base_pos']), len(keep['call_pos'])
+    p.n_keys, p.n_groups = len(keep['base_off']) - 1, int(arrays['n_groups'])
+    p.n_base_uid, p.n_call_uid = int(arrays['n_base_uid']), int(arrays['n_call_uid'])
+    p.refdist, p.ratio = clamp_u32(refdist), float(ratio)
+    return p, keep
+
+
 class DuetLibraryError(RuntimeError):
     pass
 
@@ -333,6 +358,8 @@ def load():
     lib.duet_ef_rows_run_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(EfProblem), ctypes.POINTER(RowsProblem), ctypes.c_void_p,
                                           ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     lib.duet_eval_run_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(EvalProblem), ctypes.POINTER(EvalCounts)]
+    lib.duet_eval_details_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(EvalProblem), ctypes.POINTER(EvalCounts), ctypes.c_void_p,
+                                           ctypes.c_void_p]
     lib.duet_svim_phase_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult),
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
     lib.duet_svim_phase_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(SvimProblem), ctypes.POINTER(ClusterResult),
@@ -761,23 +788,27 @@ class Context(object):
 
     def eval_counts(self, arrays, refdist, ratio):
         """duet_eval_run_host: `arrays` = dict of the flat host arrays (duet_amd/evaluation.py: flatten) -> EvalCounts."""
-        p = EvalProblem()
-        keep = {}
-        for name, dt in (('base_off', np.uint32), ('base_pos', np.uint32), ('base_len', np.uint32), ('base_uid', np.uint32),
-                         ('base_hp', np.uint8), ('call_key', np.uint32), ('call_pos', np.uint32), ('call_len', np.uint32),
-                         ('call_uid', np.uint32), ('call_group', np.uint32), ('call_hp', np.uint8)):
-            keep[name] = np.ascontiguousarray(arrays[name], dtype=dt)
-            setattr(p, name, keep[name].ctypes.data if keep[name].size else None)
-        p.n_base, p.n_calls = len(keep['base_pos']), len(keep['call_pos'])
-        p.n_keys, p.n_groups = len(keep['base_off']) - 1, int(arrays['n_groups'])
-        p.n_base_uid, p.n_call_uid = int(arrays['n_base_uid']), int(arrays['n_call_uid'])
-        p.refdist, p.ratio = clamp_u32(refdist), float(ratio)
+        p, keep = eval_problem(arrays, refdist, ratio)
         out = EvalCounts()
         rc = self.lib.duet_eval_run_host(self.handle, ctypes.byref(p), ctypes.byref(out))
         del keep
         if rc:
             self._raise(rc)
         return out
+
+    def eval_details_host(self, problem):
+        """duet_eval_details_host: `problem` = the flat host arrays of evaluation.flatten with 'refdist' and 'ratio' beside them
+        -> (EvalCounts, calls EVAL_CALL_DTYPE[n_calls], base EVAL_BASE_DTYPE[n_base])."""
+        p, keep = eval_problem(problem, problem['refdist'], problem['ratio'])
+        counts = EvalCounts()
+        calls = np.zeros(p.n_calls, dtype=EVAL_CALL_DTYPE)
+        base = np.zeros(p.n_base, dtype=EVAL_BASE_DTYPE)
+        rc = self.lib.duet_eval_details_host(self.handle, ctypes.byref(p), ctypes.byref(counts), calls.ctypes.data if p.n_calls else None,
+                                             base.ctypes.data if p.n_base else None)
+        del keep
+        if rc:
+            self._raise(rc)
+        return counts, calls, base
 
     def features_host(self, soa, svlen_thres, suppread_thres, pc_cap=None):
         """duet_ef_features_host -> structured array of FEATURE_DTYPE[C].  Raises ZeroDivisionError where E/F would.

@@ -34,10 +34,15 @@ __device__ __forceinline__ uint32_t nearest_truth(const uint32_t *bp, uint32_t n
 }
 
 // ... and its acceptance test (:126-127): the length quotient in binary64, as numpy divides
-__device__ __forceinline__ bool truth_accepts(uint32_t pos, uint32_t bpos, uint32_t cl, uint32_t bl, uint32_t refdist, double ratio)
+__device__ __forceinline__ bool length_ratio_accepts(uint32_t cl, uint32_t bl, double ratio)
 {
     const uint32_t mn = cl < bl ? cl : bl, mx = cl < bl ? bl : cl;
-    return (uint64_t)llabs((long long)pos - (long long)bpos) <= (uint64_t)refdist && (double)mn / (double)mx >= ratio;
+    return (double)mn / (double)mx >= ratio;
+}
+
+__device__ __forceinline__ bool truth_accepts(uint32_t pos, uint32_t bpos, uint32_t cl, uint32_t bl, uint32_t refdist, double ratio)
+{
+    return (uint64_t)llabs((long long)pos - (long long)bpos) <= (uint64_t)refdist && length_ratio_accepts(cl, bl, ratio);
 }
 
 // 1024 threads per 4096-key tile (the tile of rx_scatter): four keys per thread, so that a small input -- one tile per CU at

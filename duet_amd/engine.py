@@ -131,3 +131,11 @@ def run_ef(soa, svlen_thres, suppread_thres, ctx=None, want_stats=False):
     if ctx is None:
         ctx = default_context()
     return ctx.run_host(soa, svlen_thres, suppread_thres, want_stats=want_stats)
+
+
+def eval_details(problem, ctx=None):
+    """The evaluator's per-record outcome on the GPU (duet_eval_details_host): `problem` = the flat arrays of
+    evaluation.flatten with 'refdist' and 'ratio' -> (EvalCounts, calls _lib.EVAL_CALL_DTYPE[n_calls], base _lib.EVAL_BASE_DTYPE[n_base])."""
+    if ctx is None:
+        ctx = default_context()
+    return ctx.eval_details_host(problem)

@@ -13,6 +13,12 @@ each phase set is matched with one vectorised `searchsorted` instead of Python l
 `evaluation_gpu` is the same scoring on the MI355X (duet_eval_run_host, duet_amd/csrc/duet_eval.hip): the host flattens the
 parsed records (`flatten`), the device matches, builds the id sets and picks each phase set's labelling, and the six set
 sizes come back; the ten numbers are the same binary64 quotients.  `--gpu` on the command line selects it.
+
+`details` says what was scored, per record: for every call the truth record it was compared with, the distance, each test and
+the labelling its phase-set group took; for every truth record how many calls hit it, its nearest call and, when it was missed,
+why (include/duet_ef.h: duet_eval_call_rec, duet_eval_base_rec).  With a context the records come from the device
+(duet_eval_details_host), without one from `details_host`, the same rule in numpy and plain Python.  `--details PREFIX` writes
+them as PREFIX.calls.tsv and PREFIX.truth.tsv (`details_text`).
 """
 
 import argparse
@@ -157,6 +163,11 @@ _HP_FIXED = {'1|0': 0, '0|1': 1, '1|1': 2}
 def flatten(baseinfo, callinfo):
     """The parsed records as the flat arrays of include/duet_ef.h's duet_eval_problem.  Raises IndexError where upstream
     indexes an empty truth list (a call whose (contig, type) has no truth record, evaluation.py:120-125)."""
+    return flatten_rows(baseinfo, callinfo)[0]
+
+
+def flatten_rows(baseinfo, callinfo):
+    """-> (the arrays of `flatten`, the truth records in the order of the base arrays, the calls in the order of the call arrays)"""
     hp_code = dict(_HP_FIXED)
 
     def code(hp):
@@ -182,7 +193,7 @@ def flatten(baseinfo, callinfo):
         base_off[i + 1] = len(rows)
     a = dict(base_off=base_off, base_pos=[r['pos'] for r in rows], base_len=[r['len'] for r in rows],
              base_uid=[base_uid[r['id']] for r in rows], base_hp=[code(r['hp']) for r in rows])
-    ck, cp, cl, cu, cg, ch = [], [], [], [], [], []
+    ck, cp, cl, cu, cg, ch, scored = [], [], [], [], [], [], []
     for r in callinfo:
         call_uid.setdefault(r['id'], len(call_uid))
         if r['chr'] not in contig:
@@ -193,14 +204,14 @@ def flatten(baseinfo, callinfo):
         key = 2 * contig[r['chr']] + types[r['type']]
         if base_off[key + 1] == base_off[key]:
             raise IndexError('list index out of range')
-        ck.append(key); cp.append(r['pos']); cl.append(r['len']); cu.append(call_uid[r['id']]); cg.append(g); ch.append(code(r['hp']))
+        ck.append(key); cp.append(r['pos']); cl.append(r['len']); cu.append(call_uid[r['id']]); cg.append(g); ch.append(code(r['hp'])); scored.append(r)
     a.update(call_key=ck, call_pos=cp, call_len=cl, call_uid=cu, call_group=cg, call_hp=ch, n_groups=len(groups),
              n_base_uid=len(base_uid), n_call_uid=len(call_uid))
     for k in ('base_pos', 'base_len', 'call_pos', 'call_len'):
         v = np.asarray(a[k], dtype=np.int64)
         if v.size and (int(v.min()) < 0 or int(v.max()) > 0xFFFFFFFF):
             raise ValueError(k + ' outside the 32-bit range of the device arrays')
-    return a
+    return a, rows, scored
 
 
 def evaluation_gpu(baseinfo, callinfo, threshold_tp_range, ratio, ctx=None):
@@ -223,6 +234,141 @@ def evaluation_gpu(baseinfo, callinfo, threshold_tp_range, ratio, ctx=None):
     return (avg_sv_num,) + prf(n.call_tp, n.base_tp) + prf(n.call_gt, n.base_gt) + prf(n.call_hp, n.base_hp)
 
 
+CALL_COLUMNS = ('CHROM', 'POS', 'ID', 'TYPE', 'LEN', 'HP', 'GROUP', 'T_POS', 'T_ID', 'T_LEN', 'T_HP', 'DIST', 'MATCHED', 'GT', 'REL',
+                'LABEL', 'HP_OK')
+TRUTH_COLUMNS = ('CHROM', 'POS', 'ID', 'TYPE', 'LEN', 'HP', 'N_CALLS', 'N_GT', 'N_HP', 'C_POS', 'C_ID', 'C_DIST', 'REASON')
+
+
+def details_host(a, refdist, ratio):
+    """The records of include/duet_ef.h's duet_eval_details_host from the flat arrays of `flatten`, on the host: the rule of
+    evaluation.py:99-148 kept per record, and the nearest call of every truth record.  -> (the six counts in the order of
+    duet_eval_counts, calls EVAL_CALL_DTYPE[n_calls], base EVAL_BASE_DTYPE[n_base])"""
+    from duet_amd import _lib as L
+    i64 = lambda k: np.asarray(a[k], dtype=np.int64)
+    off, bpos, blen, buid, bhp = i64('base_off'), i64('base_pos'), i64('base_len'), i64('base_uid'), i64('base_hp')
+    ckey, cpos, clen, cuid, cgrp, chp = (i64(k) for k in ('call_key', 'call_pos', 'call_len', 'call_uid', 'call_group', 'call_hp'))
+    nb, nc = len(bpos), len(cpos)
+    refdist, ratio = int(refdist), float(ratio)
+    calls = np.zeros(nc, dtype=L.EVAL_CALL_DTYPE)
+    base = np.zeros(nb, dtype=L.EVAL_BASE_DTYPE)
+    listed = ckey != L.EVAL_NONE
+    # the call side: the nearest record of the call's list (:117-125), the two tests (:126-127), the haplotype tests (:130-139)
+    j = np.zeros(nc, dtype=np.int64)
+    for key in np.unique(ckey[listed]):
+        at = np.nonzero(ckey == key)[0]
+        lo, hi = int(off[key]), int(off[key + 1])
+        j[at] = lo + _nearest(bpos[lo:hi], cpos[at])
+    dist = np.abs(cpos - bpos[j]) if nb else np.zeros(nc, dtype=np.int64)
+    near = listed & (dist <= refdist)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        size = listed & ((np.minimum(clen, blen[j]) / np.maximum(clen, blen[j]) >= ratio) if nb else np.zeros(nc, dtype=bool))
+    matched = near & size
+    th = bhp[j] if nb else np.zeros(nc, dtype=np.int64)
+    gt = matched & (((chp < 2) & (th < 2)) | ((chp == 2) & (th == 2)))
+    same = matched & (chp == th)
+    flip = matched & (((chp == 2) & (th == 2)) | ((chp == 1) & (th == 0)) | ((chp == 0) & (th == 1)))
+    # the labelling of every phase-set group (:140-145): sets of ids, call side plus truth side; a tie goes to "flip"
+    sets = {}
+    for c in np.nonzero(same | flip)[0]:
+        s = sets.setdefault(int(cgrp[c]), (set(), set(), set(), set()))
+        if same[c]:
+            s[0].add(int(cuid[c])); s[1].add(int(buid[j[c]]))
+        if flip[c]:
+            s[2].add(int(cuid[c])); s[3].add(int(buid[j[c]]))
+    label = np.ones(int(a['n_groups']) if nc == 0 else max(int(a['n_groups']), int(cgrp.max()) + 1), dtype=np.int64)
+    for g, s in sets.items():
+        if len(s[0]) + len(s[1]) > len(s[2]) + len(s[3]):
+            label[g] = 0
+    flipped = label[cgrp] == 1
+    hp = matched & np.where(flipped, flip, same)
+    calls['base'] = np.where(listed, j, L.EVAL_NONE)
+    calls['dist'] = np.where(listed, dist, L.EVAL_NONE)
+    for bit, on in ((L.EVAL_NEAR, near), (L.EVAL_SIZE, size), (L.EVAL_MATCHED, matched), (L.EVAL_GT, gt), (L.EVAL_SAME, same),
+                    (L.EVAL_FLIP, flip), (L.EVAL_LABEL, flipped), (L.EVAL_HP, hp)):
+        calls['bits'] |= np.where(on, bit, 0).astype(np.uint32)
+    # the truth side: how many calls were counted at the record, and the nearest call of its list -- smallest distance, then the
+    # smaller position, then the smaller index
+    for field, on in (('n_calls', matched), ('n_gt', gt), ('n_hp', hp)):
+        base[field] = np.bincount(j[on], minlength=nb)
+    base['nearest'] = base['nearest_dist'] = L.EVAL_NONE
+    for key in range(len(off) - 1):
+        lo, hi = int(off[key]), int(off[key + 1])
+        at = np.nonzero(ckey == key)[0]
+        if hi == lo or len(at) == 0:
+            continue
+        at = at[np.argsort(cpos[at], kind='stable')]              # by (pos, index)
+        sp, bp = cpos[at], bpos[lo:hi]
+        i = np.searchsorted(sp, bp, side='left')
+        right = np.minimum(i, len(sp) - 1)
+        left = np.searchsorted(sp, sp[np.maximum(i - 1, 0)], side='left')        # the first call of the run below the record
+        d_right = np.where(i < len(sp), np.abs(sp[right] - bp), np.int64(1) << 40)
+        d_left = np.where(i > 0, np.abs(bp - sp[left]), np.int64(1) << 40)
+        take_left = d_left <= d_right
+        base['nearest'][lo:hi] = at[np.where(take_left, left, right)]
+        base['nearest_dist'][lo:hi] = np.where(take_left, d_left, d_right)
+    n = base['nearest'].astype(np.int64)
+    has = n != L.EVAL_NONE
+    nn = np.where(has, n, 0)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        fits = (np.minimum(clen[nn], blen) / np.maximum(clen[nn], blen) >= ratio) if nc else np.zeros(nb, dtype=bool)
+    reason = np.where(~has, 0, np.where(base['nearest_dist'].astype(np.int64) > refdist, 1, np.where(~fits, 2, 3)))
+    base['reason'] = np.where(base['n_calls'] > 0, L.EVAL_HIT, reason)
+    counts = tuple(len(set(ids[on].tolist())) for ids, on in ((cuid, matched), (buid[j] if nb else cuid, matched), (cuid, gt),
+                                                             (buid[j] if nb else cuid, gt), (cuid, hp), (buid[j] if nb else cuid, hp)))
+    return counts, calls, base
+
+
+def _details_problem(baseinfo, callinfo, refdist, ratio):
+    if refdist < 0:
+        raise ValueError('a negative refdist matches nothing: there is no outcome to detail')       # (evaluation() divides by zero)
+    a, rows, scored = flatten_rows(baseinfo, callinfo)
+    a['refdist'], a['ratio'] = int(refdist), float(ratio)
+    return a, rows, scored
+
+
+def details(baseinfo, callinfo, refdist, ratio, ctx=None):
+    """What was scored, per record: (calls EVAL_CALL_DTYPE, base EVAL_BASE_DTYPE) in the order of flatten_rows' calls and truth
+    records.  With a context the records come from the device, without one from details_host.  Raises what flatten raises."""
+    a = _details_problem(baseinfo, callinfo, refdist, ratio)[0]
+    return (ctx.eval_details_host(a) if ctx is not None else details_host(a, refdist, ratio))[1:]
+
+
+def details_text(rows, scored, calls, base):
+    """The two tables as text, header line first: one row per scored call in callset order and one per scored truth record in the
+    order of the base arrays (contig, type, position).  rows, scored: flatten_rows' records; calls, base: `details`' records."""
+    from duet_amd import _lib as L
+    rel = {0: '.', L.EVAL_SAME: 'same', L.EVAL_FLIP: 'flip', L.EVAL_SAME | L.EVAL_FLIP: 'both'}
+    flag = lambda bits, bit: '1' if bits & bit else '0'
+    out_c = ['\t'.join(CALL_COLUMNS) + '\n']
+    for r, rec in zip(scored, calls):
+        bits, t = int(rec['bits']), rows[int(rec['base'])]
+        out_c.append('\t'.join([r['chr'], str(r['pos']), r['id'], r['type'], str(r['len']), r['hp'], r['ps'], str(t['pos']), t['id'],
+                                str(t['len']), t['hp'], str(int(rec['dist'])), flag(bits, L.EVAL_MATCHED), flag(bits, L.EVAL_GT),
+                                rel[bits & (L.EVAL_SAME | L.EVAL_FLIP)], 'flip' if bits & L.EVAL_LABEL else 'same',
+                                flag(bits, L.EVAL_HP)]) + '\n')
+    out_t = ['\t'.join(TRUTH_COLUMNS) + '\n']
+    for t, rec in zip(rows, base):
+        if int(rec['nearest']) == L.EVAL_NONE:
+            near = ['.', '.', '.']
+        else:
+            c = scored[int(rec['nearest'])]
+            near = [str(c['pos']), c['id'], str(int(rec['nearest_dist']))]
+        reason = '.' if int(rec['reason']) == L.EVAL_HIT else L.EVAL_REASON_NAMES[int(rec['reason'])]
+        out_t.append('\t'.join([t['chr'], str(t['pos']), t['id'], t['type'], str(t['len']), t['hp'], str(int(rec['n_calls'])),
+                                str(int(rec['n_gt'])), str(int(rec['n_hp']))] + near + [reason]) + '\n')
+    return ''.join(out_c), ''.join(out_t)
+
+
+def write_details(prefix, baseinfo, callinfo, refdist, ratio, ctx=None):
+    """PREFIX.calls.tsv and PREFIX.truth.tsv; the records are complete before either file is created."""
+    a, rows, scored = _details_problem(baseinfo, callinfo, refdist, ratio)
+    calls, base = (ctx.eval_details_host(a) if ctx is not None else details_host(a, refdist, ratio))[1:]
+    text = details_text(rows, scored, calls, base)
+    for suffix, t in zip(('.calls.tsv', '.truth.tsv'), text):
+        with open(prefix + suffix, 'w') as out:
+            out.write(t)
+
+
 def parse_args(argv):
     ap = argparse.ArgumentParser(description='precision / recall / F1 of SV calling, genotyping and phasing against a truth set')
     ap.add_argument('callset', type=str, help='VCF of phased SV calls to score')
@@ -235,6 +381,8 @@ def parse_args(argv):
     ap.add_argument('--skip_phasing', action='store_true',
                     help='score calling and genotyping only')
     ap.add_argument('--gpu', action='store_true', help='score on the MI355X (libduet_ef.so) instead of with numpy')
+    ap.add_argument('--details', metavar='PREFIX', type=str,
+                    help='also write PREFIX.calls.tsv and PREFIX.truth.tsv: what was scored, per call and per truth record')
     return ap.parse_args(argv)
 
 
@@ -250,6 +398,12 @@ def main(argv):
         if what == 'phasing' and args.skip_phasing:
             continue
         print('The precision, recall and F1 score of SV %s are' % what, res[at], res[at + 1], res[at + 2])
+    if args.details:
+        ctx = None
+        if args.gpu:
+            from duet_amd import engine
+            ctx = engine.default_context()
+        write_details(args.details, truth, calls, args.refdist, args.pctsim, ctx)
 
 
 if __name__ == '__main__':

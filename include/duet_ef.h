@@ -417,6 +417,59 @@ typedef struct duet_eval_counts {
 /* All arrays are HOST pointers; uploads, runs four small kernels, synchronises. */
 DUET_API int duet_eval_run_host(duet_ctx *ctx, const duet_eval_problem *prob, duet_eval_counts *counts);
 
+/* The same scoring, said per record (duet_eval_details.hip): what became of every call and of every truth record.
+ *
+ * Call c (the order of the call arrays).  `base` is the truth record the call is compared with -- the nearest one of its list by
+ * :117-125, an index into the base arrays --, `dist` = |call_pos[c] - base_pos[base]|, and `bits`:
+ *   NEAR     dist <= refdist (:126)
+ *   SIZE     min(len) / max(len) >= ratio, the binary64 quotient of :127 (0 / 0 is nan: refused)
+ *   MATCHED  NEAR and SIZE: the pair the evaluator scores
+ *   GT, SAME, FLIP   the tests of :130-131, :134 and :137-139 on a MATCHED pair (a '1|1' pair sets SAME and FLIP); never set without
+ *            MATCHED, as the evaluator makes them on accepted pairs only
+ *   LABEL    the labelling the call's phase-set group took (:143-148): 0 "same", 1 "flip" -- "same" only with strictly more ids,
+ *            call ids plus truth ids; set on every call of the group, matched or not
+ *   HP       MATCHED and the one of SAME / FLIP that LABEL names: the call is in call_tp_hp, its record in base_tp_hp
+ * All bits but LABEL are about this record's own pair, not about its id: two calls with one id can differ.  A call whose
+ * call_key is 0xFFFFFFFF is compared with nothing: base and dist all-ones, LABEL alone in bits.
+ *
+ * Truth record j (the order of the base arrays).  n_calls / n_gt / n_hp: the calls with base == j that have MATCHED / GT / HP.
+ * `nearest`: the call of j's list key with the smallest |call_pos - base_pos[j]|, ties to the smaller call position, then to the
+ * smaller call index; all-ones (and nearest_dist all-ones) when the key has no call.  `reason` says why a record with
+ * n_calls == 0 was missed: NO_CALL the key has no call; FAR nearest_dist > refdist; SIZE the nearest call is within refdist and
+ * the length ratio fails; ELSEWHERE the nearest call passes both tests against j and was compared with another record;
+ * DUET_EVAL_HIT (255) when n_calls > 0. */
+#define DUET_EVAL_NEAR 1u
+#define DUET_EVAL_SIZE 2u
+#define DUET_EVAL_MATCHED 4u
+#define DUET_EVAL_GT 8u
+#define DUET_EVAL_SAME 16u
+#define DUET_EVAL_FLIP 32u
+#define DUET_EVAL_LABEL 64u
+#define DUET_EVAL_HP 128u
+
+#define DUET_EVAL_NO_CALL 0
+#define DUET_EVAL_FAR 1
+#define DUET_EVAL_WRONG_SIZE 2
+#define DUET_EVAL_ELSEWHERE 3
+#define DUET_EVAL_HIT 255
+
+typedef struct duet_eval_call_rec {
+    uint32_t base, dist, bits;
+} duet_eval_call_rec;                                /* 12 bytes */
+
+typedef struct duet_eval_base_rec {
+    uint32_t n_calls, n_gt, n_hp;
+    uint32_t nearest, nearest_dist;
+    uint8_t reason, reserved[3];                     /* reserved: 0 */
+} duet_eval_base_rec;                                /* 24 bytes */
+
+/* All arrays are HOST pointers.  counts: what duet_eval_run_host gives for *prob; calls[n_calls], base[n_base].  Checked on the
+ * host before anything is uploaded (DUET_ERR_INVALID): n_keys in 1 .. 2^24 - 1; base_off ascends from 0 to n_base; every call_key
+ * is 0xFFFFFFFF or names a non-empty list; every call_uid < n_call_uid and call_group < n_groups (of a call without a list key
+ * too); every base_uid < n_base_uid.  n_calls == 0 launches nothing: every truth record is a NO_CALL. */
+DUET_API int duet_eval_details_host(duet_ctx *ctx, const duet_eval_problem *prob, duet_eval_counts *counts, duet_eval_call_rec *calls,
+                           duet_eval_base_rec *base);
+
 /* ---------------------------------------------------------------------------------------------
  * Threshold sweep (duet_tune.hip): the T1-T5 tree of predict_hp (src/duet/sv_phasing_fn.py:142-183) with its constants
  * replaced by a vector of binary64 values, applied to K vectors at once and scored against a truth set.
